@@ -85,8 +85,15 @@ def parse_args(argv=None):
     ap.add_argument("--plan-bands", type=int, default=0,
                     help="cut every pixel's samples into work items as for this many row bands (default: --gpus); a 1-GPU run with "
                          "--plan-bands N produces the N-GPU run's images bit for bit (GdptRenderParams.plan_rows)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float64): out (the "
+                         "reconstructed image) and, with one GPU, the five render buffers img, cx0, cy0, cx1, cy1; at most 64 MB "
+                         "in all (larger films: the same seeded sample of pixels from every array, flat indices in pixel_index.npy)")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)   # internal: workload under rocprofv3
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def film_of(args):
@@ -332,6 +339,11 @@ def run_rank(args):
             pipe = make_pipeline(spp_total)
     r0, r1 = pipe.rows
     elapsed = timed(pipe, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:       # before anything else runs the pipeline again: the last timed step's arrays
+        dumped = {"out": pipe.out}
+        if world == 1:
+            dumped.update(pipe.bufs)
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in dumped.items()})
     ph = phases(pipe, max(3, min(args.steps, 10)))
     rs, ps = pipe.step(want_stats=True)       # counters of one launch (synchronises)
     samples_all = W * H * spp_total
@@ -504,6 +516,30 @@ def run_rank(args):
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+DUMP_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+    """Writes {name: HxWxC float64 array} as outdir/<name>.npy, at most `budget` bytes in all. Over budget, every array is
+    cut to the same sample of pixels, drawn with a fixed seed so that two runs at one film size pick the same pixels; their
+    flat indices (y * W + x, ascending) go to pixel_index.npy as float64."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    h, w = next(iter(arrays.values())).shape[:2]
+    flat = {k: np.ascontiguousarray(v, dtype=np.float64).reshape(h * w, -1) for k, v in arrays.items()}
+    header = 128 * (len(flat) + 1)                       # one .npy header per file
+    if sum(v.nbytes for v in flat.values()) + header > budget:
+        per_pixel = sum(v.shape[1] for v in flat.values()) * 8 + 8
+        idx = np.sort(np.random.default_rng(0).choice(h * w, size=(budget - header) // per_pixel, replace=False))
+        flat = {k: v[idx] for k, v in flat.items()}
+        flat["pixel_index"] = idx.astype(np.float64)
+    else:
+        flat = {k: v.reshape(arrays[k].shape) for k, v in flat.items()}
+    for k, v in flat.items():
+        np.save(os.path.join(outdir, k + ".npy"), v)
+    return sorted(flat)
 
 
 def _find(table, name):

@@ -113,3 +113,48 @@ def test_band_cuts_at_any_row_and_the_feedback_step():
     same = sharding.refine_row_costs(model, rows, mod)      # times proportional to the model: nothing to correct
     assert all(abs(a - b) < 1e-12 for a, b in zip(same, model))
     assert sharding.refine_row_costs(model, rows, [0.0, 0.0, 0.0, 0.0]) == model                  # no clock, no change
+
+
+def test_dump_outputs_writes_whole_arrays_or_one_seeded_sample(tmp_path):
+    """bench.dump_outputs: whole float64 arrays under the budget; over it, the same pixels of every array, the same pixels
+    from run to run, and the files together within the budget."""
+    rng = np.random.default_rng(5)
+    arrays = {"out": rng.random((48, 64, 3)), "img": rng.random((48, 64, 3)).astype(np.float32)}
+    assert bench.dump_outputs(str(tmp_path / "all"), arrays) == ["img", "out"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / f"{k}.npy")
+        assert got.dtype == np.float64 and np.array_equal(got, v)
+    budget = 20000
+    for run in ("a", "b"):
+        names = bench.dump_outputs(str(tmp_path / run), arrays, budget=budget)
+        assert names == ["img", "out", "pixel_index"]
+        assert sum(os.path.getsize(tmp_path / run / f"{k}.npy") for k in names) <= budget
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "pixel_index.npy"))
+    assert len(idx) > 100 and np.all(np.diff(idx) > 0) and idx[-1] < 48 * 64
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "a" / f"{k}.npy")
+        assert np.array_equal(got, v.reshape(-1, 3)[idx.astype(np.int64)].astype(np.float64)), k
+
+
+@pytest.mark.gpu
+def test_bench_dumps_what_its_last_timed_step_computed(G, O, tmp_path):
+    """`bench.py --dump-outputs DIR`: the reconstructed image and the five render buffers of the timed path, checked against
+    the CPU oracle on the same PCG streams (the tolerances of __graft_entry__.smoke)."""
+    from helpers import rel_l2
+    out_dir = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--spp", "4", "--film", "48x32",
+           "--no-pmc", "--no-cpu-baseline", "--no-strong", "--dump-outputs", str(out_dir)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert sorted(os.listdir(out_dir)) == ["cx0.npy", "cx1.npy", "cy0.npy", "cy1.npy", "img.npy", "out.npy"]
+    sd = G.parse_scene(bench.DEFAULT_SCENE, film=(48, 32))
+    ob, _ = O.OracleScene(sd.ptr).render(4, G.RNG_SAMPLE, threads=4)
+    for k in ("img", "cx0", "cy0", "cx1", "cy1"):
+        got = np.load(out_dir / f"{k}.npy")
+        assert got.shape == (32, 48, 3) and got.dtype == np.float64
+        assert rel_l2(got, ob[k]) < 1e-9, k
+    c, cx, cy = O.assemble(ob)
+    assert rel_l2(np.load(out_dir / "out.npy"), O.fourier_solve(c, cx, cy, 0.04)) < 1e-6
