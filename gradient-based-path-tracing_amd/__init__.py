@@ -88,6 +88,8 @@ def lib():
         L.gdpt_debug_chunk_plan.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.POINTER(C.c_int32), C.c_int]
         L.gdpt_debug_get_stamps.argtypes = [C.POINTER(C.c_double)]
         L.gdpt_debug_get_stamps.restype = None
+        L.gdpt_debug_last_route.restype = C.c_char_p
+        L.gdpt_debug_route_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
         _LIB = L
     return _LIB
 
@@ -461,6 +463,20 @@ class debug_knobs:
         d["busy_us"] = (v[13] - v[12]) / 100.0      # first wave started -> first wave found the queue empty
         d["drain_us"] = (v[14] - v[13]) / 100.0     # ... -> last wave ended
         return d
+
+    @staticmethod
+    def last_route():
+        """Kernel route of this thread's last render (include/gdpt_debug.h: gdpt_debug_last_route)."""
+        return lib().gdpt_debug_last_route().decode()
+
+    @staticmethod
+    def route_names():
+        """Every route name the library can report (include/gdpt_debug.h: gdpt_debug_route_names)."""
+        n = lib().gdpt_debug_route_names(None, 0)
+        buf = (C.c_char_p * n)()
+        if lib().gdpt_debug_route_names(buf, n) != n:
+            raise GdptError("gdpt_debug_route_names: capacity")
+        return [x.decode() for x in buf]
 
     @staticmethod
     def from_env(environ=None):

@@ -425,6 +425,7 @@ namespace gdpt {
 void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
                         double *img, double *cx0, double *cy0, double *cx1, double *cy1,
                         hipStream_t stream, GdptRenderStats *stats) {
+    gdpt::set_route("");           // (include/gdpt_debug.h: "" until this render has launched its kernel)
     ck(hipSetDevice(sc->device), "hipSetDevice");
     Band b = resolve(sc, params);
     if (b.spp <= 0) b.spp = scene_spp;
@@ -464,7 +465,9 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
     }
     if (env_int("no_lds_scene", 0)) rl.scene_fits_lds = false;
     // two-sided lobes (DisneyGlass, DisneyBSDF) without rough ones: lane machine with offsets replayed from a bounce log
-    rl.two_sided_machine = !sc->one_sided && !sc->has_rough && !rl.force_eager && b.rng == GDPT_RNG_SAMPLE && !env_int("no_twosided_machine", 0);
+    // (a depth bound that lets a path outrun the replay's bounce log takes the straight-loop evaluator: render_twosided.h)
+    rl.two_sided_machine = !sc->one_sided && !sc->has_rough && !rl.force_eager && b.rng == GDPT_RNG_SAMPLE && !env_int("no_twosided_machine", 0) &&
+                           gdpt::twosided_log_covers(b.max_depth, sc->view.rr_depth);
     if (rl.two_sided_machine) {
         const long long tiles = (long long)((sc->view.cam.width + 15) / 16) * ((b.row_end - b.row_begin + 15) / 16);
         const long long items = (tiles * 256) * gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)sc->view.cam.width * b.plan_rows,
@@ -539,6 +542,7 @@ namespace {
 using gdpt::render_device_impl;
 // Integrator::Path: enqueues one render of `img`; returns after enqueue unless stats are requested.
 void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, double *img, hipStream_t stream, GdptRenderStats *stats) {
+    gdpt::set_route("");
     ck(hipSetDevice(sc->device), "hipSetDevice");
     if (sc->view.num_lights <= 0) throw std::runtime_error("gdpt_path_render: the scene has no emitter to sample");
     Band b = resolve(sc, params);
@@ -603,6 +607,10 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
     for (int c = 0; c <= p.n; c++) begin[c] = p.begin[c];
     return p.n;
 }
+
+// include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: set_route)
+const char *gdpt_debug_last_route(void) { return gdpt::last_route(); }
+int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
 
 int gdpt_scene_upload(const GdptSceneDesc *desc, int device, GdptScene **out_scene) {
     return gdpt::guarded([&]() {

@@ -123,9 +123,11 @@ struct AccLds {
     }
 };
 
+// Non-finite samples are counted once each, as the oracle counts them: `counted` / `flagged` say that the sample's
+// offsets already did (the lane machines keep that in Lane::kc, bit kKcNonfinite, across the four offset steps).
 template <class ACC>
-GD void acc_base(ACC &a, D3 radiance, double prob, double spp, LaneCounters &lc) {
-    if (!(isfinite(prob) && isfinite(radiance.x + radiance.y + radiance.z))) lc.nonfinite++;
+GD void acc_base(ACC &a, D3 radiance, double prob, double spp, LaneCounters &lc, bool counted = false) {
+    if (!counted && !(isfinite(prob) && isfinite(radiance.x + radiance.y + radiance.z))) lc.nonfinite++;
     if (prob > 0.0) a.add(0, radiance / spp);
 }
 // k: 0 = x0, 1 = x1, 2 = y0, 3 = y1
@@ -596,10 +598,11 @@ struct LanePriv {
 };
 constexpr int kPrivDoubles = 8;
 
+constexpr int kKcNonfinite = 1 << 30;
 struct Lane {
     int st, s, s_end, num_vertices;
     int mats;                 // mat0 | mat1 << 12 (material ids of the base primary hit / the bounce-1 hit), 0xFFF = none
-    int kc;                   // offset index k | cmode << 2
+    int kc;                   // offset index k | cmode << 2 | kKcNonfinite (an offset of this sample was non-finite)
     unsigned long long rng_state, rng_inc;
     D3 org, dir;              // the pending ray
     D3 f; double pdf;         // S_BOUNCE: f*|cos| and solid-angle pdf of `dir` at the vertex the ray leaves
@@ -610,7 +613,7 @@ struct Lane {
     GD int mat0() const { return mats & 0xFFF; }
     GD int mat1() const { return (mats >> 12) & 0xFFF; }
     GD int k() const { return kc & 3; }
-    GD int cmode() const { return kc >> 2; }
+    GD int cmode() const { return (kc & ~kKcNonfinite) >> 2; }
 };
 
 // SERIAL_RNG: one PCG stream runs through consecutive samples (TILE scheme); otherwise each sample owns stream
@@ -731,9 +734,10 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             }
             if (alive) { cX = c0 * jac; wgt = L.prob / (L.prob + 1.0 * jac); }      // :1019-1045
         }
-        bool flagged = false;
+        bool flagged = (L.kc & kKcNonfinite) != 0;
         acc_offset(acc, k, L.contrib, cX, wgt, L.prob, spp, lc, flagged);
-        if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
+        if (flagged) L.kc |= kKcNonfinite;
+        if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc, flagged); L.kc &= ~kKcNonfinite; act = ACT_NEXT_SAMPLE; }
         else { L.kc = (L.kc & ~3) | (k + 1); act = ACT_OFFSET_RAY; }
     } else if (act == ACT_BOUNCE) {                                                  // bounce iteration L.num_vertices starts at `nv`
         if (!sampled) act = ACT_NEXT_SAMPLE;                                        // :545-548: GraidentPTRadiance{}
@@ -1234,10 +1238,10 @@ GD void grad_sample_eager(const DevSceneView &sv, const TraceCtx &tx, int max_de
 }
 
 GD void accumulate_eager(AccReg &a, const SampleOut &s, double spp, LaneCounters &lc) {
-    acc_base(a, s.radiance, s.prob, spp, lc);
     bool flagged = false;
 #pragma unroll
     for (int k = 0; k < 4; k++) acc_offset(a, k, s.contrib, s.cX[k], s.w[k], s.prob, spp, lc, flagged);
+    acc_base(a, s.radiance, s.prob, spp, lc, flagged);
 }
 
 __global__ __launch_bounds__(kBlock, 2) void gdpt_render_eager(DevSceneView sv, KernelArgs a) {

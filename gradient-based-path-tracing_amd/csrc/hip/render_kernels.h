@@ -81,4 +81,13 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
 // Name of the dominant kernel of the last launch configuration (for rocprof matching).
 const char *render_kernel_name(int rng_scheme);
 
+// Route of the calling thread's last render launch (include/gdpt_debug.h: gdpt_debug_last_route). Every launcher that
+// picks a kernel records its name with set_route; the names are the entries of route_names.
+void set_route(const char *name);
+const char *last_route();
+int route_names(const char **out, int capacity);
+// The two-sided replay machine logs gd::kLogCap bounce iterations per sample (render_twosided.h); false when the depth
+// bound lets a path run past the log, where the replay would stop following the reference.
+bool twosided_log_covers(int max_depth, int rr_depth);
+
 } // namespace gdpt

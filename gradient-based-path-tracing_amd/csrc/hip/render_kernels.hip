@@ -11,6 +11,35 @@ const char *render_kernel_name(int rng_scheme) {
     return rng_scheme == GDPT_RNG_TILE ? "gdpt_render_tile_stream_phases" : "gdpt_render_phases";
 }
 
+namespace {
+thread_local const char *g_route = "";
+// every name set_route is called with (include/gdpt_debug.h lists what they mean)
+const char *const kRouteNames[] = {
+    "lambert_plain/lds_const", "lambert_plain/lds_tex", "lambert_plain/hbm_const", "lambert_plain/hbm_tex",
+    "lambert/lds_wide", "lambert/lds_bvh2", "lambert/hbm",
+    "lambert_stamped/lds_plain", "lambert_stamped/lds", "lambert_stamped/hbm",
+    "general_set_a/disney_diffuse", "general_set_a/disney_metal", "general_set_b/disney_clearcoat", "general_set_b/disney_sheen",
+    "general/lds_wide", "general/lds_bvh2", "general/hbm",
+    "twosided/lds", "twosided/hbm", "twosided/hbm_glass",
+    "wavefront/lambert", "wavefront/general",
+    "eager", "tile_eager", "tile_phases_lambert", "tile_phases_general",
+    "reconnect/lds_lambert", "reconnect/hbm_lambert", "reconnect/general",
+    "path/tile", "path/eager",
+    "path_persistent/lds_lambert_plain", "path_persistent/lds_lambert", "path_persistent/lds_lambert_env",
+    "path_persistent/hbm_lambert", "path_persistent/hbm_lambert_env",
+    "path_persistent/lds_general", "path_persistent/lds_general_env", "path_persistent/hbm_general", "path_persistent/hbm_general_env",
+};
+} // namespace
+void set_route(const char *name) { g_route = name; }
+const char *last_route() { return g_route; }
+int route_names(const char **out, int capacity) {
+    const int n = (int)(sizeof(kRouteNames) / sizeof(kRouteNames[0]));
+    if (!out) return n;
+    if (capacity < n) return -1;
+    for (int i = 0; i < n; i++) out[i] = kRouteNames[i];
+    return n;
+}
+
 static long long resident_lanes(const RenderLaunch &rl) { return (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * gd::kBlock; }
 
 // item layout of the persistent kernels (render_device.h: item_to_pixel)
@@ -75,6 +104,7 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
     t.ovf = (int *)(aux + lay.ovf); t.ovf_stride = (unsigned)rl.wf_slots; t.counters = rl.counters;
     t.num_tris = sv.num_tris; t.num_nodes4 = sv.num_nodes4; t.num_spheres = sv.num_spheres; t.search_frac = a.thresh_c; t.count_stats = a.count;
     auto ckh = [](hipError_t e, const char *what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e)); };
+    set_route(rl.lambert_only ? "wavefront/lambert" : "wavefront/general");
     ckh(hipMemsetAsync(rl.wf_counters, 0, sizeof(unsigned) * 3 * gd::kWfMaxGen, stream), "hipMemsetAsync(wavefront counters)");
     ckh(hipMemsetAsync(w.hist, 0, sizeof(unsigned) * gd::kWfBins, stream), "hipMemsetAsync(wavefront histogram)");
     launch_wf_init(w, stream);
@@ -132,13 +162,14 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
         a.tile_h = ppb / a.tile_w;
         a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
         int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
+        set_route(!rl.lambert_only ? "reconnect/general" : (rl.scene_fits_lds && rl.lds_wide) ? "reconnect/lds_lambert" : "reconnect/hbm_lambert");
         launch_reconnect(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), rl.scene_fits_lds && rl.lds_wide, rl.lambert_only, stream);
     } else if (rl.rng_scheme == GDPT_RNG_TILE) {
         int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;
         dim3 grid((unsigned)((ntx * nty + 63) / 64));
-        if (!phases) launch_tile_eager(sv, a, grid, ntx, nty, stream);
-        else if (rl.lambert_only) launch_tile_phases_lambert(sv, a, grid, ntx, nty, stream);
-        else launch_tile_phases_general(sv, a, grid, ntx, nty, stream);
+        if (!phases) { set_route("tile_eager"); launch_tile_eager(sv, a, grid, ntx, nty, stream); }
+        else if (rl.lambert_only) { set_route("tile_phases_lambert"); launch_tile_phases_lambert(sv, a, grid, ntx, nty, stream); }
+        else { set_route("tile_phases_general"); launch_tile_phases_general(sv, a, grid, ntx, nty, stream); }
     } else if (rl.rng_scheme == GDPT_RNG_SAMPLE) {
         if (!phases) {
             // eager evaluator: static mapping, K = 2^log2k lanes per pixel
@@ -152,6 +183,7 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
             a.tile_h = ppb / a.tile_w;
             a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
             int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
+            set_route("eager");
             launch_eager(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), stream);
         } else {
             // persistent lanes pulling (pixel, chunk) items: >= 4 samples per item, at most 8 items per pixel
@@ -172,11 +204,23 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
             } else if (rl.two_sided_machine) {
                 if (!rl.bounce_log || rl.bounce_log_bytes < twosided_log_bytes(blocks)) throw std::runtime_error("launch_render: bounce log missing");
                 launch_phases_twosided(sv, a, grid, rl.scene_fits_lds && rl.lds_wide, rl.material_mask, rl.bounce_log, stream);
-            } else if (rl.lambert_only && rl.stamped && (!rl.scene_fits_lds || rl.lds_wide)) launch_phases_lambert_stamped(sv, a, grid, rl.scene_fits_lds, rl.no_spheres && rl.const_textures, stream);
-            else if (rl.lambert_only && rl.no_spheres && (!rl.scene_fits_lds || rl.lds_wide)) launch_phases_lambert_plain(sv, a, grid, rl.scene_fits_lds, rl.const_textures, stream);
-            else if (rl.lambert_only) launch_phases_lambert(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
-            else if (!rl.scene_fits_lds && rl.no_spheres && (launch_phases_general_set_a(sv, a, grid, rl.material_mask, stream) || launch_phases_general_set_b(sv, a, grid, rl.material_mask, stream))) {}   // kernel built for the scene's material set
-            else launch_phases_general(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
+            } else if (rl.lambert_only && rl.stamped && (!rl.scene_fits_lds || rl.lds_wide)) {
+                const bool plain = rl.no_spheres && rl.const_textures;
+                set_route(!rl.scene_fits_lds ? "lambert_stamped/hbm" : plain ? "lambert_stamped/lds_plain" : "lambert_stamped/lds");
+                launch_phases_lambert_stamped(sv, a, grid, rl.scene_fits_lds, plain, stream);
+            } else if (rl.lambert_only && rl.no_spheres && (!rl.scene_fits_lds || rl.lds_wide)) {
+                set_route(rl.scene_fits_lds ? (rl.const_textures ? "lambert_plain/lds_const" : "lambert_plain/lds_tex")
+                                            : (rl.const_textures ? "lambert_plain/hbm_const" : "lambert_plain/hbm_tex"));
+                launch_phases_lambert_plain(sv, a, grid, rl.scene_fits_lds, rl.const_textures, stream);
+            } else if (rl.lambert_only) {
+                set_route(!rl.scene_fits_lds ? "lambert/hbm" : rl.lds_wide ? "lambert/lds_wide" : "lambert/lds_bvh2");
+                launch_phases_lambert(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
+            } else if (!rl.scene_fits_lds && rl.no_spheres && (launch_phases_general_set_a(sv, a, grid, rl.material_mask, stream) || launch_phases_general_set_b(sv, a, grid, rl.material_mask, stream))) {
+                // kernel built for the scene's material set (the set launchers record the route)
+            } else {
+                set_route(!rl.scene_fits_lds ? "general/hbm" : rl.lds_wide ? "general/lds_wide" : "general/lds_bvh2");
+                launch_phases_general(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
+            }
             launch_reduce_partials(sv, a, stream);
         }
     } else {
@@ -195,6 +239,7 @@ void launch_path_render(const DevSceneView &sv, const RenderLaunch &rl, hipStrea
     const int W = sv.cam.width, rows = rl.row_end - rl.row_begin;
     if (W <= 0 || rows <= 0 || rl.spp <= 0) throw std::runtime_error("launch_path_render: empty image band or spp <= 0");
     if (rl.rng_scheme == GDPT_RNG_TILE) {
+        set_route("path/tile");
         int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;
         launch_tile_path(sv, a, dim3((unsigned)((ntx * nty + 63) / 64)), ntx, nty, stream);
     } else if (rl.rng_scheme == GDPT_RNG_SAMPLE && !rl.force_eager) {
@@ -224,6 +269,7 @@ void launch_path_render(const DevSceneView &sv, const RenderLaunch &rl, hipStrea
         a.tile_h = ppb / a.tile_w;
         a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
         int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
+        set_route("path/eager");
         launch_path(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), stream);
     } else {
         throw std::runtime_error("launch_path_render: unknown rng_scheme");

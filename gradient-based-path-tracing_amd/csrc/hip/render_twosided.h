@@ -11,8 +11,12 @@
 // the same shared BSDF block the base path's bounces use. Exact for every material (no one-sidedness argument), with
 // the lane machine's work queue, resumable trace phase and occupancy.
 //
-// Log capacity: kLogCap iterations per sample. A path longer than that (probability < 0.95^1000 with Russian
-// roulette) stops being logged; an offset still alive at that point keeps the jacobian it has.
+// Log capacity: kLogCap iterations per sample. A path longer than that stops being logged, and an offset still alive at
+// that point would keep the jacobian it has while the reference goes on multiplying p2 / p2_offset. So the machine only
+// runs where the depth bound keeps paths inside the log (render_phases_twosided.hip: twosided_log_covers): maxDepth - 1
+// <= kLogCap, or rrDepth <= kLogCap - 800, so that a longer path needs at least 800 survived roulette draws of
+// probability <= 0.95 each (about 1e-18 per path; 1019 draws at the default rrDepth 5). Every other depth bound takes
+// the straight-loop evaluator (capi_device.hip).
 #pragma once
 #include "render_device.h"
 
@@ -113,7 +117,7 @@ GD void lane_step2(const DevSceneView &sv, const TraceCtx &tx, int max_depth, do
     if (st0 == S_OFFSET) {
         if (hit && nv.material_id == L.mat0()) {                                    // :424-443
             L.f = L.dir; L.pdf = 1.0;                                               // o.dir, o.jacob
-            L.kc &= 3;                                                              // replay index 0
+            L.kc &= 3 | kKcNonfinite;                                               // replay index 0
             Pcg r2 = pcg_init(base + (unsigned long long)L.s);
             (void)pcg_next(r2); (void)pcg_next(r2);                                 // the sample's two sub-pixel numbers
             L.rng_state = r2.state; L.rng_inc = r2.inc;
@@ -137,7 +141,7 @@ GD void lane_step2(const DevSceneView &sv, const TraceCtx &tx, int max_depth, do
     double pdf = 0;
     if (SHARE) {
         const bool replaying = off_alive;
-        int r = L.kc >> 2, budget = replay_per_step;
+        int r = (L.kc & ~kKcNonfinite) >> 2, budget = replay_per_step;
         const int n_it = n_iter(L);
         Pcg rs; rs.state = L.rng_state; rs.inc = L.rng_inc;
         D3 odir = L.f;
@@ -186,12 +190,12 @@ GD void lane_step2(const DevSceneView &sv, const TraceCtx &tx, int max_depth, do
             }
         }
         if (replaying) {
-            L.f = odir; L.pdf = jac; L.kc = (L.kc & 3) | (r << 2);
+            L.f = odir; L.pdf = jac; L.kc = (L.kc & (3 | kKcNonfinite)) | (r << 2);
             L.rng_state = rs.state;
         }
     } else {
         if (off_alive) {
-            int r = L.kc >> 2, budget = replay_per_step;
+            int r = (L.kc & ~kKcNonfinite) >> 2, budget = replay_per_step;
             const int n_it = n_iter(L);
             Pcg rs; rs.state = L.rng_state; rs.inc = L.rng_inc;
             D3 odir = L.f;
@@ -213,7 +217,7 @@ GD void lane_step2(const DevSceneView &sv, const TraceCtx &tx, int max_depth, do
                 if (!osampled || opdf <= 0.0) { off_done = true; off_alive = false; break; }             // :773-959
                 jac *= e.p2 / opdf; odir = obs.dir_out; r++;                            // :813, :815-816
             }
-            L.f = odir; L.pdf = jac; L.kc = (L.kc & 3) | (r << 2);
+            L.f = odir; L.pdf = jac; L.kc = (L.kc & (3 | kKcNonfinite)) | (r << 2);
             L.rng_state = rs.state;
         }
         // ---------------- shared BSDF block (base path) ----------------
@@ -236,10 +240,10 @@ GD void lane_step2(const DevSceneView &sv, const TraceCtx &tx, int max_depth, do
             const D3 c0 = (nv.light_id >= 0) ? emission(sv, nv, -ray.dir) : splat(1.0);   // :496-508
             cX = c0 * L.pdf; wgt = L.prob / (L.prob + 1.0 * L.pdf);
         }
-        bool flagged = false;
+        bool flagged = (L.kc & kKcNonfinite) != 0;
         acc_offset(acc, k, L.contrib, cX, wgt, L.prob, spp, lc, flagged);
-        if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
-        else { L.kc = k + 1; act = ACT_OFFSET_RAY; }
+        if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc, flagged); L.kc = 0; act = ACT_NEXT_SAMPLE; }
+        else { L.kc = (flagged ? kKcNonfinite : 0) | (k + 1); act = ACT_OFFSET_RAY; }
     } else if (act == ACT_BOUNCE) {                                                  // iteration `it` starts at nv
         const int it = L.num_vertices - 3;
         if (!sampled) act = ACT_NEXT_SAMPLE;                                        // :545-548: GraidentPTRadiance{}

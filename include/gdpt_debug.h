@@ -38,6 +38,26 @@
  *   full_material_switch (0/1)  lane machines: the kernel with the full material switch even when the scene fits a small set
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
+ *
+ * Route names (gdpt_debug_last_route): the kernel a render launched, as `family/variant`. "lds" = the scene copied to
+ * LDS (lds_wide: in its BVH4 form, lds_bvh2: BVH2), "hbm" = walked from HBM; "plain" / "const" = the build without sphere
+ * and texture code, "tex" = without sphere code only; "env" = with the environment-map lookups.
+ *   GradPath, GDPT_RNG_SAMPLE, GDPT_SHIFT_REFERENCE, one-sided lobes (lane machine with lazy offsets):
+ *     lambert_plain/{lds_const, lds_tex, hbm_const, hbm_tex}   Lambertian, triangles only
+ *     lambert/{lds_wide, lds_bvh2, hbm}                         Lambertian, with spheres (or an LDS scene in BVH2 form)
+ *     lambert_stamped/{lds_plain, lds, hbm}                     the diagnostic build (knob stamps)
+ *     general_set_a/{disney_diffuse, disney_metal}, general_set_b/{disney_clearcoat, disney_sheen}
+ *                                                               HBM triangle scenes of Lambertian + that one lobe
+ *     general/{lds_wide, lds_bvh2, hbm}                         the full material switch
+ *     wavefront/{lambert, general}                              HBM scenes under the knob wavefront
+ *   GradPath, two-sided lobes (DisneyGlass, DisneyBSDF), replay machine:
+ *     twosided/{lds, hbm, hbm_glass}                            hbm_glass: Lambertian + DisneyGlass only
+ *   GradPath, straight per-sample loops: eager (rough lobes; two-sided lobes whose depth bound outruns the replay's
+ *     bounce log; knob force_eager), tile_eager (GDPT_RNG_TILE with rough or two-sided lobes)
+ *   GradPath, GDPT_RNG_TILE, one-sided lobes: tile_phases_lambert, tile_phases_general
+ *   GradPath, GDPT_SHIFT_RECONNECT: reconnect/{lds_lambert, hbm_lambert, general} (one general kernel, walked from HBM)
+ *   Path: path/tile (GDPT_RNG_TILE), path/eager (knob force_eager), path_persistent/{lds_lambert_plain, lds_lambert,
+ *     lds_lambert_env, hbm_lambert, hbm_lambert_env, lds_general, lds_general_env, hbm_general, hbm_general_env}
  */
 #ifndef GDPT_DEBUG_H
 #define GDPT_DEBUG_H
@@ -57,6 +77,12 @@ void gdpt_debug_get_stamps(double out[16]);
  * covers samples [begin[c], begin[c+1]). Returns the number of chunks (begin[] gets n + 1 entries), -1 if `capacity` is too
  * small. force_log2k < 0: the product plan. Host only. */
 int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long long resident_lanes, int32_t *begin, int capacity);
+/* Route of the last gdpt_render / gdpt_path_render (and their _device forms) made by the CALLING thread: one of the
+ * names above, "" before the first one (or after a render that failed before its launch). The string is static. */
+const char *gdpt_debug_last_route(void);
+/* Every name gdpt_debug_last_route can return: fills out[0..n) and returns n, or -1 if `capacity` < n; out == NULL
+ * returns n alone. */
+int gdpt_debug_route_names(const char **out, int capacity);
 /* Removes every override: the library is back on its product path. */
 void gdpt_debug_knobs_reset(void);
 

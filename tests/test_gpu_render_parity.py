@@ -223,8 +223,9 @@ def test_argument_errors(G, scene_tmp):
 
 
 def test_roughplastic_and_roughdielectric_boxes(G, O, scene_tmp):
-    """the cbox with its two boxes switched to RoughPlastic (one-sided: lane machine with lazy
-    offsets) and RoughDielectric (two-sided: eager evaluator), GradPath and Path against the oracle."""
+    """the cbox with its two boxes switched to RoughPlastic and RoughDielectric, GradPath and Path
+    against the oracle. Rough lobes take the straight-loop (eager) evaluator, the one-sided RoughPlastic included: the
+    lane machines are built for the lobes without roughness parameters (capi_device.hip: has_rough)."""
     for variant, tol in ((("roughplastic",), 1e-9), (("roughplastic", "roughdielectric"), 1e-7)):
         xml = scene_variant(scene_tmp, "cbox/cbox_gdpt.xml", width=40, height=32)
         text = open(xml).read()
@@ -239,6 +240,7 @@ def test_roughplastic_and_roughdielectric_boxes(G, O, scene_tmp):
         assert G.MAT_ROUGHPLASTIC in types and ((G.MAT_ROUGHDIELECTRIC in types) == (len(variant) > 1))
         sc = G.Scene(sd)
         got, st = sc.render(6, G.RNG_SAMPLE)
+        assert G.debug_knobs.last_route() == "eager"
         want, ost = O.OracleScene(sd.ptr).render(6, G.RNG_SAMPLE, threads=8)
         assert st.bounces == ost.bounces
         check_buffers(got, want, tol)
