@@ -418,44 +418,46 @@ Band resolve(const GdptScene *sc, const GdptRenderParams *p) {
     return b;
 }
 
-} // namespace
-
-namespace gdpt {
-// Enqueues one render; returns after enqueue unless stats are requested.
-void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
-                        double *img, double *cx0, double *cy0, double *cx1, double *cy1,
-                        hipStream_t stream, GdptRenderStats *stats) {
-    gdpt::set_route("");           // (include/gdpt_debug.h: "" until this render has launched its kernel)
-    ck(hipSetDevice(sc->device), "hipSetDevice");
-    Band b = resolve(sc, params);
+// The band with its samples per pixel (the params' spp, else `scene_spp`).
+Band resolve_spp(const GdptScene *sc, const GdptRenderParams *p, int scene_spp, const char *what) {
+    Band b = resolve(sc, p);
     if (b.spp <= 0) b.spp = scene_spp;
-    if (b.spp <= 0) throw std::runtime_error("gdpt_render: samples per pixel must be > 0");
-    if (!img || !cx0 || !cy0 || !cx1 || !cy1) throw std::runtime_error("gdpt_render: null output buffer");
+    if (b.spp <= 0) throw std::runtime_error(std::string(what) + ": samples per pixel must be > 0");
+    return b;
+}
+
+// Chooses the route of a render of band `b` and fills the launch fields both integrators share; a persistent route gets its
+// work-item plan (made here, once) and a partials buffer that holds it. The knobs are the A/B overrides of the parity tests
+// (include/gdpt_debug.h); every default is the product path.
+gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int take_pct, hipStream_t stream, const GdptRenderStats *stats) {
+    auto knob = [](const char *name, int def) { return gdpt::debug_knob_int(name, def); };
+    const DevSceneView &v = sc->view;
+    gdpt::RouteInputs in{};
+    in.path = path; in.rng_scheme = b.rng; in.shift_mode = b.shift; in.max_depth = b.max_depth; in.rr_depth = v.rr_depth;
+    in.one_sided = sc->one_sided; in.has_rough = sc->has_rough; in.lambert_only = sc->lambert_only; in.material_mask = sc->material_mask;
+    in.has_spheres = v.num_spheres != 0; in.const_textures = v.all_textures_constant != 0; in.has_envmap = v.has_envmap != 0;
+    in.fits_lds = gdpt::scene_fits_lds(v.num_nodes, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->bvh_depth);
+    in.fits_lds_wide = gdpt::scene_fits_lds_wide(v.num_nodes4, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->wide_stack_need);
+    in.force_eager = knob("force_eager", 0) != 0; in.no_lds_scene = knob("no_lds_scene", 0) != 0; in.lds_wide = knob("lds_wide", 1) != 0;
+    in.no_twosided_machine = knob("no_twosided_machine", 0) != 0; in.wavefront = knob("wavefront", kWavefrontDefault) != 0;
+    in.stamps = knob("stamps", 0) != 0; in.no_plain_kernel = knob("no_plain_kernel", 0) != 0;
+    in.full_material_switch = knob("full_material_switch", 0) != 0;
     gdpt::RenderLaunch rl{};
-    rl.spp = b.spp; rl.rng_scheme = b.rng; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth; rl.shift_mode = b.shift; rl.plan_rows = b.plan_rows;
-    rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
+    rl.route = gdpt::choose_route(in);
+    rl.spp = b.spp; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
     rl.counters = sc->d_counters;
     rl.count_traversal = stats && stats->nodes_visited == ~0ull;   // request flag: caller presets nodes_visited = UINT64_MAX
-    rl.one_sided_materials = sc->one_sided && !sc->has_rough; rl.lambert_only = sc->lambert_only;
-    rl.material_mask = sc->material_mask;
-    rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
-    rl.num_materials = sc->view.num_materials;
-    rl.scene_fits_lds = gdpt::scene_fits_lds(sc->view.num_nodes, sc->view.num_prims, sc->view.num_tris, sc->view.num_materials, sc->view.num_lights, sc->bvh_depth);
-    // A/B overrides of the parity tests (include/gdpt_debug.h); every default below is the product path
-    auto env_int = [](const char *name, int def) { return gdpt::debug_knob_int(name, def); };
-    if (env_int("full_material_switch", 0)) rl.material_mask = 0x1FFu;
-    rl.no_spheres = sc->view.num_spheres == 0 && !env_int("no_plain_kernel", 0);
-    rl.const_textures = sc->view.all_textures_constant != 0;
-    rl.replay_per_step = env_int("replay_per_step", 0);
-    rl.force_eager = env_int("force_eager", 0) != 0;
-    rl.thresh_a = env_int("keep_frac", -1); rl.thresh_c = env_int("search_frac", -1);
-    rl.force_log2k = env_int("log2k", -1);
-    rl.num_cus = sc->num_cus;
-    rl.plan_take_pct = sc->plan_take_pct;
-    rl.blocks_per_cu = env_int("blocks_per_cu", 0);
-    rl.stamped = env_int("stamps", 0) != 0;
-    {
-        size_t need = gdpt::render_partials_doubles(sc->view.cam.width, b.row_end - b.row_begin, b.plan_rows, b.spp, rl.force_log2k, (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * 256, rl.plan_take_pct);
+    rl.force_log2k = knob("log2k", -1);
+    rl.thresh_a = knob("keep_frac", -1); rl.thresh_c = knob("search_frac", -1);
+    rl.num_cus = sc->num_cus; rl.blocks_per_cu = knob("blocks_per_cu", 0);
+    if (gdpt::is_persistent(rl.route)) {
+        // The plan is made for a band of plan_rows rows (default: the whole film), whatever band is rendered: a pixel's samples
+        // are cut (and its partial sums merged) the same way by every render that names the same plan_rows, so a sharded render
+        // equals the unsharded one with that plan bit for bit. (Round 2 always planned for the whole film: a 64-row band of the
+        // 512x512x256 film, 1/8 of the work, then held 32 k items of 128 samples and took 9.3 ms instead of 3.8 —
+        // profiles/r03_band_costs.txt.)
+        rl.plan = gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)v.cam.width * b.plan_rows, gdpt::resident_lanes(rl), take_pct);
+        const size_t need = (size_t)16 * (size_t)gdpt::band_slots(v.cam.width, b.row_end - b.row_begin) * (size_t)rl.plan.n;
         if (need > sc->partials_doubles) {
             if (sc->d_partials) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); hipFree(sc->d_partials); sc->d_partials = nullptr; }
             ck(hipMalloc((void **)&sc->d_partials, need * sizeof(double)), "hipMalloc(work-item partials)");
@@ -463,16 +465,54 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
         }
         rl.partials = sc->d_partials; rl.queue_head = sc->d_queue;
     }
-    if (env_int("no_lds_scene", 0)) rl.scene_fits_lds = false;
-    // two-sided lobes (DisneyGlass, DisneyBSDF) without rough ones: lane machine with offsets replayed from a bounce log
-    // (a depth bound that lets a path outrun the replay's bounce log takes the straight-loop evaluator: render_twosided.h)
-    rl.two_sided_machine = !sc->one_sided && !sc->has_rough && !rl.force_eager && b.rng == GDPT_RNG_SAMPLE && !env_int("no_twosided_machine", 0) &&
-                           gdpt::twosided_log_covers(b.max_depth, sc->view.rr_depth);
-    if (rl.two_sided_machine) {
-        const long long tiles = (long long)((sc->view.cam.width + 15) / 16) * ((b.row_end - b.row_begin + 15) / 16);
-        const long long items = (tiles * 256) * gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)sc->view.cam.width * b.plan_rows,
-                                                                      (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * 256, rl.plan_take_pct).n;
-        const size_t need = gdpt::twosided_log_bytes(gdpt::persistent_blocks(rl, items));
+    return rl;
+}
+
+// Enqueues the counter reset, the launch and, when stats are requested, waits for the render and reports it.
+void run_launch(GdptScene *sc, const gdpt::RenderLaunch &rl, const Band &b, hipStream_t stream, GdptRenderStats *stats) {
+    const bool stamped = gdpt::is_stamped(rl.route);
+    ck(hipMemsetAsync(sc->d_counters, 0, sizeof(gdpt::RenderCounters), stream), "hipMemsetAsync(counters)");
+    if (stamped) ck(hipMemsetAsync(&sc->d_counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), stream), "hipMemsetAsync(stamps)");   // min slots
+    if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
+    gdpt::launch_render(sc->view, rl, stream);
+    if (!stats) return;
+    ck(hipEventRecord(sc->ev1, stream), "hipEventRecord");
+    ck(hipMemcpyAsync(sc->h_counters, sc->d_counters, sizeof(gdpt::RenderCounters), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(counters)");
+    ck(hipStreamSynchronize(stream), "hipStreamSynchronize(render)");
+    float ms = 0;
+    ck(hipEventElapsedTime(&ms, sc->ev0, sc->ev1), "hipEventElapsedTime");
+    const gdpt::RenderCounters &c = *sc->h_counters;
+    std::memset(stats, 0, sizeof(*stats));
+    stats->samples = (uint64_t)sc->view.cam.width * (uint64_t)(b.row_end - b.row_begin) * (uint64_t)b.spp;
+    stats->rays = c.rays; stats->bounces = c.bounces; stats->nonfinite_samples = c.nonfinite;
+    stats->nodes_visited = c.nodes; stats->tris_tested = c.prims;
+    stats->render_ms = ms;
+    if (!gdpt::is_path(rl.route)) {   // (Integrator::Path leaves them 0)
+        stats->wave_node_trips = c.wave_node_trips; stats->wave_leaf_trips = c.wave_leaf_trips;
+        stats->wave_steps = c.wave_steps; stats->lane_steps = c.lane_steps;
+    }
+    if (stamped) gdpt::debug_store_stamps(c.stamps, 16);
+    stats->node_bytes = gdpt::walks_bvh2(rl.route) ? sizeof(DevBvhNode) : sizeof(DevBvh4Node);
+}
+
+} // namespace
+
+namespace gdpt {
+// Enqueues one render; returns after enqueue unless stats are requested.
+void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
+                        double *img, double *cx0, double *cy0, double *cx1, double *cy1,
+                        hipStream_t stream, GdptRenderStats *stats) {
+    reset_route();           // (include/gdpt_debug.h: "" until this render has launched its kernel)
+    ck(hipSetDevice(sc->device), "hipSetDevice");
+    const Band b = resolve_spp(sc, params, scene_spp, "gdpt_render");
+    if (!img || !cx0 || !cy0 || !cx1 || !cy1) throw std::runtime_error("gdpt_render: null output buffer");
+    RenderLaunch rl = begin_launch(sc, b, false, sc->plan_take_pct, stream, stats);
+    rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
+    rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
+    rl.replay_per_step = debug_knob_int("replay_per_step", 0);
+    const long long items = band_slots(sc->view.cam.width, b.row_end - b.row_begin) * rl.plan.n;
+    if (needs_bounce_log(rl.route)) {
+        const size_t need = twosided_log_bytes(persistent_blocks(rl, items));
         if (need > sc->bounce_log_bytes) {
             if (sc->d_bounce_log) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); hipFree(sc->d_bounce_log); sc->d_bounce_log = nullptr; }
             ck(hipMalloc(&sc->d_bounce_log, need), "hipMalloc(bounce log)");
@@ -480,60 +520,31 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
         }
         rl.bounce_log = sc->d_bounce_log; rl.bounce_log_bytes = sc->bounce_log_bytes;
     }
-    // scenes walked from HBM with one-sided lobes: the wavefront pipeline (test knob "wavefront": 0 = lane machine, 1 = wavefront)
-    rl.wavefront = env_int("wavefront", kWavefrontDefault) != 0 && rl.one_sided_materials && !rl.scene_fits_lds && !rl.force_eager &&
-                   b.rng == GDPT_RNG_SAMPLE && b.shift == GDPT_SHIFT_REFERENCE;
-    if (rl.wavefront) {
-        const long long tiles = (long long)((sc->view.cam.width + 15) / 16) * ((b.row_end - b.row_begin + 15) / 16);
-        const long long items = (tiles * 256) * gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)sc->view.cam.width * b.plan_rows,
-                                                                      (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * 256, rl.plan_take_pct).n;
-        int slots = gdpt::wf_slot_count(items);
-        { const int forced = env_int("wf_slots", 0); if (forced > 0) slots = std::min(slots, (forced + 255) / 256 * 256); }   // tests: force slot reuse
+    if (is_wavefront(rl.route)) {
+        int slots = wf_slot_count(items);
+        { const int forced = debug_knob_int("wf_slots", 0); if (forced > 0) slots = std::min(slots, (forced + 255) / 256 * 256); }   // tests: force slot reuse
         if (slots > sc->wf_slots) {
             ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
             if (sc->d_wf_state) hipFree(sc->d_wf_state);
             if (sc->d_wf_live) hipFree(sc->d_wf_live);
             if (sc->d_wf_aux) hipFree(sc->d_wf_aux);
             sc->d_wf_state = nullptr; sc->d_wf_live = nullptr; sc->d_wf_aux = nullptr; sc->wf_slots = 0;
-            ck(hipMalloc((void **)&sc->d_wf_state, (size_t)slots * gdpt::wf_words() * sizeof(unsigned long long)), "hipMalloc(wavefront state)");
+            ck(hipMalloc((void **)&sc->d_wf_state, (size_t)slots * wf_words() * sizeof(unsigned long long)), "hipMalloc(wavefront state)");
             ck(hipMalloc((void **)&sc->d_wf_live, (size_t)slots * sizeof(unsigned)), "hipMalloc(wavefront live list)");
-            ck(hipMalloc(&sc->d_wf_aux, gdpt::wf_aux_bytes(slots)), "hipMalloc(wavefront ray / hit records)");
+            ck(hipMalloc(&sc->d_wf_aux, wf_aux_bytes(slots)), "hipMalloc(wavefront ray / hit records)");
             sc->wf_slots = slots;
         }
         if (!sc->d_wf_counters) {
-            ck(hipMalloc((void **)&sc->d_wf_counters, sizeof(unsigned) * 3 * gdpt::wf_max_generations()), "hipMalloc(wavefront counters)");
+            ck(hipMalloc((void **)&sc->d_wf_counters, sizeof(unsigned) * 3 * wf_max_generations()), "hipMalloc(wavefront counters)");
             ck(hipHostMalloc((void **)&sc->h_wf_word, sizeof(unsigned)), "hipHostMalloc(wavefront)");
             ck(hipEventCreateWithFlags(&sc->wf_event, hipEventDisableTiming), "hipEventCreate");
         }
-        rl.wf_aux = sc->d_wf_aux; rl.wf_sort = env_int("wf_sort", 1);
+        rl.wf_aux = sc->d_wf_aux; rl.wf_sort = debug_knob_int("wf_sort", 1);
         for (int k = 0; k < 6; k++) rl.wf_bounds[k] = sc->bounds[k];
         rl.wf_state = sc->d_wf_state; rl.wf_live = sc->d_wf_live; rl.wf_counters = sc->d_wf_counters; rl.wf_host = sc->h_wf_word;
         rl.wf_event = sc->wf_event; rl.wf_slots = slots;       // exactly the slots this band needs (the buffers may be larger)
     }
-    rl.lds_wide = rl.scene_fits_lds && env_int("lds_wide", 1) != 0 &&
-                  gdpt::scene_fits_lds_wide(sc->view.num_nodes4, sc->view.num_prims, sc->view.num_tris, sc->view.num_materials, sc->view.num_lights, sc->wide_stack_need);
-    ck(hipMemsetAsync(sc->d_counters, 0, sizeof(gdpt::RenderCounters), stream), "hipMemsetAsync(counters)");
-    if (rl.stamped) ck(hipMemsetAsync(&sc->d_counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), stream), "hipMemsetAsync(stamps)");   // min slots
-    if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
-    gdpt::launch_render(sc->view, rl, stream);
-    if (stats) {
-        ck(hipEventRecord(sc->ev1, stream), "hipEventRecord");
-        ck(hipMemcpyAsync(sc->h_counters, sc->d_counters, sizeof(gdpt::RenderCounters), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(counters)");
-        ck(hipStreamSynchronize(stream), "hipStreamSynchronize(render)");
-        float ms = 0;
-        ck(hipEventElapsedTime(&ms, sc->ev0, sc->ev1), "hipEventElapsedTime");
-        stats->samples = (uint64_t)sc->view.cam.width * (uint64_t)(b.row_end - b.row_begin) * (uint64_t)b.spp;
-        stats->rays = sc->h_counters->rays; stats->bounces = sc->h_counters->bounces;
-        stats->nonfinite_samples = sc->h_counters->nonfinite;
-        stats->nodes_visited = sc->h_counters->nodes; stats->tris_tested = sc->h_counters->prims;
-        stats->render_ms = ms;
-        stats->wave_node_trips = sc->h_counters->wave_node_trips; stats->wave_leaf_trips = sc->h_counters->wave_leaf_trips;
-        stats->wave_steps = sc->h_counters->wave_steps; stats->lane_steps = sc->h_counters->lane_steps;
-        if (rl.stamped) gdpt::debug_store_stamps(sc->h_counters->stamps, 16);
-        // only the persistent kernel over an LDS-resident scene can still walk the BVH2 form
-        const bool lds_kernel = rl.one_sided_materials && !rl.force_eager && b.rng == GDPT_RNG_SAMPLE && rl.scene_fits_lds;
-        stats->node_bytes = (lds_kernel && !rl.lds_wide) ? sizeof(DevBvhNode) : sizeof(DevBvh4Node);
-    }
+    run_launch(sc, rl, b, stream, stats);
 }
 
 } // namespace gdpt
@@ -542,53 +553,14 @@ namespace {
 using gdpt::render_device_impl;
 // Integrator::Path: enqueues one render of `img`; returns after enqueue unless stats are requested.
 void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, double *img, hipStream_t stream, GdptRenderStats *stats) {
-    gdpt::set_route("");
+    gdpt::reset_route();
     ck(hipSetDevice(sc->device), "hipSetDevice");
     if (sc->view.num_lights <= 0) throw std::runtime_error("gdpt_path_render: the scene has no emitter to sample");
-    Band b = resolve(sc, params);
-    if (b.spp <= 0) b.spp = sc->scene_spp;
-    if (b.spp <= 0) throw std::runtime_error("gdpt_path_render: samples per pixel must be > 0");
+    const Band b = resolve_spp(sc, params, sc->scene_spp, "gdpt_path_render");
     if (!img) throw std::runtime_error("gdpt_path_render: null output buffer");
-    gdpt::RenderLaunch rl{};
-    rl.spp = b.spp; rl.rng_scheme = b.rng; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth; rl.shift_mode = b.shift; rl.plan_rows = b.plan_rows;
+    gdpt::RenderLaunch rl = begin_launch(sc, b, true, 0, stream, stats);   // (the plan takes the default share: see make_chunk_plan)
     rl.img = img;
-    rl.counters = sc->d_counters;
-    rl.count_traversal = stats && stats->nodes_visited == ~0ull;
-    auto env_int = [](const char *name, int def) { return gdpt::debug_knob_int(name, def); };   // include/gdpt_debug.h
-    rl.force_log2k = env_int("log2k", -1);
-    rl.force_eager = env_int("force_eager", 0) != 0;
-    rl.thresh_a = env_int("keep_frac", -1); rl.thresh_c = env_int("search_frac", -1);
-    rl.num_cus = sc->num_cus; rl.blocks_per_cu = env_int("blocks_per_cu", 0);
-    rl.lambert_only = sc->lambert_only;
-    rl.no_spheres = sc->view.num_spheres == 0 && !env_int("no_plain_kernel", 0); rl.const_textures = sc->view.all_textures_constant != 0;
-    rl.scene_fits_lds = !env_int("no_lds_scene", 0) &&
-                        gdpt::scene_fits_lds_wide(sc->view.num_nodes4, sc->view.num_prims, sc->view.num_tris, sc->view.num_materials, sc->view.num_lights, sc->wide_stack_need);
-    {
-        size_t need = gdpt::render_partials_doubles(sc->view.cam.width, b.row_end - b.row_begin, b.plan_rows, b.spp, rl.force_log2k, (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * 256, rl.plan_take_pct);
-        if (need > sc->partials_doubles) {
-            if (sc->d_partials) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); hipFree(sc->d_partials); sc->d_partials = nullptr; }
-            ck(hipMalloc((void **)&sc->d_partials, need * sizeof(double)), "hipMalloc(work-item partials)");
-            sc->partials_doubles = need;
-        }
-        rl.partials = sc->d_partials; rl.queue_head = sc->d_queue;
-    }
-    ck(hipMemsetAsync(sc->d_counters, 0, sizeof(gdpt::RenderCounters), stream), "hipMemsetAsync(counters)");
-    if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
-    gdpt::launch_path_render(sc->view, rl, stream);
-    if (stats) {
-        ck(hipEventRecord(sc->ev1, stream), "hipEventRecord");
-        ck(hipMemcpyAsync(sc->h_counters, sc->d_counters, sizeof(gdpt::RenderCounters), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(counters)");
-        ck(hipStreamSynchronize(stream), "hipStreamSynchronize(path render)");
-        float ms = 0;
-        ck(hipEventElapsedTime(&ms, sc->ev0, sc->ev1), "hipEventElapsedTime");
-        std::memset(stats, 0, sizeof(*stats));
-        stats->samples = (uint64_t)sc->view.cam.width * (uint64_t)(b.row_end - b.row_begin) * (uint64_t)b.spp;
-        stats->rays = sc->h_counters->rays; stats->bounces = sc->h_counters->bounces;
-        stats->nonfinite_samples = sc->h_counters->nonfinite;
-        stats->nodes_visited = sc->h_counters->nodes; stats->tris_tested = sc->h_counters->prims;
-        stats->render_ms = ms;
-        stats->node_bytes = sizeof(DevBvh4Node);
-    }
+    run_launch(sc, rl, b, stream, stats);
 }
 
 } // namespace
@@ -608,7 +580,7 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
     return p.n;
 }
 
-// include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: set_route)
+// include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: launch_render)
 const char *gdpt_debug_last_route(void) { return gdpt::last_route(); }
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
 

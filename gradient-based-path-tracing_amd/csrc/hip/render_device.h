@@ -1307,22 +1307,24 @@ __global__ __launch_bounds__(64) void gdpt_render_tile_stream_eager(DevSceneView
 } // namespace gd
 
 namespace gdpt {
-// host launchers, one translation unit per kernel family (parallel compilation)
+// host launchers, one translation unit per kernel family (parallel compilation); each launches the kernel its arguments name
+// (render_kernels.hip: launch_render calls one per route)
 void launch_phases_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, hipStream_t stream);
 void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, hipStream_t stream);   // triangles only (and constant textures)
 void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, hipStream_t stream);   // diagnostic build
 void launch_reduce_partials(const DevSceneView &sv, const gd::KernelArgs &a, hipStream_t stream);
 void launch_phases_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, hipStream_t stream);
-// kernels built for {Lambertian, one Disney lobe} (render_phases_general_sets_*.hip): false if the scene's set is not one of theirs
-bool launch_phases_general_set_a(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, unsigned material_mask, hipStream_t stream);
-bool launch_phases_general_set_b(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, unsigned material_mask, hipStream_t stream);
-void launch_phases_twosided(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, unsigned material_mask, void *bounce_log, hipStream_t stream);
+// kernels built for {Lambertian, `lobe`} (render_phases_general_sets_*.hip): GDPT_MAT_DISNEY_DIFFUSE / _METAL (a), _CLEARCOAT / _SHEEN (b)
+void launch_phases_general_set_a(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int lobe, hipStream_t stream);
+void launch_phases_general_set_b(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int lobe, hipStream_t stream);
+void launch_phases_twosided(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, void *bounce_log, hipStream_t stream);
+void launch_phases_twosided_glass(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, void *bounce_log, hipStream_t stream);   // HBM, kSetGlass
 void launch_tile_phases_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int ntx, int nty, hipStream_t stream);
 void launch_tile_phases_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int ntx, int nty, hipStream_t stream);
 void launch_eager(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, hipStream_t stream);
 void launch_tile_eager(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int ntx, int nty, hipStream_t stream);
 void launch_reconnect(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lambert, hipStream_t stream);
 void launch_path(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, hipStream_t stream);
-void launch_path_persistent(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lambert, bool plain, hipStream_t stream);
+void launch_path_persistent(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lambert, bool lds, bool env, bool plain, hipStream_t stream);
 void launch_tile_path(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int ntx, int nty, hipStream_t stream);
 } // namespace gdpt

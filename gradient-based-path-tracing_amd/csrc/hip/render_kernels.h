@@ -15,34 +15,71 @@ struct RenderCounters {            // device-resident, zeroed per render
     unsigned long long stamps[16];  // diagnostic build (knob "stamps"): wave cycles per segment, render_device.h SEG_*
 };
 
+// The kernel a render launches, one per name of include/gdpt_debug.h (route_name gives it), grouped as listed there:
+// GradPath lane machines that pull work items (.. WAVEFRONT_GENERAL), GradPath straight loops (EAGER .. RECONNECT_GENERAL),
+// Integrator::Path (PATH_TILE ..).
+enum class Route : int {
+    LAMBERT_PLAIN_LDS_CONST, LAMBERT_PLAIN_LDS_TEX, LAMBERT_PLAIN_HBM_CONST, LAMBERT_PLAIN_HBM_TEX,
+    LAMBERT_LDS_WIDE, LAMBERT_LDS_BVH2, LAMBERT_HBM,
+    LAMBERT_STAMPED_LDS_PLAIN, LAMBERT_STAMPED_LDS, LAMBERT_STAMPED_HBM,
+    GENERAL_SET_A_DISNEY_DIFFUSE, GENERAL_SET_A_DISNEY_METAL, GENERAL_SET_B_DISNEY_CLEARCOAT, GENERAL_SET_B_DISNEY_SHEEN,
+    GENERAL_LDS_WIDE, GENERAL_LDS_BVH2, GENERAL_HBM,
+    TWOSIDED_LDS, TWOSIDED_HBM, TWOSIDED_HBM_GLASS,
+    WAVEFRONT_LAMBERT, WAVEFRONT_GENERAL,
+    EAGER, TILE_EAGER, TILE_PHASES_LAMBERT, TILE_PHASES_GENERAL,
+    RECONNECT_LDS_LAMBERT, RECONNECT_HBM_LAMBERT, RECONNECT_GENERAL,
+    PATH_TILE, PATH_EAGER,
+    PATH_PERSISTENT_LDS_LAMBERT_PLAIN, PATH_PERSISTENT_LDS_LAMBERT, PATH_PERSISTENT_LDS_LAMBERT_ENV,
+    PATH_PERSISTENT_HBM_LAMBERT, PATH_PERSISTENT_HBM_LAMBERT_ENV,
+    PATH_PERSISTENT_LDS_GENERAL, PATH_PERSISTENT_LDS_GENERAL_ENV, PATH_PERSISTENT_HBM_GENERAL, PATH_PERSISTENT_HBM_GENERAL_ENV,
+    COUNT
+};
+const char *route_name(Route r);
+inline bool is_path(Route r) { return r >= Route::PATH_TILE; }
+// pulls (pixel, chunk) work items from the queue into `partials` (GradPath: merged by gdpt_reduce_partials)
+inline bool is_persistent(Route r) { return r <= Route::WAVEFRONT_GENERAL || r >= Route::PATH_PERSISTENT_LDS_LAMBERT_PLAIN; }
+inline bool is_wavefront(Route r) { return r == Route::WAVEFRONT_LAMBERT || r == Route::WAVEFRONT_GENERAL; }
+inline bool needs_bounce_log(Route r) { return r >= Route::TWOSIDED_LDS && r <= Route::TWOSIDED_HBM_GLASS; }
+inline bool is_stamped(Route r) { return r >= Route::LAMBERT_STAMPED_LDS_PLAIN && r <= Route::LAMBERT_STAMPED_HBM; }
+// the only kernels that walk the LDS copy in its BVH2 form; every other route walks a BVH4 (or the HBM tree)
+inline bool walks_bvh2(Route r) { return r == Route::LAMBERT_LDS_BVH2 || r == Route::GENERAL_LDS_BVH2; }
+
+// Everything the route depends on. The caller resolves the knobs (include/gdpt_debug.h) into the overrides.
+struct RouteInputs {
+    bool path;                     // Integrator::Path (else GradPath)
+    int rng_scheme, shift_mode;    // GDPT_RNG_*, GDPT_SHIFT_*
+    int max_depth, rr_depth;       // effective maxDepth, the scene's rrDepth (twosided_log_covers)
+    // scene traits
+    bool one_sided;                // no DisneyGlass / DisneyBSDF / RoughDielectric
+    bool has_rough;                // RoughPlastic / RoughDielectric
+    bool lambert_only;             // every material is Lambertian
+    unsigned material_mask;        // bit t = some material of the scene has type t (selects kernels built for small sets)
+    bool has_spheres, const_textures, has_envmap;
+    bool fits_lds;                 // scene_fits_lds: the BVH2 form + primitive records fit the block's LDS copy
+    bool fits_lds_wide;            // scene_fits_lds_wide: the same for the BVH4 form
+    // knob overrides (defaults: the product path)
+    bool force_eager, no_lds_scene, lds_wide, no_twosided_machine, wavefront, stamps, no_plain_kernel, full_material_switch;
+};
+// Pure: no HIP call, no knob read. Throws std::runtime_error for an rng_scheme / shift_mode pair no kernel serves.
+Route choose_route(const RouteInputs &in);
+
 struct RenderLaunch {
+    Route route;                   // choose_route
     int spp;
-    int rng_scheme;                // GDPT_RNG_*
     int row_begin, row_end;
-    int plan_rows;                 // the work-item plan is made for a band of this many rows (GdptRenderParams::plan_rows, resolved)
     int max_depth;                 // effective (scene value or override)
-    double *img, *cx0, *cy0, *cx1, *cy1;   // device, W*H*3 each
+    double *img, *cx0, *cy0, *cx1, *cy1;   // device, W*H*3 each (Path: img only)
     RenderCounters *counters;      // device
     bool count_traversal;          // counting build: BVH nodes / primitives per ray
-    int shift_mode;                // GDPT_SHIFT_*: 0 = the reference's offsets (parity mode), 1 = reconnection shift
-    // scene classification (decided at upload) and tuning knobs
-    bool one_sided_materials;      // no DisneyGlass / DisneyBSDF: the phase machine with lazy offsets is exact
-    bool lambert_only;             // every material is Lambertian
-    bool scene_fits_lds;           // BVH nodes + primitive records fit the block's LDS copy
-    bool force_eager;              // run the eager evaluator regardless (checks / A-B runs)
+    ChunkPlan plan;                // persistent routes: the work-item plan (make_chunk_plan)
     int thresh_a, thresh_c;        // trace-phase exit fractions /256 (unfinished rays; lanes still searching a leaf), -1 = default
     int force_log2k;               // lanes per pixel = 2^force_log2k (-1 = automatic)
-    bool lds_wide;                 // LDS-resident scene walked in its BVH4 form
     int wide_stack_need;           // traversal-stack bound of the tree the HBM kernels walk (host-verified)
-    int num_materials;
-    unsigned material_mask;        // bit t = some material of the scene has type t (selects kernels built for small sets)
-    bool two_sided_machine;        // two-sided lobes present (and no rough ones): lane machine with replayed offsets
-    void *bounce_log;              // its per-lane log (device), sized by twosided_log_bytes(blocks)
+    void *bounce_log;              // two-sided routes: per-lane log (device), sized by twosided_log_bytes(blocks)
     size_t bounce_log_bytes;
     int num_cus;                   // compute units of the device (persistent grid size)
     int blocks_per_cu;             // persistent blocks per CU (0 = default 2)
-    // wavefront pipeline (render_wavefront.h): scenes walked from HBM, one-sided lobes, SAMPLE streams
-    bool wavefront;
+    // wavefront pipeline (render_wavefront.h)
     unsigned long long *wf_state;  // device, wf_words() * wf_slots 8-byte words
     unsigned *wf_live;             // device, wf_slots
     void *wf_aux;                  // device, wf_aux_bytes(wf_slots): ray / hit records, sort keys, histogram, overflow stacks
@@ -53,37 +90,34 @@ struct RenderLaunch {
     hipEvent_t wf_event;
     int wf_slots;
     int replay_per_step;           // two-sided lane machine (render_twosided.h), 0 = default
-    bool no_spheres, const_textures;   // triangles only / every texture constant: kernels built without sphere / texture code
-    bool stamped;                  // diagnostic build with in-kernel cycle stamps (test-only knob "stamps")
-    int plan_take_pct;             // work-item plan: share of the unassigned samples a chunk takes, percent (0 = default; scenes of long-tailed paths take less)
-    double *partials;              // device, >= 15 * W * rows * 8 doubles (work-item partial sums)
+    double *partials;              // device, >= 16 doubles per work item (partial sums)
     unsigned long long *queue_head;// device, work-queue head
 };
 bool scene_fits_lds(int num_nodes, int num_prims, int num_tris, int num_materials, int num_lights, int bvh_depth);
 bool scene_fits_lds_wide(int num_nodes4, int num_prims, int num_tris, int num_materials, int num_lights, int wide_stack_need);
 
-// Doubles the `partials` buffer must hold for a band of `pixels` pixels at `spp`.
+// Lanes of the persistent grid resident at once (blocks_per_cu 0 = 2 blocks per CU).
+inline long long resident_lanes(const RenderLaunch &rl) { return (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * 256; }
+// Pixel slots of a band: 16x16-pixel tiles of 256 slots (ragged edge tiles keep all 256). Work items = slots * plan.n.
+inline long long band_slots(int width, int rows) { return (long long)((width + 15) / 16) * ((rows + 15) / 16) * 256; }
 size_t twosided_log_bytes(unsigned blocks);
 unsigned persistent_blocks(const RenderLaunch &rl, long long num_items);
-void launch_path_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream);
 // Chunk sizes shrink along the queue (about 40 % of what is left each time, ending in single samples) unless
 // force_log2k >= 0 asks for 2^k equal chunks (tests). `lanes` = resident lanes of the persistent grid.
 ChunkPlan make_chunk_plan(int spp, int force_log2k, long long pixels, long long lanes, int take_pct = 0);    // take_pct: share of the unassigned samples a chunk takes (0 = the default 55)
-size_t render_partials_doubles(int width, int rows, int plan_rows, int spp, int force_log2k, long long lanes, int take_pct = 0);
 
 int wf_words();
 int wf_max_generations();
 // Path slots of the wavefront pipeline for a band of `num_items` work items.
 int wf_slot_count(long long num_items);
 size_t wf_aux_bytes(int slots);
-// Enqueues the five-buffer render on `stream`. Throws std::runtime_error on a launch failure.
+// Enqueues the render of rl.route on `stream` and records the route (last_route). Throws std::runtime_error on a launch failure.
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream);
-// Name of the dominant kernel of the last launch configuration (for rocprof matching).
-const char *render_kernel_name(int rng_scheme);
 
-// Route of the calling thread's last render launch (include/gdpt_debug.h: gdpt_debug_last_route). Every launcher that
-// picks a kernel records its name with set_route; the names are the entries of route_names.
-void set_route(const char *name);
+// Route of the calling thread's last render launch (include/gdpt_debug.h: gdpt_debug_last_route): launch_render sets it,
+// reset_route clears it ("") at the start of a render.
+void set_route(Route r);
+void reset_route();
 const char *last_route();
 int route_names(const char **out, int capacity);
 // The two-sided replay machine logs gd::kLogCap bounce iterations per sample (render_twosided.h); false when the depth

@@ -1,4 +1,5 @@
-// render_kernels.hip — launch dispatch of the GDPT render kernels (device code: render_device.h).
+// render_kernels.hip — route choice and launch dispatch of the GDPT render kernels (device code: render_device.h).
+#include "render_twosided.h"
 #include "render_wavefront.h"
 
 #include "../capi_common.h"
@@ -7,13 +8,9 @@
 
 namespace gdpt {
 
-const char *render_kernel_name(int rng_scheme) {
-    return rng_scheme == GDPT_RNG_TILE ? "gdpt_render_tile_stream_phases" : "gdpt_render_phases";
-}
-
 namespace {
 thread_local const char *g_route = "";
-// every name set_route is called with (include/gdpt_debug.h lists what they mean)
+// include/gdpt_debug.h lists what they mean; the order is that of enum Route
 const char *const kRouteNames[] = {
     "lambert_plain/lds_const", "lambert_plain/lds_tex", "lambert_plain/hbm_const", "lambert_plain/hbm_tex",
     "lambert/lds_wide", "lambert/lds_bvh2", "lambert/hbm",
@@ -29,32 +26,101 @@ const char *const kRouteNames[] = {
     "path_persistent/hbm_lambert", "path_persistent/hbm_lambert_env",
     "path_persistent/lds_general", "path_persistent/lds_general_env", "path_persistent/hbm_general", "path_persistent/hbm_general_env",
 };
+constexpr int kNumRoutes = (int)(sizeof(kRouteNames) / sizeof(kRouteNames[0]));
+static_assert(kNumRoutes == (int)Route::COUNT, "one name per Route");
 } // namespace
-void set_route(const char *name) { g_route = name; }
+const char *route_name(Route r) { return kRouteNames[(int)r]; }
+void set_route(Route r) { g_route = route_name(r); }
+void reset_route() { g_route = ""; }
 const char *last_route() { return g_route; }
 int route_names(const char **out, int capacity) {
-    const int n = (int)(sizeof(kRouteNames) / sizeof(kRouteNames[0]));
-    if (!out) return n;
-    if (capacity < n) return -1;
-    for (int i = 0; i < n; i++) out[i] = kRouteNames[i];
-    return n;
+    if (!out) return kNumRoutes;
+    if (capacity < kNumRoutes) return -1;
+    for (int i = 0; i < kNumRoutes; i++) out[i] = kRouteNames[i];
+    return kNumRoutes;
 }
 
-static long long resident_lanes(const RenderLaunch &rl) { return (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * gd::kBlock; }
+Route choose_route(const RouteInputs &in) {
+    const bool sample = in.rng_scheme == GDPT_RNG_SAMPLE;
+    if (!sample && in.rng_scheme != GDPT_RNG_TILE) throw std::runtime_error("choose_route: unknown rng_scheme");
+    const bool no_spheres = !in.has_spheres && !in.no_plain_kernel;   // kernels built without sphere code
+    if (in.path) {
+        // LDS-resident scenes are walked in their BVH4 form
+        const bool lds = in.fits_lds_wide && !in.no_lds_scene;
+        if (!sample) return Route::PATH_TILE;
+        if (in.force_eager) return Route::PATH_EAGER;
+        if (in.lambert_only) {
+            if (lds && no_spheres && in.const_textures && !in.has_envmap) return Route::PATH_PERSISTENT_LDS_LAMBERT_PLAIN;
+            return lds ? (in.has_envmap ? Route::PATH_PERSISTENT_LDS_LAMBERT_ENV : Route::PATH_PERSISTENT_LDS_LAMBERT)
+                       : (in.has_envmap ? Route::PATH_PERSISTENT_HBM_LAMBERT_ENV : Route::PATH_PERSISTENT_HBM_LAMBERT);
+        }
+        return lds ? (in.has_envmap ? Route::PATH_PERSISTENT_LDS_GENERAL_ENV : Route::PATH_PERSISTENT_LDS_GENERAL)
+                   : (in.has_envmap ? Route::PATH_PERSISTENT_HBM_GENERAL_ENV : Route::PATH_PERSISTENT_HBM_GENERAL);
+    }
+    const bool fits = in.fits_lds && !in.no_lds_scene;            // the scene is copied to LDS ...
+    const bool wide = fits && in.lds_wide && in.fits_lds_wide;     // ... in its BVH4 form
+    if (in.shift_mode == GDPT_SHIFT_RECONNECT) {
+        // straight per-sample loop; the general kernel walks the HBM tree
+        if (!sample) throw std::runtime_error("choose_route: GDPT_SHIFT_RECONNECT needs GDPT_RNG_SAMPLE");
+        return !in.lambert_only ? Route::RECONNECT_GENERAL : wide ? Route::RECONNECT_LDS_LAMBERT : Route::RECONNECT_HBM_LAMBERT;
+    }
+    const bool one_sided = in.one_sided && !in.has_rough;          // the phase machine with lazy offsets is exact
+    // two-sided lobes (DisneyGlass, DisneyBSDF) without rough ones: lane machine with offsets replayed from a bounce log
+    // (a depth bound that lets a path outrun the replay's bounce log takes the straight-loop evaluator: render_twosided.h)
+    const bool two_sided = !in.one_sided && !in.has_rough && !in.force_eager && sample && !in.no_twosided_machine &&
+                           twosided_log_covers(in.max_depth, in.rr_depth);
+    const bool phases = (one_sided || two_sided) && !in.force_eager;
+    if (!sample) return !phases ? Route::TILE_EAGER : in.lambert_only ? Route::TILE_PHASES_LAMBERT : Route::TILE_PHASES_GENERAL;
+    if (!phases) return Route::EAGER;
+    // scenes walked from HBM with one-sided lobes: the wavefront pipeline (knob; the product default is the lane machine)
+    if (in.wavefront && one_sided && !fits && in.shift_mode == GDPT_SHIFT_REFERENCE && !two_sided)
+        return in.lambert_only ? Route::WAVEFRONT_LAMBERT : Route::WAVEFRONT_GENERAL;
+    const unsigned mask = in.full_material_switch ? 0x1FFu : in.material_mask;
+    if (two_sided) return wide ? Route::TWOSIDED_LDS : (mask & ~gd::kSetGlass) == 0 ? Route::TWOSIDED_HBM_GLASS : Route::TWOSIDED_HBM;
+    if (in.lambert_only && in.stamps && (!fits || wide))
+        return !fits ? Route::LAMBERT_STAMPED_HBM : (no_spheres && in.const_textures) ? Route::LAMBERT_STAMPED_LDS_PLAIN : Route::LAMBERT_STAMPED_LDS;
+    if (in.lambert_only && no_spheres && (!fits || wide))
+        return fits ? (in.const_textures ? Route::LAMBERT_PLAIN_LDS_CONST : Route::LAMBERT_PLAIN_LDS_TEX)
+                    : (in.const_textures ? Route::LAMBERT_PLAIN_HBM_CONST : Route::LAMBERT_PLAIN_HBM_TEX);
+    if (in.lambert_only) return !fits ? Route::LAMBERT_HBM : wide ? Route::LAMBERT_LDS_WIDE : Route::LAMBERT_LDS_BVH2;
+    // HBM triangle scenes of Lambertian + one Disney lobe: the kernel built for that set (render_phases_general_sets.h)
+    auto only = [&](int lobe) { return (mask & ~(1u << GDPT_MAT_LAMBERTIAN | 1u << lobe)) == 0; };
+    if (!fits && no_spheres) {
+        if (only(GDPT_MAT_DISNEY_DIFFUSE)) return Route::GENERAL_SET_A_DISNEY_DIFFUSE;
+        if (only(GDPT_MAT_DISNEY_METAL)) return Route::GENERAL_SET_A_DISNEY_METAL;
+        if (only(GDPT_MAT_DISNEY_CLEARCOAT)) return Route::GENERAL_SET_B_DISNEY_CLEARCOAT;
+        if (only(GDPT_MAT_DISNEY_SHEEN)) return Route::GENERAL_SET_B_DISNEY_SHEEN;
+    }
+    return !fits ? Route::GENERAL_HBM : wide ? Route::GENERAL_LDS_WIDE : Route::GENERAL_LDS_BVH2;
+}
 
-// item layout of the persistent kernels (render_device.h: item_to_pixel)
-// The plan is made for a band of rl.plan_rows rows (default: the whole film), whatever band is rendered: a pixel's samples
-// are cut (and its partial sums merged) the same way by every render that names the same plan_rows, so a sharded render
-// equals the unsharded one with that plan bit for bit. (Round 2 always planned for the whole film: a 64-row band of the
-// 512x512x256 film, 1/8 of the work, then held 32 k items of 128 samples and took 9.3 ms instead of 3.8 —
-// profiles/r03_band_costs.txt.)
-static void set_chunks(gd::KernelArgs &a, const RenderLaunch &rl, int W, int rows) {
-    const ChunkPlan plan = make_chunk_plan(rl.spp, rl.force_log2k, (long long)W * rl.plan_rows, resident_lanes(rl), rl.plan_take_pct);
-    a.num_chunks = plan.n;
-    for (int c = 0; c <= plan.n; c++) a.chunk_begin[c] = plan.begin[c];
+// Straight per-sample loops: K = 2^log2k lanes per pixel, blocks of kBlock / K pixels in tiles of tile_w x tile_h.
+static dim3 static_mapping(gd::KernelArgs &a, const RenderLaunch &rl, int W, int rows) {
+    const long long pixels = (long long)W * rows;
+    int log2k = 0;
+    while ((1 << (log2k + 1)) <= rl.spp && log2k < 6 && (pixels << log2k) < (1LL << 19)) log2k++;
+    if (rl.force_log2k >= 0) { log2k = rl.force_log2k; while (log2k > 0 && (1 << log2k) > rl.spp) log2k--; }
+    a.log2k = log2k;
+    const int ppb = gd::kBlock >> log2k;                 // pixels per block
+    a.tile_w = ppb >= 16 ? 16 : ppb;
+    a.tile_h = ppb / a.tile_w;
+    a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
+    return dim3((unsigned)(a.tiles_x * ((rows + a.tile_h - 1) / a.tile_h)));
+}
+
+// Persistent lanes pulling (pixel, chunk) items of rl.plan: the item layout (render_device.h: item_to_pixel), the queue reset
+// and the grid.
+static dim3 start_queue(gd::KernelArgs &a, const RenderLaunch &rl, int W, hipStream_t stream) {
+    a.num_chunks = rl.plan.n;
+    for (int c = 0; c <= rl.plan.n; c++) a.chunk_begin[c] = rl.plan.begin[c];
     a.tiles_x = (W + 15) / 16;
-    a.num_slots = (long long)a.tiles_x * ((rows + 15) / 16) * 256;
-    a.num_items = a.num_slots * plan.n;
+    a.num_slots = band_slots(W, rl.row_end - rl.row_begin);
+    a.num_items = a.num_slots * rl.plan.n;
+    if (a.num_items >= (1LL << 32)) throw std::runtime_error("launch_render: image band too large for the 32-bit work queue");
+    a.partials = rl.partials; a.queue_head = rl.queue_head;
+    if (!a.partials || !a.queue_head) throw std::runtime_error("launch_render: work-queue buffers missing");
+    if (hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), stream) != hipSuccess) throw std::runtime_error("launch_render: queue reset failed");
+    return dim3(persistent_blocks(rl, a.num_items));
 }
 
 int wf_words() { return gd::WF_WORDS; }
@@ -83,8 +149,7 @@ size_t wf_aux_bytes(int slots) { return wf_aux_layout(slots).total; }
 
 // Generations are enqueued in chunks; the host reads the number of slots that still need a step one chunk behind the
 // launches (the speculative chunk behind a finished render finds nothing to do: its kernels return at once).
-static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const RenderLaunch &rl, hipStream_t stream) {
-    if (!rl.wf_state || !rl.wf_live || !rl.wf_counters || !rl.wf_host || !rl.wf_aux || rl.wf_slots <= 0) throw std::runtime_error("launch_render: wavefront buffers missing");
+static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const RenderLaunch &rl, bool lambert, hipStream_t stream) {
     static_assert(GDPT_BVH_MAX_DEPTH > gd::kWfLdsLevels, "overflow stack levels");
     const WfAux lay = wf_aux_layout(rl.wf_slots);
     char *aux = (char *)rl.wf_aux;
@@ -104,7 +169,6 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
     t.ovf = (int *)(aux + lay.ovf); t.ovf_stride = (unsigned)rl.wf_slots; t.counters = rl.counters;
     t.num_tris = sv.num_tris; t.num_nodes4 = sv.num_nodes4; t.num_spheres = sv.num_spheres; t.search_frac = a.thresh_c; t.count_stats = a.count;
     auto ckh = [](hipError_t e, const char *what) { if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e)); };
-    set_route(rl.lambert_only ? "wavefront/lambert" : "wavefront/general");
     ckh(hipMemsetAsync(rl.wf_counters, 0, sizeof(unsigned) * 3 * gd::kWfMaxGen, stream), "hipMemsetAsync(wavefront counters)");
     ckh(hipMemsetAsync(w.hist, 0, sizeof(unsigned) * gd::kWfBins, stream), "hipMemsetAsync(wavefront histogram)");
     launch_wf_init(w, stream);
@@ -118,7 +182,7 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
         for (int k = 0; k < chunk; k++, gen++) {
             if (gen >= gd::kWfMaxGen) throw std::runtime_error("launch_render: wavefront generation limit reached");
             w.gen = gen;
-            if (rl.lambert_only) launch_wf_step_lambert(sv, a, w, stream); else launch_wf_step_general(sv, a, w, stream);
+            if (lambert) launch_wf_step_lambert(sv, a, w, stream); else launch_wf_step_general(sv, a, w, stream);
             launch_wf_sort(w, stream);
             t.count = rl.wf_counters + gen;
             launch_wf_trace(t, sv.num_spheres > 0, (active_bound + gd::kWfTraceBlock - 1) / gd::kWfTraceBlock, stream);
@@ -138,6 +202,7 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
 }
 
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream) {
+    const Route r = rl.route;
     gd::KernelArgs a{};
     a.spp = rl.spp; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
     a.img = rl.img; a.cx0 = rl.cx0; a.cy0 = rl.cy0; a.cx1 = rl.cx1; a.cy1 = rl.cy1; a.counters = rl.counters;
@@ -148,139 +213,70 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
     a.count = rl.count_traversal ? 1 : 0;
     const int W = sv.cam.width, rows = rl.row_end - rl.row_begin;
     if (W <= 0 || rows <= 0 || rl.spp <= 0) throw std::runtime_error("launch_render: empty image band or spp <= 0");
-    const bool phases = (rl.one_sided_materials || rl.two_sided_machine) && !rl.force_eager;
-    if (rl.shift_mode == GDPT_SHIFT_RECONNECT) {
-        // reconnection shift (render_reconnect.hip): straight per-sample loop, K = 2^log2k lanes per pixel
-        if (rl.rng_scheme != GDPT_RNG_SAMPLE) throw std::runtime_error("launch_render: GDPT_SHIFT_RECONNECT needs GDPT_RNG_SAMPLE");
-        long long pixels = (long long)W * rows;
-        int log2k = 0;
-        while ((1 << (log2k + 1)) <= rl.spp && log2k < 6 && (pixels << log2k) < (1LL << 19)) log2k++;
-        if (rl.force_log2k >= 0) { log2k = rl.force_log2k; while (log2k > 0 && (1 << log2k) > rl.spp) log2k--; }
-        a.log2k = log2k;
-        int ppb = gd::kBlock >> log2k;
-        a.tile_w = ppb >= 16 ? 16 : ppb;
-        a.tile_h = ppb / a.tile_w;
-        a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
-        int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
-        set_route(!rl.lambert_only ? "reconnect/general" : (rl.scene_fits_lds && rl.lds_wide) ? "reconnect/lds_lambert" : "reconnect/hbm_lambert");
-        launch_reconnect(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), rl.scene_fits_lds && rl.lds_wide, rl.lambert_only, stream);
-    } else if (rl.rng_scheme == GDPT_RNG_TILE) {
-        int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;
-        dim3 grid((unsigned)((ntx * nty + 63) / 64));
-        if (!phases) { set_route("tile_eager"); launch_tile_eager(sv, a, grid, ntx, nty, stream); }
-        else if (rl.lambert_only) { set_route("tile_phases_lambert"); launch_tile_phases_lambert(sv, a, grid, ntx, nty, stream); }
-        else { set_route("tile_phases_general"); launch_tile_phases_general(sv, a, grid, ntx, nty, stream); }
-    } else if (rl.rng_scheme == GDPT_RNG_SAMPLE) {
-        if (!phases) {
-            // eager evaluator: static mapping, K = 2^log2k lanes per pixel
-            long long pixels = (long long)W * rows;
-            int log2k = 0;
-            while ((1 << (log2k + 1)) <= rl.spp && log2k < 6 && (pixels << log2k) < (1LL << 19)) log2k++;
-            if (rl.force_log2k >= 0) { log2k = rl.force_log2k; while (log2k > 0 && (1 << log2k) > rl.spp) log2k--; }
-            a.log2k = log2k;
-            int ppb = gd::kBlock >> log2k;                 // pixels per block
-            a.tile_w = ppb >= 16 ? 16 : ppb;
-            a.tile_h = ppb / a.tile_w;
-            a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
-            int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
-            set_route("eager");
-            launch_eager(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), stream);
-        } else {
-            // persistent lanes pulling (pixel, chunk) items: >= 4 samples per item, at most 8 items per pixel
-            set_chunks(a, rl, W, rows);
-            if (a.num_items >= (1LL << 32)) throw std::runtime_error("launch_render: image band too large for the 32-bit work queue");
-            // scenes walked from HBM: stack slots = the tree's own bound (host-verified at upload)
-            a.stack_levels = rl.wide_stack_need > 0 ? rl.wide_stack_need : GDPT_BVH_MAX_DEPTH;
-            a.replay_per_step = rl.replay_per_step >= 1 ? rl.replay_per_step : 4;       // render_twosided.h: kReplayPerStep
-            if (a.stack_levels > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("launch_render: traversal stack bound exceeds the builder's maximum");
-            a.partials = rl.partials; a.queue_head = rl.queue_head;
-            if (!a.partials || !a.queue_head) throw std::runtime_error("launch_render: work-queue buffers missing");
-            hipError_t me = hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), stream);
-            if (me != hipSuccess) throw std::runtime_error("launch_render: queue reset failed");
-            const unsigned blocks = persistent_blocks(rl, a.num_items);   // 2 resident blocks per CU (LDS-bound)
-            dim3 grid(blocks);
-            if (rl.wavefront && !rl.two_sided_machine && !rl.scene_fits_lds) {
-                run_wavefront(sv, a, rl, stream);
-            } else if (rl.two_sided_machine) {
-                if (!rl.bounce_log || rl.bounce_log_bytes < twosided_log_bytes(blocks)) throw std::runtime_error("launch_render: bounce log missing");
-                launch_phases_twosided(sv, a, grid, rl.scene_fits_lds && rl.lds_wide, rl.material_mask, rl.bounce_log, stream);
-            } else if (rl.lambert_only && rl.stamped && (!rl.scene_fits_lds || rl.lds_wide)) {
-                const bool plain = rl.no_spheres && rl.const_textures;
-                set_route(!rl.scene_fits_lds ? "lambert_stamped/hbm" : plain ? "lambert_stamped/lds_plain" : "lambert_stamped/lds");
-                launch_phases_lambert_stamped(sv, a, grid, rl.scene_fits_lds, plain, stream);
-            } else if (rl.lambert_only && rl.no_spheres && (!rl.scene_fits_lds || rl.lds_wide)) {
-                set_route(rl.scene_fits_lds ? (rl.const_textures ? "lambert_plain/lds_const" : "lambert_plain/lds_tex")
-                                            : (rl.const_textures ? "lambert_plain/hbm_const" : "lambert_plain/hbm_tex"));
-                launch_phases_lambert_plain(sv, a, grid, rl.scene_fits_lds, rl.const_textures, stream);
-            } else if (rl.lambert_only) {
-                set_route(!rl.scene_fits_lds ? "lambert/hbm" : rl.lds_wide ? "lambert/lds_wide" : "lambert/lds_bvh2");
-                launch_phases_lambert(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
-            } else if (!rl.scene_fits_lds && rl.no_spheres && (launch_phases_general_set_a(sv, a, grid, rl.material_mask, stream) || launch_phases_general_set_b(sv, a, grid, rl.material_mask, stream))) {
-                // kernel built for the scene's material set (the set launchers record the route)
-            } else {
-                set_route(!rl.scene_fits_lds ? "general/hbm" : rl.lds_wide ? "general/lds_wide" : "general/lds_bvh2");
-                launch_phases_general(sv, a, grid, rl.scene_fits_lds, rl.lds_wide, stream);
-            }
-            launch_reduce_partials(sv, a, stream);
-        }
-    } else {
-        throw std::runtime_error("launch_render: unknown rng_scheme");
+    const int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;    // tile streams: one lane per 16x16 tile
+    dim3 grid((unsigned)((ntx * nty + 63) / 64));
+    if (is_persistent(r)) {
+        // scenes walked from HBM: stack slots = the tree's own bound (host-verified at upload)
+        a.stack_levels = rl.wide_stack_need > 0 ? rl.wide_stack_need : GDPT_BVH_MAX_DEPTH;
+        a.replay_per_step = rl.replay_per_step >= 1 ? rl.replay_per_step : 4;       // render_twosided.h: kReplayPerStep
+        if (a.stack_levels > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("launch_render: traversal stack bound exceeds the builder's maximum");
+        grid = start_queue(a, rl, W, stream);
     }
+    if (needs_bounce_log(r) && (!rl.bounce_log || rl.bounce_log_bytes < twosided_log_bytes(grid.x))) throw std::runtime_error("launch_render: bounce log missing");
+    if (is_wavefront(r) && (!rl.wf_state || !rl.wf_live || !rl.wf_counters || !rl.wf_host || !rl.wf_aux || rl.wf_slots <= 0))
+        throw std::runtime_error("launch_render: wavefront buffers missing");
+    set_route(r);
+    switch (r) {
+    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, stream); break;
+    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, stream); break;
+    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, stream); break;
+    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, stream); break;
+    case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, stream); break;
+    case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, stream); break;
+    case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, stream); break;
+    case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, stream); break;
+    case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, stream); break;
+    case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, stream); break;
+    case Route::GENERAL_SET_A_DISNEY_DIFFUSE: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_DIFFUSE, stream); break;
+    case Route::GENERAL_SET_A_DISNEY_METAL: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_METAL, stream); break;
+    case Route::GENERAL_SET_B_DISNEY_CLEARCOAT: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_CLEARCOAT, stream); break;
+    case Route::GENERAL_SET_B_DISNEY_SHEEN: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_SHEEN, stream); break;
+    case Route::GENERAL_LDS_WIDE: launch_phases_general(sv, a, grid, true, true, stream); break;
+    case Route::GENERAL_LDS_BVH2: launch_phases_general(sv, a, grid, true, false, stream); break;
+    case Route::GENERAL_HBM: launch_phases_general(sv, a, grid, false, false, stream); break;
+    case Route::TWOSIDED_LDS: launch_phases_twosided(sv, a, grid, true, rl.bounce_log, stream); break;
+    case Route::TWOSIDED_HBM: launch_phases_twosided(sv, a, grid, false, rl.bounce_log, stream); break;
+    case Route::TWOSIDED_HBM_GLASS: launch_phases_twosided_glass(sv, a, grid, rl.bounce_log, stream); break;
+    case Route::WAVEFRONT_LAMBERT: run_wavefront(sv, a, rl, true, stream); break;
+    case Route::WAVEFRONT_GENERAL: run_wavefront(sv, a, rl, false, stream); break;
+    case Route::EAGER: launch_eager(sv, a, static_mapping(a, rl, W, rows), stream); break;
+    case Route::TILE_EAGER: launch_tile_eager(sv, a, grid, ntx, nty, stream); break;
+    case Route::TILE_PHASES_LAMBERT: launch_tile_phases_lambert(sv, a, grid, ntx, nty, stream); break;
+    case Route::TILE_PHASES_GENERAL: launch_tile_phases_general(sv, a, grid, ntx, nty, stream); break;
+    case Route::RECONNECT_LDS_LAMBERT: launch_reconnect(sv, a, static_mapping(a, rl, W, rows), true, true, stream); break;
+    case Route::RECONNECT_HBM_LAMBERT: launch_reconnect(sv, a, static_mapping(a, rl, W, rows), false, true, stream); break;
+    case Route::RECONNECT_GENERAL: launch_reconnect(sv, a, static_mapping(a, rl, W, rows), false, false, stream); break;
+    case Route::PATH_TILE: launch_tile_path(sv, a, grid, ntx, nty, stream); break;
+    case Route::PATH_EAGER: launch_path(sv, a, static_mapping(a, rl, W, rows), stream); break;
+    case Route::PATH_PERSISTENT_LDS_LAMBERT_PLAIN: launch_path_persistent(sv, a, grid, true, true, false, true, stream); break;
+    case Route::PATH_PERSISTENT_LDS_LAMBERT: launch_path_persistent(sv, a, grid, true, true, false, false, stream); break;
+    case Route::PATH_PERSISTENT_LDS_LAMBERT_ENV: launch_path_persistent(sv, a, grid, true, true, true, false, stream); break;
+    case Route::PATH_PERSISTENT_HBM_LAMBERT: launch_path_persistent(sv, a, grid, true, false, false, false, stream); break;
+    case Route::PATH_PERSISTENT_HBM_LAMBERT_ENV: launch_path_persistent(sv, a, grid, true, false, true, false, stream); break;
+    case Route::PATH_PERSISTENT_LDS_GENERAL: launch_path_persistent(sv, a, grid, false, true, false, false, stream); break;
+    case Route::PATH_PERSISTENT_LDS_GENERAL_ENV: launch_path_persistent(sv, a, grid, false, true, true, false, stream); break;
+    case Route::PATH_PERSISTENT_HBM_GENERAL: launch_path_persistent(sv, a, grid, false, false, false, false, stream); break;
+    case Route::PATH_PERSISTENT_HBM_GENERAL_ENV: launch_path_persistent(sv, a, grid, false, false, true, false, stream); break;
+    case Route::COUNT: throw std::runtime_error("launch_render: no route");
+    }
+    if (is_persistent(r) && !is_path(r)) launch_reduce_partials(sv, a, stream);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) throw std::runtime_error(std::string("render kernel launch failed: ") + hipGetErrorString(e));
 }
 
-// Integrator::Path (render_path.hip): img only.
-void launch_path_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream) {
-    gd::KernelArgs a{};
-    a.spp = rl.spp; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
-    a.img = rl.img; a.counters = rl.counters;
-    a.count = rl.count_traversal ? 1 : 0;
-    const int W = sv.cam.width, rows = rl.row_end - rl.row_begin;
-    if (W <= 0 || rows <= 0 || rl.spp <= 0) throw std::runtime_error("launch_path_render: empty image band or spp <= 0");
-    if (rl.rng_scheme == GDPT_RNG_TILE) {
-        set_route("path/tile");
-        int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;
-        launch_tile_path(sv, a, dim3((unsigned)((ntx * nty + 63) / 64)), ntx, nty, stream);
-    } else if (rl.rng_scheme == GDPT_RNG_SAMPLE && !rl.force_eager) {
-        // persistent lanes pulling (pixel, chunk) items, as the GradPath kernel does
-        a.thresh_a = rl.thresh_a >= 0 ? (rl.thresh_a > 255 ? 255 : rl.thresh_a) : 64;
-        a.thresh_c = rl.thresh_c >= 0 ? (rl.thresh_c > 255 ? 255 : rl.thresh_c) : 112;
-        set_chunks(a, rl, W, rows);
-        if (a.num_items >= (1LL << 32)) throw std::runtime_error("launch_path_render: image band too large for the 32-bit work queue");
-        a.partials = rl.partials; a.queue_head = rl.queue_head;
-        if (!a.partials || !a.queue_head) throw std::runtime_error("launch_path_render: work-queue buffers missing");
-        hipError_t me = hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), stream);
-        if (me != hipSuccess) throw std::runtime_error("launch_path_render: queue reset failed");
-        long long waves_needed = (a.num_items + 63) / 64;
-        long long blocks = (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2);
-        if (blocks > (waves_needed + 3) / 4) blocks = (waves_needed + 3) / 4;
-        if (blocks < 1) blocks = 1;
-        launch_path_persistent(sv, a, dim3((unsigned)blocks), rl.scene_fits_lds, rl.lambert_only, rl.no_spheres && rl.const_textures, stream);
-    } else if (rl.rng_scheme == GDPT_RNG_SAMPLE) {
-        // straight per-sample loop (A/B checks): static mapping, K = 2^log2k lanes per pixel
-        long long pixels = (long long)W * rows;
-        int log2k = 0;
-        while ((1 << (log2k + 1)) <= rl.spp && log2k < 6 && (pixels << log2k) < (1LL << 19)) log2k++;
-        if (rl.force_log2k >= 0) { log2k = rl.force_log2k; while (log2k > 0 && (1 << log2k) > rl.spp) log2k--; }
-        a.log2k = log2k;
-        int ppb = gd::kBlock >> log2k;
-        a.tile_w = ppb >= 16 ? 16 : ppb;
-        a.tile_h = ppb / a.tile_w;
-        a.tiles_x = (W + a.tile_w - 1) / a.tile_w;
-        int tiles_y = (rows + a.tile_h - 1) / a.tile_h;
-        set_route("path/eager");
-        launch_path(sv, a, dim3((unsigned)(a.tiles_x * tiles_y)), stream);
-    } else {
-        throw std::runtime_error("launch_path_render: unknown rng_scheme");
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) throw std::runtime_error(std::string("path kernel launch failed: ") + hipGetErrorString(e));
-}
-
 unsigned persistent_blocks(const RenderLaunch &rl, long long num_items) {
     long long waves_needed = (num_items + 63) / 64;
-    long long blocks = (long long)rl.num_cus * (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2);
+    long long blocks = resident_lanes(rl) / gd::kBlock;                 // 2 resident blocks per CU by default (LDS-bound)
     if (blocks > (waves_needed + 3) / 4) blocks = (waves_needed + 3) / 4;
     return (unsigned)(blocks < 1 ? 1 : blocks);
 }
@@ -366,11 +362,6 @@ ChunkPlan make_chunk_plan(int spp, int force_log2k, long long pixels, long long 
     if (shrink < 0) n -= excess;                                // (every chunk a single sample: q * v - spp of them too many)
     p.n = n;
     return p;
-}
-
-size_t render_partials_doubles(int width, int rows, int plan_rows, int spp, int force_log2k, long long lanes, int take_pct) {
-    const long long tiles = (long long)((width + 15) / 16) * ((rows + 15) / 16);
-    return (size_t)16 * (size_t)(tiles * 256) * (size_t)make_chunk_plan(spp, force_log2k, (long long)width * plan_rows, lanes, take_pct).n;
 }
 
 bool scene_fits_lds(int num_nodes, int num_prims, int num_tris, int num_materials, int num_lights, int bvh_depth) {

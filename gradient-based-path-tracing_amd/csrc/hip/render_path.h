@@ -614,6 +614,6 @@ __global__ __launch_bounds__(256) void gdpt_path_reduce(KernelArgs a, int W) {
 
 namespace gdpt {
 // one translation unit per kernel family (parallel compilation)
-void launch_path_persistent_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, hipStream_t stream);
-void launch_path_persistent_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, hipStream_t stream);
+void launch_path_persistent_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool env, bool plain, hipStream_t stream);
+void launch_path_persistent_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool env, hipStream_t stream);
 } // namespace gdpt

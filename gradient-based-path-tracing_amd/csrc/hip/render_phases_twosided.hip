@@ -13,9 +13,7 @@ bool twosided_log_covers(int max_depth, int rr_depth) {
     if (max_depth >= 0 && max_depth - 1 <= gd::kLogCap) return true;
     return rr_depth <= gd::kLogCap - kRouletteMargin;
 }
-void launch_phases_twosided(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, unsigned material_mask, void *bounce_log, hipStream_t stream) {
-    if (!lds && (material_mask & ~gd::kSetGlass) == 0) { set_route("twosided/hbm_glass"); launch_phases_twosided_glass(sv, a, grid, bounce_log, stream); return; }
-    set_route(lds ? "twosided/lds" : "twosided/hbm");
+void launch_phases_twosided(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, void *bounce_log, hipStream_t stream) {
     if (lds) hipLaunchKernelGGL((gd::gdpt_render_twosided<true>), grid, dim3(gd::kBlock), 0, stream, sv, a, (gd::BounceLog *)bounce_log);
     else hipLaunchKernelGGL((gd::gdpt_render_twosided<false>), grid, dim3(gd::kBlock), gd::hbm_dynamic_lds(a), stream, sv, a, (gd::BounceLog *)bounce_log);
 }

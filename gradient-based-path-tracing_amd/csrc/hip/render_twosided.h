@@ -360,7 +360,5 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_twosided(DevSceneView s
 } // namespace gd
 
 namespace gdpt {
-void launch_phases_twosided(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, unsigned material_mask, void *bounce_log, hipStream_t stream);
-void launch_phases_twosided_glass(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, void *bounce_log, hipStream_t stream);
 size_t twosided_log_bytes(unsigned blocks);
 } // namespace gdpt
