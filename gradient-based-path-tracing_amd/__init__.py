@@ -66,6 +66,12 @@ def lib():
                                                  vp, C.POINTER(defs.GdptPoissonStats)]
         L.gdpt_gradient_path_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.c_double, dp, dp, dp, dp, dp, dp,
                                                 C.POINTER(defs.GdptRenderStats), C.POINTER(defs.GdptPoissonStats)]
+        L.gdpt_reconstruct.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, C.POINTER(defs.GdptReconParams), dp,
+                                       C.POINTER(defs.GdptReconStats)]
+        L.gdpt_reconstruct_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_double, C.POINTER(defs.GdptReconParams), vp, vp,
+                                              C.POINTER(defs.GdptReconStats)]
+        L.gdpt_gradient_path_render_recon.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.c_double, C.POINTER(defs.GdptReconParams),
+                                                      dp, dp, dp, dp, dp, dp, C.POINTER(defs.GdptRenderStats), C.POINTER(defs.GdptReconStats)]
         L.gdpt_imwrite.argtypes = [C.c_char_p, C.c_int, C.c_int, dp]
         L.gdpt_imread.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(dp)]
         L.gdpt_image_free.argtypes = [dp]
@@ -203,16 +209,23 @@ class Scene:
         _check(lib().gdpt_path_render_device(self.handle, C.byref(p), C.c_void_p(int(ptr)), C.c_void_p(int(stream) if stream else 0), None))
 
     def gradient_path_render(self, spp=0, rng_scheme=defs.RNG_SAMPLE, alpha=0.04, return_buffers=False,
-                             shift=defs.SHIFT_REFERENCE, plan_rows=0):
-        """Whole Integrator::GradPath: render + assembly + screened-Poisson solve (src/render.cpp:257-370)."""
+                             shift=defs.SHIFT_REFERENCE, plan_rows=0, reconstruct=None):
+        """Whole Integrator::GradPath: render + assembly + screened-Poisson solve (src/render.cpp:257-370).
+        `reconstruct`: None = that solve; recon_params(...) = gdpt_gradient_path_render_recon (the last element returned with
+        return_buffers is then a GdptReconStats)."""
         shape = (self.height, self.width, 3)
         out = np.zeros(shape, dtype=np.float64)
         bufs = {k: np.zeros(shape, dtype=np.float64) for k in ("img", "cx0", "cy0", "cx1", "cy1")}
-        rs, ps = defs.GdptRenderStats(), defs.GdptPoissonStats()
+        rs = defs.GdptRenderStats()
         p = _params(spp, rng_scheme, (0, 0), shift=shift, plan_rows=plan_rows)
-        _check(lib().gdpt_gradient_path_render(self.handle, C.byref(p), float(alpha), _dp(out),
-                                               _dp(bufs["img"]), _dp(bufs["cx0"]), _dp(bufs["cy0"]), _dp(bufs["cx1"]), _dp(bufs["cy1"]),
-                                               C.byref(rs), C.byref(ps)))
+        raw = [_dp(bufs[k]) for k in ("img", "cx0", "cy0", "cx1", "cy1")]
+        if reconstruct is None:
+            ps = defs.GdptPoissonStats()
+            _check(lib().gdpt_gradient_path_render(self.handle, C.byref(p), float(alpha), _dp(out), *raw, C.byref(rs), C.byref(ps)))
+        else:
+            ps = defs.GdptReconStats()
+            _check(lib().gdpt_gradient_path_render_recon(self.handle, C.byref(p), float(alpha), C.byref(reconstruct), _dp(out), *raw,
+                                                         C.byref(rs), C.byref(ps)))
         return (out, bufs, rs, ps) if return_buffers else out
 
     def tile_row_costs(self, spp=1):
@@ -244,6 +257,37 @@ def fourierSolve(width, height, imgData, imgGradX, imgGradY, dataCost=0.04, solv
     _check(lib().gdpt_poisson_solve_ex(int(width), int(height), _dp(a[0]), _dp(a[1]), _dp(a[2]), float(dataCost), _dp(out),
                                        int(solver), float(tol), int(max_iters), C.byref(st)))
     return (out, st) if return_stats else out
+
+
+def recon_params(norm=defs.RECON_L1, irls_iters=None, eps_init=0.0, eps_decay=0.0, eps_floor=0.0, cg_tol=0.0, cg_max_iters=0):
+    """GdptReconParams (include/gdpt.h). None / 0 select the library's defaults (20 rounds, eps 0.05 halved per round down to 1e-3,
+    CG to 1e-6 within 1000 iterations); irls_iters=0 means no reweighted round (the C struct spells that as a negative count)."""
+    p = defs.GdptReconParams()
+    p.norm = int(norm)
+    p.irls_iters = 0 if irls_iters is None else (int(irls_iters) if int(irls_iters) > 0 else -1)
+    p.cg_max_iters = int(cg_max_iters)
+    p.eps_init, p.eps_decay, p.eps_floor, p.cg_tol = float(eps_init), float(eps_decay), float(eps_floor), float(cg_tol)
+    return p
+
+
+def reconstruct(width, height, c, gx, gy, dataCost=0.04, norm=defs.RECON_L1, **params):
+    """Reconstruction of the final image from primal and gradients on the GPU (gdpt_reconstruct): RECON_L1 = IRLS over a weighted
+    screened-Poisson solve, robust to outliers in the gradients; RECON_L2 = fourierSolve with the default solver, bit for bit.
+    `params`: the keywords of recon_params. Inputs HxWx3 (or flat W*H*3) float64; returns (HxWx3 image, GdptReconStats)."""
+    a = [np.ascontiguousarray(x, dtype=np.float64).reshape(height, width, 3) for x in (c, gx, gy)]
+    out = np.empty((height, width, 3), dtype=np.float64)
+    p, st = recon_params(norm, **params), defs.GdptReconStats()
+    _check(lib().gdpt_reconstruct(int(width), int(height), _dp(a[0]), _dp(a[1]), _dp(a[2]), float(dataCost), C.byref(p), _dp(out), C.byref(st)))
+    return out, st
+
+
+def reconstruct_device(width, height, c_ptr, gx_ptr, gy_ptr, out_ptr, dataCost=0.04, norm=defs.RECON_L1, stream=None, **params):
+    """reconstruct() on device addresses (gdpt_reconstruct_device); returns GdptReconStats. The L1 path waits for `stream`."""
+    p, st = recon_params(norm, **params), defs.GdptReconStats()
+    _check(lib().gdpt_reconstruct_device(int(width), int(height), C.c_void_p(int(c_ptr)), C.c_void_p(int(gx_ptr)), C.c_void_p(int(gy_ptr)),
+                                         float(dataCost), C.byref(p), C.c_void_p(int(out_ptr)), C.c_void_p(int(stream) if stream else 0),
+                                         C.byref(st)))
+    return st
 
 
 def assemble_device(width, height, src_ptrs, dst_ptrs, stream=None, rows=(0, 0)):

@@ -82,6 +82,19 @@ class GdptPoissonStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("solver", C.c_int32), ("rel_residual", C.c_double), ("solve_ms", C.c_double)]
 
 
+RECON_L2, RECON_L1 = 0, 1
+
+
+class GdptReconParams(C.Structure):
+    _fields_ = [("norm", C.c_int32), ("irls_iters", C.c_int32), ("cg_max_iters", C.c_int32), ("reserved", C.c_int32),
+                ("eps_init", C.c_double), ("eps_decay", C.c_double), ("eps_floor", C.c_double), ("cg_tol", C.c_double)]
+
+
+class GdptReconStats(C.Structure):
+    _fields_ = [("norm", C.c_int32), ("irls_rounds", C.c_int32), ("cg_iters_total", C.c_int32), ("cg_iters_last", C.c_int32),
+                ("energy_first", C.c_double), ("energy_last", C.c_double), ("rel_residual_last", C.c_double), ("solve_ms", C.c_double)]
+
+
 GDPT_MULTI_MAX_DEVICES = 16
 EXCHANGE_RCCL, EXCHANGE_PEER_COPY = 0, 1
 

@@ -6,6 +6,7 @@
 #include "../host/bvh.h"
 #include "../host/tri_precompute.h"
 #include "poisson_kernels.h"
+#include "recon_l1.h"
 #include "render_kernels.h"
 #include "scene_internal.h"
 
@@ -563,6 +564,32 @@ void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, doub
     run_launch(sc, rl, b, stream, stats);
 }
 
+// GdptReconParams -> the L1 solver's parameters, defaults filled in (include/gdpt.h); refuses what the header says is refused
+gdpt::ReconL1Params resolve_recon(const GdptReconParams &in) {
+    if (in.norm != GDPT_RECON_L1) throw std::runtime_error("gdpt_reconstruct: unknown norm (GDPT_RECON_L2 | GDPT_RECON_L1)");
+    for (double v : {in.eps_init, in.eps_decay, in.eps_floor, in.cg_tol})
+        if (!std::isfinite(v) || v < 0) throw std::runtime_error("gdpt_reconstruct: eps_init, eps_decay, eps_floor and cg_tol must be finite and >= 0 (0 = default)");
+    if (in.eps_decay > 1.0) throw std::runtime_error("gdpt_reconstruct: eps_decay must lie in (0, 1]");
+    gdpt::ReconL1Params p;
+    p.irls_iters = in.irls_iters == 0 ? 20 : std::max(in.irls_iters, 0);
+    p.cg_max_iters = in.cg_max_iters > 0 ? in.cg_max_iters : 1000;
+    p.eps_init = in.eps_init > 0 ? in.eps_init : 0.05;
+    p.eps_decay = in.eps_decay > 0 ? in.eps_decay : 0.5;
+    p.eps_floor = in.eps_floor > 0 ? in.eps_floor : 1e-3;
+    p.cg_tol = in.cg_tol > 0 ? in.cg_tol : 1e-6;
+    return p;
+}
+void fill_recon_stats(GdptReconStats *s, const gdpt::ReconL1Result &r) {
+    if (!s) return;
+    s->norm = GDPT_RECON_L1; s->irls_rounds = r.irls_rounds; s->cg_iters_total = r.cg_iters_total; s->cg_iters_last = r.cg_iters_last;
+    s->energy_first = r.energy_first; s->energy_last = r.energy_last; s->rel_residual_last = r.rel_residual_last; s->solve_ms = r.solve_ms;
+}
+void fill_recon_stats_l2(GdptReconStats *s, double solve_ms) {
+    if (!s) return;
+    *s = GdptReconStats{};
+    s->norm = GDPT_RECON_L2; s->solve_ms = solve_ms;
+}
+
 } // namespace
 
 extern "C" {
@@ -706,6 +733,7 @@ int gdpt_poisson_forget_stream(void *stream) {
         int dev = 0;
         ck(hipGetDevice(&dev), "hipGetDevice");
         gdpt::poisson_forget_stream(dev, (hipStream_t)stream);
+        gdpt::recon_l1_forget_stream(dev, (hipStream_t)stream);
     });
 }
 
@@ -764,6 +792,79 @@ int gdpt_gradient_path_render(GdptScene *scene, const GdptRenderParams *params, 
         render_device_impl(scene, &p, scene->scene_spp, b[0], b[1], b[2], b[3], b[4], nullptr, rstats ? rstats : &local);
         gdpt::PoissonResult r = gdpt::assemble_solve_device(w, h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], dataCost, b[8], GDPT_SOLVER_DEFAULT, 0.0, 0, nullptr, pstats != nullptr);
         if (pstats) { pstats->iterations = r.iterations; pstats->solver = r.solver; pstats->rel_residual = r.rel_residual; pstats->solve_ms = r.solve_ms; }
+        ck(hipMemcpy(out_image, b[8], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        double *host[5] = {img, cx0, cy0, cx1, cy1};
+        for (int k = 0; k < 5; k++) if (host[k]) ck(hipMemcpy(host[k], b[k], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+    });
+}
+
+int gdpt_reconstruct_device(int width, int height, const double *d_c, const double *d_gx, const double *d_gy, double dataCost,
+                            const GdptReconParams *params, double *d_out, void *stream, GdptReconStats *stats) {
+    if (!params || params->norm == GDPT_RECON_L2) {
+        GdptPoissonStats ps{};
+        const int rc = gdpt_poisson_solve_device(width, height, d_c, d_gx, d_gy, dataCost, d_out, GDPT_SOLVER_DEFAULT, 0.0, 0, stream, stats ? &ps : nullptr);
+        if (rc == 0) fill_recon_stats_l2(stats, ps.solve_ms);
+        return rc;
+    }
+    return gdpt::guarded([&]() {
+        if (!d_c || !d_gx || !d_gy || !d_out) throw std::runtime_error("gdpt_reconstruct_device: null buffer");
+        const gdpt::ReconL1Params p = resolve_recon(*params);
+        fill_recon_stats(stats, gdpt::recon_l1_device(width, height, d_c, d_gx, d_gy, dataCost, p, d_out, (hipStream_t)stream));
+    });
+}
+
+int gdpt_reconstruct(int width, int height, const double *c, const double *gx, const double *gy, double dataCost,
+                     const GdptReconParams *params, double *out, GdptReconStats *stats) {
+    if (!params || params->norm == GDPT_RECON_L2) {
+        GdptPoissonStats ps{};
+        const int rc = gdpt_poisson_solve_ex(width, height, c, gx, gy, dataCost, out, GDPT_SOLVER_DEFAULT, 0.0, 0, stats ? &ps : nullptr);
+        if (rc == 0) fill_recon_stats_l2(stats, ps.solve_ms);
+        return rc;
+    }
+    return gdpt::guarded([&]() {
+        if (!c || !gx || !gy || !out) throw std::runtime_error("gdpt_reconstruct: null buffer");
+        if (width < 2 || height < 2) throw std::runtime_error("gdpt_reconstruct: width and height must be >= 2");
+        const gdpt::ReconL1Params p = resolve_recon(*params);
+        int ndev = 0;
+        ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
+        if (ndev <= 0) throw std::runtime_error("gdpt_reconstruct: no HIP device visible (this library has no CPU fallback)");
+        const size_t bytes = (size_t)width * height * 3 * sizeof(double);
+        double *d[4] = {nullptr, nullptr, nullptr, nullptr};
+        auto cleanup = [&]() { for (auto q : d) if (q) hipFree(q); };
+        try {
+            for (auto &q : d) ck(hipMalloc((void **)&q, bytes), "hipMalloc(reconstruct io)");
+            const double *host[3] = {c, gx, gy};
+            for (int k = 0; k < 3; k++) ck(hipMemcpy(d[k], host[k], bytes, hipMemcpyHostToDevice), "hipMemcpy");
+            fill_recon_stats(stats, gdpt::recon_l1_device(width, height, d[0], d[1], d[2], dataCost, p, d[3], nullptr));
+            ck(hipMemcpy(out, d[3], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+        } catch (...) { cleanup(); throw; }
+        cleanup();
+    });
+}
+
+int gdpt_gradient_path_render_recon(GdptScene *scene, const GdptRenderParams *params, double dataCost, const GdptReconParams *recon,
+                                    double *out_image, double *img, double *cx0, double *cy0, double *cx1, double *cy1,
+                                    GdptRenderStats *rstats, GdptReconStats *cstats) {
+    if (!recon || recon->norm == GDPT_RECON_L2) {
+        GdptPoissonStats ps{};
+        const int rc = gdpt_gradient_path_render(scene, params, dataCost, out_image, img, cx0, cy0, cx1, cy1, rstats, cstats ? &ps : nullptr);
+        if (rc == 0) fill_recon_stats_l2(cstats, ps.solve_ms);
+        return rc;
+    }
+    return gdpt::guarded([&]() {
+        if (!scene || !out_image) throw std::runtime_error("gdpt_gradient_path_render_recon: null argument");
+        const gdpt::ReconL1Params rp = resolve_recon(*recon);
+        ck(hipSetDevice(scene->device), "hipSetDevice");
+        const int w = scene->view.cam.width, h = scene->view.cam.height;
+        size_t elems = (size_t)w * h * 3;
+        scene->ensure_buffers(elems);
+        double **b = scene->d_buf;
+        GdptRenderParams p = params ? *params : GdptRenderParams{};
+        p.row_begin = 0; p.row_end = 0;   // the reconstruction is global: whole image only
+        GdptRenderStats local{};
+        render_device_impl(scene, &p, scene->scene_spp, b[0], b[1], b[2], b[3], b[4], nullptr, rstats ? rstats : &local);
+        gdpt::launch_assemble(w, h, 0, 0, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], nullptr);
+        fill_recon_stats(cstats, gdpt::recon_l1_device(w, h, b[5], b[6], b[7], dataCost, rp, b[8], nullptr));
         ck(hipMemcpy(out_image, b[8], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
         double *host[5] = {img, cx0, cy0, cx1, cy1};
         for (int k = 0; k < 5; k++) if (host[k]) ck(hipMemcpy(host[k], b[k], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");

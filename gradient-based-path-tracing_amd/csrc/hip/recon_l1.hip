@@ -1,0 +1,391 @@
+// recon_l1.hip — robust (L1) reconstruction of a gradient-domain render for gfx950: iteratively reweighted least squares
+// (IRLS) over a weighted screened-Poisson system solved by Jacobi-preconditioned conjugate gradients.
+//
+// Definition (include/gdpt.h, gdpt_reconstruct). Image f, primal u, gradients gx, gy: H x W x 3 fp64, interleaved RGB.
+// Residual rows, three channels each:
+//     data row of pixel (x,y):   r_d = sqrt(alpha) (f - u)
+//     x-edge row, x >= 1:        r_x = f(x,y) - f(x-1,y) - gx(x,y)
+//     y-edge row, y >= 1:        r_y = f(x,y) - f(x,y-1) - gy(x,y)
+// Edges exist inside the film only (natural boundary; gx(0,.) and gy(.,0) are not read) — NOT the mirror operator of
+// fourierSolve. One weight per row, shared by its channels (no colour shift): w = 1 / (eps_k + |r|_2). Round 0 has w = 1;
+// round k = 1..K takes w from f_{k-1} with eps_k = max(eps_init eps_decay^(k-1), eps_floor) and solves, per channel,
+//     (alpha diag(w_d) + Dx^T diag(w_x) Dx + Dy^T diag(w_y) Dy) f = alpha w_d u + Dx^T (w_x gx) + Dy^T (w_y gy)
+// warm-started from f_{k-1} (round 0: from u), until |r| <= cg_tol |b| or cg_max_iters. Energy E(f) = sum over rows of |r|_2.
+//
+// Kernels. A thread owns a PIXEL (its three channels), so every weight is loaded once for three unknowns.
+//   weights_kernel   one pass over f, u, gx, gy per round: the two edge-weight planes wx(x,y) (edge x-1|x; 0 at x = 0) and
+//                    wy(x,y), the diagonal alpha w_d + sum of the four edge weights (the Jacobi preconditioner AND the
+//                    centre tap: w_d itself is never needed again, so it is not stored), the initial residual b - A f
+//                    (formed from the residual rows, not as a difference of two large numbers) and the block partials of
+//                    <r,z>, <r,r>, <b,b> and the energy E(f) of the iterate the weights were taken from.
+//   pcg_step_a       p' = z + beta p with z = r / diag, staged for a 32 x 8 pixel tile and its one-pixel halo in LDS
+//                    (planar per channel: a half-wave reads 32 consecutive doubles, conflict-free); q = A p' from the LDS
+//                    tile; partial <p',q>.
+//   pcg_step_b       x += a p', r -= a q; partials <r,z>, <r,r>.
+// Two launches per iteration and no host round trip: scalars are reduced from per-block partials by every block in the
+// same fixed order, so the same inputs give the same bits. The host reads the convergence flag one chunk of iterations
+// behind the launches, as the CG of poisson_kernels.hip does; kernels of a converged solve return at once.
+// Grid: one block of 256 threads per tile, at most kMaxBlocks blocks striding over the tiles (so that the partial arrays
+// every block re-reduces stay short); 8 KB of LDS, 50 VGPRs and no scratch, i.e. occupancy is bound by neither.
+#include "recon_l1.h"
+#include "../capi_common.h"
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+
+namespace rl1 {
+
+constexpr int kBlock = 256, kTileW = 32, kTileH = 8, kPitch = kTileW + 2, kMaxBlocks = 1024;
+static_assert(kTileW * kTileH == kBlock, "one thread per tile pixel");
+constexpr int kHalo = 2 * kTileW + 2 * kTileH;       // the 5-tap needs no corners
+
+struct State {
+    double rz[2];         // <r,z> ping-pong by iteration parity
+    double bb;            // <b,b>
+    double tol;           // relative residual to stop at
+    double rel;           // |r| / |b| of the iterate (pcg_residual_kernel)
+    double energy;        // E(f) of the iterate the last weights pass read
+    int iters;
+    int converged;
+};
+
+struct Geo { int w, h, tiles_x, tiles; };
+
+__device__ __forceinline__ double block_sum(double v, double *red) {
+    // fixed order: xor tree inside each wave, then the wave totals in index order
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / 64; k++) s += red[k];
+    return s;
+}
+__device__ __forceinline__ double reduce_partials(const double *part, int n, double *red) {
+    double v = 0;
+    for (int i = threadIdx.x; i < n; i += kBlock) v += part[i];
+    return block_sum(v, red);
+}
+__device__ __forceinline__ double norm3(const double *v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
+
+// partials layout: slot s of gridDim.x doubles: [0] <r,z>, [1] <r,r>, [2] <b,b>, [3] energy, [4] <p,q>
+// unit != 0: all weights 1 (round 0). x_init (nullable): receives a copy of f (round 0: the iterate starts at u).
+// WRITE = false: only the energy partials (the energy of the last iterate).
+template <bool WRITE>
+__global__ __launch_bounds__(kBlock) void weights_kernel(Geo g, double alpha, double eps, int unit, const double *f, const double *u,
+                                                         const double *gx, const double *gy, double *x_init, double *wx, double *wy,
+                                                         double *diag, double *r, double *partials) {
+    __shared__ double red[kBlock / 64];
+    const int row = 3 * g.w;
+    double s_rz = 0, s_rr = 0, s_bb = 0, s_e = 0;
+    for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        const int ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
+        const int x = tx * kTileW + (threadIdx.x & (kTileW - 1)), y = ty * kTileH + (threadIdx.x / kTileW);
+        if (x >= g.w || y >= g.h) continue;
+        const int pix = y * g.w + x, i = 3 * pix;
+        const bool has_l = x > 0, has_u = y > 0, has_r = x + 1 < g.w, has_d = y + 1 < g.h;
+        double fc[3], uc[3], d[3], el[3] = {0, 0, 0}, er[3] = {0, 0, 0}, eu[3] = {0, 0, 0}, ed[3] = {0, 0, 0};
+        double gl[3] = {0, 0, 0}, gr[3] = {0, 0, 0}, gu[3] = {0, 0, 0}, gd[3] = {0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            fc[c] = f[i + c]; uc[c] = u[i + c]; d[c] = fc[c] - uc[c];
+            if (has_l) { gl[c] = gx[i + c]; el[c] = (fc[c] - f[i - 3 + c]) - gl[c]; }
+            if (has_r) { gr[c] = gx[i + 3 + c]; er[c] = (f[i + 3 + c] - fc[c]) - gr[c]; }
+            if (has_u) { gu[c] = gy[i + c]; eu[c] = (fc[c] - f[i - row + c]) - gu[c]; }
+            if (has_d) { gd[c] = gy[i + row + c]; ed[c] = (f[i + row + c] - fc[c]) - gd[c]; }
+        }
+        const double n_d = sqrt(alpha) * norm3(d), n_l = norm3(el), n_u = norm3(eu);
+        s_e += n_d + (has_l ? n_l : 0.0) + (has_u ? n_u : 0.0);      // every row once: its data row and the two edges it owns
+        if (!WRITE) continue;
+        const double w_d = unit ? 1.0 : 1.0 / (eps + n_d);
+        const double w_l = has_l ? (unit ? 1.0 : 1.0 / (eps + n_l)) : 0.0;
+        const double w_u = has_u ? (unit ? 1.0 : 1.0 / (eps + n_u)) : 0.0;
+        const double w_r = has_r ? (unit ? 1.0 : 1.0 / (eps + norm3(er))) : 0.0;
+        const double w_dn = has_d ? (unit ? 1.0 : 1.0 / (eps + norm3(ed))) : 0.0;
+        const double dg = alpha * w_d + ((w_l + w_r) + (w_u + w_dn));
+        wx[pix] = w_l; wy[pix] = w_u; diag[pix] = dg;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double b = alpha * w_d * uc[c] + ((w_l * gl[c] - w_r * gr[c]) + (w_u * gu[c] - w_dn * gd[c]));
+            const double ri = -(alpha * w_d * d[c] + ((w_l * el[c] - w_r * er[c]) + (w_u * eu[c] - w_dn * ed[c])));     // b - A f
+            r[i + c] = ri;
+            if (x_init) x_init[i + c] = fc[c];
+            s_rr += ri * ri; s_rz += ri * ri / dg; s_bb += b * b;
+        }
+    }
+    const int nb = gridDim.x;
+    double v;
+    v = block_sum(s_e, red); if (threadIdx.x == 0) partials[3 * nb + blockIdx.x] = v;
+    if (!WRITE) return;
+    v = block_sum(s_rz, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
+    v = block_sum(s_rr, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
+    v = block_sum(s_bb, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
+}
+
+// one block, after a weights pass: the round's scalars. reset == 0: only the energy (after weights_kernel<false>).
+__global__ __launch_bounds__(kBlock) void round_init_kernel(int nb, const double *partials, State *st, double tol, int reset) {
+    __shared__ double red[kBlock / 64];
+    const double e = reduce_partials(partials + 3 * nb, nb, red);
+    double bb = 0;
+    if (reset) bb = reduce_partials(partials + 2 * nb, nb, red);
+    if (threadIdx.x == 0) {
+        st->energy = e;
+        if (reset) { st->bb = bb; st->rz[0] = 1.0; st->rz[1] = 1.0; st->tol = tol; st->rel = 0.0; st->iters = 0; st->converged = 0; }
+    }
+}
+
+// iteration `it` of a round (parity selects the p buffers; it == 0 reads no p_in): p_out = z + beta p_in, q = A p_out, partial <p_out,q>
+__global__ __launch_bounds__(kBlock) void pcg_step_a(Geo g, int it, const double *r, const double *p_in, double *p_out, double *q,
+                                                     const double *wx, const double *wy, const double *diag,
+                                                     const double *part_rz, const double *part_rr, double *part_pq, State *st) {
+    __shared__ double sp[3][kTileH + 2][kPitch];
+    __shared__ double red[kBlock / 64];
+    if (st->converged) return;
+    const int nb = gridDim.x;
+    const double rz_new = reduce_partials(part_rz, nb, red);
+    const double rr_new = reduce_partials(part_rr, nb, red);
+    const double bb = st->bb;
+    const double rel = bb > 0 ? sqrt(rr_new / bb) : 0.0;
+    if (rel <= st->tol) {                                  // uniform over the whole grid: same inputs in every block
+        if (blockIdx.x == 0 && threadIdx.x == 0) st->converged = 1;
+        return;
+    }
+    const double beta = it == 0 ? 0.0 : rz_new / st->rz[(it + 1) & 1];
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->rz[it & 1] = rz_new;
+    // p' of pixel (x,y), 0 outside the film
+    auto direction = [&](int x, int y, double *pv, double &dg) {
+        pv[0] = pv[1] = pv[2] = 0.0; dg = 0.0;
+        if (x < 0 || y < 0 || x >= g.w || y >= g.h) return;
+        const int pix = y * g.w + x, i = 3 * pix;
+        dg = diag[pix];
+        const double inv = 1.0 / dg;
+#pragma unroll
+        for (int c = 0; c < 3; c++) pv[c] = it == 0 ? r[i + c] * inv : r[i + c] * inv + beta * p_in[i + c];
+    };
+    const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
+    double s = 0;
+    for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        const int ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
+        const int x0 = tx * kTileW, y0 = ty * kTileH, x = x0 + lx, y = y0 + ly;
+        double pv[3], dg;
+        direction(x, y, pv, dg);
+        __syncthreads();                                   // the previous tile's taps have been read
+#pragma unroll
+        for (int c = 0; c < 3; c++) sp[c][ly + 1][lx + 1] = pv[c];
+        if (threadIdx.x < kHalo) {
+            const int k = threadIdx.x;
+            int hx, hy;                                    // tile-local, -1 .. kTileW / kTileH
+            if (k < kTileW) { hx = k; hy = -1; }
+            else if (k < 2 * kTileW) { hx = k - kTileW; hy = kTileH; }
+            else if (k < 2 * kTileW + kTileH) { hx = -1; hy = k - 2 * kTileW; }
+            else { hx = kTileW; hy = k - 2 * kTileW - kTileH; }
+            double hv[3], hd;
+            direction(x0 + hx, y0 + hy, hv, hd);
+#pragma unroll
+            for (int c = 0; c < 3; c++) sp[c][hy + 1][hx + 1] = hv[c];
+        }
+        __syncthreads();
+        if (x < g.w && y < g.h) {
+            const int pix = y * g.w + x, i = 3 * pix;
+            const double w_l = wx[pix], w_u = wy[pix];     // 0 on the film's first column / row
+            const double w_r = x + 1 < g.w ? wx[pix + 1] : 0.0, w_d = y + 1 < g.h ? wy[pix + g.w] : 0.0;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double qi = dg * pv[c] - ((w_l * sp[c][ly + 1][lx] + w_r * sp[c][ly + 1][lx + 2]) + (w_u * sp[c][ly][lx + 1] + w_d * sp[c][ly + 2][lx + 1]));
+                p_out[i + c] = pv[c]; q[i + c] = qi;
+                s += pv[c] * qi;
+            }
+        }
+    }
+    const double v = block_sum(s, red);
+    if (threadIdx.x == 0) part_pq[blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(kBlock) void pcg_step_b(int npix, int it, const double *p, const double *q, const double *diag, double *x, double *r,
+                                                     const double *part_pq, double *part_rz, double *part_rr, State *st) {
+    __shared__ double red[kBlock / 64];
+    if (st->converged) return;
+    const int nb = gridDim.x;
+    const double pq = reduce_partials(part_pq, nb, red);
+    const double a = st->rz[it & 1] / pq;
+    double s_rr = 0, s_rz = 0;
+    for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < npix; pix += gridDim.x * kBlock) {
+        const double dg = diag[pix];
+        const int i = 3 * pix;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            x[i + c] += a * p[i + c];
+            const double ri = r[i + c] - a * q[i + c];
+            r[i + c] = ri;
+            s_rr += ri * ri; s_rz += ri * ri / dg;
+        }
+    }
+    double v = block_sum(s_rz, red);
+    if (threadIdx.x == 0) part_rz[blockIdx.x] = v;
+    v = block_sum(s_rr, red);
+    if (threadIdx.x == 0) {
+        part_rr[blockIdx.x] = v;
+        if (blockIdx.x == 0) st->iters = it + 1;
+    }
+}
+
+// one block, at the end of a round: |r| / |b| of the iterate as it stands
+__global__ __launch_bounds__(kBlock) void pcg_residual_kernel(int nb, const double *part_rr, State *st) {
+    __shared__ double red[kBlock / 64];
+    const double rr = reduce_partials(part_rr, nb, red);
+    if (threadIdx.x == 0) st->rel = st->bb > 0 ? sqrt(rr / st->bb) : 0.0;
+}
+
+} // namespace rl1
+
+namespace gdpt {
+
+namespace {
+
+void ck(hipError_t e, const char *what) {
+    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+struct Workspace {
+    std::mutex mu;                    // held while a reconstruction runs on this (device, stream) pair
+    size_t npix = 0;
+    double *r = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;      // 3 npix each
+    double *wx = nullptr, *wy = nullptr, *diag = nullptr;                  // npix each
+    double *partials = nullptr;
+    rl1::State *state = nullptr, *h_state = nullptr;                       // device / pinned host
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};                        // timing pair + chunk marker
+    void release() {
+        for (double *p : {r, q, p0, p1, wx, wy, diag, partials}) if (p) hipFree(p);
+        if (state) hipFree(state);
+        if (h_state) hipHostFree(h_state);
+        for (auto &e : ev) if (e) hipEventDestroy(e);
+        r = q = p0 = p1 = wx = wy = diag = partials = nullptr; state = h_state = nullptr;
+        for (auto &e : ev) e = nullptr;
+        npix = 0;
+    }
+    void ensure(size_t n) {
+        if (n <= npix) return;
+        release();
+        npix = n;
+        for (double **p : {&r, &q, &p0, &p1}) ck(hipMalloc((void **)p, 3 * n * sizeof(double)), "hipMalloc(recon workspace)");
+        for (double **p : {&wx, &wy, &diag}) ck(hipMalloc((void **)p, n * sizeof(double)), "hipMalloc(recon weights)");
+        ck(hipMalloc((void **)&partials, 5 * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon partials)");
+        ck(hipMalloc((void **)&state, sizeof(rl1::State)), "hipMalloc(recon state)");
+        ck(hipHostMalloc((void **)&h_state, sizeof(rl1::State)), "hipHostMalloc");
+        for (auto &e : ev) ck(hipEventCreate(&e), "hipEventCreate");
+    }
+};
+std::mutex g_registry_mu;
+std::map<std::pair<int, hipStream_t>, std::unique_ptr<Workspace>> g_workspaces;
+
+Workspace &workspace(int dev, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(g_registry_mu);
+    auto &slot = g_workspaces[{dev, stream}];
+    if (!slot) slot.reset(new Workspace());
+    return *slot;
+}
+
+} // namespace
+
+void recon_l1_forget_stream(int dev, hipStream_t stream) {
+    std::unique_ptr<Workspace> gone;
+    {
+        std::lock_guard<std::mutex> lk(g_registry_mu);
+        auto it = g_workspaces.find({dev, stream});
+        if (it == g_workspaces.end()) return;
+        gone = std::move(it->second);
+        g_workspaces.erase(it);
+    }
+    int cur = 0;
+    hipGetDevice(&cur);
+    hipSetDevice(dev);
+    gone->release();
+    hipSetDevice(cur);
+}
+
+ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, double alpha,
+                              const ReconL1Params &p, double *d_out, hipStream_t stream) {
+    if (w < 2 || h < 2) throw std::runtime_error("reconstruct: width and height must be >= 2");
+    if (!(alpha > 0) || !std::isfinite(alpha)) throw std::runtime_error("reconstruct: dataCost must be > 0");
+    if ((long long)w * h > (1LL << 29)) throw std::runtime_error("reconstruct: film too large");
+    if (d_out == d_c || d_out == d_gx || d_out == d_gy) throw std::runtime_error("reconstruct: the output must not alias an input");
+    int dev = 0;
+    ck(hipGetDevice(&dev), "hipGetDevice");
+    Workspace &ws = workspace(dev, stream);
+    std::lock_guard<std::mutex> lk(ws.mu);
+    const size_t npix = (size_t)w * h;
+    if (npix > ws.npix && ws.npix) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
+    ws.ensure(npix);
+    rl1::Geo g{w, h, (w + rl1::kTileW - 1) / rl1::kTileW, 0};
+    g.tiles = g.tiles_x * ((h + rl1::kTileH - 1) / rl1::kTileH);
+    const int nb = std::min(rl1::kMaxBlocks, g.tiles);
+    double *part_rz = ws.partials, *part_rr = ws.partials + nb, *part_pq = ws.partials + 4 * (size_t)nb;
+    const dim3 grid(nb), block(rl1::kBlock);
+    auto read_state = [&]() {
+        ck(hipMemcpyAsync(ws.h_state, ws.state, sizeof(rl1::State), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(state)");
+        ck(hipEventRecord(ws.ev[2], stream), "hipEventRecord");
+    };
+    ReconL1Result res{};
+    ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
+    const int chunk = 32;
+    for (int k = 0; k <= p.irls_iters; k++) {
+        const double eps = k == 0 ? 0.0 : std::max(p.eps_init * std::pow(p.eps_decay, k - 1), p.eps_floor);
+        hipLaunchKernelGGL(rl1::weights_kernel<true>, grid, block, 0, stream, g, alpha, eps, k == 0 ? 1 : 0, k == 0 ? d_c : (const double *)d_out, d_c, d_gx, d_gy,
+                           k == 0 ? d_out : (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
+        hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), block, 0, stream, nb, ws.partials, ws.state, p.cg_tol, 1);
+        ck(hipGetLastError(), "recon round launch");
+        int launched = 0;
+        auto enqueue_chunk = [&]() {
+            const int n = std::min(chunk, p.cg_max_iters - launched);
+            for (int j = 0; j < n; j++) {
+                const int it = launched + j;
+                const double *pin = (it & 1) ? ws.p1 : ws.p0;
+                double *pout = (it & 1) ? ws.p0 : ws.p1;
+                hipLaunchKernelGGL(rl1::pcg_step_a, grid, block, 0, stream, g, it, ws.r, pin, pout, ws.q, ws.wx, ws.wy, ws.diag, part_rz, part_rr, part_pq, ws.state);
+                hipLaunchKernelGGL(rl1::pcg_step_b, grid, block, 0, stream, (int)npix, it, pout, ws.q, ws.diag, d_out, ws.r, part_pq, part_rz, part_rr, ws.state);
+            }
+            launched += n;
+            ck(hipGetLastError(), "recon chunk launch");
+        };
+        // one chunk is always in flight ahead of the status check of the previous one; its kernels return at once if converged
+        enqueue_chunk();
+        for (bool done = false; !done;) {
+            read_state();
+            const bool more = launched < p.cg_max_iters;
+            if (more) enqueue_chunk();
+            ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
+            if (ws.h_state->converged || !more) done = true;
+        }
+        hipLaunchKernelGGL(rl1::pcg_residual_kernel, dim3(1), block, 0, stream, nb, part_rr, ws.state);
+        ck(hipGetLastError(), "recon residual launch");
+        read_state();
+        ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
+        if (k == 1) res.energy_first = ws.h_state->energy;       // the weights of round 1 were taken from f_0
+        res.cg_iters_last = ws.h_state->iters; res.cg_iters_total += ws.h_state->iters;
+        res.rel_residual_last = ws.h_state->rel;
+        res.irls_rounds = k + 1;
+    }
+    hipLaunchKernelGGL(rl1::weights_kernel<false>, grid, block, 0, stream, g, alpha, 0.0, 1, (const double *)d_out, d_c, d_gx, d_gy,
+                       (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
+    hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), block, 0, stream, nb, ws.partials, ws.state, p.cg_tol, 0);
+    ck(hipGetLastError(), "recon energy launch");
+    read_state();
+    ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
+    ck(hipEventSynchronize(ws.ev[1]), "hipEventSynchronize");
+    res.energy_last = ws.h_state->energy;
+    if (p.irls_iters == 0) res.energy_first = res.energy_last;
+    float ms = 0;
+    ck(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]), "hipEventElapsedTime");
+    res.solve_ms = ms;
+    return res;
+}
+
+} // namespace gdpt

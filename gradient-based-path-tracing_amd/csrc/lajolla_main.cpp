@@ -15,6 +15,9 @@
 //   --exchange rccl|peer   transport of the halo row + all-gather between the bands (default rccl)
 //   --plan-rows R   cut every pixel's samples into work items as for a band of R rows (GdptRenderParams::plan_rows): a
 //                 single-device run with the R of an N-band run (its largest band) writes that run's image bit for bit
+//   --reconstruct l2|l1   final reconstruction: l2 = the reference's fourierSolve (default), l1 = IRLS, robust to fireflies in
+//                 the gradient buffers (include/gdpt.h: gdpt_reconstruct); --irls-iters N reweighted rounds (default 20),
+//                 --irls-eps INIT[,DECAY[,FLOOR]] (default 0.05,0.5,1e-3). Single device only
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -33,6 +36,7 @@ int main(int argc, char *argv[]) {
     int num_threads = 0, spp = 0, device = 0, rng = GDPT_RNG_SAMPLE, shift = GDPT_SHIFT_REFERENCE;
     int film_w = 0, film_h = 0, plan_rows = 0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
+    GdptReconParams recon{};          // norm == GDPT_RECON_L2: the reference's reconstruction
     double alpha = 0.04;
     std::string outputfile = "";
     std::vector<std::string> filenames;
@@ -82,8 +86,27 @@ int main(int argc, char *argv[]) {
             else if (v == "reference") shift = GDPT_SHIFT_REFERENCE;
             else { std::cerr << "unknown --shift " << v << " (reference | reconnect)" << std::endl; return 2; }
         }
+        else if (a == "--reconstruct") {
+            std::string v = next();
+            if (v == "l1") recon.norm = GDPT_RECON_L1;
+            else if (v == "l2") recon.norm = GDPT_RECON_L2;
+            else { std::cerr << "unknown --reconstruct " << v << " (l2 | l1)" << std::endl; return 2; }
+        }
+        else if (a == "--irls-iters") { int n = std::stoi(next()); recon.irls_iters = n > 0 ? n : -1; }
+        else if (a == "--irls-eps") {     // INIT[,DECAY[,FLOOR]]
+            std::string v = next();
+            double *dst[3] = {&recon.eps_init, &recon.eps_decay, &recon.eps_floor};
+            size_t pos = 0;
+            for (int k = 0; k < 3 && pos <= v.size(); k++) {
+                size_t c = v.find(',', pos);
+                if (c == std::string::npos) c = v.size();
+                *dst[k] = std::stod(v.substr(pos, c - pos));
+                pos = c + 1;
+            }
+        }
         else filenames.push_back(a);
     }
+    if (recon.norm == GDPT_RECON_L1 && multi.num_devices > 0) { std::cerr << "--reconstruct l1 is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
     (void)num_threads;
 
     using clock = std::chrono::system_clock;
@@ -116,13 +139,17 @@ int main(int argc, char *argv[]) {
         GdptRenderStats rs{};
         GdptPoissonStats ps{};
         GdptMultiStats ms{};
+        GdptReconStats cs{};
         // render() dispatches on the integrator (src/render.cpp:374-392)
         int rc;
         if (sharded) {
             rc = gdpt_multi_gradient_path_render(mscene, &p, alpha, image.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &rs, &ms);
             ps.solve_ms = ms.solve_ms; ps.solver = GDPT_SOLVER_DEFAULT;
         } else if (desc->integrator == GDPT_INTEGRATOR_PATH) rc = gdpt_path_render(scene, &p, image.data(), &rs);
-        else rc = gdpt_gradient_path_render(scene, &p, alpha, image.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &rs, &ps);
+        else if (recon.norm == GDPT_RECON_L1) {
+            rc = gdpt_gradient_path_render_recon(scene, &p, alpha, &recon, image.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &rs, &cs);
+            ps.iterations = cs.cg_iters_total; ps.solve_ms = cs.solve_ms;
+        } else rc = gdpt_gradient_path_render(scene, &p, alpha, image.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &rs, &ps);
         if (rc != 0) {
             std::cerr << "terminate: " << gdpt_last_error() << std::endl;
             return 134;

@@ -287,6 +287,56 @@ int gdpt_gradient_path_render(GdptScene *scene, const GdptRenderParams *params, 
                               double *img, double *cx0, double *cy0, double *cx1, double *cy1,
                               GdptRenderStats *rstats, GdptPoissonStats *pstats);
 
+/* ---- robust (L1) reconstruction: IRLS over a weighted screened-Poisson solve (not part of the reference) ----
+ * fourierSolve is a least-squares solve: one firefly in a gradient buffer is spread over the image as a dipole. The L1
+ * reconstruction minimises  E(f) = sum over rows of |r|_2  instead, rows of three channels each:
+ *     data row of pixel (x,y):  r_d = sqrt(dataCost) (f - c)
+ *     x-edge row, x >= 1:       r_x = f(x,y) - f(x-1,y) - gx(x,y)
+ *     y-edge row, y >= 1:       r_y = f(x,y) - f(x,y-1) - gy(x,y)
+ * Edges exist inside the film only (natural boundary: gx(0,.) and gy(.,0) are not read; NOT fourierSolve's mirror operator).
+ * Round 0 solves the unweighted system from f = c; round k = 1..irls_iters gives every row the weight
+ * w = 1 / (eps_k + |r|_2) of the previous image (one weight for its three channels: no colour shift),
+ * eps_k = max(eps_init eps_decay^(k-1), eps_floor), and solves, per channel,
+ *     (a diag(w_d) + Dx^T diag(w_x) Dx + Dy^T diag(w_y) Dy) f = a w_d c + Dx^T (w_x gx) + Dy^T (w_y gy),   a = dataCost,
+ * by Jacobi-preconditioned conjugate gradients warm-started from the previous image, until |residual| <= cg_tol |rhs| or
+ * cg_max_iters. Deterministic: the same inputs give the same bits. */
+enum { GDPT_RECON_L2 = 0, GDPT_RECON_L1 = 1 };
+typedef struct GdptReconParams {
+    int32_t norm;              /* GDPT_RECON_*; GDPT_RECON_L2 = the default fourierSolve path, every other field ignored */
+    int32_t irls_iters;        /* reweighted rounds K after round 0. 0: default 20; < 0: none (round 0 alone) */
+    int32_t cg_max_iters;      /* per round. <= 0: default 1000 */
+    int32_t reserved;          /* 0 */
+    double eps_init;           /* 0: default 0.05 */
+    double eps_decay;          /* in (0, 1]. 0: default 0.5 */
+    double eps_floor;          /* 0: default 1e-3 (without a floor the systems become too ill-conditioned for the CG) */
+    double cg_tol;             /* 0: default 1e-6 */
+} GdptReconParams;             /* negative or non-finite eps_* / cg_tol and eps_decay > 1 are refused */
+typedef struct GdptReconStats {
+    int32_t norm;              /* GDPT_RECON_* actually used */
+    int32_t irls_rounds;       /* systems solved: K + 1 (L2: 0) */
+    int32_t cg_iters_total;    /* CG iterations over all rounds */
+    int32_t cg_iters_last;     /* ... of the last round */
+    double energy_first;       /* E(f_0): after the unweighted round */
+    double energy_last;        /* E(f_K): of the image returned */
+    double rel_residual_last;  /* |b - A f| / |b| at the exit of the last round */
+    double solve_ms;           /* device time, HIP events */
+} GdptReconStats;
+/* Host pointers (W*H*3 doubles each, as gdpt_poisson_solve). params == NULL or norm == GDPT_RECON_L2: gdpt_poisson_solve's result,
+ * bit for bit. No CPU fallback. */
+int gdpt_reconstruct(int width, int height, const double *c, const double *gx, const double *gy, double dataCost,
+                     const GdptReconParams *params /* nullable */, double *out, GdptReconStats *stats /* nullable */);
+/* Device pointers; `out` must not alias an input. The L1 path waits for `stream` (host-side convergence checks) and keeps its
+ * scratch per (device, stream): gdpt_poisson_forget_stream drops it with the solver's. */
+int gdpt_reconstruct_device(int width, int height, const double *d_c, const double *d_gx, const double *d_gy, double dataCost,
+                            const GdptReconParams *params /* nullable */, double *d_out, void *stream,
+                            GdptReconStats *stats /* nullable */);
+/* gdpt_gradient_path_render with the final solve replaced by gdpt_reconstruct on the assembled c, cx, cy; the five raw buffers
+ * are those of gdpt_gradient_path_render. */
+int gdpt_gradient_path_render_recon(GdptScene *scene, const GdptRenderParams *params, double dataCost,
+                                    const GdptReconParams *recon /* nullable */, double *out_image,
+                                    double *img, double *cx0, double *cy0, double *cx1, double *cy1,
+                                    GdptRenderStats *rstats /* nullable */, GdptReconStats *cstats /* nullable */);
+
 /* ---- several devices of one node: the tile loop sharded into row bands ----
  * Replaces the reference's only parallelism, parallel_for over 16x16 tiles on a std::thread pool
  * (src/render.cpp:271-277, src/parallel.cpp:183-256): contiguous bands of whole tile rows go to the devices, one host
