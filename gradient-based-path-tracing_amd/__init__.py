@@ -56,6 +56,18 @@ def lib():
         L.gdpt_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), vp, vp, vp, vp, vp, vp, C.POINTER(defs.GdptRenderStats)]
         L.gdpt_path_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), dp, C.POINTER(defs.GdptRenderStats)]
         L.gdpt_path_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), vp, vp, C.POINTER(defs.GdptRenderStats)]
+        L.gdpt_render_window_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp, vp, vp, vp, vp,
+                                                C.POINTER(defs.GdptRenderStats)]
+        L.gdpt_path_render_window_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp,
+                                                     C.POINTER(defs.GdptRenderStats)]
+        L.gdpt_progressive_create.argtypes = [vp, C.POINTER(defs.GdptProgressiveConfig), vp, C.POINTER(vp)]
+        L.gdpt_progressive_free.argtypes = [vp]
+        L.gdpt_progressive_free.restype = None
+        L.gdpt_progressive_add_pass.argtypes = [vp, C.c_int, C.POINTER(defs.GdptRenderStats)]
+        L.gdpt_progressive_status.argtypes = [vp, C.POINTER(defs.GdptProgressiveStatus)]
+        L.gdpt_progressive_read.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+        L.gdpt_progressive_reconstruct.argtypes = [vp, C.c_double, C.POINTER(defs.GdptReconParams), C.c_int, vp, C.POINTER(defs.GdptReconStats)]
+        L.gdpt_progressive_run.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
         L.gdpt_assemble_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gdpt_poisson_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         L.gdpt_poisson_solve_ex.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, C.c_int, C.c_double, C.c_int,
@@ -186,12 +198,18 @@ class Scene:
         return bufs, st
 
     def render_device(self, ptrs, spp=0, rng_scheme=defs.RNG_SAMPLE, rows=(0, 0), stream=None, want_stats=False,
-                      shift=defs.SHIFT_REFERENCE, plan_rows=0):
-        """Five-buffer render into device memory; `ptrs` = 5 device addresses (e.g. torch tensor.data_ptr())."""
+                      shift=defs.SHIFT_REFERENCE, plan_rows=0, window=None):
+        """Five-buffer render into device memory; `ptrs` = 5 device addresses (e.g. torch tensor.data_ptr()).
+        `window` = (stream_spp, first_sample): the spp samples are streams [first_sample, first_sample + spp) of every pixel's
+        block of stream_spp streams (GdptSampleWindow, gdpt_render_window_device)."""
         st = defs.GdptRenderStats() if want_stats else None
         p = _params(spp, rng_scheme, rows, shift=shift, plan_rows=plan_rows)
-        _check(lib().gdpt_render_device(self.handle, C.byref(p), *[C.c_void_p(int(x)) for x in ptrs],
-                                        C.c_void_p(int(stream) if stream else 0), C.byref(st) if st is not None else None))
+        tail = [C.c_void_p(int(x)) for x in ptrs] + [C.c_void_p(int(stream) if stream else 0), C.byref(st) if st is not None else None]
+        if window is None:
+            _check(lib().gdpt_render_device(self.handle, C.byref(p), *tail))
+        else:
+            win = defs.GdptSampleWindow(int(window[0]), int(window[1]))
+            _check(lib().gdpt_render_window_device(self.handle, C.byref(p), C.byref(win), *tail))
         return st
 
     def path_render(self, spp=0, rng_scheme=defs.RNG_SAMPLE, rows=(0, 0), want_counts=False):
@@ -204,9 +222,17 @@ class Scene:
         _check(lib().gdpt_path_render(self.handle, C.byref(p), _dp(img), C.byref(st)))
         return img, st
 
-    def path_render_device(self, ptr, spp=0, rng_scheme=defs.RNG_SAMPLE, rows=(0, 0), stream=None):
+    def path_render_device(self, ptr, spp=0, rng_scheme=defs.RNG_SAMPLE, rows=(0, 0), stream=None, window=None, want_stats=False):
+        """`window` as in render_device (gdpt_path_render_window_device)."""
+        st = defs.GdptRenderStats() if want_stats else None
         p = _params(spp, rng_scheme, rows)
-        _check(lib().gdpt_path_render_device(self.handle, C.byref(p), C.c_void_p(int(ptr)), C.c_void_p(int(stream) if stream else 0), None))
+        tail = [C.c_void_p(int(ptr)), C.c_void_p(int(stream) if stream else 0), C.byref(st) if st is not None else None]
+        if window is None:
+            _check(lib().gdpt_path_render_device(self.handle, C.byref(p), *tail))
+        else:
+            win = defs.GdptSampleWindow(int(window[0]), int(window[1]))
+            _check(lib().gdpt_path_render_window_device(self.handle, C.byref(p), C.byref(win), *tail))
+        return st
 
     def gradient_path_render(self, spp=0, rng_scheme=defs.RNG_SAMPLE, alpha=0.04, return_buffers=False,
                              shift=defs.SHIFT_REFERENCE, plan_rows=0, reconstruct=None):
@@ -238,6 +264,99 @@ class Scene:
     def close(self):
         if getattr(self, "handle", None):
             lib().gdpt_scene_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+BUFFERS = ("img", "cx0", "cy0", "cx1", "cy1")
+
+
+class Progressive:
+    """A progressive render session on the device (include/gdpt.h, gdpt_progressive_*): passes over disjoint sample windows of
+    every pixel's block of `budget_spp` PCG streams, folded into running means and per-pixel variances of the mean.
+    `path=True`: Integrator::Path (the img plane alone). `stream`: a hipStream_t address carrying all of the session's work."""
+
+    def __init__(self, scene, budget_spp, shift=defs.SHIFT_REFERENCE, path=False, stream=None, max_depth_override=0):
+        self.scene = scene                       # keeps the scene handle alive
+        self.path = bool(path)
+        self.names = BUFFERS[:1] if self.path else BUFFERS
+        self.shape = (scene.height, scene.width, 3)
+        cfg = defs.GdptProgressiveConfig(defs.PROGRESSIVE_PATH if self.path else defs.PROGRESSIVE_GRADPATH, int(shift), int(budget_spp),
+                                         int(max_depth_override))
+        h = C.c_void_p()
+        _check(lib().gdpt_progressive_create(scene.handle, C.byref(cfg), C.c_void_p(int(stream) if stream else 0), C.byref(h)))
+        self.handle = h
+
+    def add_pass(self, spp):
+        """Renders and folds in the next `spp` samples of every pixel; returns the pass's GdptRenderStats."""
+        st = defs.GdptRenderStats()
+        _check(lib().gdpt_progressive_add_pass(self.handle, int(spp), C.byref(st)))
+        return st
+
+    @staticmethod
+    def _status_dict(st):
+        return dict(passes=st.passes, spp=st.spp_done, budget_spp=st.budget_spp, error=st.error_estimate,
+                    pixels_left_out=st.pixels_left_out, fold_ms=st.fold_ms, stop_reason=defs.STOP_NAMES[st.stop_reason], totals=st.totals)
+
+    def status(self):
+        """dict: passes, spp (so far), budget_spp, error (estimated relative RMSE of the primal mean; NaN before 2 passes),
+        pixels_left_out (of the estimate), fold_ms (device time of the last fold), stop_reason (of the last run), totals (GdptRenderStats summed over the passes)."""
+        st = defs.GdptProgressiveStatus()
+        _check(lib().gdpt_progressive_status(self.handle, C.byref(st)))
+        return self._status_dict(st)
+
+    def read(self, variances=True):
+        """Host copies, HxWx3 float64: (means, vars, assembled_vars). means / vars: dicts over the session's buffers (running mean,
+        variance of the mean); assembled_vars: dict of the variances of the assembled c, cx, cy (GradPath). With `variances=False`, and before the
+        second pass (no variance is defined yet), the means alone: (means, None, None)."""
+        variances = bool(variances) and self.status()["passes"] >= 2
+        means = {k: np.empty(self.shape, dtype=np.float64) for k in self.names}
+        vars_ = {k: np.empty(self.shape, dtype=np.float64) for k in self.names} if variances else None
+        asm = {k: np.empty(self.shape, dtype=np.float64) for k in ("c", "cx", "cy")} if variances and not self.path else None
+
+        def table(d, keys):
+            arr = (C.c_void_p * len(keys))()
+            for i, k in enumerate(keys):
+                arr[i] = d[k].ctypes.data if d is not None and k in d else None
+            return arr
+        _check(lib().gdpt_progressive_read(self.handle, 0, table(means, BUFFERS), table(vars_, BUFFERS), table(asm, ("c", "cx", "cy"))))
+        return means, vars_, asm
+
+    def read_device(self, mean_ptrs=None, var_ptrs=None, assembled_var_ptrs=None):
+        """read() into device memory: lists of 5 / 5 / 3 device addresses (None or 0 entries are skipped)."""
+        def table(ptrs, n):
+            arr = (C.c_void_p * n)()
+            for i in range(n):
+                arr[i] = int(ptrs[i]) if ptrs is not None and i < len(ptrs) and ptrs[i] else None
+            return arr
+        _check(lib().gdpt_progressive_read(self.handle, 1, table(mean_ptrs, 5), table(var_ptrs, 5), table(assembled_var_ptrs, 3)))
+
+    def reconstruct(self, alpha=0.04, norm=defs.RECON_L2, out_ptr=None, **params):
+        """The reconstruction of the running means (a preview after any pass): RECON_L2 = fourierSolve, RECON_L1 = IRLS (`params`: the
+        keywords of recon_params). Returns (HxWx3 image, GdptReconStats), or the stats alone when `out_ptr` names device memory."""
+        p, st = recon_params(norm, **params), defs.GdptReconStats()
+        if out_ptr is not None:
+            _check(lib().gdpt_progressive_reconstruct(self.handle, float(alpha), C.byref(p), 1, C.c_void_p(int(out_ptr)), C.byref(st)))
+            return st
+        out = np.empty(self.shape, dtype=np.float64)
+        _check(lib().gdpt_progressive_reconstruct(self.handle, float(alpha), C.byref(p), 0, C.c_void_p(out.ctypes.data), C.byref(st)))
+        return out, st
+
+    def run(self, target_error=0.0, pass_spp=16, max_passes=0):
+        """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
+        <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
+        st = defs.GdptProgressiveStatus()
+        _check(lib().gdpt_progressive_run(self.handle, float(target_error), int(pass_spp), int(max_passes), C.byref(st)))
+        return self._status_dict(st)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().gdpt_progressive_free(self.handle)
             self.handle = None
 
     def __del__(self):

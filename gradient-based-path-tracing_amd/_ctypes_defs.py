@@ -78,6 +78,10 @@ class GdptRenderStats(C.Structure):
                 ("wave_node_trips", C.c_uint64), ("wave_leaf_trips", C.c_uint64), ("wave_steps", C.c_uint64), ("lane_steps", C.c_uint64)]
 
 
+class GdptSampleWindow(C.Structure):
+    _fields_ = [("stream_spp", C.c_int32), ("first_sample", C.c_int32)]
+
+
 class GdptPoissonStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("solver", C.c_int32), ("rel_residual", C.c_double), ("solve_ms", C.c_double)]
 
@@ -93,6 +97,20 @@ class GdptReconParams(C.Structure):
 class GdptReconStats(C.Structure):
     _fields_ = [("norm", C.c_int32), ("irls_rounds", C.c_int32), ("cg_iters_total", C.c_int32), ("cg_iters_last", C.c_int32),
                 ("energy_first", C.c_double), ("energy_last", C.c_double), ("rel_residual_last", C.c_double), ("solve_ms", C.c_double)]
+
+
+PROGRESSIVE_GRADPATH, PROGRESSIVE_PATH = 0, 1
+STOP_NONE, STOP_TARGET, STOP_BUDGET, STOP_MAX_PASSES = 0, 1, 2, 3
+STOP_NAMES = {STOP_NONE: "none", STOP_TARGET: "target", STOP_BUDGET: "budget", STOP_MAX_PASSES: "max_passes"}
+
+
+class GdptProgressiveConfig(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("shift_mode", C.c_int32), ("budget_spp", C.c_int32), ("max_depth_override", C.c_int32)]
+
+
+class GdptProgressiveStatus(C.Structure):
+    _fields_ = [("passes", C.c_int32), ("spp_done", C.c_int32), ("budget_spp", C.c_int32), ("stop_reason", C.c_int32),
+                ("error_estimate", C.c_double), ("pixels_left_out", C.c_uint64), ("fold_ms", C.c_double), ("totals", GdptRenderStats)]
 
 
 GDPT_MULTI_MAX_DEVICES = 16

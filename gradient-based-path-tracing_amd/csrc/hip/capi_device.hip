@@ -396,7 +396,7 @@ namespace {
 
 using gdpt::build_scene;
 
-struct Band { int spp, rng, row_begin, row_end, max_depth, shift, plan_rows; };
+struct Band { int spp, rng, row_begin, row_end, max_depth, shift, plan_rows, stream_spp, first_sample; };
 
 Band resolve(const GdptScene *sc, const GdptRenderParams *p) {
     if (!sc) throw std::runtime_error("null scene handle");
@@ -420,10 +420,21 @@ Band resolve(const GdptScene *sc, const GdptRenderParams *p) {
 }
 
 // The band with its samples per pixel (the params' spp, else `scene_spp`).
-Band resolve_spp(const GdptScene *sc, const GdptRenderParams *p, int scene_spp, const char *what) {
+// `win` (nullable) makes the samples a window of a larger stream block (include/gdpt.h: GdptSampleWindow).
+Band resolve_spp(const GdptScene *sc, const GdptRenderParams *p, int scene_spp, const char *what, const GdptSampleWindow *win = nullptr) {
     Band b = resolve(sc, p);
     if (b.spp <= 0) b.spp = scene_spp;
     if (b.spp <= 0) throw std::runtime_error(std::string(what) + ": samples per pixel must be > 0");
+    b.stream_spp = b.spp; b.first_sample = 0;
+    if (win) {
+        if (b.rng == GDPT_RNG_TILE) throw std::runtime_error(std::string(what) + ": GDPT_RNG_TILE has one stream per tile and no sample window (use GDPT_RNG_SAMPLE)");
+        if (win->stream_spp <= 0 || win->first_sample < 0 || (long long)win->first_sample + b.spp > (long long)win->stream_spp)
+            throw std::runtime_error(std::string(what) + ": sample window [first_sample, first_sample + spp) must lie inside [0, stream_spp)");
+        // the largest stream index, W * H * stream_spp - 1, goes through pcg_init's (index << 1) | 1
+        if ((unsigned long long)sc->view.cam.width * (unsigned long long)sc->view.cam.height > (~0ull >> 1) / (unsigned long long)win->stream_spp)
+            throw std::runtime_error(std::string(what) + ": width * height * stream_spp does not fit 63 bits");
+        b.stream_spp = win->stream_spp; b.first_sample = win->first_sample;
+    }
     return b;
 }
 
@@ -445,7 +456,7 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     in.full_material_switch = knob("full_material_switch", 0) != 0;
     gdpt::RenderLaunch rl{};
     rl.route = gdpt::choose_route(in);
-    rl.spp = b.spp; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
+    rl.spp = b.spp; rl.stream_spp = b.stream_spp; rl.first_sample = b.first_sample; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
     rl.counters = sc->d_counters;
     rl.count_traversal = stats && stats->nodes_visited == ~0ull;   // request flag: caller presets nodes_visited = UINT64_MAX
     rl.force_log2k = knob("log2k", -1);
@@ -502,10 +513,10 @@ namespace gdpt {
 // Enqueues one render; returns after enqueue unless stats are requested.
 void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
                         double *img, double *cx0, double *cy0, double *cx1, double *cy1,
-                        hipStream_t stream, GdptRenderStats *stats) {
+                        hipStream_t stream, GdptRenderStats *stats, const GdptSampleWindow *window) {
     reset_route();           // (include/gdpt_debug.h: "" until this render has launched its kernel)
     ck(hipSetDevice(sc->device), "hipSetDevice");
-    const Band b = resolve_spp(sc, params, scene_spp, "gdpt_render");
+    const Band b = resolve_spp(sc, params, scene_spp, "gdpt_render", window);
     if (!img || !cx0 || !cy0 || !cx1 || !cy1) throw std::runtime_error("gdpt_render: null output buffer");
     RenderLaunch rl = begin_launch(sc, b, false, sc->plan_take_pct, stream, stats);
     rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
@@ -553,11 +564,12 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
 namespace {
 using gdpt::render_device_impl;
 // Integrator::Path: enqueues one render of `img`; returns after enqueue unless stats are requested.
-void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, double *img, hipStream_t stream, GdptRenderStats *stats) {
+void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, double *img, hipStream_t stream, GdptRenderStats *stats,
+                             const GdptSampleWindow *window) {
     gdpt::reset_route();
     ck(hipSetDevice(sc->device), "hipSetDevice");
     if (sc->view.num_lights <= 0) throw std::runtime_error("gdpt_path_render: the scene has no emitter to sample");
-    const Band b = resolve_spp(sc, params, sc->scene_spp, "gdpt_path_render");
+    const Band b = resolve_spp(sc, params, sc->scene_spp, "gdpt_path_render", window);
     if (!img) throw std::runtime_error("gdpt_path_render: null output buffer");
     gdpt::RenderLaunch rl = begin_launch(sc, b, true, 0, stream, stats);   // (the plan takes the default share: see make_chunk_plan)
     rl.img = img;
@@ -685,7 +697,26 @@ int gdpt_tile_row_costs(GdptScene *scene, int spp, double *cost, int capacity) {
 int gdpt_path_render_device(GdptScene *scene, const GdptRenderParams *params, double *d_img, void *stream, GdptRenderStats *stats) {
     return gdpt::guarded([&]() {
         if (!scene) throw std::runtime_error("null scene handle");
-        path_render_device_impl(scene, params, d_img, (hipStream_t)stream, stats);
+        path_render_device_impl(scene, params, d_img, (hipStream_t)stream, stats, nullptr);
+    });
+}
+
+int gdpt_render_window_device(GdptScene *scene, const GdptRenderParams *params, const GdptSampleWindow *window,
+                              double *d_img, double *d_cx0, double *d_cy0, double *d_cx1, double *d_cy1,
+                              void *stream, GdptRenderStats *stats) {
+    if (!window) return gdpt_render_device(scene, params, d_img, d_cx0, d_cy0, d_cx1, d_cy1, stream, stats);
+    return gdpt::guarded([&]() {
+        if (!scene) throw std::runtime_error("null scene handle");
+        render_device_impl(scene, params, scene->scene_spp, d_img, d_cx0, d_cy0, d_cx1, d_cy1, (hipStream_t)stream, stats, window);
+    });
+}
+
+int gdpt_path_render_window_device(GdptScene *scene, const GdptRenderParams *params, const GdptSampleWindow *window, double *d_img,
+                                   void *stream, GdptRenderStats *stats) {
+    if (!window) return gdpt_path_render_device(scene, params, d_img, stream, stats);
+    return gdpt::guarded([&]() {
+        if (!scene) throw std::runtime_error("null scene handle");
+        path_render_device_impl(scene, params, d_img, (hipStream_t)stream, stats, window);
     });
 }
 
@@ -700,7 +731,7 @@ int gdpt_path_render(GdptScene *scene, const GdptRenderParams *params, double *i
         const bool partial = (b.row_begin != 0 || b.row_end != scene->view.cam.height);
         if (partial) ck(hipMemcpy(scene->d_buf[0], img, elems * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(H2D)");
         GdptRenderStats local{};
-        path_render_device_impl(scene, params, scene->d_buf[0], nullptr, stats ? stats : &local);
+        path_render_device_impl(scene, params, scene->d_buf[0], nullptr, stats ? stats : &local, nullptr);
         ck(hipMemcpy(img, scene->d_buf[0], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
     });
 }

@@ -1,0 +1,356 @@
+// progressive.hip — progressive rendering for gfx950: a session that renders a scene in passes over disjoint sample windows of
+// one stream block, folds every pass into running means and sums of weighted squared deviations, and reports per-pixel
+// variances and an error estimate (include/gdpt.h: gdpt_progressive_*).
+//
+// Definition. Pass k is a mean m over its n samples, per buffer component. West's weighted update (1979):
+//     W += n;  d = m - mean;  mean += (n / W) d;  M2 += n d (m - mean_new)
+// gives mean = sum n_k m_k / sum n_k and M2 = sum n_k (m_k - mean)^2 after any number of passes of any sizes, and
+// E[M2] = (K - 1) sigma^2 for per-sample variance sigma^2: var_mean = M2 / ((K - 1) W) estimates the variance of the running
+// mean. The error estimate is sqrt(sum var_mean(img) / sum mean(img)^2) over the pixels whose img mean and M2 are finite.
+//
+// Kernels. A thread owns a PIXEL: its three channels in every buffer (the film is interleaved, [(y*W+x)*3+c], so consecutive
+// threads read consecutive 24-byte triples and a wave covers 1536 contiguous bytes per plane).
+//   fold_kernel      one pass over the film for all buffers: reads pass, mean, M2, writes mean, M2 (the first pass reads no
+//                    mean / M2: they start at 0), and leaves the block partials of the two sums and of the left-out count.
+//   finish_kernel    one block: the partials reduced in a fixed order (xor tree in a wave, waves in index order, blocks strided
+//                    in index order), so that the same session gives the same bits and the same stopping pass.
+//   variance_kernel  read-out: M2 / ((K-1) W) per buffer and the variances of the assembled cx, cy.
+// The fold is memory bound: 5 doubles of traffic per component (3 read, 2 written), 40 bytes x 15 components per GradPath pixel.
+#include "../../../include/gdpt.h"
+#include "../capi_common.h"
+#include "poisson_kernels.h"
+#include "scene_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <limits>
+#include <memory>
+
+namespace prg {
+
+constexpr int kBlock = 256, kMaxBlocks = 1024;
+
+struct Planes {
+    const double *pass[5];
+    double *mean[5], *m2[5];
+};
+struct Estimate { double sum_var, sum_mean2, left_out; };
+
+__device__ __forceinline__ double block_sum(double v, double *red) {
+    // fixed order: xor tree inside each wave, then the wave totals in index order
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / 64; k++) s += red[k];
+    return s;
+}
+
+// n: samples of the pass; w_new: samples so far, this pass included; norm = (K - 1) w_new, K passes this one included (0 while K < 2:
+// no estimate). FIRST: the running planes are not read (mean = M2 = 0 before the first pass).
+// partials: [0] sum var_mean(img), [1] sum mean(img)^2, [2] pixels left out; gridDim.x doubles each.
+template <int NBUF, bool FIRST>
+__global__ __launch_bounds__(kBlock) void fold_kernel(Planes p, int npix, double n, double w_new, double norm, double *partials) {
+    __shared__ double red[kBlock / 64];
+    const double f = n / w_new;
+    double s_var = 0, s_m2 = 0, s_out = 0;
+    for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < npix; pix += gridDim.x * kBlock) {
+        const size_t i = (size_t)3 * pix;
+#pragma unroll
+        for (int b = 0; b < NBUF; b++) {
+            double mu[3], q[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double m = p.pass[b][i + c];
+                const double mu0 = FIRST ? 0.0 : p.mean[b][i + c], q0 = FIRST ? 0.0 : p.m2[b][i + c];
+                const double d = m - mu0;
+                mu[c] = mu0 + f * d;
+                q[c] = q0 + n * d * (m - mu[c]);
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) { p.mean[b][i + c] = mu[c]; p.m2[b][i + c] = q[c]; }
+            if (b == 0 && norm > 0.0) {
+                const bool ok = isfinite(mu[0]) && isfinite(mu[1]) && isfinite(mu[2]) && isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
+                if (ok) {
+                    s_var += (q[0] / norm + q[1] / norm) + q[2] / norm;
+                    s_m2 += (mu[0] * mu[0] + mu[1] * mu[1]) + mu[2] * mu[2];
+                } else s_out += 1.0;
+            }
+        }
+    }
+    const int nb = gridDim.x;
+    double v;
+    v = block_sum(s_var, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
+    v = block_sum(s_m2, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
+    v = block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
+}
+
+__global__ __launch_bounds__(kBlock) void finish_kernel(int nb, const double *partials, Estimate *est) {
+    __shared__ double red[kBlock / 64];
+    double r[3];
+    for (int k = 0; k < 3; k++) {
+        double v = 0;
+        for (int i = threadIdx.x; i < nb; i += kBlock) v += partials[k * nb + i];
+        r[k] = block_sum(v, red);
+    }
+    if (threadIdx.x == 0) { est->sum_var = r[0]; est->sum_mean2 = r[1]; est->left_out = r[2]; }
+}
+
+// var[b] = M2[b] / norm for b < NBUF; NBUF == 5: vcx(x,y) = var cx0(x,y) + var cx1(x-1,y), vcy(x,y) = var cy0(x,y) + var cy1(x,y-1),
+// the second term absent on the film's first column / row (as gdpt_assemble_device assembles cx, cy).
+struct VarPlanes { const double *m2[5]; double *var[5], *vcx, *vcy; };
+template <int NBUF>
+__global__ __launch_bounds__(kBlock) void variance_kernel(VarPlanes p, int w, int h, double norm) {
+    const int n3 = 3 * w * h, row = 3 * w;
+    for (int i = blockIdx.x * kBlock + threadIdx.x; i < n3; i += gridDim.x * kBlock) {
+#pragma unroll
+        for (int b = 0; b < NBUF; b++) p.var[b][i] = p.m2[b][i] / norm;
+        if (NBUF == 5) {
+            const int y = i / row, x = (i - y * row) / 3;
+            const double vx = p.m2[1][i] / norm, vy = p.m2[2][i] / norm;
+            p.vcx[i] = x == 0 ? vx : vx + p.m2[3][i - 3] / norm;
+            p.vcy[i] = y == 0 ? vy : vy + p.m2[4][i - row] / norm;
+        }
+    }
+}
+
+} // namespace prg
+
+struct GdptProgressive {
+    GdptScene *scene = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int mode = GDPT_PROGRESSIVE_GRADPATH, shift = GDPT_SHIFT_REFERENCE, max_depth_override = 0;
+    int nbuf = 5, w = 0, h = 0;
+    int budget = 0, done = 0, passes = 0, stop_reason = GDPT_STOP_NONE;
+    size_t elems = 0;
+    double *pass[5] = {}, *mean[5] = {}, *m2[5] = {};
+    double *var[7] = {};             // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
+    double *asm_buf[4] = {};         // c, cx, cy, reconstruction: allocated by the first reconstruct
+    double *partials = nullptr;
+    prg::Estimate *d_est = nullptr, *h_est = nullptr;     // device / pinned host
+    prg::Estimate est{};             // of the last fold (valid from 2 passes)
+    hipEvent_t ev[2] = {nullptr, nullptr};                // around the fold launches
+    double fold_ms = 0;              // device time of the last pass's fold (fold_kernel + finish_kernel)
+    GdptRenderStats totals{};
+
+    ~GdptProgressive() {
+        hipSetDevice(device);
+        for (auto *set : {pass, mean, m2}) for (int k = 0; k < 5; k++) if (set[k]) hipFree(set[k]);
+        for (double *p : var) if (p) hipFree(p);
+        for (double *p : asm_buf) if (p) hipFree(p);
+        if (partials) hipFree(partials);
+        if (d_est) hipFree(d_est);
+        if (h_est) hipHostFree(h_est);
+        for (auto &e : ev) if (e) hipEventDestroy(e);
+    }
+};
+
+namespace {
+
+using gdpt::ck;
+
+int fold_blocks(int npix) { return std::max(1, std::min(prg::kMaxBlocks, (npix + prg::kBlock - 1) / prg::kBlock)); }
+
+double error_estimate(const GdptProgressive &s) {
+    if (s.passes < 2) return std::numeric_limits<double>::quiet_NaN();
+    return std::sqrt(s.est.sum_var / s.est.sum_mean2);
+}
+
+void fill_status(const GdptProgressive &s, GdptProgressiveStatus *st) {
+    if (!st) return;
+    std::memset(st, 0, sizeof(*st));
+    st->passes = s.passes; st->spp_done = s.done; st->budget_spp = s.budget; st->stop_reason = s.stop_reason;
+    st->error_estimate = error_estimate(s);
+    st->pixels_left_out = s.passes < 2 ? 0 : (uint64_t)s.est.left_out;
+    st->fold_ms = s.fold_ms;
+    st->totals = s.totals;
+}
+
+void add_pass(GdptProgressive &s, int spp, GdptRenderStats *stats) {
+    if (spp <= 0) throw std::runtime_error("gdpt_progressive_add_pass: spp must be > 0");
+    if ((long long)s.done + spp > (long long)s.budget)
+        throw std::runtime_error("gdpt_progressive_add_pass: the pass exceeds the session's budget (" + std::to_string(s.done) + " + " + std::to_string(spp) +
+                                 " > " + std::to_string(s.budget) + " samples per pixel)");
+    ck(hipSetDevice(s.scene->device), "hipSetDevice");
+    GdptRenderParams p{};
+    p.spp = spp; p.rng_scheme = GDPT_RNG_SAMPLE; p.shift_mode = s.shift; p.max_depth_override = s.max_depth_override;
+    const GdptSampleWindow win{s.budget, s.done};
+    GdptRenderStats rs{};
+    const int rc = s.mode == GDPT_PROGRESSIVE_PATH
+                       ? gdpt_path_render_window_device(s.scene, &p, &win, s.pass[0], s.stream, &rs)
+                       : gdpt_render_window_device(s.scene, &p, &win, s.pass[0], s.pass[1], s.pass[2], s.pass[3], s.pass[4], s.stream, &rs);
+    if (rc != 0) throw std::runtime_error(gdpt_last_error());
+
+    prg::Planes pl{};
+    for (int k = 0; k < s.nbuf; k++) { pl.pass[k] = s.pass[k]; pl.mean[k] = s.mean[k]; pl.m2[k] = s.m2[k]; }
+    const int npix = s.w * s.h, nb = fold_blocks(npix), K = s.passes + 1;
+    const double n = (double)spp, w_new = (double)(s.done + spp), norm = (double)(K - 1) * w_new;
+    const dim3 grid(nb), block(prg::kBlock);
+    const bool first = s.passes == 0;
+    ck(hipEventRecord(s.ev[0], s.stream), "hipEventRecord");
+    if (s.nbuf == 5) {
+        if (first) hipLaunchKernelGGL((prg::fold_kernel<5, true>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
+        else hipLaunchKernelGGL((prg::fold_kernel<5, false>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
+    } else {
+        if (first) hipLaunchKernelGGL((prg::fold_kernel<1, true>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
+        else hipLaunchKernelGGL((prg::fold_kernel<1, false>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
+    }
+    hipLaunchKernelGGL(prg::finish_kernel, dim3(1), block, 0, s.stream, nb, s.partials, s.d_est);
+    ck(hipGetLastError(), "progressive fold launch");
+    ck(hipEventRecord(s.ev[1], s.stream), "hipEventRecord");
+    ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
+    ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(fold)");
+    s.est = *s.h_est;
+    { float ms = 0; ck(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]), "hipEventElapsedTime"); s.fold_ms = ms; }
+    s.done += spp; s.passes = K;
+    s.totals.samples += rs.samples; s.totals.rays += rs.rays; s.totals.bounces += rs.bounces;
+    s.totals.nodes_visited += rs.nodes_visited; s.totals.tris_tested += rs.tris_tested; s.totals.nonfinite_samples += rs.nonfinite_samples;
+    s.totals.render_ms += rs.render_ms; s.totals.node_bytes = rs.node_bytes;
+    s.totals.wave_node_trips += rs.wave_node_trips; s.totals.wave_leaf_trips += rs.wave_leaf_trips;
+    s.totals.wave_steps += rs.wave_steps; s.totals.lane_steps += rs.lane_steps;
+    if (stats) *stats = rs;
+}
+
+void copy_out(const GdptProgressive &s, double *dst, const double *src, int on_device) {
+    if (!dst) return;
+    ck(hipMemcpyAsync(dst, src, s.elems * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(progressive read)");
+}
+
+} // namespace
+
+extern "C" {
+
+int gdpt_progressive_create(GdptScene *scene, const GdptProgressiveConfig *config, void *stream, GdptProgressive **out) {
+    return gdpt::guarded([&]() {
+        if (!scene || !out) throw std::runtime_error("gdpt_progressive_create: null argument");
+        GdptProgressiveConfig cfg = config ? *config : GdptProgressiveConfig{};
+        if (cfg.mode != GDPT_PROGRESSIVE_GRADPATH && cfg.mode != GDPT_PROGRESSIVE_PATH) throw std::runtime_error("gdpt_progressive_create: unknown mode");
+        if (cfg.shift_mode != GDPT_SHIFT_REFERENCE && cfg.shift_mode != GDPT_SHIFT_RECONNECT) throw std::runtime_error("gdpt_progressive_create: unknown shift_mode");
+        if (cfg.mode == GDPT_PROGRESSIVE_PATH && scene->view.num_lights <= 0) throw std::runtime_error("gdpt_progressive_create: the scene has no emitter to sample");
+        const int budget = cfg.budget_spp > 0 ? cfg.budget_spp : scene->scene_spp;
+        if (budget <= 0) throw std::runtime_error("gdpt_progressive_create: budget_spp must be > 0");
+        const int w = scene->view.cam.width, h = scene->view.cam.height;
+        if ((unsigned long long)w * (unsigned long long)h > (~0ull >> 1) / (unsigned long long)budget)
+            throw std::runtime_error("gdpt_progressive_create: width * height * budget_spp does not fit 63 bits");
+        if ((long long)w * h > (1LL << 29)) throw std::runtime_error("gdpt_progressive_create: film too large");
+        ck(hipSetDevice(scene->device), "hipSetDevice");
+        std::unique_ptr<GdptProgressive> s(new GdptProgressive());
+        s->scene = scene; s->device = scene->device; s->stream = (hipStream_t)stream;
+        s->mode = cfg.mode; s->shift = cfg.shift_mode; s->max_depth_override = cfg.max_depth_override;
+        s->nbuf = cfg.mode == GDPT_PROGRESSIVE_PATH ? 1 : 5;
+        s->w = w; s->h = h; s->budget = budget; s->elems = (size_t)w * h * 3;
+        for (auto *set : {s->pass, s->mean, s->m2})
+            for (int k = 0; k < s->nbuf; k++) ck(hipMalloc((void **)&set[k], s->elems * sizeof(double)), "hipMalloc(progressive planes)");
+        ck(hipMalloc((void **)&s->partials, 3 * prg::kMaxBlocks * sizeof(double)), "hipMalloc(progressive partials)");
+        ck(hipMalloc((void **)&s->d_est, sizeof(prg::Estimate)), "hipMalloc(progressive estimate)");
+        ck(hipHostMalloc((void **)&s->h_est, sizeof(prg::Estimate)), "hipHostMalloc(progressive estimate)");
+        for (auto &e : s->ev) ck(hipEventCreate(&e), "hipEventCreate");
+        *out = s.release();
+    });
+}
+
+void gdpt_progressive_free(GdptProgressive *session) {
+    if (!session) return;
+    hipSetDevice(session->device);
+    hipStreamSynchronize(session->stream);
+    delete session;
+}
+
+int gdpt_progressive_add_pass(GdptProgressive *session, int spp, GdptRenderStats *stats) {
+    return gdpt::guarded([&]() {
+        if (!session) throw std::runtime_error("gdpt_progressive_add_pass: null session");
+        add_pass(*session, spp, stats);
+    });
+}
+
+int gdpt_progressive_status(const GdptProgressive *session, GdptProgressiveStatus *status) {
+    return gdpt::guarded([&]() {
+        if (!session || !status) throw std::runtime_error("gdpt_progressive_status: null argument");
+        fill_status(*session, status);
+    });
+}
+
+int gdpt_progressive_read(GdptProgressive *session, int on_device, double *const means[5], double *const vars[5], double *const assembled_vars[3]) {
+    return gdpt::guarded([&]() {
+        if (!session) throw std::runtime_error("gdpt_progressive_read: null session");
+        GdptProgressive &s = *session;
+        if (s.passes < 1) throw std::runtime_error("gdpt_progressive_read: no pass has been added");
+        bool want_var = false;
+        for (int k = 0; k < 5; k++) {
+            if (k >= s.nbuf && ((means && means[k]) || (vars && vars[k]))) throw std::runtime_error("gdpt_progressive_read: an Integrator::Path session has the img plane only");
+            if (vars && vars[k]) want_var = true;
+        }
+        for (int k = 0; k < 3; k++) if (assembled_vars && assembled_vars[k]) {
+            if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_read: assembled variances need a GradPath session");
+            want_var = true;
+        }
+        if (want_var && s.passes < 2) throw std::runtime_error("gdpt_progressive_read: variances need at least 2 passes");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        if (want_var) {
+            const int nvar = s.nbuf == 5 ? 7 : 1;
+            for (int k = 0; k < nvar; k++) if (!s.var[k]) ck(hipMalloc((void **)&s.var[k], s.elems * sizeof(double)), "hipMalloc(progressive variances)");
+            prg::VarPlanes vp{};
+            for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
+            vp.vcx = s.var[5]; vp.vcy = s.var[6];
+            const double norm = (double)(s.passes - 1) * (double)s.done;
+            const int nb = std::max(1, std::min(4 * prg::kMaxBlocks, (int)((s.elems + prg::kBlock - 1) / prg::kBlock)));
+            if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+            else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+            ck(hipGetLastError(), "progressive variance launch");
+        }
+        for (int k = 0; k < s.nbuf; k++) {
+            if (means) copy_out(s, means[k], s.mean[k], on_device);
+            if (vars) copy_out(s, vars[k], s.var[k], on_device);
+        }
+        if (assembled_vars) {
+            copy_out(s, assembled_vars[0], s.var[0], on_device);
+            copy_out(s, assembled_vars[1], s.var[5], on_device);
+            copy_out(s, assembled_vars[2], s.var[6], on_device);
+        }
+        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive read)");
+    });
+}
+
+int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, const GdptReconParams *recon, int on_device, double *out,
+                                 GdptReconStats *stats) {
+    return gdpt::guarded([&]() {
+        if (!session || !out) throw std::runtime_error("gdpt_progressive_reconstruct: null argument");
+        GdptProgressive &s = *session;
+        if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct: an Integrator::Path session has no gradients (read its mean)");
+        if (s.passes < 1) throw std::runtime_error("gdpt_progressive_reconstruct: no pass has been added");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        for (double *&p : s.asm_buf) if (!p) ck(hipMalloc((void **)&p, s.elems * sizeof(double)), "hipMalloc(progressive assembly)");
+        gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
+        if (gdpt_reconstruct_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], dataCost, recon, s.asm_buf[3], s.stream, stats) != 0)
+            throw std::runtime_error(gdpt_last_error());
+        copy_out(s, out, s.asm_buf[3], on_device);
+        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");
+    });
+}
+
+int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass_spp, int max_passes, GdptProgressiveStatus *status) {
+    return gdpt::guarded([&]() {
+        if (!session) throw std::runtime_error("gdpt_progressive_run: null session");
+        if (pass_spp <= 0) throw std::runtime_error("gdpt_progressive_run: pass_spp must be > 0");
+        if (std::isnan(target_error)) throw std::runtime_error("gdpt_progressive_run: target_error is NaN");
+        GdptProgressive &s = *session;
+        auto reached = [&]() { return target_error > 0 && s.passes >= 2 && error_estimate(s) <= target_error; };
+        int added = 0;
+        for (;;) {
+            if (reached()) { s.stop_reason = GDPT_STOP_TARGET; break; }
+            if (s.done >= s.budget) { s.stop_reason = GDPT_STOP_BUDGET; break; }
+            if (max_passes > 0 && added >= max_passes) { s.stop_reason = GDPT_STOP_MAX_PASSES; break; }
+            add_pass(s, std::min(pass_spp, s.budget - s.done), nullptr);
+            added++;
+        }
+        fill_status(s, status);
+    });
+}
+
+} // extern "C"

@@ -74,9 +74,13 @@ struct KernelArgs {
     int row_begin, row_end, max_depth;
     int thresh_a, thresh_c;
     int count;
+    int stream_spp, first_sample;      // the spp samples are streams [first_sample, first_sample + spp) of the pixel's block of stream_spp
+                                       // PCG streams (include/gdpt.h: GdptSampleWindow); a plain render has stream_spp = spp, first_sample = 0.
+                                       // The kernels that pull work items find first_sample in chunk_begin and do not read the field
     int stack_levels;                  // scenes walked from HBM: traversal-stack slots per lane in dynamic LDS (= the tree's bound)
     int replay_per_step;               // two-sided lane machine: replay iterations of an offset per wave step (>= 1)
-    int num_chunks;                    // work items per pixel: chunk c covers samples [chunk_begin[c], chunk_begin[c+1])
+    int num_chunks;                    // work items per pixel: chunk c covers streams [chunk_begin[c], chunk_begin[c+1]) of the pixel's block
+                                       // (= first_sample + the plan's sample range)
     long long num_slots;               // pixel slots of the band: tiles * 256 (ragged edge tiles keep all 256)
     long long num_items;               // num_slots * num_chunks (< 2^32); item = chunk * num_slots + slot ("tier-major")
     double *partials;                  // [num_items][16]: 15 sums (r, dx0, dy0, dx1, dy1 as xyz) + pad, 128-B records
@@ -1032,7 +1036,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             my_item = got_item;
             int s0, s1;
             const bool inside = item_to_pixel(a, W, (unsigned)my_item, x, y, s0, s1, s_chunks);
-            base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+            base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;     // (s0, s1 carry the window's first_sample)
             L.s = s0; L.s_end = s1;
             if (inside && s0 < s1) act = ACT_PRIMARY_RAY;       // (an empty slot of a ragged edge tile stays S_DONE and is published as zeros)
         }
@@ -1260,7 +1264,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_eager(DevSceneView sv, 
     TraceCounters tc = {0, 0, 0, 0, 0, 0};
     if (valid) {
         const int s0 = (int)(((long long)c * a.spp) >> a.log2k), s1 = (int)(((long long)(c + 1) * a.spp) >> a.log2k);
-        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp + (unsigned long long)a.first_sample;
         for (int s = s0; s < s1; s++) {
             Pcg rng = pcg_init(base + (unsigned long long)s);
             SampleOut so;

@@ -66,6 +66,7 @@ Route choose_route(const RouteInputs &in);
 struct RenderLaunch {
     Route route;                   // choose_route
     int spp;
+    int stream_spp, first_sample;  // sample window (GdptSampleWindow); a plain render has stream_spp = spp, first_sample = 0
     int row_begin, row_end;
     int max_depth;                 // effective (scene value or override)
     double *img, *cx0, *cy0, *cx1, *cy1;   // device, W*H*3 each (Path: img only)

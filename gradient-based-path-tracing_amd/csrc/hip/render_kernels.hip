@@ -112,7 +112,7 @@ static dim3 static_mapping(gd::KernelArgs &a, const RenderLaunch &rl, int W, int
 // and the grid.
 static dim3 start_queue(gd::KernelArgs &a, const RenderLaunch &rl, int W, hipStream_t stream) {
     a.num_chunks = rl.plan.n;
-    for (int c = 0; c <= rl.plan.n; c++) a.chunk_begin[c] = rl.plan.begin[c];
+    for (int c = 0; c <= rl.plan.n; c++) a.chunk_begin[c] = rl.first_sample + rl.plan.begin[c];   // a sample's index in its pixel's stream block
     a.tiles_x = (W + 15) / 16;
     a.num_slots = band_slots(W, rl.row_end - rl.row_begin);
     a.num_items = a.num_slots * rl.plan.n;
@@ -204,7 +204,7 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream) {
     const Route r = rl.route;
     gd::KernelArgs a{};
-    a.spp = rl.spp; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
+    a.spp = rl.spp; a.stream_spp = rl.stream_spp; a.first_sample = rl.first_sample; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
     a.img = rl.img; a.cx0 = rl.cx0; a.cy0 = rl.cy0; a.cx1 = rl.cx1; a.cy1 = rl.cy1; a.counters = rl.counters;
     // trace phase is left when this fraction (/256) of the rays that entered it is still unfinished
     a.thresh_a = rl.thresh_a >= 0 ? (rl.thresh_a > 255 ? 255 : rl.thresh_a) : 64;
@@ -213,6 +213,7 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
     a.count = rl.count_traversal ? 1 : 0;
     const int W = sv.cam.width, rows = rl.row_end - rl.row_begin;
     if (W <= 0 || rows <= 0 || rl.spp <= 0) throw std::runtime_error("launch_render: empty image band or spp <= 0");
+    if (rl.first_sample < 0 || (long long)rl.first_sample + rl.spp > (long long)rl.stream_spp) throw std::runtime_error("launch_render: sample window outside its stream block");
     const int ntx = (W + 15) / 16, nty = (sv.cam.height + 15) / 16;    // tile streams: one lane per 16x16 tile
     dim3 grid((unsigned)((ntx * nty + 63) / 64));
     if (is_persistent(r)) {

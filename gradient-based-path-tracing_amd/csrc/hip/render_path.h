@@ -282,7 +282,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_path_eager(DevSceneView sv, Ke
     D3 sum = splat(0);
     if (valid) {
         const int s0 = (int)(((long long)c * a.spp) >> a.log2k), s1 = (int)(((long long)(c + 1) * a.spp) >> a.log2k);
-        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp + (unsigned long long)a.first_sample;
         for (int s = s0; s < s1; s++) {
             Pcg rng = pcg_init(base + (unsigned long long)s);
             const D3 r = path_sample(sv, tx, a.max_depth, x, y, rng, lc, tc);
@@ -578,7 +578,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_path_persistent(DevSceneView s
             my_item = got_item;
             int s0, s1;
             const bool inside = item_to_pixel(a, W, (unsigned)my_item, x, y, s0, s1, a.chunk_begin);
-            base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+            base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;
             L.s = s0; L.s_end = s1;
             L.st = (inside && s0 < s1) ? P_START : P_DONE;
         }

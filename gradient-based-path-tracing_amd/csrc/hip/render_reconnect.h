@@ -229,7 +229,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_reconnect(DevSceneView 
     TraceCounters tc = {0, 0, 0, 0, 0, 0};
     if (valid) {
         const int s0 = (int)(((long long)c * a.spp) >> a.log2k), s1 = (int)(((long long)(c + 1) * a.spp) >> a.log2k);
-        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp + (unsigned long long)a.first_sample;
         for (int s = s0; s < s1; s++) {
             Pcg rng = pcg_init(base + (unsigned long long)s);
             grad_sample_reconnect<TC, LAMBERT>(sv, tx, a.max_depth, x, y, rng, (double)a.spp, acc, lc, tc);

@@ -212,7 +212,7 @@ __global__ __launch_bounds__(kBlock) void gdpt_wf_step(DevSceneView sv, KernelAr
             tv.best.t = h0.x; tv.best.u = h0.y; tv.best.v = h0.z; tv.best.gid = (int)__float_as_uint(h0.w);
             if (tv.best.gid >= sv.num_tris) { const float4 h1 = w.hits[2 * slot + 1]; tv.best.ngx = h1.x; tv.best.ngy = h1.y; tv.best.ngz = h1.z; }
         }
-        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.spp;
+        const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;
         L.rng_inc = ((base + (unsigned long long)L.s) << 1u) | 1u;       // pcg_init's increment of the sample in flight
 
         lane_step<LAMBERT, false>(sv, tx, a.max_depth, spp, x, y, base, L, tv, lp, acc, lc, tc);

@@ -81,7 +81,8 @@ namespace gdpt {
 // Own BVH build + HBM upload of a flattened scene (replaces Scene::Scene, src/scene.cpp:4-53).
 void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc);
 // Enqueues one five-buffer render of rows [params->row_begin, row_end) on `stream`; waits only when `stats` is given.
+// `window` (nullable): the samples are a window of a larger stream block (include/gdpt.h: GdptSampleWindow).
 void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
                         double *img, double *cx0, double *cy0, double *cx1, double *cy1,
-                        hipStream_t stream, GdptRenderStats *stats);
+                        hipStream_t stream, GdptRenderStats *stats, const GdptSampleWindow *window = nullptr);
 } // namespace gdpt

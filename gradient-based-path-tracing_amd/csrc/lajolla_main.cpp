@@ -18,6 +18,10 @@
 //   --reconstruct l2|l1   final reconstruction: l2 = the reference's fourierSolve (default), l1 = IRLS, robust to fireflies in
 //                 the gradient buffers (include/gdpt.h: gdpt_reconstruct); --irls-iters N reweighted rounds (default 20),
 //                 --irls-eps INIT[,DECAY[,FLOOR]] (default 0.05,0.5,1e-3). Single device only
+//   --pass-spp N  progressive session (include/gdpt.h: gdpt_progressive_*): passes of N samples per pixel up to the budget --spp; the
+//                 output is the session's reconstruction (Integrator::Path scenes: the mean). --target-error E stops at the first
+//                 pass (from the second on) whose estimated relative RMSE of the primal is <= E; --variance FILE writes the
+//                 variance of the primal mean. Single device, --rng sample only
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -34,7 +38,9 @@ int main(int argc, char *argv[]) {
         return 0;
     }
     int num_threads = 0, spp = 0, device = 0, rng = GDPT_RNG_SAMPLE, shift = GDPT_SHIFT_REFERENCE;
-    int film_w = 0, film_h = 0, plan_rows = 0;
+    int film_w = 0, film_h = 0, plan_rows = 0, pass_spp = 0;
+    double target_error = 0.0;
+    std::string variance_file = "";
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
     GdptReconParams recon{};          // norm == GDPT_RECON_L2: the reference's reconstruction
     double alpha = 0.04;
@@ -79,6 +85,9 @@ int main(int argc, char *argv[]) {
             else { std::cerr << "unknown --exchange " << v << " (rccl | peer)" << std::endl; return 2; }
         }
         else if (a == "--plan-rows") plan_rows = std::stoi(next());
+        else if (a == "--pass-spp") { pass_spp = std::stoi(next()); if (pass_spp <= 0) { std::cerr << "--pass-spp must be > 0" << std::endl; return 2; } }
+        else if (a == "--target-error") target_error = std::stod(next());
+        else if (a == "--variance") variance_file = next();
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
         else if (a == "--shift") {        // extension: "reconnect" = GDPT_SHIFT_RECONNECT (include/gdpt.h); default = the reference's offsets
             std::string v = next();
@@ -107,6 +116,9 @@ int main(int argc, char *argv[]) {
         else filenames.push_back(a);
     }
     if (recon.norm == GDPT_RECON_L1 && multi.num_devices > 0) { std::cerr << "--reconstruct l1 is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
+    if (pass_spp > 0 && multi.num_devices > 0) { std::cerr << "--pass-spp is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
+    if (pass_spp > 0 && rng == GDPT_RNG_TILE) { std::cerr << "--pass-spp needs --rng sample (the tile streams have no sample window)" << std::endl; return 2; }
+    if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
     (void)num_threads;
 
     using clock = std::chrono::system_clock;
@@ -142,7 +154,31 @@ int main(int argc, char *argv[]) {
         GdptReconStats cs{};
         // render() dispatches on the integrator (src/render.cpp:374-392)
         int rc;
-        if (sharded) {
+        GdptProgressiveStatus prog{};
+        if (pass_spp > 0) {
+            const bool path = desc->integrator == GDPT_INTEGRATOR_PATH;
+            GdptProgressiveConfig cfg{};
+            cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = shift; cfg.budget_spp = spp;
+            GdptProgressive *session = nullptr;
+            rc = gdpt_progressive_create(scene, &cfg, nullptr, &session);
+            if (rc == 0) rc = gdpt_progressive_run(session, target_error, pass_spp, 0, &prog);
+            double *means[5] = {path ? image.data() : nullptr, nullptr, nullptr, nullptr, nullptr};
+            if (rc == 0 && path) rc = gdpt_progressive_read(session, 0, means, nullptr, nullptr);
+            if (rc == 0 && !path) {
+                rc = gdpt_progressive_reconstruct(session, alpha, recon.norm == GDPT_RECON_L1 ? &recon : nullptr, 0, image.data(), &cs);
+                ps.iterations = cs.cg_iters_total; ps.solve_ms = cs.solve_ms;
+            }
+            if (rc == 0 && !variance_file.empty()) {
+                std::vector<double> variance((size_t)w * h * 3);
+                double *vars[5] = {variance.data(), nullptr, nullptr, nullptr, nullptr};
+                rc = gdpt_progressive_read(session, 0, nullptr, vars, nullptr);
+                if (rc == 0) rc = gdpt_imwrite(variance_file.c_str(), w, h, variance.data());
+            }
+            std::string err = rc != 0 ? gdpt_last_error() : "";
+            gdpt_progressive_free(session);
+            if (rc != 0) { std::cerr << "terminate: " << err << std::endl; return 134; }
+            rs = prog.totals;
+        } else if (sharded) {
             rc = gdpt_multi_gradient_path_render(mscene, &p, alpha, image.data(), nullptr, nullptr, nullptr, nullptr, nullptr, &rs, &ms);
             ps.solve_ms = ms.solve_ms; ps.solver = GDPT_SOLVER_DEFAULT;
         } else if (desc->integrator == GDPT_INTEGRATOR_PATH) rc = gdpt_path_render(scene, &p, image.data(), &rs);
@@ -168,6 +204,12 @@ int main(int argc, char *argv[]) {
         std::cout << "[gdpt] " << rs.samples << " samples, " << rs.rays << " rays, render " << rs.render_ms << " ms ("
                   << (rs.render_ms > 0 ? rs.samples / rs.render_ms / 1e3 : 0.0) << " Msamples/s), Poisson " << ps.iterations
                   << " CG iterations " << ps.solve_ms << " ms, non-finite samples " << rs.nonfinite_samples << std::endl;
+        if (pass_spp > 0) {
+            static const char *const why[] = {"none", "target", "budget", "max_passes"};
+            std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << prog.budget_spp
+                      << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
+                      << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
+        }
         if (sharded) {
             std::cout << "[gdpt] " << ms.num_devices << " row bands (" << (ms.exchange == GDPT_EXCHANGE_RCCL ? "RCCL" : "peer copies") << "): render";
             for (int k = 0; k < ms.num_devices; k++) std::cout << " " << ms.render_ms[k];

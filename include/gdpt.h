@@ -166,6 +166,12 @@ typedef struct GdptRenderParams {
     int32_t reserved;          /* 0 */
 } GdptRenderParams;
 
+/* A render's spp samples as a window of a larger block of PCG streams (GDPT_RNG_SAMPLE only): sample s of pixel (x,y) draws from
+ * stream (y*W + x)*stream_spp + first_sample + s, and first_sample + spp <= stream_spp. The buffers stay means over the window's spp
+ * samples. Windows that tile [0, stream_spp) hold, together, exactly the samples of the one-shot render at spp = stream_spp;
+ * stream_spp = spp, first_sample = 0 IS that render. W*H*stream_spp must fit 63 bits. */
+typedef struct GdptSampleWindow { int32_t stream_spp, first_sample; } GdptSampleWindow;
+
 typedef struct GdptRenderStats {
     uint64_t samples;          /* grad_path_tracing calls */
     uint64_t rays;             /* closest-hit queries (5 primaries + 1 per bounce; the reference's 4 tfar=0 rays are omitted) */
@@ -237,6 +243,14 @@ int gdpt_render_device(GdptScene *scene, const GdptRenderParams *params,
 int gdpt_path_render(GdptScene *scene, const GdptRenderParams *params, double *img, GdptRenderStats *stats /* nullable */);
 int gdpt_path_render_device(GdptScene *scene, const GdptRenderParams *params, double *d_img,
                             void *stream, GdptRenderStats *stats /* nullable */);
+
+/* gdpt_render_device / gdpt_path_render_device on a sample window. window == NULL forwards to the plain call. Refused with an error:
+ * GDPT_RNG_TILE (one stream per tile, no window), a window that leaves [0, stream_spp), a stream_spp too large for the film. */
+int gdpt_render_window_device(GdptScene *scene, const GdptRenderParams *params, const GdptSampleWindow *window /* nullable */,
+                              double *d_img, double *d_cx0, double *d_cy0, double *d_cx1, double *d_cy1,
+                              void *stream, GdptRenderStats *stats /* nullable */);
+int gdpt_path_render_window_device(GdptScene *scene, const GdptRenderParams *params, const GdptSampleWindow *window /* nullable */,
+                                   double *d_img, void *stream, GdptRenderStats *stats /* nullable */);
 
 /* c=img; cx=cx0(x,y)+cx1(x-1,y); cy=cy0(x,y)+cy1(x,y-1)  (src/render.cpp:340-350). Device pointers. */
 int gdpt_assemble_device(int width, int height,
@@ -336,6 +350,62 @@ int gdpt_gradient_path_render_recon(GdptScene *scene, const GdptRenderParams *pa
                                     const GdptReconParams *recon /* nullable */, double *out_image,
                                     double *img, double *cx0, double *cy0, double *cx1, double *cy1,
                                     GdptRenderStats *rstats /* nullable */, GdptReconStats *cstats /* nullable */);
+
+/* ---- progressive rendering: accumulated passes with per-pixel variance (not part of the reference) ----
+ * A session renders a scene in passes. Pass k draws the window [done, done + n_k) of every pixel's block of budget_spp streams, so
+ * a session that spends its budget has drawn exactly the samples of the one-shot render at spp = budget_spp. Each pass (a mean
+ * m over its n samples, per buffer component) is folded into a running mean and a sum of weighted squared deviations
+ * (West 1979):   W += n;  d = m - mean;  mean += (n/W) d;  M2 += n d (m - mean_new).
+ * After K passes, E[M2] = (K-1) sigma^2 for per-sample variance sigma^2, so the variance of the running mean is estimated by
+ *     var_mean = M2 / ((K-1) done)                                                          (defined from K >= 2)
+ * and the session's error estimate is the estimated relative RMSE of the primal mean,
+ *     sqrt( sum var_mean(img) / sum mean(img)^2 )   over pixels and channels.
+ * A non-finite pass value propagates into the mean, as everywhere in this library; pixels whose img mean or M2 is not finite are
+ * left out of both sums and counted. The sums are reduced in a fixed order: the same session gives the same bits.
+ * The session holds all its planes in HBM and uses the scene handle's launch scratch: one render per scene handle at a time. */
+enum { GDPT_PROGRESSIVE_GRADPATH = 0, GDPT_PROGRESSIVE_PATH = 1 };
+enum { GDPT_STOP_NONE = 0, GDPT_STOP_TARGET = 1, GDPT_STOP_BUDGET = 2, GDPT_STOP_MAX_PASSES = 3 };
+typedef struct GdptProgressiveConfig {
+    int32_t mode;              /* GDPT_PROGRESSIVE_*: GradPath (five buffers) or Integrator::Path (img alone) */
+    int32_t shift_mode;        /* GDPT_SHIFT_* (GradPath) */
+    int32_t budget_spp;        /* samples per pixel the session may draw: the stream_spp of every pass. <= 0: the scene's */
+    int32_t max_depth_override;/* 0 = use scene */
+} GdptProgressiveConfig;
+typedef struct GdptProgressiveStatus {
+    int32_t passes;            /* K */
+    int32_t spp_done;          /* samples per pixel so far */
+    int32_t budget_spp;
+    int32_t stop_reason;       /* GDPT_STOP_* of the last gdpt_progressive_run (GDPT_STOP_NONE before one) */
+    double error_estimate;     /* NaN while K < 2 */
+    uint64_t pixels_left_out;  /* of the error estimate (non-finite) */
+    double fold_ms;            /* device time of the last pass's fold launches, HIP events */
+    GdptRenderStats totals;    /* counters and render_ms summed over the passes; node_bytes of the last pass */
+} GdptProgressiveStatus;
+typedef struct GdptProgressive GdptProgressive;   /* opaque */
+
+/* `stream` (hipStream_t as void*, NULL = default) carries all of the session's work. The scene must outlive the session. */
+int gdpt_progressive_create(GdptScene *scene, const GdptProgressiveConfig *config, void *stream, GdptProgressive **out);
+void gdpt_progressive_free(GdptProgressive *session);
+/* Renders the window [done, done + spp) into the pass buffers, folds it in (one launch over the film), advances done. Blocking.
+ * A pass beyond the budget, or spp <= 0, is refused. stats (nullable): this pass's. */
+int gdpt_progressive_add_pass(GdptProgressive *session, int spp, GdptRenderStats *stats);
+int gdpt_progressive_status(const GdptProgressive *session, GdptProgressiveStatus *status);
+/* Copies out W*H*3 doubles per plane; any pointer may be NULL; on_device != 0: the pointers are device memory. Blocking.
+ *   means[k], vars[k]: running mean and variance of the mean of buffer k = img, cx0, cy0, cx1, cy1 (Path: k = 0 only, the
+ *                      others must be NULL). Variances need K >= 2.
+ *   assembled_vars[3]: variances of the assembled c, cx, cy. cx0(x,y) and cx1(x-1,y) come from different pixels' streams and are
+ *                      independent: var(cx)(x,y) = var(cx0)(x,y) + var(cx1)(x-1,y), var(cy)(x,y) = var(cy0)(x,y) + var(cy1)(x,y-1)
+ *                      (the second term absent at x = 0 / y = 0); var(c) = var(img). GradPath only. */
+int gdpt_progressive_read(GdptProgressive *session, int on_device, double *const means[5], double *const vars[5],
+                          double *const assembled_vars[3]);
+/* gdpt_assemble_device on the running means, then gdpt_reconstruct_device (recon NULL: L2) into `out` (W*H*3 doubles, host, or
+ * device with on_device != 0). May be called after any pass: a preview. GradPath only. Blocking. */
+int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, const GdptReconParams *recon /* nullable */,
+                                 int on_device, double *out, GdptReconStats *stats /* nullable */);
+/* Adds passes of pass_spp samples (the last one shortened to the budget) until the budget is spent (GDPT_STOP_BUDGET),
+ * max_passes passes were added by this call (GDPT_STOP_MAX_PASSES; max_passes <= 0: no limit), or K >= 2 and the error estimate is
+ * <= target_error (GDPT_STOP_TARGET; target_error <= 0: no target). Blocking; status (nullable) as gdpt_progressive_status. */
+int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass_spp, int max_passes, GdptProgressiveStatus *status);
 
 /* ---- several devices of one node: the tile loop sharded into row bands ----
  * Replaces the reference's only parallelism, parallel_for over 16x16 tiles on a std::thread pool
