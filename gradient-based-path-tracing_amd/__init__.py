@@ -84,6 +84,10 @@ def lib():
                                               C.POINTER(defs.GdptReconStats)]
         L.gdpt_gradient_path_render_recon.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.c_double, C.POINTER(defs.GdptReconParams),
                                                       dp, dp, dp, dp, dp, dp, C.POINTER(defs.GdptRenderStats), C.POINTER(defs.GdptReconStats)]
+        wp, wst = C.POINTER(defs.GdptWeightedReconParams), C.POINTER(defs.GdptWeightedReconStats)
+        L.gdpt_reconstruct_weighted.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, C.c_double, wp, dp, C.POINTER(vp), wst]
+        L.gdpt_reconstruct_weighted_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_double, wp, vp, C.POINTER(vp), vp, wst]
+        L.gdpt_progressive_reconstruct_weighted.argtypes = [vp, C.c_double, wp, C.c_int, vp, C.POINTER(vp), wst]
         L.gdpt_imwrite.argtypes = [C.c_char_p, C.c_int, C.c_int, dp]
         L.gdpt_imread.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(dp)]
         L.gdpt_image_free.argtypes = [dp]
@@ -347,6 +351,24 @@ class Progressive:
         _check(lib().gdpt_progressive_reconstruct(self.handle, float(alpha), C.byref(p), 0, C.c_void_p(out.ctypes.data), C.byref(st)))
         return out, st
 
+    def reconstruct_weighted(self, alpha=0.04, norm=defs.RECON_L2, conf_floor=0.0, confidence=False, out_ptr=None, confidence_ptrs=None,
+                             **params):
+        """The variance-weighted reconstruction of the running means on the session's assembled variances
+        (gdpt_progressive_reconstruct_weighted; from 2 passes on, GradPath): RECON_L2 = generalised least squares, RECON_L1 = its
+        IRLS form (`params`: the keywords of recon_params). Returns (HxWx3 image, GdptWeightedReconStats), with `confidence=True`
+        (image, HxWx3 confidences of the data, x-edge and y-edge rows, stats); with `out_ptr` (and `confidence_ptrs`, 3 device
+        addresses) everything stays in device memory and the stats alone are returned."""
+        p, st = weighted_recon_params(norm, conf_floor, **params), defs.GdptWeightedReconStats()
+        if out_ptr is not None:
+            _check(lib().gdpt_progressive_reconstruct_weighted(self.handle, float(alpha), C.byref(p), 1, C.c_void_p(int(out_ptr)),
+                                                               _ptr_table(confidence_ptrs), C.byref(st)))
+            return st
+        out = np.empty(self.shape, dtype=np.float64)
+        planes = [np.empty(self.shape[:2], dtype=np.float64) for _ in range(3)] if confidence else None
+        _check(lib().gdpt_progressive_reconstruct_weighted(self.handle, float(alpha), C.byref(p), 0, C.c_void_p(out.ctypes.data),
+                                                           _ptr_table([a.ctypes.data for a in planes] if confidence else None), C.byref(st)))
+        return (out, np.stack(planes, axis=2), st) if confidence else (out, st)
+
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
         <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
@@ -406,6 +428,51 @@ def reconstruct_device(width, height, c_ptr, gx_ptr, gy_ptr, out_ptr, dataCost=0
     _check(lib().gdpt_reconstruct_device(int(width), int(height), C.c_void_p(int(c_ptr)), C.c_void_p(int(gx_ptr)), C.c_void_p(int(gy_ptr)),
                                          float(dataCost), C.byref(p), C.c_void_p(int(out_ptr)), C.c_void_p(int(stream) if stream else 0),
                                          C.byref(st)))
+    return st
+
+
+def weighted_recon_params(norm=defs.RECON_L2, conf_floor=0.0, **params):
+    """GdptWeightedReconParams (include/gdpt.h): RECON_L2 = weighted least squares (one solve), RECON_L1 = weighted IRLS; conf_floor 0
+    selects the default 0.05; `params`: the keywords of recon_params."""
+    p = defs.GdptWeightedReconParams()
+    p.recon = recon_params(norm, **params)
+    p.conf_floor = float(conf_floor)
+    return p
+
+
+def _ptr_table(ptrs):
+    """3 addresses (None or 0 entries: not wanted) as the `double *const [3]` of the C ABI; None: a NULL table."""
+    if ptrs is None:
+        return None
+    arr = (C.c_void_p * 3)()
+    for i in range(3):
+        arr[i] = int(ptrs[i]) if i < len(ptrs) and ptrs[i] else None
+    return arr
+
+
+def reconstruct_weighted(width, height, c, gx, gy, var_c, var_gx, var_gy, dataCost=0.04, norm=defs.RECON_L2, conf_floor=0.0,
+                         confidence=False, **params):
+    """Variance-weighted reconstruction on the GPU (gdpt_reconstruct_weighted): every residual row weighted by a confidence
+    s / (v + conf_floor s) from the variance v of its input; RECON_L2 = one weighted solve, RECON_L1 = weighted IRLS (`params`: the
+    keywords of recon_params). Inputs HxWx3 float64. Returns (image, GdptWeightedReconStats), or with `confidence=True`
+    (image, HxWx3 confidences of the data, x-edge and y-edge rows, stats)."""
+    a = [np.ascontiguousarray(x, dtype=np.float64).reshape(height, width, 3) for x in (c, gx, gy, var_c, var_gx, var_gy)]
+    out = np.empty((height, width, 3), dtype=np.float64)
+    planes = [np.empty((height, width), dtype=np.float64) for _ in range(3)] if confidence else None
+    p, st = weighted_recon_params(norm, conf_floor, **params), defs.GdptWeightedReconStats()
+    _check(lib().gdpt_reconstruct_weighted(int(width), int(height), *[_dp(x) for x in a], float(dataCost), C.byref(p), _dp(out),
+                                           _ptr_table([x.ctypes.data for x in planes] if confidence else None), C.byref(st)))
+    return (out, np.stack(planes, axis=2), st) if confidence else (out, st)
+
+
+def reconstruct_weighted_device(width, height, c_ptr, gx_ptr, gy_ptr, var_c_ptr, var_gx_ptr, var_gy_ptr, out_ptr, dataCost=0.04,
+                                norm=defs.RECON_L2, conf_floor=0.0, confidence_ptrs=None, stream=None, **params):
+    """reconstruct_weighted() on device addresses (gdpt_reconstruct_weighted_device); `confidence_ptrs`: 3 device addresses of W*H
+    doubles (or None). Returns GdptWeightedReconStats. Waits for `stream`."""
+    p, st = weighted_recon_params(norm, conf_floor, **params), defs.GdptWeightedReconStats()
+    ins = [C.c_void_p(int(x)) for x in (c_ptr, gx_ptr, gy_ptr, var_c_ptr, var_gx_ptr, var_gy_ptr)]
+    _check(lib().gdpt_reconstruct_weighted_device(int(width), int(height), *ins, float(dataCost), C.byref(p), C.c_void_p(int(out_ptr)),
+                                                  _ptr_table(confidence_ptrs), C.c_void_p(int(stream) if stream else 0), C.byref(st)))
     return st
 
 

@@ -99,6 +99,15 @@ class GdptReconStats(C.Structure):
                 ("energy_first", C.c_double), ("energy_last", C.c_double), ("rel_residual_last", C.c_double), ("solve_ms", C.c_double)]
 
 
+class GdptWeightedReconParams(C.Structure):
+    _fields_ = [("recon", GdptReconParams), ("conf_floor", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
+class GdptWeightedReconStats(C.Structure):
+    _fields_ = [("recon", GdptReconStats), ("scale_data", C.c_double), ("scale_grad", C.c_double),
+                ("rows_dropped", C.c_uint64), ("pixels_isolated", C.c_uint64)]
+
+
 PROGRESSIVE_GRADPATH, PROGRESSIVE_PATH = 0, 1
 STOP_NONE, STOP_TARGET, STOP_BUDGET, STOP_MAX_PASSES = 0, 1, 2, 3
 STOP_NAMES = {STOP_NONE: "none", STOP_TARGET: "target", STOP_BUDGET: "budget", STOP_MAX_PASSES: "max_passes"}

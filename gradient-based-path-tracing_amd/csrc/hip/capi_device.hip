@@ -7,6 +7,7 @@
 #include "../host/tri_precompute.h"
 #include "poisson_kernels.h"
 #include "recon_l1.h"
+#include "recon_weighted.h"
 #include "render_kernels.h"
 #include "scene_internal.h"
 
@@ -602,6 +603,27 @@ void fill_recon_stats_l2(GdptReconStats *s, double solve_ms) {
     s->norm = GDPT_RECON_L2; s->solve_ms = solve_ms;
 }
 
+// GdptWeightedReconParams (nullable) -> the solver's parameters; GDPT_RECON_L2 here means round 0 alone
+gdpt::ReconL1Params resolve_weighted(const GdptWeightedReconParams *in, double *conf_floor, int *norm) {
+    GdptReconParams rp = in ? in->recon : GdptReconParams{};
+    *norm = rp.norm;
+    if (rp.norm != GDPT_RECON_L2 && rp.norm != GDPT_RECON_L1) throw std::runtime_error("gdpt_reconstruct_weighted: unknown norm (GDPT_RECON_L2 | GDPT_RECON_L1)");
+    rp.norm = GDPT_RECON_L1;
+    gdpt::ReconL1Params p = resolve_recon(rp);
+    if (*norm == GDPT_RECON_L2) p.irls_iters = 0;
+    const double d = in ? in->conf_floor : 0.0;
+    if (!std::isfinite(d) || d < 0) throw std::runtime_error("gdpt_reconstruct_weighted: conf_floor must be finite and > 0 (0 = default 0.05)");
+    *conf_floor = d > 0 ? d : 0.05;
+    return p;
+}
+void fill_weighted_stats(GdptWeightedReconStats *s, int norm, const gdpt::ReconWeightedResult &r) {
+    if (!s) return;
+    *s = GdptWeightedReconStats{};
+    fill_recon_stats(&s->recon, r.recon);
+    s->recon.norm = norm;
+    s->scale_data = r.scale_data; s->scale_grad = r.scale_grad; s->rows_dropped = r.rows_dropped; s->pixels_isolated = r.pixels_isolated;
+}
+
 } // namespace
 
 extern "C" {
@@ -868,6 +890,51 @@ int gdpt_reconstruct(int width, int height, const double *c, const double *gx, c
             for (int k = 0; k < 3; k++) ck(hipMemcpy(d[k], host[k], bytes, hipMemcpyHostToDevice), "hipMemcpy");
             fill_recon_stats(stats, gdpt::recon_l1_device(width, height, d[0], d[1], d[2], dataCost, p, d[3], nullptr));
             ck(hipMemcpy(out, d[3], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+        } catch (...) { cleanup(); throw; }
+        cleanup();
+    });
+}
+
+int gdpt_reconstruct_weighted_device(int width, int height, const double *d_c, const double *d_gx, const double *d_gy,
+                                     const double *d_var_c, const double *d_var_gx, const double *d_var_gy, double dataCost,
+                                     const GdptWeightedReconParams *params, double *d_out, double *const d_confidence[3], void *stream,
+                                     GdptWeightedReconStats *stats) {
+    return gdpt::guarded([&]() {
+        if (!d_c || !d_gx || !d_gy || !d_out) throw std::runtime_error("gdpt_reconstruct_weighted_device: null buffer");
+        if (!d_var_c || !d_var_gx || !d_var_gy) throw std::runtime_error("gdpt_reconstruct_weighted_device: null variance plane");
+        double conf_floor = 0;
+        int norm = 0;
+        const gdpt::ReconL1Params p = resolve_weighted(params, &conf_floor, &norm);
+        fill_weighted_stats(stats, norm, gdpt::recon_weighted_device(width, height, d_c, d_gx, d_gy, d_var_c, d_var_gx, d_var_gy, dataCost, p, conf_floor,
+                                                                     d_out, d_confidence, (hipStream_t)stream));
+    });
+}
+
+int gdpt_reconstruct_weighted(int width, int height, const double *c, const double *gx, const double *gy, const double *var_c,
+                              const double *var_gx, const double *var_gy, double dataCost, const GdptWeightedReconParams *params, double *out,
+                              double *const confidence[3], GdptWeightedReconStats *stats) {
+    return gdpt::guarded([&]() {
+        if (!c || !gx || !gy || !out) throw std::runtime_error("gdpt_reconstruct_weighted: null buffer");
+        if (!var_c || !var_gx || !var_gy) throw std::runtime_error("gdpt_reconstruct_weighted: null variance plane");
+        if (width < 2 || height < 2) throw std::runtime_error("gdpt_reconstruct_weighted: width and height must be >= 2");
+        if (!(dataCost > 0) || !std::isfinite(dataCost)) throw std::runtime_error("gdpt_reconstruct_weighted: dataCost must be finite and > 0");
+        const double *host[6] = {c, gx, gy, var_c, var_gx, var_gy};
+        for (const double *in : host) if (out == in) throw std::runtime_error("gdpt_reconstruct_weighted: the output must not alias an input");
+        double conf_floor = 0;
+        int norm = 0;
+        const gdpt::ReconL1Params p = resolve_weighted(params, &conf_floor, &norm);
+        int ndev = 0;
+        ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
+        if (ndev <= 0) throw std::runtime_error("gdpt_reconstruct_weighted: no HIP device visible (this library has no CPU fallback)");
+        const size_t bytes = (size_t)width * height * 3 * sizeof(double);
+        double *d[7] = {};
+        auto cleanup = [&]() { for (auto q : d) if (q) hipFree(q); };
+        try {
+            for (auto &q : d) ck(hipMalloc((void **)&q, bytes), "hipMalloc(reconstruct io)");
+            for (int k = 0; k < 6; k++) ck(hipMemcpy(d[k], host[k], bytes, hipMemcpyHostToDevice), "hipMemcpy");
+            fill_weighted_stats(stats, norm, gdpt::recon_weighted_device(width, height, d[0], d[1], d[2], d[3], d[4], d[5], dataCost, p, conf_floor, d[6],
+                                                                         confidence, nullptr));
+            ck(hipMemcpy(out, d[6], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
         } catch (...) { cleanup(); throw; }
         cleanup();
     });

@@ -222,6 +222,20 @@ void copy_out(const GdptProgressive &s, double *dst, const double *src, int on_d
     ck(hipMemcpyAsync(dst, src, s.elems * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(progressive read)");
 }
 
+// the read-out planes s.var[0..4] and, for a GradPath session, the assembled s.var[5], s.var[6]; enqueued on the session's stream
+void compute_variances(GdptProgressive &s) {
+    const int nvar = s.nbuf == 5 ? 7 : 1;
+    for (int k = 0; k < nvar; k++) if (!s.var[k]) ck(hipMalloc((void **)&s.var[k], s.elems * sizeof(double)), "hipMalloc(progressive variances)");
+    prg::VarPlanes vp{};
+    for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
+    vp.vcx = s.var[5]; vp.vcy = s.var[6];
+    const double norm = (double)(s.passes - 1) * (double)s.done;
+    const int nb = std::max(1, std::min(4 * prg::kMaxBlocks, (int)((s.elems + prg::kBlock - 1) / prg::kBlock)));
+    if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+    else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+    ck(hipGetLastError(), "progressive variance launch");
+}
+
 } // namespace
 
 extern "C" {
@@ -292,18 +306,7 @@ int gdpt_progressive_read(GdptProgressive *session, int on_device, double *const
         }
         if (want_var && s.passes < 2) throw std::runtime_error("gdpt_progressive_read: variances need at least 2 passes");
         ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        if (want_var) {
-            const int nvar = s.nbuf == 5 ? 7 : 1;
-            for (int k = 0; k < nvar; k++) if (!s.var[k]) ck(hipMalloc((void **)&s.var[k], s.elems * sizeof(double)), "hipMalloc(progressive variances)");
-            prg::VarPlanes vp{};
-            for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
-            vp.vcx = s.var[5]; vp.vcy = s.var[6];
-            const double norm = (double)(s.passes - 1) * (double)s.done;
-            const int nb = std::max(1, std::min(4 * prg::kMaxBlocks, (int)((s.elems + prg::kBlock - 1) / prg::kBlock)));
-            if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
-            else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
-            ck(hipGetLastError(), "progressive variance launch");
-        }
+        if (want_var) compute_variances(s);
         for (int k = 0; k < s.nbuf; k++) {
             if (means) copy_out(s, means[k], s.mean[k], on_device);
             if (vars) copy_out(s, vars[k], s.var[k], on_device);
@@ -328,6 +331,26 @@ int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, cons
         for (double *&p : s.asm_buf) if (!p) ck(hipMalloc((void **)&p, s.elems * sizeof(double)), "hipMalloc(progressive assembly)");
         gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
         if (gdpt_reconstruct_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], dataCost, recon, s.asm_buf[3], s.stream, stats) != 0)
+            throw std::runtime_error(gdpt_last_error());
+        copy_out(s, out, s.asm_buf[3], on_device);
+        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");
+    });
+}
+
+int gdpt_progressive_reconstruct_weighted(GdptProgressive *session, double dataCost, const GdptWeightedReconParams *params, int on_device,
+                                          double *out, double *const confidence[3], GdptWeightedReconStats *stats) {
+    return gdpt::guarded([&]() {
+        if (!session || !out) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: null argument");
+        GdptProgressive &s = *session;
+        if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: an Integrator::Path session has no gradients (read its mean)");
+        if (s.passes < 2) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: variances need at least 2 passes");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        for (double *&p : s.asm_buf) if (!p) ck(hipMalloc((void **)&p, s.elems * sizeof(double)), "hipMalloc(progressive assembly)");
+        gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
+        compute_variances(s);
+        // (the confidence planes go straight to their destination: the copy kind is taken from the pointers, host or device)
+        if (gdpt_reconstruct_weighted_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.var[0], s.var[5], s.var[6], dataCost, params, s.asm_buf[3],
+                                             confidence, s.stream, stats) != 0)
             throw std::runtime_error(gdpt_last_error());
         copy_out(s, out, s.asm_buf[3], on_device);
         ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");

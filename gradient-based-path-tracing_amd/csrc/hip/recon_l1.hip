@@ -28,6 +28,7 @@
 // Grid: one block of 256 threads per tile, at most kMaxBlocks blocks striding over the tiles (so that the partial arrays
 // every block re-reduces stay short); 8 KB of LDS, 50 VGPRs and no scratch, i.e. occupancy is bound by neither.
 #include "recon_l1.h"
+#include "recon_pcg.h"
 #include "../capi_common.h"
 
 #include <algorithm>
@@ -39,42 +40,6 @@
 #include <string>
 
 namespace rl1 {
-
-constexpr int kBlock = 256, kTileW = 32, kTileH = 8, kPitch = kTileW + 2, kMaxBlocks = 1024;
-static_assert(kTileW * kTileH == kBlock, "one thread per tile pixel");
-constexpr int kHalo = 2 * kTileW + 2 * kTileH;       // the 5-tap needs no corners
-
-struct State {
-    double rz[2];         // <r,z> ping-pong by iteration parity
-    double bb;            // <b,b>
-    double tol;           // relative residual to stop at
-    double rel;           // |r| / |b| of the iterate (pcg_residual_kernel)
-    double energy;        // E(f) of the iterate the last weights pass read
-    int iters;
-    int converged;
-};
-
-struct Geo { int w, h, tiles_x, tiles; };
-
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    // fixed order: xor tree inside each wave, then the wave totals in index order
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / 64; k++) s += red[k];
-    return s;
-}
-__device__ __forceinline__ double reduce_partials(const double *part, int n, double *red) {
-    double v = 0;
-    for (int i = threadIdx.x; i < n; i += kBlock) v += part[i];
-    return block_sum(v, red);
-}
-__device__ __forceinline__ double norm3(const double *v) { return sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); }
 
 // partials layout: slot s of gridDim.x doubles: [0] <r,z>, [1] <r,r>, [2] <b,b>, [3] energy, [4] <p,q>
 // unit != 0: all weights 1 (round 0). x_init (nullable): receives a copy of f (round 0: the iterate starts at u).
@@ -254,49 +219,114 @@ void ck(hipError_t e, const char *what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
-struct Workspace {
-    std::mutex mu;                    // held while a reconstruction runs on this (device, stream) pair
-    size_t npix = 0;
-    double *r = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;      // 3 npix each
-    double *wx = nullptr, *wy = nullptr, *diag = nullptr;                  // npix each
-    double *partials = nullptr;
-    rl1::State *state = nullptr, *h_state = nullptr;                       // device / pinned host
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};                        // timing pair + chunk marker
-    void release() {
-        for (double *p : {r, q, p0, p1, wx, wy, diag, partials}) if (p) hipFree(p);
-        if (state) hipFree(state);
-        if (h_state) hipHostFree(h_state);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
-        r = q = p0 = p1 = wx = wy = diag = partials = nullptr; state = h_state = nullptr;
-        for (auto &e : ev) e = nullptr;
-        npix = 0;
-    }
-    void ensure(size_t n) {
-        if (n <= npix) return;
-        release();
-        npix = n;
-        for (double **p : {&r, &q, &p0, &p1}) ck(hipMalloc((void **)p, 3 * n * sizeof(double)), "hipMalloc(recon workspace)");
-        for (double **p : {&wx, &wy, &diag}) ck(hipMalloc((void **)p, n * sizeof(double)), "hipMalloc(recon weights)");
-        ck(hipMalloc((void **)&partials, 5 * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon partials)");
-        ck(hipMalloc((void **)&state, sizeof(rl1::State)), "hipMalloc(recon state)");
-        ck(hipHostMalloc((void **)&h_state, sizeof(rl1::State)), "hipHostMalloc");
-        for (auto &e : ev) ck(hipEventCreate(&e), "hipEventCreate");
-    }
-};
 std::mutex g_registry_mu;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<Workspace>> g_workspaces;
-
-Workspace &workspace(int dev, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_registry_mu);
-    auto &slot = g_workspaces[{dev, stream}];
-    if (!slot) slot.reset(new Workspace());
-    return *slot;
-}
+std::map<std::pair<int, hipStream_t>, std::unique_ptr<ReconWorkspace>> g_workspaces;
 
 } // namespace
 
+void ReconWorkspace::release() {
+    for (double *p : {r, q, p0, p1, wx, wy, diag, partials, var[0], var[1], var[2], conf[0], conf[1], conf[2], conf_partials}) if (p) hipFree(p);
+    if (state) hipFree(state);
+    if (h_state) hipHostFree(h_state);
+    if (conf_stats) hipFree(conf_stats);
+    if (h_conf_stats) hipHostFree(h_conf_stats);
+    for (auto &e : ev) if (e) hipEventDestroy(e);
+    r = q = p0 = p1 = wx = wy = diag = partials = conf_partials = nullptr; state = h_state = nullptr;
+    for (int k = 0; k < 3; k++) var[k] = conf[k] = nullptr;
+    conf_stats = h_conf_stats = nullptr;
+    for (auto &e : ev) e = nullptr;
+    npix = conf_npix = 0;
+}
+void ReconWorkspace::ensure(size_t n) {
+    if (n <= npix) return;
+    release();
+    npix = n;
+    for (double **p : {&r, &q, &p0, &p1}) ck(hipMalloc((void **)p, 3 * n * sizeof(double)), "hipMalloc(recon workspace)");
+    for (double **p : {&wx, &wy, &diag}) ck(hipMalloc((void **)p, n * sizeof(double)), "hipMalloc(recon weights)");
+    ck(hipMalloc((void **)&partials, 5 * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon partials)");
+    ck(hipMalloc((void **)&state, sizeof(rl1::State)), "hipMalloc(recon state)");
+    ck(hipHostMalloc((void **)&h_state, sizeof(rl1::State)), "hipHostMalloc");
+    for (auto &e : ev) ck(hipEventCreate(&e), "hipEventCreate");
+}
+void ReconWorkspace::ensure_confidence(size_t n) {
+    if (n <= conf_npix) return;
+    for (int k = 0; k < 3; k++) {
+        if (var[k]) hipFree(var[k]);
+        if (conf[k]) hipFree(conf[k]);
+        var[k] = conf[k] = nullptr;
+    }
+    conf_npix = 0;
+    for (int k = 0; k < 3; k++) {
+        ck(hipMalloc((void **)&var[k], n * sizeof(double)), "hipMalloc(recon row variances)");
+        ck(hipMalloc((void **)&conf[k], n * sizeof(double)), "hipMalloc(recon confidences)");
+    }
+    if (!conf_partials) ck(hipMalloc((void **)&conf_partials, kConfSlots * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon confidence partials)");
+    if (!conf_stats) ck(hipMalloc((void **)&conf_stats, sizeof(ConfStats)), "hipMalloc(recon confidence scalars)");
+    if (!h_conf_stats) ck(hipHostMalloc((void **)&h_conf_stats, sizeof(ConfStats)), "hipHostMalloc");
+    conf_npix = n;
+}
+
+ReconWorkspace &recon_workspace(int dev, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(g_registry_mu);
+    auto &slot = g_workspaces[{dev, stream}];
+    if (!slot) slot.reset(new ReconWorkspace());
+    return *slot;
+}
+
+rl1::Geo recon_geo(int w, int h) {
+    rl1::Geo g{w, h, (w + rl1::kTileW - 1) / rl1::kTileW, 0};
+    g.tiles = g.tiles_x * ((h + rl1::kTileH - 1) / rl1::kTileH);
+    return g;
+}
+
+void recon_round_init(ReconWorkspace &ws, int nb, double tol, int reset, hipStream_t stream) {
+    hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), dim3(rl1::kBlock), 0, stream, nb, ws.partials, ws.state, tol, reset);
+}
+
+void recon_read_state(ReconWorkspace &ws, hipStream_t stream) {
+    ck(hipMemcpyAsync(ws.h_state, ws.state, sizeof(rl1::State), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(state)");
+    ck(hipEventRecord(ws.ev[2], stream), "hipEventRecord");
+}
+
+void recon_pcg_round(ReconWorkspace &ws, const rl1::Geo &g, int nb, double *d_out, const ReconL1Params &p, hipStream_t stream, int k,
+                     ReconL1Result &res) {
+    double *part_rz = ws.partials, *part_rr = ws.partials + nb, *part_pq = ws.partials + 4 * (size_t)nb;
+    const dim3 grid(nb), block(rl1::kBlock);
+    const int npix = g.w * g.h, chunk = 32;
+    int launched = 0;
+    auto enqueue_chunk = [&]() {
+        const int n = std::min(chunk, p.cg_max_iters - launched);
+        for (int j = 0; j < n; j++) {
+            const int it = launched + j;
+            const double *pin = (it & 1) ? ws.p1 : ws.p0;
+            double *pout = (it & 1) ? ws.p0 : ws.p1;
+            hipLaunchKernelGGL(rl1::pcg_step_a, grid, block, 0, stream, g, it, ws.r, pin, pout, ws.q, ws.wx, ws.wy, ws.diag, part_rz, part_rr, part_pq, ws.state);
+            hipLaunchKernelGGL(rl1::pcg_step_b, grid, block, 0, stream, npix, it, pout, ws.q, ws.diag, d_out, ws.r, part_pq, part_rz, part_rr, ws.state);
+        }
+        launched += n;
+        ck(hipGetLastError(), "recon chunk launch");
+    };
+    // one chunk is always in flight ahead of the status check of the previous one; its kernels return at once if converged
+    enqueue_chunk();
+    for (bool done = false; !done;) {
+        recon_read_state(ws, stream);
+        const bool more = launched < p.cg_max_iters;
+        if (more) enqueue_chunk();
+        ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
+        if (ws.h_state->converged || !more) done = true;
+    }
+    hipLaunchKernelGGL(rl1::pcg_residual_kernel, dim3(1), block, 0, stream, nb, part_rr, ws.state);
+    ck(hipGetLastError(), "recon residual launch");
+    recon_read_state(ws, stream);
+    ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
+    if (k == 1) res.energy_first = ws.h_state->energy;       // the weights of round 1 were taken from f_0
+    res.cg_iters_last = ws.h_state->iters; res.cg_iters_total += ws.h_state->iters;
+    res.rel_residual_last = ws.h_state->rel;
+    res.irls_rounds = k + 1;
+}
+
 void recon_l1_forget_stream(int dev, hipStream_t stream) {
-    std::unique_ptr<Workspace> gone;
+    std::unique_ptr<ReconWorkspace> gone;
     {
         std::lock_guard<std::mutex> lk(g_registry_mu);
         auto it = g_workspaces.find({dev, stream});
@@ -319,65 +349,29 @@ ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_g
     if (d_out == d_c || d_out == d_gx || d_out == d_gy) throw std::runtime_error("reconstruct: the output must not alias an input");
     int dev = 0;
     ck(hipGetDevice(&dev), "hipGetDevice");
-    Workspace &ws = workspace(dev, stream);
+    ReconWorkspace &ws = recon_workspace(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
     const size_t npix = (size_t)w * h;
     if (npix > ws.npix && ws.npix) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
     ws.ensure(npix);
-    rl1::Geo g{w, h, (w + rl1::kTileW - 1) / rl1::kTileW, 0};
-    g.tiles = g.tiles_x * ((h + rl1::kTileH - 1) / rl1::kTileH);
-    const int nb = std::min(rl1::kMaxBlocks, g.tiles);
-    double *part_rz = ws.partials, *part_rr = ws.partials + nb, *part_pq = ws.partials + 4 * (size_t)nb;
+    const rl1::Geo g = recon_geo(w, h);
+    const int nb = recon_blocks(g);
     const dim3 grid(nb), block(rl1::kBlock);
-    auto read_state = [&]() {
-        ck(hipMemcpyAsync(ws.h_state, ws.state, sizeof(rl1::State), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(state)");
-        ck(hipEventRecord(ws.ev[2], stream), "hipEventRecord");
-    };
     ReconL1Result res{};
     ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
-    const int chunk = 32;
     for (int k = 0; k <= p.irls_iters; k++) {
         const double eps = k == 0 ? 0.0 : std::max(p.eps_init * std::pow(p.eps_decay, k - 1), p.eps_floor);
         hipLaunchKernelGGL(rl1::weights_kernel<true>, grid, block, 0, stream, g, alpha, eps, k == 0 ? 1 : 0, k == 0 ? d_c : (const double *)d_out, d_c, d_gx, d_gy,
                            k == 0 ? d_out : (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
-        hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), block, 0, stream, nb, ws.partials, ws.state, p.cg_tol, 1);
+        recon_round_init(ws, nb, p.cg_tol, 1, stream);
         ck(hipGetLastError(), "recon round launch");
-        int launched = 0;
-        auto enqueue_chunk = [&]() {
-            const int n = std::min(chunk, p.cg_max_iters - launched);
-            for (int j = 0; j < n; j++) {
-                const int it = launched + j;
-                const double *pin = (it & 1) ? ws.p1 : ws.p0;
-                double *pout = (it & 1) ? ws.p0 : ws.p1;
-                hipLaunchKernelGGL(rl1::pcg_step_a, grid, block, 0, stream, g, it, ws.r, pin, pout, ws.q, ws.wx, ws.wy, ws.diag, part_rz, part_rr, part_pq, ws.state);
-                hipLaunchKernelGGL(rl1::pcg_step_b, grid, block, 0, stream, (int)npix, it, pout, ws.q, ws.diag, d_out, ws.r, part_pq, part_rz, part_rr, ws.state);
-            }
-            launched += n;
-            ck(hipGetLastError(), "recon chunk launch");
-        };
-        // one chunk is always in flight ahead of the status check of the previous one; its kernels return at once if converged
-        enqueue_chunk();
-        for (bool done = false; !done;) {
-            read_state();
-            const bool more = launched < p.cg_max_iters;
-            if (more) enqueue_chunk();
-            ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
-            if (ws.h_state->converged || !more) done = true;
-        }
-        hipLaunchKernelGGL(rl1::pcg_residual_kernel, dim3(1), block, 0, stream, nb, part_rr, ws.state);
-        ck(hipGetLastError(), "recon residual launch");
-        read_state();
-        ck(hipEventSynchronize(ws.ev[2]), "hipEventSynchronize");
-        if (k == 1) res.energy_first = ws.h_state->energy;       // the weights of round 1 were taken from f_0
-        res.cg_iters_last = ws.h_state->iters; res.cg_iters_total += ws.h_state->iters;
-        res.rel_residual_last = ws.h_state->rel;
-        res.irls_rounds = k + 1;
+        recon_pcg_round(ws, g, nb, d_out, p, stream, k, res);
     }
     hipLaunchKernelGGL(rl1::weights_kernel<false>, grid, block, 0, stream, g, alpha, 0.0, 1, (const double *)d_out, d_c, d_gx, d_gy,
                        (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
-    hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), block, 0, stream, nb, ws.partials, ws.state, p.cg_tol, 0);
+    recon_round_init(ws, nb, p.cg_tol, 0, stream);
     ck(hipGetLastError(), "recon energy launch");
-    read_state();
+    recon_read_state(ws, stream);
     ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
     ck(hipEventSynchronize(ws.ev[1]), "hipEventSynchronize");
     res.energy_last = ws.h_state->energy;

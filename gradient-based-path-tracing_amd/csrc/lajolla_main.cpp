@@ -18,6 +18,10 @@
 //   --reconstruct l2|l1   final reconstruction: l2 = the reference's fourierSolve (default), l1 = IRLS, robust to fireflies in
 //                 the gradient buffers (include/gdpt.h: gdpt_reconstruct); --irls-iters N reweighted rounds (default 20),
 //                 --irls-eps INIT[,DECAY[,FLOOR]] (default 0.05,0.5,1e-3). Single device only
+//                 wl2 | wl1 = the variance-weighted reconstruction of a session (gdpt_reconstruct_weighted: generalised least
+//                 squares / its IRLS form on the session's per-pixel variances); they need --pass-spp. --conf-floor X: the
+//                 confidence floor (default 0.05); --confidence FILE writes kappa of the data, x-edge and y-edge rows as the
+//                 three channels of an image
 //   --pass-spp N  progressive session (include/gdpt.h: gdpt_progressive_*): passes of N samples per pixel up to the budget --spp; the
 //                 output is the session's reconstruction (Integrator::Path scenes: the mean). --target-error E stops at the first
 //                 pass (from the second on) whose estimated relative RMSE of the primal is <= E; --variance FILE writes the
@@ -40,7 +44,9 @@ int main(int argc, char *argv[]) {
     int num_threads = 0, spp = 0, device = 0, rng = GDPT_RNG_SAMPLE, shift = GDPT_SHIFT_REFERENCE;
     int film_w = 0, film_h = 0, plan_rows = 0, pass_spp = 0;
     double target_error = 0.0;
-    std::string variance_file = "";
+    std::string variance_file = "", confidence_file = "";
+    bool weighted = false;
+    double conf_floor = 0.0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
     GdptReconParams recon{};          // norm == GDPT_RECON_L2: the reference's reconstruction
     double alpha = 0.04;
@@ -99,8 +105,12 @@ int main(int argc, char *argv[]) {
             std::string v = next();
             if (v == "l1") recon.norm = GDPT_RECON_L1;
             else if (v == "l2") recon.norm = GDPT_RECON_L2;
-            else { std::cerr << "unknown --reconstruct " << v << " (l2 | l1)" << std::endl; return 2; }
+            else if (v == "wl1") { recon.norm = GDPT_RECON_L1; weighted = true; }
+            else if (v == "wl2") { recon.norm = GDPT_RECON_L2; weighted = true; }
+            else { std::cerr << "unknown --reconstruct " << v << " (l2 | l1 | wl2 | wl1)" << std::endl; return 2; }
         }
+        else if (a == "--conf-floor") conf_floor = std::stod(next());
+        else if (a == "--confidence") confidence_file = next();
         else if (a == "--irls-iters") { int n = std::stoi(next()); recon.irls_iters = n > 0 ? n : -1; }
         else if (a == "--irls-eps") {     // INIT[,DECAY[,FLOOR]]
             std::string v = next();
@@ -119,6 +129,8 @@ int main(int argc, char *argv[]) {
     if (pass_spp > 0 && multi.num_devices > 0) { std::cerr << "--pass-spp is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
     if (pass_spp > 0 && rng == GDPT_RNG_TILE) { std::cerr << "--pass-spp needs --rng sample (the tile streams have no sample window)" << std::endl; return 2; }
     if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
+    if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
+    if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
     (void)num_threads;
 
     using clock = std::chrono::system_clock;
@@ -164,7 +176,22 @@ int main(int argc, char *argv[]) {
             if (rc == 0) rc = gdpt_progressive_run(session, target_error, pass_spp, 0, &prog);
             double *means[5] = {path ? image.data() : nullptr, nullptr, nullptr, nullptr, nullptr};
             if (rc == 0 && path) rc = gdpt_progressive_read(session, 0, means, nullptr, nullptr);
-            if (rc == 0 && !path) {
+            if (rc == 0 && !path && weighted) {
+                GdptWeightedReconParams wp{};
+                wp.recon = recon; wp.conf_floor = conf_floor;
+                GdptWeightedReconStats ws{};
+                std::vector<double> kappa[3];
+                double *planes[3] = {nullptr, nullptr, nullptr};
+                if (!confidence_file.empty()) for (int k = 0; k < 3; k++) { kappa[k].resize((size_t)w * h); planes[k] = kappa[k].data(); }
+                rc = gdpt_progressive_reconstruct_weighted(session, alpha, &wp, 0, image.data(), planes, &ws);
+                cs = ws.recon;
+                ps.iterations = cs.cg_iters_total; ps.solve_ms = cs.solve_ms;
+                if (rc == 0 && !confidence_file.empty()) {
+                    std::vector<double> conf((size_t)w * h * 3);
+                    for (size_t i = 0; i < (size_t)w * h; i++) for (int k = 0; k < 3; k++) conf[3 * i + k] = kappa[k][i];
+                    rc = gdpt_imwrite(confidence_file.c_str(), w, h, conf.data());
+                }
+            } else if (rc == 0 && !path) {
                 rc = gdpt_progressive_reconstruct(session, alpha, recon.norm == GDPT_RECON_L1 ? &recon : nullptr, 0, image.data(), &cs);
                 ps.iterations = cs.cg_iters_total; ps.solve_ms = cs.solve_ms;
             }

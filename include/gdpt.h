@@ -407,6 +407,57 @@ int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, cons
  * <= target_error (GDPT_STOP_TARGET; target_error <= 0: no target). Blocking; status (nullable) as gdpt_progressive_status. */
 int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass_spp, int max_passes, GdptProgressiveStatus *status);
 
+/* ---- variance-weighted reconstruction: generalised least squares on per-row confidences (not part of the reference) ----
+ * gdpt_reconstruct's rows (data row per pixel, x-edge for x >= 1, y-edge for y >= 1, natural boundary), each weighted by a
+ * confidence taken from the variance of its input: minimises  sum kappa_row |r_row|^2  with kappa ~ 1 / variance. A firefly sits in
+ * a pixel whose sample variance is huge, so the row that carries it is all but switched off before the solve.
+ * Variance planes var_c, var_gx, var_gy: W*H*3 doubles each, the variances of c, gx, gy (a session's assembled_vars). Per row:
+ *     v      = sum of its three channel variances. The row is valid if they are finite and >= 0, v is finite, and the row's
+ *              c / gx / gy triple is finite.
+ *     s_d    = exp(mean(log v)) over the valid data rows with v > 0 (geometric mean: a few fireflies do not move it);
+ *     s_g    = the same over the valid x- and y-edge rows together (one scale: their relative precision survives; the data rows'
+ *              own scale keeps the meaning of dataCost). A family without such a row has scale 1.
+ *     kappa  = s / (v + conf_floor s)  for a valid row (v = 0: 1 / conf_floor),  0 for an invalid row.
+ * Round 0 solves gdpt_reconstruct's system with row weights kappa; IRLS round k >= 1 with kappa / (eps_k + |r|_2). A row with
+ * kappa = 0 is selected out of the system (its values may be NaN); a pixel all of whose rows have kappa = 0 gets diagonal 1 and
+ * right-hand side 0 (its value is 0) and is counted in pixels_isolated. The energies in the stats are sums of kappa |r|_2.
+ * Uniform variance planes give one kappa for all rows, i.e. gdpt_reconstruct(GDPT_RECON_L1)'s image for the same round count.
+ * recon.norm: GDPT_RECON_L2 = round 0 alone (weighted least squares; irls_iters is ignored), GDPT_RECON_L1 = weighted IRLS; the
+ * other fields as for gdpt_reconstruct. params == NULL: weighted least squares with the defaults.
+ * Weights estimated from the same samples as the means are correlated with them: a dark-biased estimate. */
+typedef struct GdptWeightedReconParams {
+    GdptReconParams recon;
+    double conf_floor;         /* delta. 0: default 0.05; must be finite and >= 0 */
+    int32_t reserved[2];       /* 0 */
+} GdptWeightedReconParams;
+typedef struct GdptWeightedReconStats {
+    GdptReconStats recon;      /* norm: the one used; irls_rounds: systems solved (weighted L2: 1) */
+    double scale_data;         /* s_d */
+    double scale_grad;         /* s_g */
+    uint64_t rows_dropped;     /* invalid rows */
+    uint64_t pixels_isolated;
+} GdptWeightedReconStats;
+/* Host pointers. confidence (nullable; any entry nullable): kappa of the data, x-edge and y-edge rows, W*H doubles each (0 where
+ * the film has no such row: x = 0, y = 0). NULL variance pointers, `out` aliasing an input, width or height < 2, a non-positive or
+ * non-finite dataCost or conf_floor are refused. No CPU fallback. */
+int gdpt_reconstruct_weighted(int width, int height, const double *c, const double *gx, const double *gy,
+                              const double *var_c, const double *var_gx, const double *var_gy, double dataCost,
+                              const GdptWeightedReconParams *params /* nullable */, double *out,
+                              double *const confidence[3] /* nullable */, GdptWeightedReconStats *stats /* nullable */);
+/* Device pointers (the confidence planes too). Waits for `stream`; scratch per (device, stream), dropped by
+ * gdpt_poisson_forget_stream. */
+int gdpt_reconstruct_weighted_device(int width, int height, const double *d_c, const double *d_gx, const double *d_gy,
+                                     const double *d_var_c, const double *d_var_gx, const double *d_var_gy, double dataCost,
+                                     const GdptWeightedReconParams *params /* nullable */, double *d_out,
+                                     double *const d_confidence[3] /* nullable */, void *stream,
+                                     GdptWeightedReconStats *stats /* nullable */);
+/* The weighted reconstruction of a session: its running means assembled into c, cx, cy and its assembled variances, all on the
+ * device. Needs a GradPath session with at least 2 passes (no variance is defined before). `out` and the confidence planes are
+ * host memory, or device memory with on_device != 0. Blocking. */
+int gdpt_progressive_reconstruct_weighted(GdptProgressive *session, double dataCost, const GdptWeightedReconParams *params /* nullable */,
+                                          int on_device, double *out, double *const confidence[3] /* nullable */,
+                                          GdptWeightedReconStats *stats /* nullable */);
+
 /* ---- several devices of one node: the tile loop sharded into row bands ----
  * Replaces the reference's only parallelism, parallel_for over 16x16 tiles on a std::thread pool
  * (src/render.cpp:271-277, src/parallel.cpp:183-256): contiguous bands of whole tile rows go to the devices, one host
