@@ -68,6 +68,16 @@ def lib():
         L.gdpt_progressive_read.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
         L.gdpt_progressive_reconstruct.argtypes = [vp, C.c_double, C.POINTER(defs.GdptReconParams), C.c_int, vp, C.POINTER(defs.GdptReconStats)]
         L.gdpt_progressive_run.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
+        L.gdpt_progressive_create_slice.argtypes = [vp, C.POINTER(defs.GdptProgressiveConfig), C.c_int, C.c_int, vp, C.POINTER(vp)]
+        L.gdpt_progressive_merge.argtypes = [vp, vp]
+        L.gdpt_progressive_group_create.argtypes = [C.POINTER(defs.GdptSceneDesc), C.POINTER(C.c_int32), C.c_int,
+                                                    C.POINTER(defs.GdptProgressiveConfig), C.POINTER(vp)]
+        L.gdpt_progressive_group_free.argtypes = [vp]
+        L.gdpt_progressive_group_free.restype = None
+        L.gdpt_progressive_group_run.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
+        L.gdpt_progressive_group_total.argtypes = [vp]
+        L.gdpt_progressive_group_total.restype = vp
+        L.gdpt_progressive_group_member_status.argtypes = [vp, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
         L.gdpt_assemble_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gdpt_poisson_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         L.gdpt_poisson_solve_ex.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, C.c_int, C.c_double, C.c_int,
@@ -283,18 +293,42 @@ BUFFERS = ("img", "cx0", "cy0", "cx1", "cy1")
 class Progressive:
     """A progressive render session on the device (include/gdpt.h, gdpt_progressive_*): passes over disjoint sample windows of
     every pixel's block of `budget_spp` PCG streams, folded into running means and per-pixel variances of the mean.
-    `path=True`: Integrator::Path (the img plane alone). `stream`: a hipStream_t address carrying all of the session's work."""
+    `path=True`: Integrator::Path (the img plane alone). `stream`: a hipStream_t address carrying all of the session's work.
+    `slice=(first, n)`: the session draws its passes from streams [first, first + n) of the block alone (gdpt_progressive_create_slice;
+    n = 0: an accumulator that only receives merges); sessions over disjoint slices combine exactly with merge()."""
 
-    def __init__(self, scene, budget_spp, shift=defs.SHIFT_REFERENCE, path=False, stream=None, max_depth_override=0):
+    def __init__(self, scene, budget_spp, shift=defs.SHIFT_REFERENCE, path=False, stream=None, max_depth_override=0, slice=None):
         self.scene = scene                       # keeps the scene handle alive
+        self._owned = True
         self.path = bool(path)
         self.names = BUFFERS[:1] if self.path else BUFFERS
         self.shape = (scene.height, scene.width, 3)
         cfg = defs.GdptProgressiveConfig(defs.PROGRESSIVE_PATH if self.path else defs.PROGRESSIVE_GRADPATH, int(shift), int(budget_spp),
                                          int(max_depth_override))
         h = C.c_void_p()
-        _check(lib().gdpt_progressive_create(scene.handle, C.byref(cfg), C.c_void_p(int(stream) if stream else 0), C.byref(h)))
+        if slice is None:
+            _check(lib().gdpt_progressive_create(scene.handle, C.byref(cfg), C.c_void_p(int(stream) if stream else 0), C.byref(h)))
+        else:
+            _check(lib().gdpt_progressive_create_slice(scene.handle, C.byref(cfg), int(slice[0]), int(slice[1]),
+                                                       C.c_void_p(int(stream) if stream else 0), C.byref(h)))
         self.handle = h
+
+    @classmethod
+    def _view(cls, owner, handle, shape, path):
+        """A session handle owned by someone else (a ProgressiveGroup's total): every call works, close() does not free."""
+        self = cls.__new__(cls)
+        self.scene, self._owned = owner, False   # keeps the owner alive
+        self.path = bool(path)
+        self.names = BUFFERS[:1] if self.path else BUFFERS
+        self.shape = shape
+        self.handle = C.c_void_p(handle)
+        return self
+
+    def merge(self, other):
+        """Takes in `other`'s statistics (gdpt_progressive_merge): afterwards this session is the one that folded the passes of both.
+        `other` is unchanged. The sessions must hold disjoint samples of one stream block. Returns status()."""
+        _check(lib().gdpt_progressive_merge(self.handle, other.handle))
+        return self.status()
 
     def add_pass(self, spp):
         """Renders and folds in the next `spp` samples of every pixel; returns the pass's GdptRenderStats."""
@@ -378,7 +412,49 @@ class Progressive:
 
     def close(self):
         if getattr(self, "handle", None):
-            lib().gdpt_progressive_free(self.handle)
+            if self._owned:
+                lib().gdpt_progressive_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ProgressiveGroup:
+    """One progressive session split over devices on the sample axis (gdpt_progressive_group_*): `devices` lists HIP ordinals (a
+    device may appear more than once); member i draws streams [i B / N, (i+1) B / N) of every pixel's block of B = `budget_spp`.
+    `total` is a Progressive view of the merged state: read(), reconstruct(), reconstruct_weighted() and status() work on it."""
+
+    def __init__(self, scene_desc, devices, budget_spp, shift=defs.SHIFT_REFERENCE, path=False, max_depth_override=0):
+        self.desc = scene_desc
+        self.num_members = len(devices)
+        cfg = defs.GdptProgressiveConfig(defs.PROGRESSIVE_PATH if path else defs.PROGRESSIVE_GRADPATH, int(shift), int(budget_spp),
+                                         int(max_depth_override))
+        dev = (C.c_int32 * max(1, len(devices)))(*[int(d) for d in devices])
+        h = C.c_void_p()
+        _check(lib().gdpt_progressive_group_create(scene_desc.ptr, dev, len(devices), C.byref(cfg), C.byref(h)))
+        self.handle = h
+        self.total = Progressive._view(self, lib().gdpt_progressive_group_total(h), (scene_desc.height, scene_desc.width, 3), path)
+
+    def run(self, target_error=0.0, pass_spp=16, max_rounds=0):
+        """Rounds of one pass per member until all slices are spent, `max_rounds` were done (0: no limit) or, from 2 passes on, the
+        total's error estimate is <= target_error (0: no target). Returns the total's status()."""
+        st = defs.GdptProgressiveStatus()
+        _check(lib().gdpt_progressive_group_run(self.handle, float(target_error), int(pass_spp), int(max_rounds), C.byref(st)))
+        return Progressive._status_dict(st)
+
+    def member_status(self, i):
+        st = defs.GdptProgressiveStatus()
+        _check(lib().gdpt_progressive_group_member_status(self.handle, int(i), C.byref(st)))
+        return Progressive._status_dict(st)
+
+    def close(self):
+        if getattr(self, "handle", None):
+            self.total.close()
+            lib().gdpt_progressive_group_free(self.handle)
             self.handle = None
 
     def __del__(self):

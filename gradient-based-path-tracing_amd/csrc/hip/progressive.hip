@@ -15,11 +15,17 @@
 //   finish_kernel    one block: the partials reduced in a fixed order (xor tree in a wave, waves in index order, blocks strided
 //                    in index order), so that the same session gives the same bits and the same stopping pass.
 //   variance_kernel  read-out: M2 / ((K-1) W) per buffer and the variances of the assembled cx, cy.
+//   merge_kernel     the fold's sibling for two sessions: dst takes in src's (mean, M2) by the pairwise update below.
 // The fold is memory bound: 5 doubles of traffic per component (3 read, 2 written), 40 bytes x 15 components per GradPath pixel.
+//
+// Slices and merges. A session draws its passes from a slice [first, first + own) of the block of `block` streams; sessions over
+// disjoint slices hold disjoint samples of the whole film, and their statistics combine exactly (Chan, Golub, LeVeque 1979):
+//     W = Wa + Wb;  d = mean_b - mean_a;  mean = mean_a + (Wb / W) d;  M2 = (M2a + M2b) + d d (Wa Wb / W);  K = Ka + Kb
+// is the state of one session that folded all the passes of both. The merge is 6 doubles of traffic per component (4 read, 2 written).
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "poisson_kernels.h"
-#include "scene_internal.h"
+#include "progressive_internal.h"
 
 #include <algorithm>
 #include <cmath>
@@ -35,7 +41,6 @@ struct Planes {
     const double *pass[5];
     double *mean[5], *m2[5];
 };
-struct Estimate { double sum_var, sum_mean2, left_out; };
 
 __device__ __forceinline__ double block_sum(double v, double *red) {
     // fixed order: xor tree inside each wave, then the wave totals in index order
@@ -90,6 +95,51 @@ __global__ __launch_bounds__(kBlock) void fold_kernel(Planes p, int npix, double
     v = block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
 }
 
+// dst (mean, m2) takes in src (smean, sm2): f = Wb / W, g = Wa Wb / W for dst's Wa, src's Wb, W = Wa + Wb; norm = (K - 1) W of the
+// merged state (0 while K < 2). FIRST: dst holds nothing (Wa = 0) and its planes are not read: src's are copied, bit for bit.
+// partials as in fold_kernel.
+struct MergePlanes {
+    const double *smean[5], *sm2[5];
+    double *mean[5], *m2[5];
+};
+template <int NBUF, bool FIRST>
+__global__ __launch_bounds__(kBlock) void merge_kernel(MergePlanes p, int npix, double f, double g, double norm, double *partials) {
+    __shared__ double red[kBlock / 64];
+    double s_var = 0, s_m2 = 0, s_out = 0;
+    for (int pix = blockIdx.x * kBlock + threadIdx.x; pix < npix; pix += gridDim.x * kBlock) {
+        const size_t i = (size_t)3 * pix;
+#pragma unroll
+        for (int b = 0; b < NBUF; b++) {
+            double mu[3], q[3];
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double mb = p.smean[b][i + c], qb = p.sm2[b][i + c];
+                if (FIRST) { mu[c] = mb; q[c] = qb; }
+                else {
+                    const double ma = p.mean[b][i + c], qa = p.m2[b][i + c];
+                    const double d = mb - ma;
+                    mu[c] = ma + f * d;
+                    q[c] = (qa + qb) + (d * d) * g;
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) { p.mean[b][i + c] = mu[c]; p.m2[b][i + c] = q[c]; }
+            if (b == 0 && norm > 0.0) {
+                const bool ok = isfinite(mu[0]) && isfinite(mu[1]) && isfinite(mu[2]) && isfinite(q[0]) && isfinite(q[1]) && isfinite(q[2]);
+                if (ok) {
+                    s_var += (q[0] / norm + q[1] / norm) + q[2] / norm;
+                    s_m2 += (mu[0] * mu[0] + mu[1] * mu[1]) + mu[2] * mu[2];
+                } else s_out += 1.0;
+            }
+        }
+    }
+    const int nb = gridDim.x;
+    double v;
+    v = block_sum(s_var, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
+    v = block_sum(s_m2, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
+    v = block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
+}
+
 __global__ __launch_bounds__(kBlock) void finish_kernel(int nb, const double *partials, Estimate *est) {
     __shared__ double red[kBlock / 64];
     double r[3];
@@ -121,41 +171,41 @@ __global__ __launch_bounds__(kBlock) void variance_kernel(VarPlanes p, int w, in
 
 } // namespace prg
 
-struct GdptProgressive {
-    GdptScene *scene = nullptr;
-    int device = 0;
-    hipStream_t stream = nullptr;
-    int mode = GDPT_PROGRESSIVE_GRADPATH, shift = GDPT_SHIFT_REFERENCE, max_depth_override = 0;
-    int nbuf = 5, w = 0, h = 0;
-    int budget = 0, done = 0, passes = 0, stop_reason = GDPT_STOP_NONE;
-    size_t elems = 0;
-    double *pass[5] = {}, *mean[5] = {}, *m2[5] = {};
-    double *var[7] = {};             // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
-    double *asm_buf[4] = {};         // c, cx, cy, reconstruction: allocated by the first reconstruct
-    double *partials = nullptr;
-    prg::Estimate *d_est = nullptr, *h_est = nullptr;     // device / pinned host
-    prg::Estimate est{};             // of the last fold (valid from 2 passes)
-    hipEvent_t ev[2] = {nullptr, nullptr};                // around the fold launches
-    double fold_ms = 0;              // device time of the last pass's fold (fold_kernel + finish_kernel)
-    GdptRenderStats totals{};
-
-    ~GdptProgressive() {
-        hipSetDevice(device);
-        for (auto *set : {pass, mean, m2}) for (int k = 0; k < 5; k++) if (set[k]) hipFree(set[k]);
-        for (double *p : var) if (p) hipFree(p);
-        for (double *p : asm_buf) if (p) hipFree(p);
-        if (partials) hipFree(partials);
-        if (d_est) hipFree(d_est);
-        if (h_est) hipHostFree(h_est);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
-    }
-};
-
 namespace {
 
 using gdpt::ck;
 
 int fold_blocks(int npix) { return std::max(1, std::min(prg::kMaxBlocks, (npix + prg::kBlock - 1) / prg::kBlock)); }
+
+void add_totals(GdptRenderStats &t, const GdptRenderStats &rs) {
+    t.samples += rs.samples; t.rays += rs.rays; t.bounces += rs.bounces;
+    t.nodes_visited += rs.nodes_visited; t.tris_tested += rs.tris_tested; t.nonfinite_samples += rs.nonfinite_samples;
+    t.render_ms += rs.render_ms; t.node_bytes = rs.node_bytes;
+    t.wave_node_trips += rs.wave_node_trips; t.wave_leaf_trips += rs.wave_leaf_trips;
+    t.wave_steps += rs.wave_steps; t.lane_steps += rs.lane_steps;
+}
+
+// the reduction of the partials a fold or merge launch left, the estimate to the host, the launches' device time; waits for the stream
+void finish_estimate(GdptProgressive &s, int nb, const char *what) {
+    hipLaunchKernelGGL(prg::finish_kernel, dim3(1), dim3(prg::kBlock), 0, s.stream, nb, s.partials, s.d_est);
+    ck(hipGetLastError(), what);
+    ck(hipEventRecord(s.ev[1], s.stream), "hipEventRecord");
+    ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
+    ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(fold)");
+    s.est = *s.h_est;
+    { float ms = 0; ck(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]), "hipEventElapsedTime"); s.fold_ms = ms; }
+}
+
+// every interval of the block whose samples the session holds: its own [first, first + own_done) and the merged ones
+std::vector<std::pair<int, int>> intervals_held(const GdptProgressive &s) {
+    std::vector<std::pair<int, int>> v = s.merged_intervals;
+    if (s.own_done > 0) v.push_back({s.first, s.first + s.own_done});
+    return v;
+}
+
+} // namespace
+
+namespace prg {
 
 double error_estimate(const GdptProgressive &s) {
     if (s.passes < 2) return std::numeric_limits<double>::quiet_NaN();
@@ -165,7 +215,7 @@ double error_estimate(const GdptProgressive &s) {
 void fill_status(const GdptProgressive &s, GdptProgressiveStatus *st) {
     if (!st) return;
     std::memset(st, 0, sizeof(*st));
-    st->passes = s.passes; st->spp_done = s.done; st->budget_spp = s.budget; st->stop_reason = s.stop_reason;
+    st->passes = s.passes; st->spp_done = s.done; st->budget_spp = s.own + s.merged; st->stop_reason = s.stop_reason;
     st->error_estimate = error_estimate(s);
     st->pixels_left_out = s.passes < 2 ? 0 : (uint64_t)s.est.left_out;
     st->fold_ms = s.fold_ms;
@@ -174,13 +224,13 @@ void fill_status(const GdptProgressive &s, GdptProgressiveStatus *st) {
 
 void add_pass(GdptProgressive &s, int spp, GdptRenderStats *stats) {
     if (spp <= 0) throw std::runtime_error("gdpt_progressive_add_pass: spp must be > 0");
-    if ((long long)s.done + spp > (long long)s.budget)
-        throw std::runtime_error("gdpt_progressive_add_pass: the pass exceeds the session's budget (" + std::to_string(s.done) + " + " + std::to_string(spp) +
-                                 " > " + std::to_string(s.budget) + " samples per pixel)");
+    if ((long long)s.own_done + spp > (long long)s.own)
+        throw std::runtime_error("gdpt_progressive_add_pass: the pass exceeds the session's budget (" + std::to_string(s.own_done) + " + " + std::to_string(spp) +
+                                 " > " + std::to_string(s.own) + " samples per pixel)");
     ck(hipSetDevice(s.scene->device), "hipSetDevice");
     GdptRenderParams p{};
     p.spp = spp; p.rng_scheme = GDPT_RNG_SAMPLE; p.shift_mode = s.shift; p.max_depth_override = s.max_depth_override;
-    const GdptSampleWindow win{s.budget, s.done};
+    const GdptSampleWindow win{s.block, s.first + s.own_done};
     GdptRenderStats rs{};
     const int rc = s.mode == GDPT_PROGRESSIVE_PATH
                        ? gdpt_path_render_window_device(s.scene, &p, &win, s.pass[0], s.stream, &rs)
@@ -201,21 +251,81 @@ void add_pass(GdptProgressive &s, int spp, GdptRenderStats *stats) {
         if (first) hipLaunchKernelGGL((prg::fold_kernel<1, true>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
         else hipLaunchKernelGGL((prg::fold_kernel<1, false>), grid, block, 0, s.stream, pl, npix, n, w_new, norm, s.partials);
     }
-    hipLaunchKernelGGL(prg::finish_kernel, dim3(1), block, 0, s.stream, nb, s.partials, s.d_est);
-    ck(hipGetLastError(), "progressive fold launch");
-    ck(hipEventRecord(s.ev[1], s.stream), "hipEventRecord");
-    ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
-    ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(fold)");
-    s.est = *s.h_est;
-    { float ms = 0; ck(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]), "hipEventElapsedTime"); s.fold_ms = ms; }
-    s.done += spp; s.passes = K;
-    s.totals.samples += rs.samples; s.totals.rays += rs.rays; s.totals.bounces += rs.bounces;
-    s.totals.nodes_visited += rs.nodes_visited; s.totals.tris_tested += rs.tris_tested; s.totals.nonfinite_samples += rs.nonfinite_samples;
-    s.totals.render_ms += rs.render_ms; s.totals.node_bytes = rs.node_bytes;
-    s.totals.wave_node_trips += rs.wave_node_trips; s.totals.wave_leaf_trips += rs.wave_leaf_trips;
-    s.totals.wave_steps += rs.wave_steps; s.totals.lane_steps += rs.lane_steps;
+    finish_estimate(s, nb, "progressive fold launch");
+    s.done += spp; s.own_done += spp; s.passes = K;
+    add_totals(s.totals, rs);
     if (stats) *stats = rs;
 }
+
+void merge(GdptProgressive &dst, const GdptProgressive &src) {
+    if (&dst == &src) throw std::runtime_error("gdpt_progressive_merge: dst and src are the same session");
+    if (dst.w != src.w || dst.h != src.h) throw std::runtime_error("gdpt_progressive_merge: the sessions' films differ");
+    if (dst.mode != src.mode) throw std::runtime_error("gdpt_progressive_merge: the sessions' modes differ (GradPath / Integrator::Path)");
+    if (dst.shift != src.shift) throw std::runtime_error("gdpt_progressive_merge: the sessions' shift modes differ");
+    if (dst.max_depth_override != src.max_depth_override) throw std::runtime_error("gdpt_progressive_merge: the sessions' max_depth_override differ");
+    if (dst.block != src.block) throw std::runtime_error("gdpt_progressive_merge: the sessions' stream blocks differ (" + std::to_string(dst.block) + ", " + std::to_string(src.block) + ")");
+    // what dst holds, and what its own passes may still draw: src must bring none of it
+    std::vector<std::pair<int, int>> mine = dst.merged_intervals;
+    if (dst.own > 0) mine.push_back({dst.first, dst.first + dst.own});
+    const std::vector<std::pair<int, int>> theirs = intervals_held(src);
+    for (const auto &a : theirs)
+        for (const auto &b : mine)
+            if (a.first < b.second && b.first < a.second)
+                throw std::runtime_error("gdpt_progressive_merge: src holds samples [" + std::to_string(a.first) + ", " + std::to_string(a.second) +
+                                         ") of the block, which overlap [" + std::to_string(b.first) + ", " + std::to_string(b.second) + ") of dst");
+    if (src.passes == 0) return;
+    if ((long long)dst.done + src.done > (long long)std::numeric_limits<int>::max() || (long long)dst.passes + src.passes > (long long)std::numeric_limits<int>::max())
+        throw std::runtime_error("gdpt_progressive_merge: sample or pass count overflow");
+    ck(hipSetDevice(dst.device), "hipSetDevice");
+    prg::MergePlanes pl{};
+    if (src.device != dst.device) {          // src's planes into staging planes on dst's device, on dst's stream
+        int can = 0;
+        ck(hipDeviceCanAccessPeer(&can, dst.device, src.device), "hipDeviceCanAccessPeer");
+        if (can) {                           // (without peer access the runtime stages the copy through the host)
+            const hipError_t e = hipDeviceEnablePeerAccess(src.device, 0);
+            if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) ck(e, "hipDeviceEnablePeerAccess");
+            (void)hipGetLastError();
+        }
+        for (int k = 0; k < 2 * dst.nbuf; k++) if (!dst.stage[k]) ck(hipMalloc((void **)&dst.stage[k], dst.elems * sizeof(double)), "hipMalloc(progressive staging)");
+        for (int k = 0; k < dst.nbuf; k++) {
+            ck(hipMemcpyPeerAsync(dst.stage[2 * k], dst.device, src.mean[k], src.device, dst.elems * sizeof(double), dst.stream), "hipMemcpyPeerAsync(mean)");
+            ck(hipMemcpyPeerAsync(dst.stage[2 * k + 1], dst.device, src.m2[k], src.device, dst.elems * sizeof(double), dst.stream), "hipMemcpyPeerAsync(M2)");
+            pl.smean[k] = dst.stage[2 * k]; pl.sm2[k] = dst.stage[2 * k + 1];
+        }
+    } else
+        for (int k = 0; k < dst.nbuf; k++) { pl.smean[k] = src.mean[k]; pl.sm2[k] = src.m2[k]; }
+    for (int k = 0; k < dst.nbuf; k++) { pl.mean[k] = dst.mean[k]; pl.m2[k] = dst.m2[k]; }
+    const int npix = dst.w * dst.h, nb = fold_blocks(npix), K = dst.passes + src.passes;
+    const double wa = (double)dst.done, wb = (double)src.done, w = wa + wb;
+    const double f = wb / w, g = wa * wb / w, norm = (double)(K - 1) * w;
+    const dim3 grid(nb), block(prg::kBlock);
+    const bool first = dst.passes == 0;
+    ck(hipEventRecord(dst.ev[0], dst.stream), "hipEventRecord");
+    if (dst.nbuf == 5) {
+        if (first) hipLaunchKernelGGL((prg::merge_kernel<5, true>), grid, block, 0, dst.stream, pl, npix, f, g, norm, dst.partials);
+        else hipLaunchKernelGGL((prg::merge_kernel<5, false>), grid, block, 0, dst.stream, pl, npix, f, g, norm, dst.partials);
+    } else {
+        if (first) hipLaunchKernelGGL((prg::merge_kernel<1, true>), grid, block, 0, dst.stream, pl, npix, f, g, norm, dst.partials);
+        else hipLaunchKernelGGL((prg::merge_kernel<1, false>), grid, block, 0, dst.stream, pl, npix, f, g, norm, dst.partials);
+    }
+    finish_estimate(dst, nb, "progressive merge launch");
+    dst.done += src.done; dst.merged += src.done; dst.passes = K;
+    dst.merged_intervals.insert(dst.merged_intervals.end(), theirs.begin(), theirs.end());
+    add_totals(dst.totals, src.totals);
+}
+
+void reset(GdptProgressive &s) {
+    s.own_done = 0; s.merged = 0; s.done = 0; s.passes = 0; s.stop_reason = GDPT_STOP_NONE;
+    s.merged_intervals.clear();
+    s.est = prg::Estimate{}; s.fold_ms = 0; s.totals = GdptRenderStats{};
+}
+
+} // namespace prg
+
+namespace {
+
+using prg::error_estimate;
+using prg::fill_status;
 
 void copy_out(const GdptProgressive &s, double *dst, const double *src, int on_device) {
     if (!dst) return;
@@ -236,36 +346,59 @@ void compute_variances(GdptProgressive &s) {
     ck(hipGetLastError(), "progressive variance launch");
 }
 
+// whole: the slice is the whole block (gdpt_progressive_create); else [first, first + num) of it
+void create_session(const char *fn, GdptScene *scene, const GdptProgressiveConfig *config, bool whole, int first, int num, void *stream, GdptProgressive **out) {
+    const std::string who(fn);
+    if (!scene || !out) throw std::runtime_error(who + ": null argument");
+    GdptProgressiveConfig cfg = config ? *config : GdptProgressiveConfig{};
+    if (cfg.mode != GDPT_PROGRESSIVE_GRADPATH && cfg.mode != GDPT_PROGRESSIVE_PATH) throw std::runtime_error(who + ": unknown mode");
+    if (cfg.shift_mode != GDPT_SHIFT_REFERENCE && cfg.shift_mode != GDPT_SHIFT_RECONNECT) throw std::runtime_error(who + ": unknown shift_mode");
+    if (cfg.mode == GDPT_PROGRESSIVE_PATH && scene->view.num_lights <= 0) throw std::runtime_error(who + ": the scene has no emitter to sample");
+    const int budget = cfg.budget_spp > 0 ? cfg.budget_spp : scene->scene_spp;
+    if (budget <= 0) throw std::runtime_error(who + ": budget_spp must be > 0");
+    if (whole) { first = 0; num = budget; }
+    if (first < 0 || num < 0 || (long long)first + num > (long long)budget)
+        throw std::runtime_error(who + ": the slice [" + std::to_string(first) + ", " + std::to_string((long long)first + num) + ") leaves the block [0, " +
+                                 std::to_string(budget) + ")");
+    const int w = scene->view.cam.width, h = scene->view.cam.height;
+    if ((unsigned long long)w * (unsigned long long)h > (~0ull >> 1) / (unsigned long long)budget)
+        throw std::runtime_error(who + ": width * height * budget_spp does not fit 63 bits");
+    if ((long long)w * h > (1LL << 29)) throw std::runtime_error(who + ": film too large");
+    ck(hipSetDevice(scene->device), "hipSetDevice");
+    std::unique_ptr<GdptProgressive> s(new GdptProgressive());
+    s->scene = scene; s->device = scene->device; s->stream = (hipStream_t)stream;
+    s->mode = cfg.mode; s->shift = cfg.shift_mode; s->max_depth_override = cfg.max_depth_override;
+    s->nbuf = cfg.mode == GDPT_PROGRESSIVE_PATH ? 1 : 5;
+    s->w = w; s->h = h; s->block = budget; s->first = first; s->own = num; s->elems = (size_t)w * h * 3;
+    for (auto *set : {s->pass, s->mean, s->m2}) {
+        if (set == s->pass && num == 0) continue;        // an accumulator renders nothing
+        for (int k = 0; k < s->nbuf; k++) ck(hipMalloc((void **)&set[k], s->elems * sizeof(double)), "hipMalloc(progressive planes)");
+    }
+    ck(hipMalloc((void **)&s->partials, 3 * prg::kMaxBlocks * sizeof(double)), "hipMalloc(progressive partials)");
+    ck(hipMalloc((void **)&s->d_est, sizeof(prg::Estimate)), "hipMalloc(progressive estimate)");
+    ck(hipHostMalloc((void **)&s->h_est, sizeof(prg::Estimate)), "hipHostMalloc(progressive estimate)");
+    for (auto &e : s->ev) ck(hipEventCreate(&e), "hipEventCreate");
+    *out = s.release();
+}
+
 } // namespace
 
 extern "C" {
 
 int gdpt_progressive_create(GdptScene *scene, const GdptProgressiveConfig *config, void *stream, GdptProgressive **out) {
+    return gdpt::guarded([&]() { create_session("gdpt_progressive_create", scene, config, true, 0, 0, stream, out); });
+}
+
+int gdpt_progressive_create_slice(GdptScene *scene, const GdptProgressiveConfig *config, int first_sample, int num_samples, void *stream,
+                                  GdptProgressive **out) {
+    return gdpt::guarded([&]() { create_session("gdpt_progressive_create_slice", scene, config, false, first_sample, num_samples, stream, out); });
+}
+
+int gdpt_progressive_merge(GdptProgressive *dst, const GdptProgressive *src) {
     return gdpt::guarded([&]() {
-        if (!scene || !out) throw std::runtime_error("gdpt_progressive_create: null argument");
-        GdptProgressiveConfig cfg = config ? *config : GdptProgressiveConfig{};
-        if (cfg.mode != GDPT_PROGRESSIVE_GRADPATH && cfg.mode != GDPT_PROGRESSIVE_PATH) throw std::runtime_error("gdpt_progressive_create: unknown mode");
-        if (cfg.shift_mode != GDPT_SHIFT_REFERENCE && cfg.shift_mode != GDPT_SHIFT_RECONNECT) throw std::runtime_error("gdpt_progressive_create: unknown shift_mode");
-        if (cfg.mode == GDPT_PROGRESSIVE_PATH && scene->view.num_lights <= 0) throw std::runtime_error("gdpt_progressive_create: the scene has no emitter to sample");
-        const int budget = cfg.budget_spp > 0 ? cfg.budget_spp : scene->scene_spp;
-        if (budget <= 0) throw std::runtime_error("gdpt_progressive_create: budget_spp must be > 0");
-        const int w = scene->view.cam.width, h = scene->view.cam.height;
-        if ((unsigned long long)w * (unsigned long long)h > (~0ull >> 1) / (unsigned long long)budget)
-            throw std::runtime_error("gdpt_progressive_create: width * height * budget_spp does not fit 63 bits");
-        if ((long long)w * h > (1LL << 29)) throw std::runtime_error("gdpt_progressive_create: film too large");
-        ck(hipSetDevice(scene->device), "hipSetDevice");
-        std::unique_ptr<GdptProgressive> s(new GdptProgressive());
-        s->scene = scene; s->device = scene->device; s->stream = (hipStream_t)stream;
-        s->mode = cfg.mode; s->shift = cfg.shift_mode; s->max_depth_override = cfg.max_depth_override;
-        s->nbuf = cfg.mode == GDPT_PROGRESSIVE_PATH ? 1 : 5;
-        s->w = w; s->h = h; s->budget = budget; s->elems = (size_t)w * h * 3;
-        for (auto *set : {s->pass, s->mean, s->m2})
-            for (int k = 0; k < s->nbuf; k++) ck(hipMalloc((void **)&set[k], s->elems * sizeof(double)), "hipMalloc(progressive planes)");
-        ck(hipMalloc((void **)&s->partials, 3 * prg::kMaxBlocks * sizeof(double)), "hipMalloc(progressive partials)");
-        ck(hipMalloc((void **)&s->d_est, sizeof(prg::Estimate)), "hipMalloc(progressive estimate)");
-        ck(hipHostMalloc((void **)&s->h_est, sizeof(prg::Estimate)), "hipHostMalloc(progressive estimate)");
-        for (auto &e : s->ev) ck(hipEventCreate(&e), "hipEventCreate");
-        *out = s.release();
+        if (!dst || !src) throw std::runtime_error("gdpt_progressive_merge: null argument");
+        if (dst->group_total) throw std::runtime_error("gdpt_progressive_merge: dst is the total of a group (its group rebuilds it)");
+        prg::merge(*dst, *src);
     });
 }
 
@@ -279,7 +412,8 @@ void gdpt_progressive_free(GdptProgressive *session) {
 int gdpt_progressive_add_pass(GdptProgressive *session, int spp, GdptRenderStats *stats) {
     return gdpt::guarded([&]() {
         if (!session) throw std::runtime_error("gdpt_progressive_add_pass: null session");
-        add_pass(*session, spp, stats);
+        if (session->group_total) throw std::runtime_error("gdpt_progressive_add_pass: the session is the total of a group (it draws no samples of its own)");
+        prg::add_pass(*session, spp, stats);
     });
 }
 
@@ -363,13 +497,14 @@ int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass
         if (pass_spp <= 0) throw std::runtime_error("gdpt_progressive_run: pass_spp must be > 0");
         if (std::isnan(target_error)) throw std::runtime_error("gdpt_progressive_run: target_error is NaN");
         GdptProgressive &s = *session;
+        if (s.group_total) throw std::runtime_error("gdpt_progressive_run: the session is the total of a group (run the group)");
         auto reached = [&]() { return target_error > 0 && s.passes >= 2 && error_estimate(s) <= target_error; };
         int added = 0;
         for (;;) {
             if (reached()) { s.stop_reason = GDPT_STOP_TARGET; break; }
-            if (s.done >= s.budget) { s.stop_reason = GDPT_STOP_BUDGET; break; }
+            if (s.own_done >= s.own) { s.stop_reason = GDPT_STOP_BUDGET; break; }
             if (max_passes > 0 && added >= max_passes) { s.stop_reason = GDPT_STOP_MAX_PASSES; break; }
-            add_pass(s, std::min(pass_spp, s.budget - s.done), nullptr);
+            prg::add_pass(s, std::min(pass_spp, s.own - s.own_done), nullptr);
             added++;
         }
         fill_status(s, status);

@@ -1,0 +1,60 @@
+// progressive_internal.h — the progressive session handle and the entry points shared by progressive.hip (sessions, the merge of
+// sessions) and progressive_group.hip (one slice session per device, a merged total).
+#pragma once
+#include "scene_internal.h"
+
+#include <utility>
+#include <vector>
+
+namespace prg {
+struct Estimate { double sum_var, sum_mean2, left_out; };
+} // namespace prg
+
+struct GdptProgressive {
+    GdptScene *scene = nullptr;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    int mode = GDPT_PROGRESSIVE_GRADPATH, shift = GDPT_SHIFT_REFERENCE, max_depth_override = 0;
+    int nbuf = 5, w = 0, h = 0;
+    int block = 0;                   // size of every pixel's stream block: the stream_spp of every pass
+    int first = 0, own = 0;          // the slice [first, first + own) of the block this session draws its passes from
+    int own_done = 0;                // ... of which [first, first + own_done) has been drawn
+    int merged = 0;                  // samples per pixel taken in by merges
+    int done = 0, passes = 0;        // W and K of the statistics held: own passes and merged sessions
+    int stop_reason = GDPT_STOP_NONE;
+    bool group_total = false;        // the borrowed total of a GdptProgressiveGroup: the public add_pass / run / merge refuse it
+    std::vector<std::pair<int, int>> merged_intervals;    // [begin, end) of the block, as taken in by merges
+    size_t elems = 0;
+    double *pass[5] = {}, *mean[5] = {}, *m2[5] = {};
+    double *stage[10] = {};          // mean / M2 planes of a merge source on another device, allocated by the first such merge
+    double *var[7] = {};             // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
+    double *asm_buf[4] = {};         // c, cx, cy, reconstruction: allocated by the first reconstruct
+    double *partials = nullptr;
+    prg::Estimate *d_est = nullptr, *h_est = nullptr;     // device / pinned host
+    prg::Estimate est{};             // of the last fold or merge (valid from 2 passes)
+    hipEvent_t ev[2] = {nullptr, nullptr};                // around the fold / merge launches
+    double fold_ms = 0;              // device time of the last fold (fold_kernel + finish_kernel) or merge (merge_kernel + finish_kernel)
+    GdptRenderStats totals{};
+
+    ~GdptProgressive() {
+        hipSetDevice(device);
+        for (auto *set : {pass, mean, m2}) for (int k = 0; k < 5; k++) if (set[k]) hipFree(set[k]);
+        for (double *p : stage) if (p) hipFree(p);
+        for (double *p : var) if (p) hipFree(p);
+        for (double *p : asm_buf) if (p) hipFree(p);
+        if (partials) hipFree(partials);
+        if (d_est) hipFree(d_est);
+        if (h_est) hipHostFree(h_est);
+        for (auto &e : ev) if (e) hipEventDestroy(e);
+    }
+};
+
+namespace prg {
+// What the C entry points of the same names do, without their guard against a group's total; they throw.
+void add_pass(GdptProgressive &s, int spp, GdptRenderStats *stats);
+void merge(GdptProgressive &dst, const GdptProgressive &src);
+// Back to the state of a fresh accumulator: nothing held (the planes keep their bytes: the next merge overwrites them).
+void reset(GdptProgressive &s);
+double error_estimate(const GdptProgressive &s);
+void fill_status(const GdptProgressive &s, GdptProgressiveStatus *st);
+} // namespace prg

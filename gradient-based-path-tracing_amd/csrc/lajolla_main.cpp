@@ -26,6 +26,9 @@
 //                 output is the session's reconstruction (Integrator::Path scenes: the mean). --target-error E stops at the first
 //                 pass (from the second on) whose estimated relative RMSE of the primal is <= E; --variance FILE writes the
 //                 variance of the primal mean. Single device, --rng sample only
+//   --sample-devices a,b,..   the session's samples split over these devices (HIP ordinals, repeats allowed) on the sample axis
+//                 (gdpt_progressive_group_*: device i draws streams [i B / N, (i+1) B / N) of every pixel's block of B = --spp, the
+//                 merged total is what is reconstructed). Needs --pass-spp; not with --gpus / --devices (row bands are another thing)
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -48,6 +51,7 @@ int main(int argc, char *argv[]) {
     bool weighted = false;
     double conf_floor = 0.0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
+    std::vector<int32_t> sample_devices;      // --sample-devices: a progressive group
     GdptReconParams recon{};          // norm == GDPT_RECON_L2: the reference's reconstruction
     double alpha = 0.04;
     std::string outputfile = "";
@@ -81,6 +85,19 @@ int main(int argc, char *argv[]) {
                 if (c == std::string::npos) c = v.size();
                 if (multi.num_devices >= GDPT_MULTI_MAX_DEVICES) { std::cerr << "--devices: too many" << std::endl; return 2; }
                 multi.devices[multi.num_devices++] = std::stoi(v.substr(pos, c - pos));
+                pos = c + 1;
+            }
+        }
+        else if (a == "--sample-devices") {
+            std::string v = next();
+            sample_devices.clear();
+            size_t pos = 0;
+            while (pos <= v.size()) {
+                size_t c = v.find(',', pos);
+                if (c == std::string::npos) c = v.size();
+                if (sample_devices.size() >= GDPT_MULTI_MAX_DEVICES) { std::cerr << "--sample-devices: too many" << std::endl; return 2; }
+                if (c == pos || v.find_first_not_of("0123456789", pos) < c || c - pos > 9) { std::cerr << "--sample-devices expects a,b,.. (HIP device ordinals)" << std::endl; return 2; }
+                sample_devices.push_back(std::stoi(v.substr(pos, c - pos)));
                 pos = c + 1;
             }
         }
@@ -126,6 +143,8 @@ int main(int argc, char *argv[]) {
         else filenames.push_back(a);
     }
     if (recon.norm == GDPT_RECON_L1 && multi.num_devices > 0) { std::cerr << "--reconstruct l1 is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
+    if (!sample_devices.empty() && pass_spp <= 0) { std::cerr << "--sample-devices needs --pass-spp (it splits a progressive session)" << std::endl; return 2; }
+    if (!sample_devices.empty() && multi.num_devices > 0) { std::cerr << "--sample-devices splits samples, --gpus / --devices split rows: not together" << std::endl; return 2; }
     if (pass_spp > 0 && multi.num_devices > 0) { std::cerr << "--pass-spp is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
     if (pass_spp > 0 && rng == GDPT_RNG_TILE) { std::cerr << "--pass-spp needs --rng sample (the tile streams have no sample window)" << std::endl; return 2; }
     if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
@@ -147,9 +166,16 @@ int main(int argc, char *argv[]) {
             return 134;
         }
         const bool sharded = multi.num_devices > 0 && desc->integrator == GDPT_INTEGRATOR_GRADPATH;
+        const bool grouped = !sample_devices.empty();
         GdptScene *scene = nullptr;
         GdptMulti *mscene = nullptr;
-        if ((sharded ? gdpt_multi_create(desc, &multi, &mscene) : gdpt_scene_upload(desc, device, &scene)) != 0) {
+        GdptProgressiveGroup *group = nullptr;
+        const bool path = desc->integrator == GDPT_INTEGRATOR_PATH;
+        GdptProgressiveConfig cfg{};      // of the session or group that --pass-spp asks for
+        cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = shift; cfg.budget_spp = spp;
+        if ((grouped   ? gdpt_progressive_group_create(desc, sample_devices.data(), (int)sample_devices.size(), &cfg, &group)
+             : sharded ? gdpt_multi_create(desc, &multi, &mscene)
+                       : gdpt_scene_upload(desc, device, &scene)) != 0) {
             std::cerr << "terminate: " << gdpt_last_error() << std::endl;
             return 134;
         }
@@ -168,12 +194,14 @@ int main(int argc, char *argv[]) {
         int rc;
         GdptProgressiveStatus prog{};
         if (pass_spp > 0) {
-            const bool path = desc->integrator == GDPT_INTEGRATOR_PATH;
-            GdptProgressiveConfig cfg{};
-            cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = shift; cfg.budget_spp = spp;
             GdptProgressive *session = nullptr;
-            rc = gdpt_progressive_create(scene, &cfg, nullptr, &session);
-            if (rc == 0) rc = gdpt_progressive_run(session, target_error, pass_spp, 0, &prog);
+            if (grouped) {                // the merged total is a session like any other: everything below reads it
+                rc = gdpt_progressive_group_run(group, target_error, pass_spp, 0, &prog);
+                session = gdpt_progressive_group_total(group);
+            } else {
+                rc = gdpt_progressive_create(scene, &cfg, nullptr, &session);
+                if (rc == 0) rc = gdpt_progressive_run(session, target_error, pass_spp, 0, &prog);
+            }
             double *means[5] = {path ? image.data() : nullptr, nullptr, nullptr, nullptr, nullptr};
             if (rc == 0 && path) rc = gdpt_progressive_read(session, 0, means, nullptr, nullptr);
             if (rc == 0 && !path && weighted) {
@@ -202,7 +230,7 @@ int main(int argc, char *argv[]) {
                 if (rc == 0) rc = gdpt_imwrite(variance_file.c_str(), w, h, variance.data());
             }
             std::string err = rc != 0 ? gdpt_last_error() : "";
-            gdpt_progressive_free(session);
+            if (!grouped) gdpt_progressive_free(session);
             if (rc != 0) { std::cerr << "terminate: " << err << std::endl; return 134; }
             rs = prog.totals;
         } else if (sharded) {
@@ -233,15 +261,38 @@ int main(int argc, char *argv[]) {
                   << " CG iterations " << ps.solve_ms << " ms, non-finite samples " << rs.nonfinite_samples << std::endl;
         if (pass_spp > 0) {
             static const char *const why[] = {"none", "target", "budget", "max_passes"};
-            std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << prog.budget_spp
+            int budget = prog.budget_spp;
+            if (grouped) {                // (the total reports as its budget what has been merged in: the group's is its members' slices together)
+                budget = 0;
+                for (int k = 0; k < (int)sample_devices.size(); k++) {
+                    GdptProgressiveStatus st{};
+                    if (gdpt_progressive_group_member_status(group, k, &st) != 0) { std::cerr << "terminate: " << gdpt_last_error() << std::endl; return 134; }
+                    budget += st.budget_spp;
+                }
+            }
+            std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << budget
                       << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
                       << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
+        }
+        if (grouped) {
+            const int n = (int)sample_devices.size();
+            int first = 0;                // the slices are contiguous, in member order: each member reports its size
+            std::cout << "[gdpt] " << n << " sample slices:";
+            for (int k = 0; k < n; k++) {
+                GdptProgressiveStatus st{};
+                if (gdpt_progressive_group_member_status(group, k, &st) != 0) { std::cerr << "terminate: " << gdpt_last_error() << std::endl; return 134; }
+                std::cout << " device " << sample_devices[(size_t)k] << " [" << first << "," << first + st.budget_spp << ") " << st.spp_done << " spp in " << st.passes
+                          << " passes, render " << st.totals.render_ms << " ms;";
+                first += st.budget_spp;
+            }
+            std::cout << " last merge " << prog.fold_ms << " ms" << std::endl;
         }
         if (sharded) {
             std::cout << "[gdpt] " << ms.num_devices << " row bands (" << (ms.exchange == GDPT_EXCHANGE_RCCL ? "RCCL" : "peer copies") << "): render";
             for (int k = 0; k < ms.num_devices; k++) std::cout << " " << ms.render_ms[k];
             std::cout << " ms, halo+assemble+gather " << ms.exchange_ms << " ms, solve " << ms.solve_ms << " ms, wall " << ms.wall_ms << " ms" << std::endl;
         }
+        gdpt_progressive_group_free(group);
         gdpt_multi_free(mscene);
         gdpt_scene_free(scene);
         gdpt_free_scene_desc(desc);

@@ -407,6 +407,53 @@ int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, cons
  * <= target_error (GDPT_STOP_TARGET; target_error <= 0: no target). Blocking; status (nullable) as gdpt_progressive_status. */
 int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass_spp, int max_passes, GdptProgressiveStatus *status);
 
+/* ---- sessions over a slice of the stream block, and their merge: a session's samples split over sessions and devices ----
+ * A pass is identified by its window of the block of budget_spp streams alone, so two sessions that own disjoint slices of one
+ * block render disjoint samples of the whole film, each at the same cost per sample (no bands, no halo, no balancing). What they
+ * hold combines exactly (Chan, Golub, LeVeque 1979), per buffer component:
+ *     W = Wa + Wb;  d = mean_b - mean_a;  mean = mean_a + (Wb/W) d;  M2 = (M2a + M2b) + d d (Wa Wb / W);  K = Ka + Kb
+ * which is the state of one session that folded all the passes of both: var_mean = M2 / ((K-1) W) and the error estimate keep
+ * their meaning.
+ * gdpt_progressive_create_slice: config->budget_spp stays the size of the block (the stream_spp of every pass); the session owns
+ * [first_sample, first_sample + num_samples) of it and its passes draw the windows {budget_spp, first_sample + own samples done}.
+ * first_sample < 0, num_samples < 0 and a slice that leaves [0, budget_spp) are refused; num_samples == 0 is an accumulator that only
+ * receives merges. gdpt_progressive_create is the slice [0, budget_spp). For every session GdptProgressiveStatus reads:
+ *     spp_done = W, all samples held, merged ones included;  passes = K;  totals include the totals of merged sessions;
+ *     budget_spp = the slice size + the samples merged in ("budget spent" stays spp_done == budget_spp);
+ * add_pass and run check the budget against the session's own slice. */
+int gdpt_progressive_create_slice(GdptScene *scene, const GdptProgressiveConfig *config, int first_sample, int num_samples, void *stream,
+                                  GdptProgressive **out);
+/* dst takes in src's statistics by the update above (one launch over the film, on dst's stream); src is unchanged. Blocking. Merging
+ * into a session that holds nothing copies src's planes, bit for bit. Afterwards error_estimate, pixels_left_out and fold_ms refer to
+ * the merge launch as they would to a fold, and dst may go on adding passes of its own. A src without passes is a no-op.
+ * Every session keeps the intervals of the block it holds (its own [first, first + own samples done) and the merged ones). Refused:
+ * a src holding samples that dst holds or that dst's own slice may still draw (so: the same src twice, overlapping slices); another
+ * film size, mode, shift mode, max_depth_override or block size; dst == src; NULL. src may live on another device: its planes are
+ * copied into staging planes on dst's device (hipMemcpyPeerAsync on dst's stream; allocated by the first such merge). Both sessions
+ * must be idle (every session call is blocking: a concern for callers with threads only). */
+int gdpt_progressive_merge(GdptProgressive *dst, const GdptProgressive *src);
+
+/* A group: the budget_spp of one session split over `num_devices` slice sessions, one per entry of `devices` (HIP ordinals; a device
+ * may appear more than once; 1..GDPT_MULTI_MAX_DEVICES entries), each with its own uploaded scene and stream. Member i owns
+ * [floor(i B / N), floor((i+1) B / N)) of the budget B. The total is an accumulator on devices[0]: a GdptProgressive that
+ * gdpt_progressive_read / _reconstruct / _reconstruct_weighted / _status accept; add_pass / run / merge on it are refused.
+ * Members on devices other than devices[0] reach the total through gdpt_progressive_merge's cross-device copy; the test of that path
+ * (test_group_on_two_gpus) needs two GPUs, every other test runs the group with one device listed several times. */
+typedef struct GdptProgressiveGroup GdptProgressiveGroup;   /* opaque */
+int gdpt_progressive_group_create(const GdptSceneDesc *desc, const int32_t *devices, int num_devices,
+                                  const GdptProgressiveConfig *config, GdptProgressiveGroup **out);
+void gdpt_progressive_group_free(GdptProgressiveGroup *group);
+/* Rounds: every member with budget left adds one pass of min(pass_spp, left), one host thread per member; then the total is
+ * rebuilt: emptied, all members merged into it in member order (the bits do not depend on thread timing). With target_error > 0
+ * the total is rebuilt after every round, otherwise once before the call returns. Stops when all slices are spent
+ * (GDPT_STOP_BUDGET), max_rounds rounds were done by this call (GDPT_STOP_MAX_PASSES; <= 0: no limit), or K >= 2 and the total's
+ * error estimate is <= target_error (GDPT_STOP_TARGET). status (nullable): the total's; totals.render_ms is the sum of the members'
+ * device times. Blocking. */
+int gdpt_progressive_group_run(GdptProgressiveGroup *group, double target_error, int pass_spp, int max_rounds,
+                               GdptProgressiveStatus *status);
+GdptProgressive *gdpt_progressive_group_total(GdptProgressiveGroup *group);   /* borrowed; valid until gdpt_progressive_group_free */
+int gdpt_progressive_group_member_status(const GdptProgressiveGroup *group, int member, GdptProgressiveStatus *status);
+
 /* ---- variance-weighted reconstruction: generalised least squares on per-row confidences (not part of the reference) ----
  * gdpt_reconstruct's rows (data row per pixel, x-edge for x >= 1, y-edge for y >= 1, natural boundary), each weighted by a
  * confidence taken from the variance of its input: minimises  sum kappa_row |r_row|^2  with kappa ~ 1 / variance. A firefly sits in
