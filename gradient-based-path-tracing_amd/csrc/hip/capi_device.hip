@@ -26,13 +26,15 @@ namespace {
 
 using gdpt::ck;
 
+// a scene table, owned by the scene
 template <class T>
-T *upload(const std::vector<T> &v) {
+T *upload(GdptScene *sc, const std::vector<T> &v) {
     if (v.empty()) return nullptr;
-    T *d = nullptr;
-    ck(hipMalloc((void **)&d, v.size() * sizeof(T)), "hipMalloc(scene)");
+    gdpt::DeviceBuffer<unsigned char> d;
+    d.alloc(v.size() * sizeof(T), "hipMalloc(scene)");
     ck(hipMemcpy(d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice), "hipMemcpy(scene)");
-    return d;
+    sc->allocations.push_back(std::move(d));
+    return (T *)sc->allocations.back().data();
 }
 
 } // namespace
@@ -279,20 +281,20 @@ void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
     v.cam.width = cam.width; v.cam.height = cam.height; v.cam.filter_type = cam.filter_type; v.cam.filter_param = cam.filter_param;
     v.cam.pow2_film = ((cam.width & (cam.width - 1)) == 0 && (cam.height & (cam.height - 1)) == 0) ? 1 : 0;
     v.cam.inv_width = 1.0 / (double)cam.width; v.cam.inv_height = 1.0 / (double)cam.height;
-    v.nodes = sc->keep(upload(bvh.nodes));
-    v.nodes4 = sc->keep(upload(nodes4));
-    v.nodes8 = sc->keep(upload(wide.nodes8));
-    v.nodes4q = GDPT_HBM_Q4 ? sc->keep(upload(gdpt::quantise_bvh4(nodes4))) : nullptr;
-    v.prims = sc->keep(upload(prims));
-    v.tris = sc->keep(upload(tris));
-    v.spheres = sc->keep(upload(spheres));
-    v.materials = sc->keep(upload(materials));
-    v.light_intensity = sc->keep(upload(light_intensity));
-    v.images = sc->keep(upload(images));
-    v.texels = sc->keep(upload(texels));
-    v.lights = sc->keep(upload(dlights));
-    v.light_tri_cdf = sc->keep(upload(light_tri_cdf));
-    v.light_tri_pos = sc->keep(upload(light_tri_pos)); v.light_tri_nrm = sc->keep(upload(light_tri_nrm));
+    v.nodes = upload(sc, bvh.nodes);
+    v.nodes4 = upload(sc, nodes4);
+    v.nodes8 = upload(sc, wide.nodes8);
+    v.nodes4q = GDPT_HBM_Q4 ? upload(sc, gdpt::quantise_bvh4(nodes4)) : nullptr;
+    v.prims = upload(sc, prims);
+    v.tris = upload(sc, tris);
+    v.spheres = upload(sc, spheres);
+    v.materials = upload(sc, materials);
+    v.light_intensity = upload(sc, light_intensity);
+    v.images = upload(sc, images);
+    v.texels = upload(sc, texels);
+    v.lights = upload(sc, dlights);
+    v.light_tri_cdf = upload(sc, light_tri_cdf);
+    v.light_tri_pos = upload(sc, light_tri_pos); v.light_tri_nrm = upload(sc, light_tri_nrm);
     sc->has_envmap = desc->has_envmap != 0;
     v.num_nodes = (int)bvh.nodes.size(); v.num_nodes4 = (int)nodes4.size(); v.num_nodes8 = (int)wide.nodes8.size(); v.num_prims = (int)prims.size();
     v.num_tris = (int)tris.size(); v.num_spheres = (int)spheres.size();
@@ -375,20 +377,20 @@ void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
         v.has_envmap = 1; v.env_light_id = e.light_id; v.env_image_id = e.image_id; v.env_w = w; v.env_h = h; v.env_scale = e.scale;
         std::memcpy(v.env_to_world, e.to_world, sizeof(v.env_to_world));
         std::memcpy(v.env_to_local, e.to_local, sizeof(v.env_to_local));
-        v.env_cdf_rows = sc->keep(upload(cdf_rows)); v.env_pdf_rows = sc->keep(upload(pdf_rows));
-        v.env_cdf_marginals = sc->keep(upload(cdf_m)); v.env_pdf_marginals = sc->keep(upload(pdf_m));
+        v.env_cdf_rows = upload(sc, cdf_rows); v.env_pdf_rows = upload(sc, pdf_rows);
+        v.env_cdf_marginals = upload(sc, cdf_m); v.env_pdf_marginals = upload(sc, pdf_m);
         if (env_power_slot >= 0 && env_power_slot < (int)light_power.size())
             light_power[(size_t)env_power_slot] = 3.14159265358979323846 * radius * radius * total_values / ((double)w * (double)h);
     }
     if (!light_power.empty()) table_1d(light_power, light_pmf, light_cdf);
-    v.light_pmf = sc->keep(upload(light_pmf)); v.light_cdf = sc->keep(upload(light_cdf));
+    v.light_pmf = upload(sc, light_pmf); v.light_cdf = upload(sc, light_cdf);
 
-    ck(hipMalloc((void **)&sc->d_counters, sizeof(gdpt::RenderCounters)), "hipMalloc(counters)");
-    ck(hipMalloc((void **)&sc->d_queue, sizeof(unsigned long long)), "hipMalloc(queue)");
+    sc->d_counters.alloc(1, "hipMalloc(counters)");
+    sc->d_queue.alloc(1, "hipMalloc(queue)");
     { hipDeviceProp_t prop; ck(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties"); sc->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
-    ck(hipHostMalloc((void **)&sc->h_counters, sizeof(gdpt::RenderCounters)), "hipHostMalloc(counters)");
-    ck(hipEventCreate(&sc->ev0), "hipEventCreate");
-    ck(hipEventCreate(&sc->ev1), "hipEventCreate");
+    sc->h_counters.alloc(1, "hipHostMalloc(counters)");
+    sc->ev0.create();
+    sc->ev1.create();
 }
 
 } // namespace gdpt
@@ -471,11 +473,7 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
         // profiles/r03_band_costs.txt.)
         rl.plan = gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)v.cam.width * b.plan_rows, gdpt::resident_lanes(rl), take_pct);
         const size_t need = (size_t)16 * (size_t)gdpt::band_slots(v.cam.width, b.row_end - b.row_begin) * (size_t)rl.plan.n;
-        if (need > sc->partials_doubles) {
-            if (sc->d_partials) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); hipFree(sc->d_partials); sc->d_partials = nullptr; }
-            ck(hipMalloc((void **)&sc->d_partials, need * sizeof(double)), "hipMalloc(work-item partials)");
-            sc->partials_doubles = need;
-        }
+        sc->d_partials.grow(need, stream, "hipMalloc(work-item partials)");
         rl.partials = sc->d_partials; rl.queue_head = sc->d_queue;
     }
     return rl;
@@ -525,33 +523,18 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
     rl.replay_per_step = debug_knob_int("replay_per_step", 0);
     const long long items = band_slots(sc->view.cam.width, b.row_end - b.row_begin) * rl.plan.n;
     if (needs_bounce_log(rl.route)) {
-        const size_t need = twosided_log_bytes(persistent_blocks(rl, items));
-        if (need > sc->bounce_log_bytes) {
-            if (sc->d_bounce_log) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); hipFree(sc->d_bounce_log); sc->d_bounce_log = nullptr; }
-            ck(hipMalloc(&sc->d_bounce_log, need), "hipMalloc(bounce log)");
-            sc->bounce_log_bytes = need;
-        }
-        rl.bounce_log = sc->d_bounce_log; rl.bounce_log_bytes = sc->bounce_log_bytes;
+        sc->d_bounce_log.grow(twosided_log_bytes(persistent_blocks(rl, items)), stream, "hipMalloc(bounce log)");
+        rl.bounce_log = sc->d_bounce_log; rl.bounce_log_bytes = sc->d_bounce_log.size();
     }
     if (is_wavefront(rl.route)) {
         int slots = wf_slot_count(items);
         { const int forced = debug_knob_int("wf_slots", 0); if (forced > 0) slots = std::min(slots, (forced + 255) / 256 * 256); }   // tests: force slot reuse
-        if (slots > sc->wf_slots) {
-            ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
-            if (sc->d_wf_state) hipFree(sc->d_wf_state);
-            if (sc->d_wf_live) hipFree(sc->d_wf_live);
-            if (sc->d_wf_aux) hipFree(sc->d_wf_aux);
-            sc->d_wf_state = nullptr; sc->d_wf_live = nullptr; sc->d_wf_aux = nullptr; sc->wf_slots = 0;
-            ck(hipMalloc((void **)&sc->d_wf_state, (size_t)slots * wf_words() * sizeof(unsigned long long)), "hipMalloc(wavefront state)");
-            ck(hipMalloc((void **)&sc->d_wf_live, (size_t)slots * sizeof(unsigned)), "hipMalloc(wavefront live list)");
-            ck(hipMalloc(&sc->d_wf_aux, wf_aux_bytes(slots)), "hipMalloc(wavefront ray / hit records)");
-            sc->wf_slots = slots;
-        }
-        if (!sc->d_wf_counters) {
-            ck(hipMalloc((void **)&sc->d_wf_counters, sizeof(unsigned) * 3 * wf_max_generations()), "hipMalloc(wavefront counters)");
-            ck(hipHostMalloc((void **)&sc->h_wf_word, sizeof(unsigned)), "hipHostMalloc(wavefront)");
-            ck(hipEventCreateWithFlags(&sc->wf_event, hipEventDisableTiming), "hipEventCreate");
-        }
+        sc->d_wf_state.grow((size_t)slots * wf_words(), stream, "hipMalloc(wavefront state)");
+        sc->d_wf_live.grow((size_t)slots, stream, "hipMalloc(wavefront live list)");
+        sc->d_wf_aux.grow(wf_aux_bytes(slots), stream, "hipMalloc(wavefront ray / hit records)");
+        if (!sc->d_wf_counters) sc->d_wf_counters.alloc((size_t)3 * wf_max_generations(), "hipMalloc(wavefront counters)");
+        if (!sc->h_wf_word) sc->h_wf_word.alloc(1, "hipHostMalloc(wavefront)");
+        if (!sc->wf_event) sc->wf_event.create(hipEventDisableTiming);
         rl.wf_aux = sc->d_wf_aux; rl.wf_sort = debug_knob_int("wf_sort", 1);
         for (int k = 0; k < 6; k++) rl.wf_bounds[k] = sc->bounds[k];
         rl.wf_state = sc->d_wf_state; rl.wf_live = sc->d_wf_live; rl.wf_counters = sc->d_wf_counters; rl.wf_host = sc->h_wf_word;
@@ -591,6 +574,24 @@ gdpt::ReconL1Params resolve_recon(const GdptReconParams &in) {
     p.eps_floor = in.eps_floor > 0 ? in.eps_floor : 1e-3;
     p.cg_tol = in.cg_tol > 0 ? in.cg_tol : 1e-6;
     return p;
+}
+// The host-pointer entry points of the solvers: the k host planes of `in` (W*H*3 doubles each) go to device planes d[0..k), `run` works
+// on them and writes the plane d[k], which comes back into `out`. The planes go when this returns or throws.
+using Planes = std::vector<gdpt::DeviceBuffer<double>>;
+template <class F>
+void on_device_planes(std::initializer_list<const double *> in, int width, int height, double *out, const char *what, F &&run) {
+    const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
+    Planes d(in.size() + 1);
+    for (auto &b : d) b.alloc(elems, what);
+    size_t k = 0;
+    for (const double *h : in) ck(hipMemcpy(d[k++], h, bytes, hipMemcpyHostToDevice), "hipMemcpy");
+    run(d);
+    ck(hipMemcpy(out, d.back(), bytes, hipMemcpyDeviceToHost), "hipMemcpy");
+}
+
+void fill_poisson_stats(GdptPoissonStats *s, const gdpt::PoissonResult &r) {
+    if (!s) return;
+    s->iterations = r.iterations; s->solver = r.solver; s->rel_residual = r.rel_residual; s->solve_ms = r.solve_ms;
 }
 void fill_recon_stats(GdptReconStats *s, const gdpt::ReconL1Result &r) {
     if (!s) return;
@@ -777,7 +778,7 @@ int gdpt_assemble_solve_device(int width, int height, const double *d_img, const
         if (!d_img || !d_cx0 || !d_cy0 || !d_cx1 || !d_cy1 || !d_c || !d_cx || !d_cy || !d_out) throw std::runtime_error("gdpt_assemble_solve_device: null buffer");
         gdpt::PoissonResult r = gdpt::assemble_solve_device(width, height, d_img, d_cx0, d_cy0, d_cx1, d_cy1, d_c, d_cx, d_cy, dataCost, d_out, solver, tol, max_iters,
                                                             (hipStream_t)stream, stats != nullptr);
-        if (stats) { stats->iterations = r.iterations; stats->solver = r.solver; stats->rel_residual = r.rel_residual; stats->solve_ms = r.solve_ms; }
+        fill_poisson_stats(stats, r);
     });
 }
 
@@ -785,8 +786,7 @@ int gdpt_poisson_forget_stream(void *stream) {
     return gdpt::guarded([&]() {
         int dev = 0;
         ck(hipGetDevice(&dev), "hipGetDevice");
-        gdpt::poisson_forget_stream(dev, (hipStream_t)stream);
-        gdpt::recon_l1_forget_stream(dev, (hipStream_t)stream);
+        gdpt::forget_stream(dev, (hipStream_t)stream);
     });
 }
 
@@ -796,7 +796,7 @@ int gdpt_poisson_solve_device(int width, int height, const double *d_c, const do
     return gdpt::guarded([&]() {
         if (!d_c || !d_gx || !d_gy || !d_out) throw std::runtime_error("gdpt_poisson_solve_device: null buffer");
         gdpt::PoissonResult r = gdpt::poisson_solve_device(width, height, d_c, d_gx, d_gy, dataCost, d_out, solver, tol, max_iters, (hipStream_t)stream, stats != nullptr);
-        if (stats) { stats->iterations = r.iterations; stats->solver = r.solver; stats->rel_residual = r.rel_residual; stats->solve_ms = r.solve_ms; }
+        fill_poisson_stats(stats, r);
     });
 }
 
@@ -808,19 +808,9 @@ int gdpt_poisson_solve_ex(int width, int height, const double *imgData, const do
         int ndev = 0;
         ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
         if (ndev <= 0) throw std::runtime_error("gdpt_poisson_solve: no HIP device visible (this library has no CPU fallback)");
-        size_t bytes = (size_t)width * height * 3 * sizeof(double);
-        double *d[4] = {nullptr, nullptr, nullptr, nullptr};
-        auto cleanup = [&]() { for (auto p : d) if (p) hipFree(p); };
-        try {
-            for (auto &p : d) ck(hipMalloc((void **)&p, bytes), "hipMalloc(poisson io)");
-            ck(hipMemcpy(d[0], imgData, bytes, hipMemcpyHostToDevice), "hipMemcpy");
-            ck(hipMemcpy(d[1], imgGradX, bytes, hipMemcpyHostToDevice), "hipMemcpy");
-            ck(hipMemcpy(d[2], imgGradY, bytes, hipMemcpyHostToDevice), "hipMemcpy");
-            gdpt::PoissonResult r = gdpt::poisson_solve_device(width, height, d[0], d[1], d[2], dataCost, d[3], solver, tol, max_iters, nullptr, stats != nullptr);
-            ck(hipMemcpy(imgOut, d[3], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-            if (stats) { stats->iterations = r.iterations; stats->solver = r.solver; stats->rel_residual = r.rel_residual; stats->solve_ms = r.solve_ms; }
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        on_device_planes({imgData, imgGradX, imgGradY}, width, height, imgOut, "hipMalloc(poisson io)", [&](const Planes &d) {
+            fill_poisson_stats(stats, gdpt::poisson_solve_device(width, height, d[0], d[1], d[2], dataCost, d[3], solver, tol, max_iters, nullptr, stats != nullptr));
+        });
     });
 }
 
@@ -838,13 +828,13 @@ int gdpt_gradient_path_render(GdptScene *scene, const GdptRenderParams *params, 
         const int w = scene->view.cam.width, h = scene->view.cam.height;
         size_t elems = (size_t)w * h * 3;
         scene->ensure_buffers(elems);
-        double **b = scene->d_buf;
+        auto &b = scene->d_buf;
         GdptRenderParams p = params ? *params : GdptRenderParams{};
         p.row_begin = 0; p.row_end = 0;   // the solve is global: whole image only
         GdptRenderStats local{};
         render_device_impl(scene, &p, scene->scene_spp, b[0], b[1], b[2], b[3], b[4], nullptr, rstats ? rstats : &local);
         gdpt::PoissonResult r = gdpt::assemble_solve_device(w, h, b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], dataCost, b[8], GDPT_SOLVER_DEFAULT, 0.0, 0, nullptr, pstats != nullptr);
-        if (pstats) { pstats->iterations = r.iterations; pstats->solver = r.solver; pstats->rel_residual = r.rel_residual; pstats->solve_ms = r.solve_ms; }
+        fill_poisson_stats(pstats, r);
         ck(hipMemcpy(out_image, b[8], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
         double *host[5] = {img, cx0, cy0, cx1, cy1};
         for (int k = 0; k < 5; k++) if (host[k]) ck(hipMemcpy(host[k], b[k], elems * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
@@ -881,17 +871,9 @@ int gdpt_reconstruct(int width, int height, const double *c, const double *gx, c
         int ndev = 0;
         ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
         if (ndev <= 0) throw std::runtime_error("gdpt_reconstruct: no HIP device visible (this library has no CPU fallback)");
-        const size_t bytes = (size_t)width * height * 3 * sizeof(double);
-        double *d[4] = {nullptr, nullptr, nullptr, nullptr};
-        auto cleanup = [&]() { for (auto q : d) if (q) hipFree(q); };
-        try {
-            for (auto &q : d) ck(hipMalloc((void **)&q, bytes), "hipMalloc(reconstruct io)");
-            const double *host[3] = {c, gx, gy};
-            for (int k = 0; k < 3; k++) ck(hipMemcpy(d[k], host[k], bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        on_device_planes({c, gx, gy}, width, height, out, "hipMalloc(reconstruct io)", [&](const Planes &d) {
             fill_recon_stats(stats, gdpt::recon_l1_device(width, height, d[0], d[1], d[2], dataCost, p, d[3], nullptr));
-            ck(hipMemcpy(out, d[3], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        });
     });
 }
 
@@ -918,25 +900,17 @@ int gdpt_reconstruct_weighted(int width, int height, const double *c, const doub
         if (!var_c || !var_gx || !var_gy) throw std::runtime_error("gdpt_reconstruct_weighted: null variance plane");
         if (width < 2 || height < 2) throw std::runtime_error("gdpt_reconstruct_weighted: width and height must be >= 2");
         if (!(dataCost > 0) || !std::isfinite(dataCost)) throw std::runtime_error("gdpt_reconstruct_weighted: dataCost must be finite and > 0");
-        const double *host[6] = {c, gx, gy, var_c, var_gx, var_gy};
-        for (const double *in : host) if (out == in) throw std::runtime_error("gdpt_reconstruct_weighted: the output must not alias an input");
+        for (const double *in : {c, gx, gy, var_c, var_gx, var_gy}) if (out == in) throw std::runtime_error("gdpt_reconstruct_weighted: the output must not alias an input");
         double conf_floor = 0;
         int norm = 0;
         const gdpt::ReconL1Params p = resolve_weighted(params, &conf_floor, &norm);
         int ndev = 0;
         ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
         if (ndev <= 0) throw std::runtime_error("gdpt_reconstruct_weighted: no HIP device visible (this library has no CPU fallback)");
-        const size_t bytes = (size_t)width * height * 3 * sizeof(double);
-        double *d[7] = {};
-        auto cleanup = [&]() { for (auto q : d) if (q) hipFree(q); };
-        try {
-            for (auto &q : d) ck(hipMalloc((void **)&q, bytes), "hipMalloc(reconstruct io)");
-            for (int k = 0; k < 6; k++) ck(hipMemcpy(d[k], host[k], bytes, hipMemcpyHostToDevice), "hipMemcpy");
+        on_device_planes({c, gx, gy, var_c, var_gx, var_gy}, width, height, out, "hipMalloc(reconstruct io)", [&](const Planes &d) {
             fill_weighted_stats(stats, norm, gdpt::recon_weighted_device(width, height, d[0], d[1], d[2], d[3], d[4], d[5], dataCost, p, conf_floor, d[6],
                                                                          confidence, nullptr));
-            ck(hipMemcpy(out, d[6], bytes, hipMemcpyDeviceToHost), "hipMemcpy");
-        } catch (...) { cleanup(); throw; }
-        cleanup();
+        });
     });
 }
 
@@ -956,7 +930,7 @@ int gdpt_gradient_path_render_recon(GdptScene *scene, const GdptRenderParams *pa
         const int w = scene->view.cam.width, h = scene->view.cam.height;
         size_t elems = (size_t)w * h * 3;
         scene->ensure_buffers(elems);
-        double **b = scene->d_buf;
+        auto &b = scene->d_buf;
         GdptRenderParams p = params ? *params : GdptRenderParams{};
         p.row_begin = 0; p.row_end = 0;   // the reconstruction is global: whole image only
         GdptRenderStats local{};

@@ -1,0 +1,137 @@
+// device_mem.h — who owns device memory on the host side: a move-only Buffer for device and pinned memory, an Event, and the
+// registry of what a solver keeps per (device, stream). Every handle (GdptScene, GdptProgressive, the solvers' workspaces, the ranks
+// of GdptMulti) holds these as members, so a handle's destructor names no field, and a buffer's size cannot disagree with its
+// pointer: after a failed allocation the buffer is empty and the next call allocates again.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <utility>
+
+namespace gdpt {
+
+inline void ck(hipError_t e, const char *what) {
+    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+struct DeviceSpace {
+    static void *alloc(size_t bytes, const char *what) { void *p = nullptr; ck(hipMalloc(&p, bytes), what); return p; }
+    static void free(void *p) { (void)hipFree(p); }
+    static void sync(hipStream_t stream) { ck(hipStreamSynchronize(stream), "hipStreamSynchronize"); }
+    static int set_device(int dev) { int cur = 0; (void)hipGetDevice(&cur); (void)hipSetDevice(dev); return cur; }   // returns the device that was current
+};
+struct PinnedSpace {
+    static void *alloc(size_t bytes, const char *what) { void *p = nullptr; ck(hipHostMalloc(&p, bytes), what); return p; }
+    static void free(void *p) { (void)hipHostFree(p); }
+};
+
+// `size()` elements of T in Space. data() == nullptr exactly when size() == 0, after every member function, one that throws included.
+// `what` is the text an allocation failure is reported with. Frees on the device that is current: a handle's destructor sets it first.
+template <class T, class Space>
+class Buffer {
+    T *p_ = nullptr;
+    size_t n_ = 0;
+public:
+    Buffer() = default;
+    Buffer(Buffer &&o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr; o.n_ = 0; }
+    Buffer &operator=(Buffer &&o) noexcept {
+        if (this != &o) { reset(); p_ = o.p_; n_ = o.n_; o.p_ = nullptr; o.n_ = 0; }
+        return *this;
+    }
+    Buffer(const Buffer &) = delete;
+    Buffer &operator=(const Buffer &) = delete;
+    ~Buffer() { reset(); }
+
+    T *data() const { return p_; }
+    size_t size() const { return n_; }
+    operator T *() const { return p_; }
+    T *operator->() const { return p_; }
+
+    void reset() {
+        if (p_) Space::free(p_);
+        p_ = nullptr; n_ = 0;
+    }
+    // for an empty buffer (one that holds something is freed first)
+    void alloc(size_t n, const char *what) {
+        reset();
+        if (n == 0) return;
+        p_ = static_cast<T *>(Space::alloc(n * sizeof(T), what));
+        n_ = n;
+    }
+    // at least n elements; the contents do not survive a growth
+    void grow(size_t n, const char *what) { if (n > n_) alloc(n, what); }
+    // ... where work enqueued on `stream` may still use the buffer held: waits for the stream before freeing it
+    void grow(size_t n, hipStream_t stream, const char *what) {
+        if (n <= n_) return;
+        if (p_) Space::sync(stream);
+        alloc(n, what);
+    }
+};
+template <class T> using DeviceBuffer = Buffer<T, DeviceSpace>;
+template <class T> using PinnedBuffer = Buffer<T, PinnedSpace>;
+
+class Event {
+    hipEvent_t e_ = nullptr;
+public:
+    Event() = default;
+    Event(Event &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    Event &operator=(Event &&o) noexcept {
+        if (this != &o) { reset(); e_ = o.e_; o.e_ = nullptr; }
+        return *this;
+    }
+    Event(const Event &) = delete;
+    Event &operator=(const Event &) = delete;
+    ~Event() { reset(); }
+    operator hipEvent_t() const { return e_; }
+    void reset() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
+    void create(unsigned flags = 0) { reset(); ck(hipEventCreateWithFlags(&e_, flags), "hipEventCreate"); }
+};
+
+// What a solver keeps per (device, stream): one T per pair, made on first use. A stream's owner calls forget_stream (below) before it
+// destroys the stream: the key is the handle's value, and a later stream with the same value must not inherit another one's state.
+// An entry is destroyed with its device current. (Space: only the device switch is taken from it.)
+template <class T, class Space = DeviceSpace>
+class PerStream {
+    std::mutex mu_;
+    std::map<std::pair<int, hipStream_t>, std::unique_ptr<T>> map_;
+public:
+    T &get(int dev, hipStream_t stream) {
+        std::lock_guard<std::mutex> lk(mu_);
+        auto &slot = map_[{dev, stream}];
+        if (!slot) slot.reset(new T());
+        return *slot;
+    }
+    // The caller guarantees that nothing of the pair is in flight.
+    void forget(int dev, hipStream_t stream) {
+        std::unique_ptr<T> gone;
+        {
+            std::lock_guard<std::mutex> lk(mu_);
+            auto it = map_.find({dev, stream});
+            if (it == map_.end()) return;
+            gone = std::move(it->second);
+            map_.erase(it);
+        }
+        const int cur = Space::set_device(dev);
+        gone.reset();
+        Space::set_device(cur);
+    }
+    void clear() {
+        std::lock_guard<std::mutex> lk(mu_);
+        for (auto &kv : map_) {
+            const int cur = Space::set_device(kv.first.first);
+            kv.second.reset();
+            Space::set_device(cur);
+        }
+        map_.clear();
+    }
+};
+
+// Drops everything the solvers keep for the pair: the Poisson solvers' and the reconstructions' scratch (poisson_kernels.hip).
+void forget_stream(int dev, hipStream_t stream);
+
+} // namespace gdpt

@@ -169,9 +169,9 @@ struct Rank {
     int device = 0, row_begin = 0, row_end = 0;
     std::unique_ptr<GdptScene> scene;
     hipStream_t stream = nullptr;
-    double *buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // img cx0 cy0 cx1 cy1 | c cx cy | out
-    hipEvent_t ev_t[4] = {nullptr, nullptr, nullptr, nullptr};  // timing: start, rendered, exchanged, solved
-    hipEvent_t ev_rendered = nullptr, ev_pushed = nullptr;       // peer-copy ordering
+    gdpt::DeviceBuffer<double> buf[9];     // img cx0 cy0 cx1 cy1 | c cx cy | out
+    gdpt::Event ev_t[4];                   // timing: start, rendered, exchanged, solved
+    gdpt::Event ev_rendered, ev_pushed;    // peer-copy ordering
     ncclComm_t comm = nullptr;
     GdptRenderStats rstats{};
     std::string error;
@@ -202,11 +202,10 @@ struct GdptMulti {
         for (Rank &r : ranks) {
             hipSetDevice(r.device);
             if (r.comm) ncclCommDestroy(r.comm);
-            for (double *&b : r.buf) if (b) hipFree(b);
-            for (hipEvent_t &e : r.ev_t) if (e) hipEventDestroy(e);
-            if (r.ev_rendered) hipEventDestroy(r.ev_rendered);
-            if (r.ev_pushed) hipEventDestroy(r.ev_pushed);
-            if (r.stream) { gdpt::poisson_forget_stream(r.device, r.stream); hipStreamDestroy(r.stream); }   // the solver's per-stream scratch goes with the stream
+            for (auto &b : r.buf) b.reset();            // (before the stream goes: the order of the hand-written destructor is kept)
+            for (auto &e : r.ev_t) e.reset();
+            r.ev_rendered.reset(); r.ev_pushed.reset();
+            if (r.stream) { gdpt::forget_stream(r.device, r.stream); hipStreamDestroy(r.stream); }   // the solvers' per-stream scratch goes with the stream
             r.scene.reset();
         }
     }
@@ -441,10 +440,10 @@ int gdpt_multi_create(const GdptSceneDesc *desc, const GdptMultiConfig *cfg, Gdp
                 r.row_begin = 0; r.row_end = std::min(first_tile[1] * kTile, m->h);
             }
             ck(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking), "hipStreamCreate");
-            for (double *&b : r.buf) { ck(hipMalloc((void **)&b, elems * sizeof(double)), "hipMalloc(band images)"); ck(hipMemset(b, 0, elems * sizeof(double)), "hipMemset"); }
-            for (hipEvent_t &e : r.ev_t) ck(hipEventCreate(&e), "hipEventCreate");
-            ck(hipEventCreateWithFlags(&r.ev_rendered, hipEventDisableTiming), "hipEventCreate");
-            ck(hipEventCreateWithFlags(&r.ev_pushed, hipEventDisableTiming), "hipEventCreate");
+            for (auto &b : r.buf) { b.alloc(elems, "hipMalloc(band images)"); ck(hipMemset(b, 0, elems * sizeof(double)), "hipMemset"); }
+            for (auto &e : r.ev_t) e.create();
+            r.ev_rendered.create(hipEventDisableTiming);
+            r.ev_pushed.create(hipEventDisableTiming);
         }
         m->equal_bands = equal;
         for (const Rank &r : m->ranks) m->plan_rows = std::max(m->plan_rows, r.row_end - r.row_begin);

@@ -24,8 +24,8 @@ PoissonResult assemble_solve_device(int w, int h, const double *img, const doubl
                                     double *d_c, double *d_cx, double *d_cy, double alpha, double *d_out, int solver, double tol, int max_iters,
                                     hipStream_t stream, bool timed);
 
-// Drops the (device, stream) pair's scratch state; call before destroying a stream the solver has run on (nothing in flight).
-void poisson_forget_stream(int dev, hipStream_t stream);
+// Drops every pair's scratch state and every device's tables (nothing in flight). One pair alone, before its stream is destroyed:
+// forget_stream (device_mem.h).
 void poisson_release_workspace();
 
 } // namespace gdpt

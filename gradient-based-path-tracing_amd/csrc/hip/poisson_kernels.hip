@@ -18,6 +18,8 @@
 //   cg_step_b: x += a p', r -= a q, partial <r,r>
 // Scalars are reduced from per-block partials by every block in the same fixed order (deterministic).
 #include "poisson_kernels.h"
+#include "device_mem.h"
+#include "recon_l1.h"
 #include "../capi_common.h"
 #include "../../../include/gdpt.h"
 
@@ -514,36 +516,23 @@ namespace gdpt {
 
 namespace {
 
-void ck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
 struct Workspace {
-    size_t n3 = 0;
-    double *x = nullptr, *r = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr, *partials = nullptr, *rel = nullptr;
-    gp::CgState *state = nullptr;
-    gp::CgState *h_state = nullptr;   // pinned
-    double *h_rel = nullptr;          // pinned
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // timing pair + chunk marker, created once
-    void release() {
-        for (double *p : {x, r, q, p0, p1, partials, rel}) if (p) hipFree(p);
-        if (state) hipFree(state);
-        if (h_state) hipHostFree(h_state);
-        if (h_rel) hipHostFree(h_rel);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
-        *this = Workspace();
-    }
-    void ensure(size_t n) {
-        if (n <= n3) return;
-        release();
-        n3 = n;
-        for (double **p : {&x, &r, &q, &p0, &p1}) ck(hipMalloc((void **)p, n * sizeof(double)), "hipMalloc(poisson workspace)");
-        ck(hipMalloc((void **)&partials, 10 * gp::kMaxBlocks * sizeof(double)), "hipMalloc(partials)");
-        ck(hipMalloc((void **)&rel, sizeof(double)), "hipMalloc(rel)");
-        ck(hipMalloc((void **)&state, sizeof(gp::CgState)), "hipMalloc(state)");
-        ck(hipHostMalloc((void **)&h_state, sizeof(gp::CgState)), "hipHostMalloc");
-        ck(hipHostMalloc((void **)&h_rel, sizeof(double)), "hipHostMalloc");
-        for (auto &e : ev) ck(hipEventCreate(&e), "hipEventCreate");
+    DeviceBuffer<double> x, r, q, p0, p1;             // n3 each
+    DeviceBuffer<double> partials, rel;
+    DeviceBuffer<gp::CgState> state;
+    PinnedBuffer<gp::CgState> h_state;
+    PinnedBuffer<double> h_rel;
+    Event ev[3];                                      // timing pair + chunk marker, created once
+    // n3 unknowns; earlier solves on `stream` may still use smaller buffers
+    void ensure(size_t n3, hipStream_t stream) {
+        for (auto *b : {&x, &r, &q, &p0, &p1}) b->grow(n3, stream, "hipMalloc(poisson workspace)");
+        if (ev[2]) return;                            // the rest has one size, and is made once
+        partials.alloc(10 * gp::kMaxBlocks, "hipMalloc(partials)");
+        rel.alloc(1, "hipMalloc(rel)");
+        state.alloc(1, "hipMalloc(state)");
+        h_state.alloc(1, "hipHostMalloc");
+        h_rel.alloc(1, "hipHostMalloc");
+        for (auto &e : ev) e.create();
     }
 };
 
@@ -555,11 +544,11 @@ namespace {
 
 struct DctPlan {
     int n = 0;
-    double *d_mat = nullptr;   // C[j][k] = w_j cos(pi j k/(n-1)), row-major n x n
-    double *d_lap = nullptr;   // 2 cos(pi i/(n-1)) (the caller adds -4 on the y axis)
+    DeviceBuffer<double> d_mat;   // C[j][k] = w_j cos(pi j k/(n-1)), row-major n x n
+    DeviceBuffer<double> d_lap;   // 2 cos(pi i/(n-1)) (the caller adds -4 on the y axis)
     // parity tables of the folded products (dct_fold_gemm_f64): E_p[x][q] = w_x cos(pi x (2q+p)/(n-1)), x < ceil(n/2),
     // and their transposes; row strides padded to an even number of doubles
-    double *d_e[2] = {nullptr, nullptr}, *d_et[2] = {nullptr, nullptr};
+    DeviceBuffer<double> d_e[2], d_et[2];
     int ld_e = 0, ld_et = 0;
 };
 // Transform matrices and eigenvalue tables depend on the extent only: one set per device, shared (read-only) by every
@@ -568,48 +557,28 @@ struct DctPlan {
 struct DctTables {
     std::mutex mu;
     std::vector<std::unique_ptr<DctPlan>> plans;
-    std::vector<std::pair<int, double *>> lap_y;
-    void release() {
-        for (auto &p : plans) {
-            if (p->d_mat) hipFree(p->d_mat);
-            if (p->d_lap) hipFree(p->d_lap);
-            for (int k = 0; k < 2; k++) { if (p->d_e[k]) hipFree(p->d_e[k]); if (p->d_et[k]) hipFree(p->d_et[k]); }
-        }
-        for (auto &l : lap_y) if (l.second) hipFree(l.second);
-        plans.clear(); lap_y.clear();
-    }
+    std::vector<std::pair<int, DeviceBuffer<double>>> lap_y;
 };
 struct DctWorkspace {
     rocblas_handle handle = nullptr;
-    size_t elems = 0;
-    double *buf[2] = {nullptr, nullptr};
-    double *partials = nullptr;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    void release() {
-        for (auto &b : buf) { if (b) hipFree(b); b = nullptr; }
-        if (partials) hipFree(partials);
-        if (handle) rocblas_destroy_handle(handle);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
-        *this = DctWorkspace();
-    }
+    DeviceBuffer<double> buf[2];
+    DeviceBuffer<double> partials;
+    Event ev[2];
+    ~DctWorkspace() { if (handle) rocblas_destroy_handle(handle); }
 };
 struct StreamState {                  // everything a solve on one (device, stream) mutates
     std::mutex mu;                    // held while a solve is being enqueued on this pair
     Workspace cg;
     DctWorkspace dct;
 };
-std::mutex g_registry_mu;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<StreamState>> g_streams;
-std::map<int, std::unique_ptr<DctTables>> g_tables;
+// Both registries are leaked on purpose: what is never forgotten stays until the process ends, and no HIP or rocBLAS call is made
+// from a static destructor (the runtime libraries may already be gone by then).
+PerStream<StreamState> &g_streams = *new PerStream<StreamState>();
+std::mutex g_tables_mu;
+std::map<int, std::unique_ptr<DctTables>> &g_tables = *new std::map<int, std::unique_ptr<DctTables>>();
 
-StreamState &stream_state(int dev, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_registry_mu);
-    auto &slot = g_streams[{dev, stream}];
-    if (!slot) slot.reset(new StreamState());
-    return *slot;
-}
 DctTables &device_tables(int dev) {
-    std::lock_guard<std::mutex> lk(g_registry_mu);
+    std::lock_guard<std::mutex> lk(g_tables_mu);
     auto &slot = g_tables[dev];
     if (!slot) slot.reset(new DctTables());
     return *slot;
@@ -630,8 +599,8 @@ const DctPlan &get_plan(DctTables &t, int n) {
         for (int k = 0; k < n; k++) m[(size_t)j * n + k] = wj * ctab[((size_t)j * k) % ctab.size()];
     }
     for (int i = 0; i < n; i++) lap[i] = 2.0 * std::cos(M_PI * i / (n - 1));     // ftLapX (:184-186)
-    ck(hipMalloc((void **)&p->d_mat, m.size() * sizeof(double)), "hipMalloc(dct matrix)");
-    ck(hipMalloc((void **)&p->d_lap, lap.size() * sizeof(double)), "hipMalloc(dct lap)");
+    p->d_mat.alloc(m.size(), "hipMalloc(dct matrix)");
+    p->d_lap.alloc(lap.size(), "hipMalloc(dct lap)");
     ck(hipMemcpy(p->d_mat, m.data(), m.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(dct matrix)");
     ck(hipMemcpy(p->d_lap, lap.data(), lap.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(dct lap)");
     {
@@ -647,8 +616,8 @@ const DctPlan &get_plan(DctTables &t, int n) {
                     e[(size_t)x * p->ld_e + q] = v; et[(size_t)q * p->ld_et + x] = v;
                 }
             }
-            ck(hipMalloc((void **)&p->d_e[par], e.size() * sizeof(double)), "hipMalloc(dct parity table)");
-            ck(hipMalloc((void **)&p->d_et[par], et.size() * sizeof(double)), "hipMalloc(dct parity table^T)");
+            p->d_e[par].alloc(e.size(), "hipMalloc(dct parity table)");
+            p->d_et[par].alloc(et.size(), "hipMalloc(dct parity table^T)");
             ck(hipMemcpy(p->d_e[par], e.data(), e.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(dct parity table)");
             ck(hipMemcpy(p->d_et[par], et.data(), et.size() * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(dct parity table^T)");
         }
@@ -661,11 +630,11 @@ const double *get_lap_y(DctTables &t, int h) {   // ftLapY = -4 + 2 cos(pi y/(h-
     for (auto &l : t.lap_y) if (l.first == h) return l.second;
     std::vector<double> ly(h);
     for (int y = 0; y < h; y++) ly[y] = -4.0 + (2.0 * std::cos(M_PI * y / (h - 1)));
-    double *d = nullptr;
-    ck(hipMalloc((void **)&d, h * sizeof(double)), "hipMalloc(lap_y)");
+    DeviceBuffer<double> d;
+    d.alloc(h, "hipMalloc(lap_y)");
     ck(hipMemcpy(d, ly.data(), h * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(lap_y)");
-    t.lap_y.push_back({h, d});
-    return d;
+    t.lap_y.emplace_back(h, std::move(d));
+    return t.lap_y.back().second;
 }
 
 // Enqueue-only unless `timed`: no event is created, recorded or waited for on the product path (stats == NULL).
@@ -689,16 +658,11 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
     }
     gp::Geo g{w, h, w * h * 3, w * 3};
     const size_t plane = (size_t)w * h;
-    if (ws.elems < 3 * plane) {
-        if (ws.buf[0]) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");   // earlier solves may still use the old buffers
-        for (auto &b : ws.buf) { if (b) hipFree(b); b = nullptr; }
-        for (auto &b : ws.buf) ck(hipMalloc((void **)&b, 3 * plane * sizeof(double)), "hipMalloc(dct buffers)");
-        ws.elems = 3 * plane;
-    }
-    if (!ws.partials) ck(hipMalloc((void **)&ws.partials, 3 * gp::kMaxBlocks * sizeof(double)), "hipMalloc(dct partials)");
+    for (auto &b : ws.buf) b.grow(3 * plane, stream, "hipMalloc(dct buffers)");   // (earlier solves may still use the old buffers)
+    if (!ws.partials) ws.partials.alloc(3 * gp::kMaxBlocks, "hipMalloc(dct partials)");
     const int nb = std::min(gp::kMaxBlocks, (g.n3 + gp::kBlock - 1) / gp::kBlock);
     if (timed) {
-        for (auto &e : ws.ev) if (!e) ck(hipEventCreate(&e), "hipEventCreate");
+        for (auto &e : ws.ev) if (!e) e.create();
         ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     }
     double *A = ws.buf[0], *B = ws.buf[1];
@@ -770,33 +734,21 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
 
 } // namespace
 
-// Drops what the solver keeps for one (device, stream) pair — scratch buffers, rocBLAS handle, timing events. Owners of a
-// stream call it before destroying the stream: the registry is keyed by the handle's value, and a later stream that reuses
-// that value must not inherit another stream's state. The caller guarantees no solve is in flight on the pair.
-void poisson_forget_stream(int dev, hipStream_t stream) {
-    std::unique_ptr<StreamState> gone;
-    {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        auto it = g_streams.find({dev, stream});
-        if (it == g_streams.end()) return;
-        gone = std::move(it->second);
-        g_streams.erase(it);
-    }
-    int cur = 0;
-    hipGetDevice(&cur);
-    hipSetDevice(dev);
-    gone->cg.release(); gone->dct.release();
-    hipSetDevice(cur);
+// Owners of a stream call it before destroying the stream (device_mem.h). The caller guarantees no solve is in flight on the pair.
+void forget_stream(int dev, hipStream_t stream) {
+    g_streams.forget(dev, stream);         // scratch buffers, rocBLAS handle, timing events
+    recon_l1_forget_stream(dev, stream);
 }
 
 void poisson_release_workspace() {
-    std::lock_guard<std::mutex> lk(g_registry_mu);
-    int cur = 0;
-    hipGetDevice(&cur);
-    for (auto &kv : g_streams) { hipSetDevice(kv.first.first); kv.second->cg.release(); kv.second->dct.release(); }
-    for (auto &kv : g_tables) { hipSetDevice(kv.first); kv.second->release(); }
-    g_streams.clear(); g_tables.clear();
-    hipSetDevice(cur);
+    g_streams.clear();
+    std::lock_guard<std::mutex> lk(g_tables_mu);
+    for (auto &kv : g_tables) {
+        const int cur = DeviceSpace::set_device(kv.first);
+        kv.second.reset();
+        DeviceSpace::set_device(cur);
+    }
+    g_tables.clear();
 }
 
 void launch_assemble(int w, int h, int row_begin, int row_end, const double *img, const double *cx0, const double *cy0, const double *cx1,
@@ -823,7 +775,7 @@ PoissonResult assemble_solve_device(int w, int h, const double *img, const doubl
     if (solver != GDPT_SOLVER_DCT && solver != GDPT_SOLVER_DCT_MFMA) throw std::runtime_error("poisson: unknown solver");
     int dev = 0;
     ck(hipGetDevice(&dev), "hipGetDevice");
-    StreamState &ss = stream_state(dev, stream);
+    StreamState &ss = g_streams.get(dev, stream);
     std::lock_guard<std::mutex> lk(ss.mu);
     const double *raw[5] = {img, cx0, cy0, cx1, cy1};
     PoissonResult r = poisson_dct(dev, ss.dct, w, h, d_c, d_cx, d_cy, alpha, d_out, stream, timed, solver == GDPT_SOLVER_DCT, raw);
@@ -840,7 +792,7 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
     if (max_iters <= 0) max_iters = 2000;
     int dev = 0;
     ck(hipGetDevice(&dev), "hipGetDevice");
-    StreamState &ss = stream_state(dev, stream);
+    StreamState &ss = g_streams.get(dev, stream);
     std::lock_guard<std::mutex> lk(ss.mu);
     if (solver != GDPT_SOLVER_CG) {
         PoissonResult r = poisson_dct(dev, ss.dct, w, h, d_c, d_gx, d_gy, alpha, d_out, stream, timed, solver == GDPT_SOLVER_DCT);
@@ -848,8 +800,7 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
         return r;
     }
     gp::Geo g{w, h, w * h * 3, w * 3};
-    if ((size_t)g.n3 > ss.cg.n3 && ss.cg.n3) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    ss.cg.ensure((size_t)g.n3);
+    ss.cg.ensure((size_t)g.n3, stream);
     Workspace &ws = ss.cg;
     const int nb = std::min(gp::kMaxBlocks, (g.n3 + gp::kBlock - 1) / gp::kBlock);
     // init layout: 8 slots of nb doubles (slot 0 = <r,r>, reused as part_rr); <p,q> partials live in slot 8

@@ -286,7 +286,7 @@ void merge(GdptProgressive &dst, const GdptProgressive &src) {
             if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) ck(e, "hipDeviceEnablePeerAccess");
             (void)hipGetLastError();
         }
-        for (int k = 0; k < 2 * dst.nbuf; k++) if (!dst.stage[k]) ck(hipMalloc((void **)&dst.stage[k], dst.elems * sizeof(double)), "hipMalloc(progressive staging)");
+        for (int k = 0; k < 2 * dst.nbuf; k++) if (!dst.stage[k]) dst.stage[k].alloc(dst.elems, "hipMalloc(progressive staging)");
         for (int k = 0; k < dst.nbuf; k++) {
             ck(hipMemcpyPeerAsync(dst.stage[2 * k], dst.device, src.mean[k], src.device, dst.elems * sizeof(double), dst.stream), "hipMemcpyPeerAsync(mean)");
             ck(hipMemcpyPeerAsync(dst.stage[2 * k + 1], dst.device, src.m2[k], src.device, dst.elems * sizeof(double), dst.stream), "hipMemcpyPeerAsync(M2)");
@@ -335,7 +335,7 @@ void copy_out(const GdptProgressive &s, double *dst, const double *src, int on_d
 // the read-out planes s.var[0..4] and, for a GradPath session, the assembled s.var[5], s.var[6]; enqueued on the session's stream
 void compute_variances(GdptProgressive &s) {
     const int nvar = s.nbuf == 5 ? 7 : 1;
-    for (int k = 0; k < nvar; k++) if (!s.var[k]) ck(hipMalloc((void **)&s.var[k], s.elems * sizeof(double)), "hipMalloc(progressive variances)");
+    for (int k = 0; k < nvar; k++) if (!s.var[k]) s.var[k].alloc(s.elems, "hipMalloc(progressive variances)");
     prg::VarPlanes vp{};
     for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
     vp.vcx = s.var[5]; vp.vcy = s.var[6];
@@ -344,6 +344,12 @@ void compute_variances(GdptProgressive &s) {
     if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
     else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
     ck(hipGetLastError(), "progressive variance launch");
+}
+
+// c, cx, cy of the running means into s.asm_buf[0..2] (s.asm_buf[3] takes the reconstruction); enqueued on the session's stream
+void assemble_means(GdptProgressive &s) {
+    for (auto &b : s.asm_buf) if (!b) b.alloc(s.elems, "hipMalloc(progressive assembly)");
+    gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
 }
 
 // whole: the slice is the whole block (gdpt_progressive_create); else [first, first + num) of it
@@ -372,12 +378,12 @@ void create_session(const char *fn, GdptScene *scene, const GdptProgressiveConfi
     s->w = w; s->h = h; s->block = budget; s->first = first; s->own = num; s->elems = (size_t)w * h * 3;
     for (auto *set : {s->pass, s->mean, s->m2}) {
         if (set == s->pass && num == 0) continue;        // an accumulator renders nothing
-        for (int k = 0; k < s->nbuf; k++) ck(hipMalloc((void **)&set[k], s->elems * sizeof(double)), "hipMalloc(progressive planes)");
+        for (int k = 0; k < s->nbuf; k++) set[k].alloc(s->elems, "hipMalloc(progressive planes)");
     }
-    ck(hipMalloc((void **)&s->partials, 3 * prg::kMaxBlocks * sizeof(double)), "hipMalloc(progressive partials)");
-    ck(hipMalloc((void **)&s->d_est, sizeof(prg::Estimate)), "hipMalloc(progressive estimate)");
-    ck(hipHostMalloc((void **)&s->h_est, sizeof(prg::Estimate)), "hipHostMalloc(progressive estimate)");
-    for (auto &e : s->ev) ck(hipEventCreate(&e), "hipEventCreate");
+    s->partials.alloc(3 * prg::kMaxBlocks, "hipMalloc(progressive partials)");
+    s->d_est.alloc(1, "hipMalloc(progressive estimate)");
+    s->h_est.alloc(1, "hipHostMalloc(progressive estimate)");
+    for (auto &e : s->ev) e.create();
     *out = s.release();
 }
 
@@ -462,8 +468,7 @@ int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, cons
         if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct: an Integrator::Path session has no gradients (read its mean)");
         if (s.passes < 1) throw std::runtime_error("gdpt_progressive_reconstruct: no pass has been added");
         ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        for (double *&p : s.asm_buf) if (!p) ck(hipMalloc((void **)&p, s.elems * sizeof(double)), "hipMalloc(progressive assembly)");
-        gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
+        assemble_means(s);
         if (gdpt_reconstruct_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], dataCost, recon, s.asm_buf[3], s.stream, stats) != 0)
             throw std::runtime_error(gdpt_last_error());
         copy_out(s, out, s.asm_buf[3], on_device);
@@ -479,8 +484,7 @@ int gdpt_progressive_reconstruct_weighted(GdptProgressive *session, double dataC
         if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: an Integrator::Path session has no gradients (read its mean)");
         if (s.passes < 2) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: variances need at least 2 passes");
         ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        for (double *&p : s.asm_buf) if (!p) ck(hipMalloc((void **)&p, s.elems * sizeof(double)), "hipMalloc(progressive assembly)");
-        gdpt::launch_assemble(s.w, s.h, 0, 0, s.mean[0], s.mean[1], s.mean[2], s.mean[3], s.mean[4], s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.stream);
+        assemble_means(s);
         compute_variances(s);
         // (the confidence planes go straight to their destination: the copy kind is taken from the pointers, host or device)
         if (gdpt_reconstruct_weighted_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.var[0], s.var[5], s.var[6], dataCost, params, s.asm_buf[3],

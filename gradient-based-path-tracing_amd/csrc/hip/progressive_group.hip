@@ -13,9 +13,7 @@
 // member order (prg::merge, progressive.hip), so its bits do not depend on which member finished first.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
-#include "poisson_kernels.h"
 #include "progressive_internal.h"
-#include "recon_l1.h"
 
 #include <algorithm>
 #include <cmath>
@@ -47,8 +45,7 @@ struct GdptProgressiveGroup {
         for (Member &m : members) if (m.session) gdpt_progressive_free(m.session);
         if (total_stream && !members.empty()) {
             hipSetDevice(members[0].device);
-            gdpt::poisson_forget_stream(members[0].device, total_stream);     // the solvers' per-stream scratch goes with the stream
-            gdpt::recon_l1_forget_stream(members[0].device, total_stream);    // (L1 and weighted reconstructions of the total)
+            gdpt::forget_stream(members[0].device, total_stream);     // the solvers' and reconstructions' per-stream scratch goes with the stream
             hipStreamDestroy(total_stream);
         }
         for (Member &m : members) {

@@ -25,28 +25,19 @@ struct GdptProgressive {
     bool group_total = false;        // the borrowed total of a GdptProgressiveGroup: the public add_pass / run / merge refuse it
     std::vector<std::pair<int, int>> merged_intervals;    // [begin, end) of the block, as taken in by merges
     size_t elems = 0;
-    double *pass[5] = {}, *mean[5] = {}, *m2[5] = {};
-    double *stage[10] = {};          // mean / M2 planes of a merge source on another device, allocated by the first such merge
-    double *var[7] = {};             // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
-    double *asm_buf[4] = {};         // c, cx, cy, reconstruction: allocated by the first reconstruct
-    double *partials = nullptr;
-    prg::Estimate *d_est = nullptr, *h_est = nullptr;     // device / pinned host
+    gdpt::DeviceBuffer<double> pass[5], mean[5], m2[5];
+    gdpt::DeviceBuffer<double> stage[10];      // mean / M2 planes of a merge source on another device, allocated by the first such merge
+    gdpt::DeviceBuffer<double> var[7];         // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
+    gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
+    gdpt::DeviceBuffer<double> partials;
+    gdpt::DeviceBuffer<prg::Estimate> d_est;
+    gdpt::PinnedBuffer<prg::Estimate> h_est;
     prg::Estimate est{};             // of the last fold or merge (valid from 2 passes)
-    hipEvent_t ev[2] = {nullptr, nullptr};                // around the fold / merge launches
+    gdpt::Event ev[2];               // around the fold / merge launches
     double fold_ms = 0;              // device time of the last fold (fold_kernel + finish_kernel) or merge (merge_kernel + finish_kernel)
     GdptRenderStats totals{};
 
-    ~GdptProgressive() {
-        hipSetDevice(device);
-        for (auto *set : {pass, mean, m2}) for (int k = 0; k < 5; k++) if (set[k]) hipFree(set[k]);
-        for (double *p : stage) if (p) hipFree(p);
-        for (double *p : var) if (p) hipFree(p);
-        for (double *p : asm_buf) if (p) hipFree(p);
-        if (partials) hipFree(partials);
-        if (d_est) hipFree(d_est);
-        if (h_est) hipHostFree(h_est);
-        for (auto &e : ev) if (e) hipEventDestroy(e);
-    }
+    ~GdptProgressive() { hipSetDevice(device); }      // the members free themselves on it
 };
 
 namespace prg {

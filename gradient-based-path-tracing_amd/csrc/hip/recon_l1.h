@@ -13,7 +13,7 @@ struct ReconL1Result { int irls_rounds, cg_iters_total, cg_iters_last; double en
 ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, double alpha,
                               const ReconL1Params &p, double *d_out, hipStream_t stream);
 
-// Drops the (device, stream) pair's scratch (gdpt_poisson_forget_stream calls it beside poisson_forget_stream).
+// Drops the (device, stream) pair's scratch; forget_stream (device_mem.h) calls it, and is what a stream's owner calls.
 void recon_l1_forget_stream(int dev, hipStream_t stream);
 
 } // namespace gdpt

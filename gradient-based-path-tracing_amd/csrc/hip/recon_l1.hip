@@ -33,8 +33,6 @@
 
 #include <algorithm>
 #include <cmath>
-#include <map>
-#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -215,63 +213,29 @@ namespace gdpt {
 
 namespace {
 
-void ck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-std::mutex g_registry_mu;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<ReconWorkspace>> g_workspaces;
+// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip)
+PerStream<ReconWorkspace> &g_workspaces = *new PerStream<ReconWorkspace>();
 
 } // namespace
 
-void ReconWorkspace::release() {
-    for (double *p : {r, q, p0, p1, wx, wy, diag, partials, var[0], var[1], var[2], conf[0], conf[1], conf[2], conf_partials}) if (p) hipFree(p);
-    if (state) hipFree(state);
-    if (h_state) hipHostFree(h_state);
-    if (conf_stats) hipFree(conf_stats);
-    if (h_conf_stats) hipHostFree(h_conf_stats);
-    for (auto &e : ev) if (e) hipEventDestroy(e);
-    r = q = p0 = p1 = wx = wy = diag = partials = conf_partials = nullptr; state = h_state = nullptr;
-    for (int k = 0; k < 3; k++) var[k] = conf[k] = nullptr;
-    conf_stats = h_conf_stats = nullptr;
-    for (auto &e : ev) e = nullptr;
-    npix = conf_npix = 0;
+void ReconWorkspace::ensure(size_t npix, hipStream_t stream) {
+    for (auto *b : {&r, &q, &p0, &p1}) b->grow(3 * npix, stream, "hipMalloc(recon workspace)");
+    for (auto *b : {&wx, &wy, &diag}) b->grow(npix, stream, "hipMalloc(recon weights)");
+    if (ev[2]) return;                    // the rest has one size, and is made once
+    partials.alloc(5 * rl1::kMaxBlocks, "hipMalloc(recon partials)");
+    state.alloc(1, "hipMalloc(recon state)");
+    h_state.alloc(1, "hipHostMalloc");
+    for (auto &e : ev) e.create();
 }
-void ReconWorkspace::ensure(size_t n) {
-    if (n <= npix) return;
-    release();
-    npix = n;
-    for (double **p : {&r, &q, &p0, &p1}) ck(hipMalloc((void **)p, 3 * n * sizeof(double)), "hipMalloc(recon workspace)");
-    for (double **p : {&wx, &wy, &diag}) ck(hipMalloc((void **)p, n * sizeof(double)), "hipMalloc(recon weights)");
-    ck(hipMalloc((void **)&partials, 5 * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon partials)");
-    ck(hipMalloc((void **)&state, sizeof(rl1::State)), "hipMalloc(recon state)");
-    ck(hipHostMalloc((void **)&h_state, sizeof(rl1::State)), "hipHostMalloc");
-    for (auto &e : ev) ck(hipEventCreate(&e), "hipEventCreate");
-}
-void ReconWorkspace::ensure_confidence(size_t n) {
-    if (n <= conf_npix) return;
-    for (int k = 0; k < 3; k++) {
-        if (var[k]) hipFree(var[k]);
-        if (conf[k]) hipFree(conf[k]);
-        var[k] = conf[k] = nullptr;
-    }
-    conf_npix = 0;
-    for (int k = 0; k < 3; k++) {
-        ck(hipMalloc((void **)&var[k], n * sizeof(double)), "hipMalloc(recon row variances)");
-        ck(hipMalloc((void **)&conf[k], n * sizeof(double)), "hipMalloc(recon confidences)");
-    }
-    if (!conf_partials) ck(hipMalloc((void **)&conf_partials, kConfSlots * rl1::kMaxBlocks * sizeof(double)), "hipMalloc(recon confidence partials)");
-    if (!conf_stats) ck(hipMalloc((void **)&conf_stats, sizeof(ConfStats)), "hipMalloc(recon confidence scalars)");
-    if (!h_conf_stats) ck(hipHostMalloc((void **)&h_conf_stats, sizeof(ConfStats)), "hipHostMalloc");
-    conf_npix = n;
+void ReconWorkspace::ensure_confidence(size_t npix, hipStream_t stream) {
+    for (auto &b : var) b.grow(npix, stream, "hipMalloc(recon row variances)");
+    for (auto &b : conf) b.grow(npix, stream, "hipMalloc(recon confidences)");
+    if (!conf_partials) conf_partials.alloc(kConfSlots * rl1::kMaxBlocks, "hipMalloc(recon confidence partials)");
+    if (!conf_stats) conf_stats.alloc(1, "hipMalloc(recon confidence scalars)");
+    if (!h_conf_stats) h_conf_stats.alloc(1, "hipHostMalloc");
 }
 
-ReconWorkspace &recon_workspace(int dev, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_registry_mu);
-    auto &slot = g_workspaces[{dev, stream}];
-    if (!slot) slot.reset(new ReconWorkspace());
-    return *slot;
-}
+ReconWorkspace &recon_workspace(int dev, hipStream_t stream) { return g_workspaces.get(dev, stream); }
 
 rl1::Geo recon_geo(int w, int h) {
     rl1::Geo g{w, h, (w + rl1::kTileW - 1) / rl1::kTileW, 0};
@@ -325,21 +289,7 @@ void recon_pcg_round(ReconWorkspace &ws, const rl1::Geo &g, int nb, double *d_ou
     res.irls_rounds = k + 1;
 }
 
-void recon_l1_forget_stream(int dev, hipStream_t stream) {
-    std::unique_ptr<ReconWorkspace> gone;
-    {
-        std::lock_guard<std::mutex> lk(g_registry_mu);
-        auto it = g_workspaces.find({dev, stream});
-        if (it == g_workspaces.end()) return;
-        gone = std::move(it->second);
-        g_workspaces.erase(it);
-    }
-    int cur = 0;
-    hipGetDevice(&cur);
-    hipSetDevice(dev);
-    gone->release();
-    hipSetDevice(cur);
-}
+void recon_l1_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
 
 ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, double alpha,
                               const ReconL1Params &p, double *d_out, hipStream_t stream) {
@@ -351,9 +301,7 @@ ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_g
     ck(hipGetDevice(&dev), "hipGetDevice");
     ReconWorkspace &ws = recon_workspace(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
-    const size_t npix = (size_t)w * h;
-    if (npix > ws.npix && ws.npix) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    ws.ensure(npix);
+    ws.ensure((size_t)w * h, stream);
     const rl1::Geo g = recon_geo(w, h);
     const int nb = recon_blocks(g);
     const dim3 grid(nb), block(rl1::kBlock);

@@ -3,6 +3,7 @@
 // recon_l1.hip; a translation unit that brings its own weights pass (recon_weighted.hip) fills wx, wy, diag, r and the partials as
 // weights_kernel does and hands the round to recon_pcg_round.
 #pragma once
+#include "device_mem.h"
 #include "recon_l1.h"
 
 #include <mutex>
@@ -55,19 +56,20 @@ constexpr int kConfSlots = 6;         // block partials of the confidence pass, 
 
 struct ReconWorkspace {
     std::mutex mu;                    // held while a reconstruction runs on this (device, stream) pair
-    size_t npix = 0, conf_npix = 0;
-    double *r = nullptr, *q = nullptr, *p0 = nullptr, *p1 = nullptr;      // 3 npix each
-    double *wx = nullptr, *wy = nullptr, *diag = nullptr;                  // npix each
-    double *partials = nullptr;
-    rl1::State *state = nullptr, *h_state = nullptr;                       // device / pinned host
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};                        // timing pair + chunk marker
+    DeviceBuffer<double> r, q, p0, p1;                                     // 3 npix each
+    DeviceBuffer<double> wx, wy, diag;                                     // npix each
+    DeviceBuffer<double> partials;
+    DeviceBuffer<rl1::State> state;
+    PinnedBuffer<rl1::State> h_state;
+    Event ev[3];                                                           // timing pair + chunk marker
     // variance-weighted reconstruction only (ensure_confidence): row variances, confidences, their partials and scalars
-    double *var[3] = {nullptr, nullptr, nullptr}, *conf[3] = {nullptr, nullptr, nullptr};   // npix each: data, x-edge, y-edge rows
-    double *conf_partials = nullptr;
-    ConfStats *conf_stats = nullptr, *h_conf_stats = nullptr;              // device / pinned host
-    void release();
-    void ensure(size_t n);
-    void ensure_confidence(size_t n);     // after ensure(n)
+    DeviceBuffer<double> var[3], conf[3];                                  // npix each: data, x-edge, y-edge rows
+    DeviceBuffer<double> conf_partials;
+    DeviceBuffer<ConfStats> conf_stats;
+    PinnedBuffer<ConfStats> h_conf_stats;
+    // room for npix pixels; earlier reconstructions on `stream` may still use smaller buffers
+    void ensure(size_t npix, hipStream_t stream);
+    void ensure_confidence(size_t npix, hipStream_t stream);
 };
 
 ReconWorkspace &recon_workspace(int dev, hipStream_t stream);

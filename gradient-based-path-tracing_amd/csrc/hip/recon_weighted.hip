@@ -190,14 +190,6 @@ __global__ __launch_bounds__(kBlock) void weighted_weights_kernel(Geo g, double 
 
 namespace gdpt {
 
-namespace {
-
-void ck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-
-} // namespace
-
 ReconWeightedResult recon_weighted_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, const double *d_vc,
                                           const double *d_vgx, const double *d_vgy, double alpha, const ReconL1Params &p, double conf_floor,
                                           double *d_out, double *const d_conf[3], hipStream_t stream) {
@@ -212,9 +204,8 @@ ReconWeightedResult recon_weighted_device(int w, int h, const double *d_c, const
     ReconWorkspace &ws = recon_workspace(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
     const size_t npix = (size_t)w * h;
-    if ((npix > ws.npix && ws.npix) || (npix > ws.conf_npix && ws.conf_npix)) ck(hipStreamSynchronize(stream), "hipStreamSynchronize");
-    ws.ensure(npix);
-    ws.ensure_confidence(npix);
+    ws.ensure(npix, stream);
+    ws.ensure_confidence(npix, stream);
     const rl1::Geo g = recon_geo(w, h);
     const int nb = recon_blocks(g);
     const dim3 grid(nb), block(rl1::kBlock);

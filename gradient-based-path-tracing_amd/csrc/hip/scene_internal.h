@@ -3,6 +3,7 @@
 #pragma once
 #include "../../../include/gdpt.h"
 #include "../device_scene.h"
+#include "device_mem.h"
 #include "render_kernels.h"
 
 #include <hip/hip_runtime.h>
@@ -10,12 +11,6 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
-
-namespace gdpt {
-inline void ck(hipError_t e, const char *what) {
-    if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
-}
-} // namespace gdpt
 
 struct GdptScene {
     int device = 0;
@@ -29,51 +24,28 @@ struct GdptScene {
     unsigned material_mask = 0;    // bit t = a material of type t is present
     int plan_take_pct = 0;         // work-item plan: share of the unassigned samples a chunk takes (0 = default 55; 40 where a refractive lobe is present)
     bool has_rough = false;        // RoughPlastic / RoughDielectric present: GradPath uses the evaluator built with those lobes
-    std::vector<void *> allocations;
+    std::vector<gdpt::DeviceBuffer<unsigned char>> allocations;   // the uploaded scene tables `view` points into
     // cached output/work buffers for the host-pointer entry points
-    double *d_buf[9] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    size_t buf_elems = 0;
-    gdpt::RenderCounters *d_counters = nullptr;
-    gdpt::RenderCounters *h_counters = nullptr; // pinned
-    void *d_bounce_log = nullptr; size_t bounce_log_bytes = 0;   // per-lane bounce log of the two-sided lane machine
-    double *d_partials = nullptr; size_t partials_doubles = 0;   // work-item partial sums of the persistent render kernel
-    unsigned long long *d_queue = nullptr;
-    // wavefront pipeline (render_wavefront.h): path state, live list, generation counters
-    unsigned long long *d_wf_state = nullptr; unsigned *d_wf_live = nullptr, *d_wf_counters = nullptr, *h_wf_word = nullptr;
-    void *d_wf_aux = nullptr;      // ray / hit records, sort keys and histogram, overflow stacks (render_kernels.hip: wf_aux_layout)
-    int wf_slots = 0;
+    gdpt::DeviceBuffer<double> d_buf[9];
+    gdpt::DeviceBuffer<gdpt::RenderCounters> d_counters;
+    gdpt::PinnedBuffer<gdpt::RenderCounters> h_counters;
+    gdpt::DeviceBuffer<unsigned char> d_bounce_log;   // per-lane bounce log of the two-sided lane machine
+    gdpt::DeviceBuffer<double> d_partials;            // work-item partial sums of the persistent render kernel
+    gdpt::DeviceBuffer<unsigned long long> d_queue;
+    // wavefront pipeline (render_wavefront.h): path state, live list (one entry per slot), generation counters
+    gdpt::DeviceBuffer<unsigned long long> d_wf_state;
+    gdpt::DeviceBuffer<unsigned> d_wf_live, d_wf_counters;
+    gdpt::PinnedBuffer<unsigned> h_wf_word;
+    gdpt::DeviceBuffer<unsigned char> d_wf_aux;       // ray / hit records, sort keys and histogram, overflow stacks (render_kernels.hip: wf_aux_layout)
     float bounds[6] = {0, 0, 0, 0, 0, 0};   // fp32 scene bounds (min xyz, max xyz), as get_intersection_epsilon sees them
-    hipEvent_t wf_event = nullptr;
+    gdpt::Event wf_event;
     int num_cus = 256;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-
-    template <class T>
-    T *keep(T *p) { if (p) allocations.push_back((void *)p); return p; }
+    gdpt::Event ev0, ev1;
 
     void ensure_buffers(size_t elems) {
-        if (elems <= buf_elems) return;
-        for (auto &b : d_buf) { if (b) hipFree(b); b = nullptr; }
-        for (auto &b : d_buf) gdpt::ck(hipMalloc((void **)&b, elems * sizeof(double)), "hipMalloc(image buffers)");
-        buf_elems = elems;
+        for (auto &b : d_buf) b.grow(elems, "hipMalloc(image buffers)");
     }
-    ~GdptScene() {
-        hipSetDevice(device);
-        for (void *p : allocations) hipFree(p);
-        for (auto &b : d_buf) if (b) hipFree(b);
-        if (d_counters) hipFree(d_counters);
-        if (d_partials) hipFree(d_partials);
-        if (d_bounce_log) hipFree(d_bounce_log);
-        if (d_queue) hipFree(d_queue);
-        if (d_wf_state) hipFree(d_wf_state);
-        if (d_wf_live) hipFree(d_wf_live);
-        if (d_wf_aux) hipFree(d_wf_aux);
-        if (d_wf_counters) hipFree(d_wf_counters);
-        if (h_wf_word) hipHostFree(h_wf_word);
-        if (wf_event) hipEventDestroy(wf_event);
-        if (h_counters) hipHostFree(h_counters);
-        if (ev0) hipEventDestroy(ev0);
-        if (ev1) hipEventDestroy(ev1);
-    }
+    ~GdptScene() { hipSetDevice(device); }      // the members free themselves on it
 };
 
 
