@@ -78,6 +78,12 @@ def lib():
         L.gdpt_progressive_group_total.argtypes = [vp]
         L.gdpt_progressive_group_total.restype = vp
         L.gdpt_progressive_group_member_status.argtypes = [vp, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
+        sst, grp = C.POINTER(defs.GdptReconSpreadStats), C.POINTER(defs.GdptGroupReconParams)
+        L.gdpt_recon_spread_device.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp), dp, vp, C.c_int, vp, vp, vp, sst]
+        L.gdpt_recon_spread.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp), dp, vp, C.c_int, vp, vp, sst]
+        L.gdpt_progressive_group_reconstruct_error.argtypes = [vp, grp, C.c_int, vp, vp, vp, sst, C.POINTER(defs.GdptReconStats)]
+        L.gdpt_progressive_group_run_recon.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, grp,
+                                                       C.POINTER(defs.GdptProgressiveStatus), sst]
         L.gdpt_assemble_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gdpt_poisson_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         L.gdpt_poisson_solve_ex.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, C.c_int, C.c_double, C.c_int,
@@ -439,12 +445,49 @@ class ProgressiveGroup:
         self.handle = h
         self.total = Progressive._view(self, lib().gdpt_progressive_group_total(h), (scene_desc.height, scene_desc.width, 3), path)
 
-    def run(self, target_error=0.0, pass_spp=16, max_rounds=0):
+    def run(self, target_error=0.0, pass_spp=16, max_rounds=0, target_recon_error=None, check_every=1, alpha=0.04, norm=defs.RECON_L2,
+            weighted=False, conf_floor=0.0, **params):
         """Rounds of one pass per member until all slices are spent, `max_rounds` were done (0: no limit) or, from 2 passes on, the
-        total's error estimate is <= target_error (0: no target). Returns the total's status()."""
+        total's error estimate is <= target_error (0: no target). Returns the total's status().
+        With `target_recon_error` (gdpt_progressive_group_run_recon) the target is the error estimate of the RECONSTRUCTION
+        (reconstruct_error(); the kind chosen by alpha, norm, weighted, conf_floor and the keywords of recon_params), taken after every
+        `check_every`-th round and once before returning: the status then carries it as "recon_error", with "recon_spread"
+        (GdptReconSpreadStats). `target_error` and `target_recon_error` together are refused."""
         st = defs.GdptProgressiveStatus()
-        _check(lib().gdpt_progressive_group_run(self.handle, float(target_error), int(pass_spp), int(max_rounds), C.byref(st)))
-        return Progressive._status_dict(st)
+        if target_recon_error is None:
+            _check(lib().gdpt_progressive_group_run(self.handle, float(target_error), int(pass_spp), int(max_rounds), C.byref(st)))
+            return Progressive._status_dict(st)
+        if target_error:
+            raise GdptError("ProgressiveGroup.run: target_error and target_recon_error exclude each other")
+        p, sp = group_recon_params(alpha, norm, weighted, 0, conf_floor, **params), defs.GdptReconSpreadStats()
+        _check(lib().gdpt_progressive_group_run_recon(self.handle, float(target_recon_error), int(pass_spp), int(max_rounds), int(check_every),
+                                                      C.byref(p), C.byref(st), C.byref(sp)))
+        d = Progressive._status_dict(st)
+        d["recon_error"] = sp.error_estimate if sp.members else float("nan")
+        d["recon_spread"] = sp
+        return d
+
+    def reconstruct_error(self, alpha=0.04, norm=defs.RECON_L2, weighted=False, radius=0, conf_floor=0.0, variance=False,
+                          out_ptrs=None, **params):
+        """The group's image with the error estimate of that image (gdpt_progressive_group_reconstruct_error): every member that holds
+        samples reconstructs its own means, and the weighted spread of those reconstructions estimates the variance of the
+        reconstruction of the total. `weighted`: the variance-weighted kinds (every member needs 2 passes); `radius`: the error map's
+        window (0..8). Returns (HxWx3 image, HxW error map, GdptReconSpreadStats, GdptReconStats of the total), with `variance=True`
+        (image, map, HxWx3 variance, spread stats, recon stats); with `out_ptrs` = (image, map or None, variance or None) device
+        addresses on devices[0] everything stays there and (spread stats, recon stats) are returned. The L2 kind is linear, so the
+        estimate is that of the image returned; for L1 and the weighted kinds it measures the members' spread, not their common bias."""
+        p = group_recon_params(alpha, norm, weighted, radius, conf_floor, **params)
+        sp, rs = defs.GdptReconSpreadStats(), defs.GdptReconStats()
+        if out_ptrs is not None:
+            ptrs = [C.c_void_p(int(x)) if x else None for x in (list(out_ptrs) + [None, None])[:3]]
+            _check(lib().gdpt_progressive_group_reconstruct_error(self.handle, C.byref(p), 1, *ptrs, C.byref(sp), C.byref(rs)))
+            return sp, rs
+        shape = self.total.shape
+        img, emap = np.empty(shape, dtype=np.float64), np.empty(shape[:2], dtype=np.float64)
+        var = np.empty(shape, dtype=np.float64) if variance else None
+        _check(lib().gdpt_progressive_group_reconstruct_error(self.handle, C.byref(p), 0, C.c_void_p(img.ctypes.data), C.c_void_p(emap.ctypes.data),
+                                                              C.c_void_p(var.ctypes.data) if variance else None, C.byref(sp), C.byref(rs)))
+        return (img, emap, var, sp, rs) if variance else (img, emap, sp, rs)
 
     def member_status(self, i):
         st = defs.GdptProgressiveStatus()
@@ -514,6 +557,58 @@ def weighted_recon_params(norm=defs.RECON_L2, conf_floor=0.0, **params):
     p.recon = recon_params(norm, **params)
     p.conf_floor = float(conf_floor)
     return p
+
+
+def group_recon_params(alpha=0.04, norm=defs.RECON_L2, weighted=False, radius=0, conf_floor=0.0, **params):
+    """GdptGroupReconParams (include/gdpt.h): the reconstruction a group's members and total go through, and the error map's radius."""
+    p = defs.GdptGroupReconParams()
+    p.dataCost, p.weighted, p.map_radius = float(alpha), int(bool(weighted)), int(radius)
+    p.recon = recon_params(norm, **params)
+    p.wrecon = weighted_recon_params(norm, conf_floor, **params)
+    return p
+
+
+def _spread_args(images, weights, shape):
+    n = len(images)
+    tab = (C.c_void_p * max(1, n))()
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if len(w) != n:
+        raise GdptError("recon_spread: one weight per image")
+    return n, tab, w
+
+
+def recon_spread(images, weights, total=None, radius=0):
+    """The weighted spread of N images of one film on the GPU (gdpt_recon_spread): per component var = M2 / ((N-1) W) around the
+    weighted mean, the variance of that mean if image i has variance sigma^2 / weights[i]. Inputs HxWx3 float64; `total` (None: the
+    weighted mean) is the image whose squares normalise the estimate. Returns (HxWx3 var, HxW map, GdptReconSpreadStats): the map is
+    var summed over the channels, averaged over the finite entries of the (2 radius + 1)^2 window for radius >= 1."""
+    a = [np.ascontiguousarray(x, dtype=np.float64) for x in images]
+    shape = a[0].shape if a else (1, 1, 3)
+    h, wd = shape[0], shape[1]
+    n, tab, w = _spread_args(a, weights, shape)
+    for i, x in enumerate(a):
+        if x.shape != shape:
+            raise GdptError("recon_spread: the images' shapes differ")
+        tab[i] = x.ctypes.data
+    t = None if total is None else np.ascontiguousarray(total, dtype=np.float64).reshape(shape)
+    var, emap = np.empty((h, wd, 3), dtype=np.float64), np.empty((h, wd), dtype=np.float64)
+    st = defs.GdptReconSpreadStats()
+    _check(lib().gdpt_recon_spread(int(wd), int(h), n, tab, _dp(w), None if t is None else C.c_void_p(t.ctypes.data), int(radius),
+                                   C.c_void_p(var.ctypes.data), C.c_void_p(emap.ctypes.data), C.byref(st)))
+    return var, emap, st
+
+
+def recon_spread_device(width, height, image_ptrs, weights, total_ptr=None, radius=0, var_ptr=None, map_ptr=None, stream=None):
+    """recon_spread() on device addresses (gdpt_recon_spread_device); `var_ptr` (W*H*3) and `map_ptr` (W*H) may be None. Returns
+    GdptReconSpreadStats. Waits for `stream`."""
+    n, tab, w = _spread_args(image_ptrs, weights, None)
+    for i, x in enumerate(image_ptrs):
+        tab[i] = int(x) if x else None
+    st = defs.GdptReconSpreadStats()
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_recon_spread_device(int(width), int(height), n, tab, _dp(w), opt(total_ptr), int(radius), opt(var_ptr), opt(map_ptr),
+                                          opt(stream), C.byref(st)))
+    return st
 
 
 def _ptr_table(ptrs):

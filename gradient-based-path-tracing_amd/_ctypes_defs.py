@@ -122,6 +122,16 @@ class GdptProgressiveStatus(C.Structure):
                 ("error_estimate", C.c_double), ("pixels_left_out", C.c_uint64), ("fold_ms", C.c_double), ("totals", GdptRenderStats)]
 
 
+class GdptReconSpreadStats(C.Structure):
+    _fields_ = [("members", C.c_int32), ("radius", C.c_int32), ("error_estimate", C.c_double), ("sum_var", C.c_double),
+                ("sum_sq", C.c_double), ("pixels_left_out", C.c_uint64), ("spread_ms", C.c_double)]
+
+
+class GdptGroupReconParams(C.Structure):
+    _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
+                ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]
+
+
 GDPT_MULTI_MAX_DEVICES = 16
 EXCHANGE_RCCL, EXCHANGE_PEER_COPY = 0, 1
 

@@ -20,6 +20,7 @@
 #include "poisson_kernels.h"
 #include "device_mem.h"
 #include "recon_l1.h"
+#include "recon_spread.h"
 #include "../capi_common.h"
 #include "../../../include/gdpt.h"
 
@@ -738,6 +739,7 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
 void forget_stream(int dev, hipStream_t stream) {
     g_streams.forget(dev, stream);         // scratch buffers, rocBLAS handle, timing events
     recon_l1_forget_stream(dev, stream);
+    recon_spread_forget_stream(dev, stream);
 }
 
 void poisson_release_workspace() {

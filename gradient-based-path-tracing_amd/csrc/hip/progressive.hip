@@ -35,26 +35,10 @@
 
 namespace prg {
 
-constexpr int kBlock = 256, kMaxBlocks = 1024;
-
 struct Planes {
     const double *pass[5];
     double *mean[5], *m2[5];
 };
-
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    // fixed order: xor tree inside each wave, then the wave totals in index order
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / 64; k++) s += red[k];
-    return s;
-}
 
 // n: samples of the pass; w_new: samples so far, this pass included; norm = (K - 1) w_new, K passes this one included (0 while K < 2:
 // no estimate). FIRST: the running planes are not read (mean = M2 = 0 before the first pass).
@@ -187,7 +171,7 @@ void add_totals(GdptRenderStats &t, const GdptRenderStats &rs) {
 
 // the reduction of the partials a fold or merge launch left, the estimate to the host, the launches' device time; waits for the stream
 void finish_estimate(GdptProgressive &s, int nb, const char *what) {
-    hipLaunchKernelGGL(prg::finish_kernel, dim3(1), dim3(prg::kBlock), 0, s.stream, nb, s.partials, s.d_est);
+    prg::launch_finish(nb, s.partials, s.d_est, s.stream);
     ck(hipGetLastError(), what);
     ck(hipEventRecord(s.ev[1], s.stream), "hipEventRecord");
     ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
@@ -206,6 +190,10 @@ std::vector<std::pair<int, int>> intervals_held(const GdptProgressive &s) {
 } // namespace
 
 namespace prg {
+
+void launch_finish(int nb, const double *partials, Estimate *est, hipStream_t stream) {
+    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, stream, nb, partials, est);
+}
 
 double error_estimate(const GdptProgressive &s) {
     if (s.passes < 2) return std::numeric_limits<double>::quiet_NaN();
@@ -389,6 +377,32 @@ void create_session(const char *fn, GdptScene *scene, const GdptProgressiveConfi
 
 } // namespace
 
+namespace prg {
+
+void reconstruct(GdptProgressive &s, double dataCost, const GdptReconParams *recon, GdptReconStats *stats) {
+    if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct: an Integrator::Path session has no gradients (read its mean)");
+    if (s.passes < 1) throw std::runtime_error("gdpt_progressive_reconstruct: no pass has been added");
+    ck(hipSetDevice(s.scene->device), "hipSetDevice");
+    assemble_means(s);
+    if (gdpt_reconstruct_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], dataCost, recon, s.asm_buf[3], s.stream, stats) != 0)
+        throw std::runtime_error(gdpt_last_error());
+}
+
+void reconstruct_weighted(GdptProgressive &s, double dataCost, const GdptWeightedReconParams *params, double *const confidence[3],
+                          GdptWeightedReconStats *stats) {
+    if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: an Integrator::Path session has no gradients (read its mean)");
+    if (s.passes < 2) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: variances need at least 2 passes");
+    ck(hipSetDevice(s.scene->device), "hipSetDevice");
+    assemble_means(s);
+    compute_variances(s);
+    // (the confidence planes go straight to their destination: the copy kind is taken from the pointers, host or device)
+    if (gdpt_reconstruct_weighted_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.var[0], s.var[5], s.var[6], dataCost, params, s.asm_buf[3],
+                                         confidence, s.stream, stats) != 0)
+        throw std::runtime_error(gdpt_last_error());
+}
+
+} // namespace prg
+
 extern "C" {
 
 int gdpt_progressive_create(GdptScene *scene, const GdptProgressiveConfig *config, void *stream, GdptProgressive **out) {
@@ -465,12 +479,7 @@ int gdpt_progressive_reconstruct(GdptProgressive *session, double dataCost, cons
     return gdpt::guarded([&]() {
         if (!session || !out) throw std::runtime_error("gdpt_progressive_reconstruct: null argument");
         GdptProgressive &s = *session;
-        if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct: an Integrator::Path session has no gradients (read its mean)");
-        if (s.passes < 1) throw std::runtime_error("gdpt_progressive_reconstruct: no pass has been added");
-        ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        assemble_means(s);
-        if (gdpt_reconstruct_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], dataCost, recon, s.asm_buf[3], s.stream, stats) != 0)
-            throw std::runtime_error(gdpt_last_error());
+        prg::reconstruct(s, dataCost, recon, stats);
         copy_out(s, out, s.asm_buf[3], on_device);
         ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");
     });
@@ -481,15 +490,7 @@ int gdpt_progressive_reconstruct_weighted(GdptProgressive *session, double dataC
     return gdpt::guarded([&]() {
         if (!session || !out) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: null argument");
         GdptProgressive &s = *session;
-        if (s.nbuf != 5) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: an Integrator::Path session has no gradients (read its mean)");
-        if (s.passes < 2) throw std::runtime_error("gdpt_progressive_reconstruct_weighted: variances need at least 2 passes");
-        ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        assemble_means(s);
-        compute_variances(s);
-        // (the confidence planes go straight to their destination: the copy kind is taken from the pointers, host or device)
-        if (gdpt_reconstruct_weighted_device(s.w, s.h, s.asm_buf[0], s.asm_buf[1], s.asm_buf[2], s.var[0], s.var[5], s.var[6], dataCost, params, s.asm_buf[3],
-                                             confidence, s.stream, stats) != 0)
-            throw std::runtime_error(gdpt_last_error());
+        prg::reconstruct_weighted(s, dataCost, params, confidence, stats);
         copy_out(s, out, s.asm_buf[3], on_device);
         ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");
     });

@@ -11,9 +11,16 @@
 // nothing and wait for nothing but their own device: a member that fails cannot leave another one waiting; its error is reported
 // after all threads have been joined. Then the total (an accumulator on devices[0]) is emptied and all members are merged into it in
 // member order (prg::merge, progressive.hip), so its bits do not depend on which member finished first.
+//
+// The error of the reconstruction (gdpt_progressive_group_reconstruct_error, _run_recon). The members are N independent estimates of
+// the film, so their reconstructions are too: every member that holds samples reconstructs its own running means on its own device
+// and stream (threads as in a round), the images of members on other devices are copied to devices[0], the total is reconstructed
+// there, and recon_spread.hip takes the weighted spread of the members' images around their mean on the total's stream. Nothing of
+// the render, the fold or the merge takes part.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "progressive_internal.h"
+#include "recon_spread.h"
 
 #include <algorithm>
 #include <cmath>
@@ -39,12 +46,17 @@ struct GdptProgressiveGroup {
     hipStream_t total_stream = nullptr;
     GdptProgressive *total = nullptr;
     bool total_current = true;       // the total holds what the members hold
+    std::vector<gdpt::DeviceBuffer<double>> recon_stage;     // on devices[0]: reconstructions of members on other devices, allocated on first use
+    gdpt::DeviceBuffer<double> spread_var, spread_map;       // on devices[0]: the statistic's planes on their way to host memory, allocated on first use
 
     ~GdptProgressiveGroup() {
         if (total) gdpt_progressive_free(total);
         for (Member &m : members) if (m.session) gdpt_progressive_free(m.session);
-        if (total_stream && !members.empty()) {
+        if (!members.empty()) {
             hipSetDevice(members[0].device);
+            recon_stage.clear(); spread_var.reset(); spread_map.reset();
+        }
+        if (total_stream && !members.empty()) {
             gdpt::forget_stream(members[0].device, total_stream);     // the solvers' and reconstructions' per-stream scratch goes with the stream
             hipStreamDestroy(total_stream);
         }
@@ -91,6 +103,107 @@ bool round(GdptProgressiveGroup &g, int pass_spp) {
         if (!m.error.empty()) throw std::runtime_error("device " + std::to_string(m.device) + " (member " + std::to_string(i) + "): " + m.error);
     }
     return true;
+}
+
+// the members that hold samples
+std::vector<int> members_with_samples(const GdptProgressiveGroup &g) {
+    std::vector<int> used;
+    for (int i = 0; i < (int)g.members.size(); i++) if (g.members[(size_t)i].session->done > 0) used.push_back(i);
+    return used;
+}
+
+// "" if the estimate can be taken now, else why not
+std::string cannot_estimate(const GdptProgressiveGroup &g, const GdptGroupReconParams &p) {
+    const std::vector<int> used = members_with_samples(g);
+    if (used.size() < 2)
+        return std::to_string(used.size()) + " of " + std::to_string(g.members.size()) + " members hold samples: the spread needs two independent estimates";
+    if (p.weighted)
+        for (int i : used)
+            if (g.members[(size_t)i].session->passes < 2)
+                return "member " + std::to_string(i) + " holds " + std::to_string(g.members[(size_t)i].session->passes) +
+                       " pass: the variance-weighted reconstruction needs at least 2 in every member";
+    return "";
+}
+
+void check_recon_params(const char *fn, const GdptProgressiveGroup &g, const GdptGroupReconParams *p) {
+    const std::string who(fn);
+    if (!p) throw std::runtime_error(who + ": null params");
+    if (g.total->nbuf != 5) throw std::runtime_error(who + ": an Integrator::Path group has no gradients to reconstruct (GradPath groups only)");
+    if (p->map_radius < 0 || p->map_radius > 8) throw std::runtime_error(who + ": map_radius must be in [0, 8]");
+    if (p->weighted != 0 && p->weighted != 1) throw std::runtime_error(who + ": weighted must be 0 or 1");
+}
+
+// Every member used reconstructs, then the total, then the spread; the outputs (all nullable) as the entry point's. The total is current.
+gdpt::ReconSpreadResult reconstruct_error(GdptProgressiveGroup &g, const GdptGroupReconParams &p, int on_device, double *out_image, double *out_map,
+                                          double *out_var, GdptReconStats *recon_stats, int *num_used) {
+    const std::vector<int> used = members_with_samples(g);
+    for (int i : used) g.members[(size_t)i].error.clear();
+    auto one = [&](int i) {
+        Member &m = g.members[(size_t)i];
+        try {
+            GdptProgressive &s = *m.session;
+            if (p.weighted) prg::reconstruct_weighted(s, p.dataCost, &p.wrecon, nullptr, nullptr);
+            else prg::reconstruct(s, p.dataCost, &p.recon, nullptr);
+            ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(member reconstruction)");
+        } catch (const std::exception &e) { m.error = e.what(); }
+        catch (...) { m.error = "unknown error"; }
+    };
+    std::vector<std::thread> th;
+    for (size_t k = 1; k < used.size(); k++) th.emplace_back(one, used[k]);
+    one(used[0]);
+    for (std::thread &t : th) t.join();
+    for (int i : used) {
+        const Member &m = g.members[(size_t)i];
+        if (!m.error.empty()) throw std::runtime_error("device " + std::to_string(m.device) + " (member " + std::to_string(i) + "): " + m.error);
+    }
+
+    GdptProgressive &t = *g.total;
+    ck(hipSetDevice(t.device), "hipSetDevice");
+    std::vector<const double *> images;
+    std::vector<double> weights;
+    g.recon_stage.resize(g.members.size());
+    for (int i : used) {
+        const GdptProgressive &s = *g.members[(size_t)i].session;
+        const double *img = s.asm_buf[3];
+        if (s.device != t.device) {          // into staging on the total's device, on the total's stream (as prg::merge copies the planes)
+            int can = 0;
+            ck(hipDeviceCanAccessPeer(&can, t.device, s.device), "hipDeviceCanAccessPeer");
+            if (can) {
+                const hipError_t e = hipDeviceEnablePeerAccess(s.device, 0);
+                if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) ck(e, "hipDeviceEnablePeerAccess");
+                (void)hipGetLastError();
+            }
+            gdpt::DeviceBuffer<double> &st = g.recon_stage[(size_t)i];
+            if (!st) st.alloc(t.elems, "hipMalloc(group reconstruction staging)");
+            ck(hipMemcpyPeerAsync(st, t.device, img, s.device, t.elems * sizeof(double), t.stream), "hipMemcpyPeerAsync(member reconstruction)");
+            img = st;
+        }
+        images.push_back(img);
+        weights.push_back((double)s.done);
+    }
+    if (p.weighted) {
+        GdptWeightedReconStats ws{};
+        prg::reconstruct_weighted(t, p.dataCost, &p.wrecon, nullptr, &ws);
+        if (recon_stats) *recon_stats = ws.recon;
+    } else
+        prg::reconstruct(t, p.dataCost, &p.recon, recon_stats);
+
+    double *d_var = out_var, *d_map = out_map;
+    if (!on_device) {
+        if (out_var) { if (!g.spread_var) g.spread_var.alloc(t.elems, "hipMalloc(group spread planes)"); d_var = g.spread_var; }
+        if (out_map) { if (!g.spread_map) g.spread_map.alloc(t.elems / 3, "hipMalloc(group spread planes)"); d_map = g.spread_map; }
+    }
+    const gdpt::ReconSpreadResult res = gdpt::recon_spread_device(t.w, t.h, (int)images.size(), images.data(), weights.data(), t.asm_buf[3], p.map_radius,
+                                                                  d_var, d_map, t.stream);
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (out_image) ck(hipMemcpyAsync(out_image, t.asm_buf[3], t.elems * sizeof(double), kind, t.stream), "hipMemcpyAsync(group reconstruction)");
+    if (!on_device) {
+        if (out_var) ck(hipMemcpyAsync(out_var, d_var, t.elems * sizeof(double), kind, t.stream), "hipMemcpyAsync(group spread planes)");
+        if (out_map) ck(hipMemcpyAsync(out_map, d_map, t.elems / 3 * sizeof(double), kind, t.stream), "hipMemcpyAsync(group spread planes)");
+    }
+    ck(hipStreamSynchronize(t.stream), "hipStreamSynchronize(group reconstruction)");
+    if (num_used) *num_used = (int)used.size();
+    return res;
 }
 
 } // namespace
@@ -175,6 +288,67 @@ int gdpt_progressive_group_run(GdptProgressiveGroup *group, double target_error,
         if (!g.total_current) rebuild_total(g);
         t.stop_reason = why;
         prg::fill_status(t, status);
+    });
+}
+
+int gdpt_progressive_group_reconstruct_error(GdptProgressiveGroup *group, const GdptGroupReconParams *params, int on_device, double *out_image,
+                                             double *out_map, double *out_var, GdptReconSpreadStats *spread_stats, GdptReconStats *recon_stats) {
+    return gdpt::guarded([&]() {
+        const char *fn = "gdpt_progressive_group_reconstruct_error";
+        if (!group || !out_image) throw std::runtime_error(std::string(fn) + ": null argument");
+        GdptProgressiveGroup &g = *group;
+        check_recon_params(fn, g, params);
+        if (!g.total_current) rebuild_total(g);
+        const std::string why = cannot_estimate(g, *params);
+        if (!why.empty()) throw std::runtime_error(std::string(fn) + ": " + why);
+        int n = 0;
+        const gdpt::ReconSpreadResult r = reconstruct_error(g, *params, on_device, out_image, out_map, out_var, recon_stats, &n);
+        gdpt::fill_spread_stats(spread_stats, n, params->map_radius, r);
+    });
+}
+
+int gdpt_progressive_group_run_recon(GdptProgressiveGroup *group, double target_recon_error, int pass_spp, int max_rounds, int check_every,
+                                     const GdptGroupReconParams *params, GdptProgressiveStatus *status, GdptReconSpreadStats *spread_stats) {
+    return gdpt::guarded([&]() {
+        const char *fn = "gdpt_progressive_group_run_recon";
+        if (!group) throw std::runtime_error(std::string(fn) + ": null group");
+        if (pass_spp <= 0) throw std::runtime_error(std::string(fn) + ": pass_spp must be > 0");
+        if (std::isnan(target_recon_error)) throw std::runtime_error(std::string(fn) + ": target_recon_error is NaN");
+        GdptProgressiveGroup &g = *group;
+        check_recon_params(fn, g, params);
+        GdptProgressive &t = *g.total;
+        const int every = check_every <= 0 ? 1 : check_every;
+        auto spent = [&]() {
+            for (const Member &m : g.members) if (m.session->own_done < m.session->own) return false;
+            return true;
+        };
+        // the estimate of the state the members hold now; false where it cannot be taken yet
+        GdptReconSpreadStats est{};
+        bool est_current = false;
+        auto evaluate = [&]() {
+            if (!g.total_current) rebuild_total(g);
+            if (est_current) return true;
+            if (!cannot_estimate(g, *params).empty()) return false;
+            int n = 0;
+            const gdpt::ReconSpreadResult r = reconstruct_error(g, *params, 1, nullptr, nullptr, nullptr, nullptr, &n);
+            gdpt::fill_spread_stats(&est, n, params->map_radius, r);
+            est_current = true;
+            return true;
+        };
+        int rounds = 0, why = GDPT_STOP_NONE;
+        for (;;) {
+            if (target_recon_error > 0 && est_current && est.error_estimate <= target_recon_error) { why = GDPT_STOP_TARGET; break; }
+            if (spent()) { why = GDPT_STOP_BUDGET; break; }
+            if (max_rounds > 0 && rounds >= max_rounds) { why = GDPT_STOP_MAX_PASSES; break; }
+            round(g, pass_spp);
+            rounds++;
+            est_current = false;
+            if (target_recon_error > 0 && rounds % every == 0) evaluate();
+        }
+        if (!evaluate()) est = GdptReconSpreadStats{};
+        t.stop_reason = why;
+        prg::fill_status(t, status);
+        if (spread_stats) *spread_stats = est;
     });
 }
 

@@ -8,6 +8,23 @@
 
 namespace prg {
 struct Estimate { double sum_var, sum_mean2, left_out; };
+
+constexpr int kBlock = 256, kMaxBlocks = 1024;
+
+// What every kernel that leaves block partials for finish_kernel (progressive.hip) reduces its block with.
+__device__ __forceinline__ double block_sum(double v, double *red) {
+    // fixed order: xor tree inside each wave, then the wave totals in index order
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+    const int wave = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[wave] = v;
+    __syncthreads();
+    double s = red[0];
+#pragma unroll
+    for (int k = 1; k < kBlock / 64; k++) s += red[k];
+    return s;
+}
 } // namespace prg
 
 struct GdptProgressive {
@@ -47,5 +64,12 @@ void merge(GdptProgressive &dst, const GdptProgressive &src);
 // Back to the state of a fresh accumulator: nothing held (the planes keep their bytes: the next merge overwrites them).
 void reset(GdptProgressive &s);
 double error_estimate(const GdptProgressive &s);
+// finish_kernel on `stream`: three runs of nb block partials (as fold_kernel leaves them) reduced in a fixed order into *est
+void launch_finish(int nb, const double *partials, Estimate *est, hipStream_t stream);
+// What gdpt_progressive_reconstruct / _reconstruct_weighted do up to the copy-out: the image is left in s.asm_buf[3], enqueued on the
+// session's stream (the weighted kinds and L1 have waited for it). They throw what the entry points report.
+void reconstruct(GdptProgressive &s, double dataCost, const GdptReconParams *recon, GdptReconStats *stats);
+void reconstruct_weighted(GdptProgressive &s, double dataCost, const GdptWeightedReconParams *params, double *const confidence[3],
+                          GdptWeightedReconStats *stats);
 void fill_status(const GdptProgressive &s, GdptProgressiveStatus *st);
 } // namespace prg

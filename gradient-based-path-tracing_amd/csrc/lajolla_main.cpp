@@ -29,6 +29,10 @@
 //   --sample-devices a,b,..   the session's samples split over these devices (HIP ordinals, repeats allowed) on the sample axis
 //                 (gdpt_progressive_group_*: device i draws streams [i B / N, (i+1) B / N) of every pixel's block of B = --spp, the
 //                 merged total is what is reconstructed). Needs --pass-spp; not with --gpus / --devices (row bands are another thing)
+//                 --target-recon-error E (in the place of --target-error) stops on the estimated relative RMSE of the RECONSTRUCTION,
+//                 taken from the spread of the members' own reconstructions (gdpt_progressive_group_run_recon); --error-map FILE
+//                 writes that estimate's per-pixel variance map (all three channels), --error-radius R (0..8) averages it over a
+//                 (2R+1)^2 window. They need two or more entries (0,0 is fine on one GPU): one session has no independent halves
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -46,7 +50,10 @@ int main(int argc, char *argv[]) {
     }
     int num_threads = 0, spp = 0, device = 0, rng = GDPT_RNG_SAMPLE, shift = GDPT_SHIFT_REFERENCE;
     int film_w = 0, film_h = 0, plan_rows = 0, pass_spp = 0;
-    double target_error = 0.0;
+    double target_error = 0.0, target_recon_error = 0.0;
+    int error_radius = 0;
+    bool error_radius_set = false;
+    std::string error_map_file = "";
     std::string variance_file = "", confidence_file = "";
     bool weighted = false;
     double conf_floor = 0.0;
@@ -110,6 +117,9 @@ int main(int argc, char *argv[]) {
         else if (a == "--plan-rows") plan_rows = std::stoi(next());
         else if (a == "--pass-spp") { pass_spp = std::stoi(next()); if (pass_spp <= 0) { std::cerr << "--pass-spp must be > 0" << std::endl; return 2; } }
         else if (a == "--target-error") target_error = std::stod(next());
+        else if (a == "--target-recon-error") target_recon_error = std::stod(next());
+        else if (a == "--error-map") error_map_file = next();
+        else if (a == "--error-radius") { error_radius = std::stoi(next()); error_radius_set = true; }
         else if (a == "--variance") variance_file = next();
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
         else if (a == "--shift") {        // extension: "reconnect" = GDPT_SHIFT_RECONNECT (include/gdpt.h); default = the reference's offsets
@@ -150,6 +160,17 @@ int main(int argc, char *argv[]) {
     if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
+    const bool recon_error = target_recon_error != 0.0 || !error_map_file.empty();
+    if ((recon_error || error_radius_set) && sample_devices.size() < 2) {
+        std::cerr << "--target-recon-error, --error-map and --error-radius need --sample-devices with two or more entries: the estimate is the spread of "
+                     "the members' reconstructions, and one session has no independent halves" << std::endl;
+        return 2;
+    }
+    if (target_recon_error != 0.0 && target_error != 0.0) { std::cerr << "--target-error and --target-recon-error exclude each other: one target per run" << std::endl; return 2; }
+    if (!(target_recon_error >= 0.0)) { std::cerr << "--target-recon-error must be >= 0" << std::endl; return 2; }
+    if (error_radius < 0 || error_radius > 8) { std::cerr << "--error-radius must be in [0, 8]" << std::endl; return 2; }
+    if (error_radius_set && error_map_file.empty()) { std::cerr << "--error-radius needs --error-map" << std::endl; return 2; }
+    if (recon_error && !confidence_file.empty()) { std::cerr << "--confidence is not written with --target-recon-error / --error-map" << std::endl; return 2; }
     (void)num_threads;
 
     using clock = std::chrono::system_clock;
@@ -193,10 +214,15 @@ int main(int argc, char *argv[]) {
         // render() dispatches on the integrator (src/render.cpp:374-392)
         int rc;
         GdptProgressiveStatus prog{};
+        GdptReconSpreadStats spread{};
+        GdptGroupReconParams gp{};        // the reconstruction the estimate of --target-recon-error / --error-map goes through
+        gp.dataCost = alpha; gp.weighted = weighted ? 1 : 0; gp.map_radius = error_radius;
+        gp.recon = recon; gp.wrecon.recon = recon; gp.wrecon.conf_floor = conf_floor;
         if (pass_spp > 0) {
             GdptProgressive *session = nullptr;
             if (grouped) {                // the merged total is a session like any other: everything below reads it
-                rc = gdpt_progressive_group_run(group, target_error, pass_spp, 0, &prog);
+                rc = target_recon_error > 0.0 ? gdpt_progressive_group_run_recon(group, target_recon_error, pass_spp, 0, 1, &gp, &prog, nullptr)
+                                              : gdpt_progressive_group_run(group, target_error, pass_spp, 0, &prog);
                 session = gdpt_progressive_group_total(group);
             } else {
                 rc = gdpt_progressive_create(scene, &cfg, nullptr, &session);
@@ -204,7 +230,16 @@ int main(int argc, char *argv[]) {
             }
             double *means[5] = {path ? image.data() : nullptr, nullptr, nullptr, nullptr, nullptr};
             if (rc == 0 && path) rc = gdpt_progressive_read(session, 0, means, nullptr, nullptr);
-            if (rc == 0 && !path && weighted) {
+            if (rc == 0 && recon_error) {    // the total's reconstruction (the same bits as below) with the spread of the members' around it
+                std::vector<double> emap((size_t)w * h);
+                rc = gdpt_progressive_group_reconstruct_error(group, &gp, 0, image.data(), emap.data(), nullptr, &spread, &cs);
+                ps.iterations = cs.cg_iters_total; ps.solve_ms = cs.solve_ms;
+                if (rc == 0 && !error_map_file.empty()) {
+                    std::vector<double> rgb((size_t)w * h * 3);
+                    for (size_t i = 0; i < (size_t)w * h; i++) for (int k = 0; k < 3; k++) rgb[3 * i + k] = emap[i];
+                    rc = gdpt_imwrite(error_map_file.c_str(), w, h, rgb.data());
+                }
+            } else if (rc == 0 && !path && weighted) {
                 GdptWeightedReconParams wp{};
                 wp.recon = recon; wp.conf_floor = conf_floor;
                 GdptWeightedReconStats ws{};
@@ -273,6 +308,10 @@ int main(int argc, char *argv[]) {
             std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << budget
                       << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
                       << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
+            if (recon_error)
+                std::cout << "[gdpt] reconstruction: error estimate " << spread.error_estimate << " from the spread of " << spread.members
+                          << " members (" << spread.pixels_left_out << " pixels left out), map radius " << spread.radius << ", spread "
+                          << spread.spread_ms << " ms" << std::endl;
         }
         if (grouped) {
             const int n = (int)sample_devices.size();

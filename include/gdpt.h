@@ -578,6 +578,70 @@ int gdpt_assemble_rows_device(int width, int height, int row_begin, int row_end,
                               const double *d_cx1, const double *d_cy1,
                               double *d_c, double *d_cx, double *d_cy, void *stream);
 
+/* ---- the error of the reconstructed image, from the members of a group (not part of the reference) ----
+ * A session's error estimate is that of the PRIMAL mean; the image delivered is a reconstruction, whose error is several times
+ * smaller and lies elsewhere on the film. The N members of a GdptProgressiveGroup hold N independent estimates of the same film over
+ * disjoint sample slices; each can be reconstructed on its own, and the spread of those reconstructions measures the error of their
+ * mean. Members i = 1..N with W_i > 0 samples per pixel and reconstructions f_i (W*H*3 doubles), per component:
+ *     W = sum W_i;   fbar = sum W_i f_i / W;   M2 = sum W_i (f_i - fbar)^2;   var = M2 / ((N - 1) W)
+ * computed with West's weighted update in member order (the fold's arithmetic with f_i in the place of a pass). If every f_i has
+ * variance sigma^2 / W_i, var is an unbiased estimate of the variance of fbar; for N = 2 it is (W_a W_b / W^2) (f_a - f_b)^2.
+ * The L2 reconstruction is linear in c, cx, cy: fbar IS the reconstruction of the merged total, up to rounding, and var estimates its
+ * variance. L1 and the variance-weighted kinds are NOT linear: var then measures the spread of the members' reconstructions, not
+ * the bias they share (every member reconstructs fewer samples than the total and is biased alike), and the total's reconstruction
+ * is not fbar. The error estimate of the reconstruction is
+ *     sqrt( sum var / sum f_tot^2 )   over pixels and channels,
+ * f_tot the reconstruction of the total (the image delivered). A pixel is left out of both sums, and counted, if any member's triple,
+ * the f_tot triple or the resulting var triple is not finite (the session's convention). The error map is var summed over the three
+ * channels, per pixel (W*H doubles); with radius r >= 1 its mean over the (2r+1)^2 window clipped to the film, taken over the finite
+ * entries alone (NaN where the window holds none). At N = 2 the raw map has one degree of freedom per pixel: use a window.
+ * The sums are reduced in a fixed order: the same call gives the same bits. */
+typedef struct GdptReconSpreadStats {
+    int32_t members;           /* N */
+    int32_t radius;            /* of the map's window */
+    double error_estimate;     /* sqrt(sum_var / sum_sq) */
+    double sum_var;
+    double sum_sq;             /* sum f_tot^2 */
+    uint64_t pixels_left_out;
+    double spread_ms;          /* device time of the spread launches (statistic, reduction, window), HIP events */
+} GdptReconSpreadStats;
+/* The statistic alone, on any images: device pointers on the current device. d_images[n], weights[n]; d_total nullable: fbar takes
+ * its place; d_var (W*H*3) and d_map (W*H) nullable. Refused: n < 2 or n > GDPT_MULTI_MAX_DEVICES, a non-positive or non-finite
+ * weight, radius outside [0, 8], width or height < 1, an output that aliases an input (or the other output), NULL images.
+ * Waits for `stream`; scratch per (device, stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_recon_spread_device(int width, int height, int n, const double *const *d_images, const double *weights,
+                             const double *d_total /* nullable */, int radius, double *d_var /* nullable */, double *d_map /* nullable */,
+                             void *stream, GdptReconSpreadStats *stats /* nullable */);
+/* Host pointers. */
+int gdpt_recon_spread(int width, int height, int n, const double *const *images, const double *weights, const double *total /* nullable */,
+                      int radius, double *var /* nullable */, double *map /* nullable */, GdptReconSpreadStats *stats /* nullable */);
+
+typedef struct GdptGroupReconParams {
+    double dataCost;
+    int32_t weighted;          /* 0: gdpt_progressive_reconstruct with `recon`; 1: gdpt_progressive_reconstruct_weighted with `wrecon` */
+    int32_t map_radius;        /* 0..8 */
+    GdptReconParams recon;
+    GdptWeightedReconParams wrecon;
+} GdptGroupReconParams;
+/* The group's image with its error: rebuilds the total if it is stale; reconstructs every member that holds samples, one host thread
+ * per member, each on its own device and stream (errors are reported after all threads have been joined); copies the images of
+ * members on another device into staging on devices[0] (hipMemcpyPeerAsync on the total's stream; allocated on first use; NOT YET RUN
+ * BETWEEN TWO DEVICES); reconstructs the total; runs the statistic above on the total's stream.
+ * out_image: the total's reconstruction, bit for bit what gdpt_progressive_reconstruct[_weighted] on the total returns. out_map
+ * (W*H) and out_var (W*H*3) nullable; host memory, or device memory on devices[0] with on_device != 0. recon_stats: the total's
+ * (GdptReconStats; for weighted != 0 the `recon` part of its GdptWeightedReconStats). Refused: fewer than two members that hold
+ * samples; for the weighted kinds a member used with fewer than 2 passes (the message names it); a Path group. Blocking. */
+int gdpt_progressive_group_reconstruct_error(GdptProgressiveGroup *group, const GdptGroupReconParams *params, int on_device,
+                                             double *out_image, double *out_map /* nullable */, double *out_var /* nullable */,
+                                             GdptReconSpreadStats *spread_stats /* nullable */, GdptReconStats *recon_stats /* nullable */);
+/* gdpt_progressive_group_run with the estimate above as the target: evaluated after every check_every-th round of this call
+ * (<= 0: 1) from the round after which two members hold samples, and once before returning (spread_stats, nullable: that last one's;
+ * zeroed if it could not be evaluated). Stops with GDPT_STOP_TARGET when the estimate is <= target_recon_error (<= 0: no target),
+ * else as gdpt_progressive_group_run. status: the total's (its error_estimate stays the primal's). */
+int gdpt_progressive_group_run_recon(GdptProgressiveGroup *group, double target_recon_error, int pass_spp, int max_rounds, int check_every,
+                                     const GdptGroupReconParams *params, GdptProgressiveStatus *status,
+                                     GdptReconSpreadStats *spread_stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
