@@ -385,8 +385,12 @@ void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
     if (!light_power.empty()) table_1d(light_power, light_pmf, light_cdf);
     v.light_pmf = upload(sc, light_pmf); v.light_cdf = upload(sc, light_cdf);
 
-    sc->d_counters.alloc(1, "hipMalloc(counters)");
-    sc->d_queue.alloc(1, "hipMalloc(queue)");
+    sc->scratch[0].counters.alloc(1, "hipMalloc(counters)");
+    sc->scratch[0].queue.alloc(1, "hipMalloc(queue)");
+    sc->d_counters = sc->scratch[0].counters;
+    for (auto &st : sc->render_stream) st.create();
+    for (auto &ss : sc->scratch) { ss.rendered.create(hipEventDisableTiming); ss.released.create(hipEventDisableTiming); }
+    for (auto &e : sc->ev_entry) e.create(hipEventDisableTiming);
     { hipDeviceProp_t prop; ck(hipGetDeviceProperties(&prop, device), "hipGetDeviceProperties"); sc->num_cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256; }
     sc->h_counters.alloc(1, "hipHostMalloc(counters)");
     sc->ev0.create();
@@ -441,10 +445,81 @@ Band resolve_spp(const GdptScene *sc, const GdptRenderParams *p, int scene_spp, 
     return b;
 }
 
+// The scratch set a launch was given, and whether an event of the handle's may follow it on the caller's stream.
+struct ScratchClaim { GdptLaunchScratch *set = nullptr; bool record_release = true; };
+
+// True while `stream` records a graph (or cannot tell: the null stream beside a capture elsewhere).
+bool is_capturing(hipStream_t stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(stream, &st) != hipSuccess) { (void)hipGetLastError(); return true; }
+    return st != hipStreamCaptureStatusNone;
+}
+
+// Host wait for everything that uses the handle's launch scratch: the render streams, and on the callers' streams the last user of
+// each set. For the rare places that cannot be ordered by an event (a buffer about to be freed; a launch recorded into a graph).
+void join_scratch(GdptScene *sc) {
+    sc->join();
+    for (auto &ss : sc->scratch) if (ss.used) ck(hipEventSynchronize(ss.released), "hipEventSynchronize(launch scratch)");
+}
+
+// The scratch set of the next launch on `stream`, with partials for `need` doubles, and the dependencies of that launch enqueued
+// (scene_internal.h: GdptLaunchScratch). In-stream: set 0, everything on the caller's stream as if the handle had no other. Overlapped:
+// sets and render streams alternate; the render stream waits for the reduction that last read the set (two frames back) and for the
+// caller's stream AS IT WAS AT THE PREVIOUS CALL: behind frame k - 1's kernel the stream then holds frame k - 2's reduction and what the
+// caller enqueued after it (its solve), so frame k's kernel starts beside frame k - 1's drain but not before frame k - 2 is through.
+// Waiting for the stream as it is at this call would put frame k - 1's solve in front of the kernel, and nothing would overlap; not
+// waiting at all lets a third kernel queue up while the small kernels of two frames (whose GEMMs need LDS the resident render blocks
+// hold) starve behind it: profiles/render_overlap_times.txt has both schemes, measured. Where the handle says so (need_fence) both render streams wait
+// for the caller's stream as it is now.
+GdptLaunchScratch &claim_scratch(GdptScene *sc, bool overlap, bool capturing, size_t need, hipStream_t stream) {
+    const int k = overlap ? (int)(sc->overlapped & 1) : 0;
+    GdptLaunchScratch &ss = sc->scratch[k];
+    const hipEvent_t entry = sc->ev_entry[sc->calls & 1], prev_entry = sc->calls ? (hipEvent_t)sc->ev_entry[(sc->calls + 1) & 1] : nullptr;
+    if (!capturing) { ck(hipEventRecord(entry, stream), "hipEventRecord(entry)"); sc->calls++; }
+    if (capturing) {
+        // the launch is recorded on today's path, with no event of ours in the graph: whatever is in flight ends first
+        hipStreamCaptureMode mode = hipStreamCaptureModeRelaxed;
+        ck(hipThreadExchangeStreamCaptureMode(&mode), "hipThreadExchangeStreamCaptureMode");
+        try { join_scratch(sc); } catch (...) { (void)hipThreadExchangeStreamCaptureMode(&mode); throw; }
+        ck(hipThreadExchangeStreamCaptureMode(&mode), "hipThreadExchangeStreamCaptureMode");
+    }
+    if (!ss.counters) ss.counters.alloc(1, "hipMalloc(counters)");
+    if (!ss.queue) ss.queue.alloc(1, "hipMalloc(queue)");
+    if (need > ss.partials.size()) {       // never free what a launch in flight uses
+        if (ss.partials) {                 // (a set's first buffer replaces nothing: no join, no fence)
+            if (!capturing) join_scratch(sc);
+            sc->need_fence = true;
+        }
+        ss.partials.alloc(need, "hipMalloc(work-item partials)");
+    }
+    if (!overlap) {
+        if (!capturing) {
+            sc->join();                    // the launch, and a host read of the counters behind it, have the handle to themselves
+            if (ss.used) ck(hipStreamWaitEvent(stream, ss.released, 0), "hipStreamWaitEvent(launch scratch)");   // (another caller's stream)
+        }
+    } else {
+        if (sc->have_caller && stream != sc->last_caller) {      // another caller's stream: it joins the render streams, they join it
+            for (auto &o : sc->scratch) ck(hipStreamWaitEvent(stream, o.rendered, 0), "hipStreamWaitEvent(render stream)");
+            sc->need_fence = true;
+        }
+        if (sc->need_fence || !prev_entry) {
+            for (auto &st : sc->render_stream) ck(hipStreamWaitEvent(st, entry, 0), "hipStreamWaitEvent(fence)");
+            sc->need_fence = false;
+        } else
+            ck(hipStreamWaitEvent(sc->render_stream[k], prev_entry, 0), "hipStreamWaitEvent(previous call)");
+        if (ss.used) ck(hipStreamWaitEvent(sc->render_stream[k], ss.released, 0), "hipStreamWaitEvent(launch scratch)");
+    }
+    sc->have_caller = true; sc->last_caller = stream;
+    return ss;
+}
+
 // Chooses the route of a render of band `b` and fills the launch fields both integrators share; a persistent route gets its
 // work-item plan (made here, once) and a partials buffer that holds it. The knobs are the A/B overrides of the parity tests
 // (include/gdpt_debug.h); every default is the product path.
-gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int take_pct, hipStream_t stream, const GdptRenderStats *stats) {
+// A launch of the one-sided lane machine that the host does not wait for is overlapped: its kernel goes on one of the handle's two
+// render streams and may start while the previous frame's kernel drains and its reduction and solve run (knob no_render_overlap
+// keeps it in-stream). Launches with stats, every other route and a launch recorded into a graph stay on the caller's stream.
+gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int take_pct, hipStream_t stream, const GdptRenderStats *stats, ScratchClaim *claim) {
     auto knob = [](const char *name, int def) { return gdpt::debug_knob_int(name, def); };
     const DevSceneView &v = sc->view;
     gdpt::RouteInputs in{};
@@ -460,11 +535,13 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     gdpt::RenderLaunch rl{};
     rl.route = gdpt::choose_route(in);
     rl.spp = b.spp; rl.stream_spp = b.stream_spp; rl.first_sample = b.first_sample; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
-    rl.counters = sc->d_counters;
     rl.count_traversal = stats && stats->nodes_visited == ~0ull;   // request flag: caller presets nodes_visited = UINT64_MAX
     rl.force_log2k = knob("log2k", -1);
     rl.thresh_a = knob("keep_frac", -1); rl.thresh_c = knob("search_frac", -1);
     rl.num_cus = sc->num_cus; rl.blocks_per_cu = knob("blocks_per_cu", 0);
+    const bool capturing = is_capturing(stream);
+    const bool overlap = !stats && gdpt::can_overlap(rl.route) && !capturing && knob("no_render_overlap", 0) == 0;
+    size_t need = 0;
     if (gdpt::is_persistent(rl.route)) {
         // The plan is made for a band of plan_rows rows (default: the whole film), whatever band is rendered: a pixel's samples
         // are cut (and its partial sums merged) the same way by every render that names the same plan_rows, so a sharded render
@@ -472,23 +549,31 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
         // 512x512x256 film, 1/8 of the work, then held 32 k items of 128 samples and took 9.3 ms instead of 3.8 —
         // profiles/r03_band_costs.txt.)
         rl.plan = gdpt::make_chunk_plan(b.spp, rl.force_log2k, (long long)v.cam.width * b.plan_rows, gdpt::resident_lanes(rl), take_pct);
-        const size_t need = (size_t)16 * (size_t)gdpt::band_slots(v.cam.width, b.row_end - b.row_begin) * (size_t)rl.plan.n;
-        sc->d_partials.grow(need, stream, "hipMalloc(work-item partials)");
-        rl.partials = sc->d_partials; rl.queue_head = sc->d_queue;
+        need = (size_t)16 * (size_t)gdpt::band_slots(v.cam.width, b.row_end - b.row_begin) * (size_t)rl.plan.n;
     }
+    GdptLaunchScratch &ss = claim_scratch(sc, overlap, capturing, need, stream);
+    rl.counters = ss.counters; sc->d_counters = ss.counters;
+    if (gdpt::is_persistent(rl.route)) { rl.partials = ss.partials; rl.queue_head = ss.queue; }
+    if (overlap) { rl.kernel_stream = sc->render_stream[sc->overlapped & 1]; rl.kernel_done = ss.rendered; }
+    claim->set = &ss; claim->record_release = !capturing;
     return rl;
 }
 
 // Enqueues the counter reset, the launch and, when stats are requested, waits for the render and reports it.
-void run_launch(GdptScene *sc, const gdpt::RenderLaunch &rl, const Band &b, hipStream_t stream, GdptRenderStats *stats) {
+void run_launch(GdptScene *sc, const gdpt::RenderLaunch &rl, const ScratchClaim &claim, const Band &b, hipStream_t stream, GdptRenderStats *stats) {
     const bool stamped = gdpt::is_stamped(rl.route);
-    ck(hipMemsetAsync(sc->d_counters, 0, sizeof(gdpt::RenderCounters), stream), "hipMemsetAsync(counters)");
-    if (stamped) ck(hipMemsetAsync(&sc->d_counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), stream), "hipMemsetAsync(stamps)");   // min slots
+    const hipStream_t ks = rl.kernel_stream ? rl.kernel_stream : stream;       // (begin_launch: an overlapped launch)
+    if (rl.kernel_stream) sc->in_flight = true;           // (from here on a render stream may hold work: GdptScene::join)
+    ck(hipMemsetAsync(rl.counters, 0, sizeof(gdpt::RenderCounters), ks), "hipMemsetAsync(counters)");
+    if (stamped) ck(hipMemsetAsync(&rl.counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), ks), "hipMemsetAsync(stamps)");   // min slots
     if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
     gdpt::launch_render(sc->view, rl, stream);
+    if (rl.kernel_stream) sc->overlapped++;               // (a launch that threw leaves the set parity where it was)
+    // the set is free again behind this point of the caller's stream (a launch recorded into a graph leaves no event of ours in it)
+    if (claim.record_release) { ck(hipEventRecord(claim.set->released, stream), "hipEventRecord(launch scratch)"); claim.set->used = true; }
     if (!stats) return;
     ck(hipEventRecord(sc->ev1, stream), "hipEventRecord");
-    ck(hipMemcpyAsync(sc->h_counters, sc->d_counters, sizeof(gdpt::RenderCounters), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(counters)");
+    ck(hipMemcpyAsync(sc->h_counters, rl.counters, sizeof(gdpt::RenderCounters), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(counters)");
     ck(hipStreamSynchronize(stream), "hipStreamSynchronize(render)");
     float ms = 0;
     ck(hipEventElapsedTime(&ms, sc->ev0, sc->ev1), "hipEventElapsedTime");
@@ -517,7 +602,8 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
     ck(hipSetDevice(sc->device), "hipSetDevice");
     const Band b = resolve_spp(sc, params, scene_spp, "gdpt_render", window);
     if (!img || !cx0 || !cy0 || !cx1 || !cy1) throw std::runtime_error("gdpt_render: null output buffer");
-    RenderLaunch rl = begin_launch(sc, b, false, sc->plan_take_pct, stream, stats);
+    ScratchClaim claim;
+    RenderLaunch rl = begin_launch(sc, b, false, sc->plan_take_pct, stream, stats, &claim);
     rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
     rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
     rl.replay_per_step = debug_knob_int("replay_per_step", 0);
@@ -540,7 +626,7 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
         rl.wf_state = sc->d_wf_state; rl.wf_live = sc->d_wf_live; rl.wf_counters = sc->d_wf_counters; rl.wf_host = sc->h_wf_word;
         rl.wf_event = sc->wf_event; rl.wf_slots = slots;       // exactly the slots this band needs (the buffers may be larger)
     }
-    run_launch(sc, rl, b, stream, stats);
+    run_launch(sc, rl, claim, b, stream, stats);
 }
 
 } // namespace gdpt
@@ -555,9 +641,10 @@ void path_render_device_impl(GdptScene *sc, const GdptRenderParams *params, doub
     if (sc->view.num_lights <= 0) throw std::runtime_error("gdpt_path_render: the scene has no emitter to sample");
     const Band b = resolve_spp(sc, params, sc->scene_spp, "gdpt_path_render", window);
     if (!img) throw std::runtime_error("gdpt_path_render: null output buffer");
-    gdpt::RenderLaunch rl = begin_launch(sc, b, true, 0, stream, stats);   // (the plan takes the default share: see make_chunk_plan)
+    ScratchClaim claim;
+    gdpt::RenderLaunch rl = begin_launch(sc, b, true, 0, stream, stats, &claim);   // (the plan takes the default share: see make_chunk_plan)
     rl.img = img;
-    run_launch(sc, rl, b, stream, stats);
+    run_launch(sc, rl, claim, b, stream, stats);
 }
 
 // GdptReconParams -> the L1 solver's parameters, defaults filled in (include/gdpt.h); refuses what the header says is refused
@@ -644,6 +731,7 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
 
 // include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: launch_render)
 const char *gdpt_debug_last_route(void) { return gdpt::last_route(); }
+long long gdpt_debug_overlapped_launches(const GdptScene *scene) { return scene ? (long long)scene->overlapped : -1; }
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
 
 int gdpt_scene_upload(const GdptSceneDesc *desc, int device, GdptScene **out_scene) {

@@ -92,6 +92,20 @@ public:
     void create(unsigned flags = 0) { reset(); ck(hipEventCreateWithFlags(&e_, flags), "hipEventCreate"); }
 };
 
+// A stream a handle owns for work of its own beside the caller's stream. Non-blocking: it takes no implicit order from the null
+// stream, every dependency is an event. Destroyed after a join, on the device that is current.
+class Stream {
+    hipStream_t s_ = nullptr;
+public:
+    Stream() = default;
+    Stream(const Stream &) = delete;
+    Stream &operator=(const Stream &) = delete;
+    ~Stream() { reset(); }
+    operator hipStream_t() const { return s_; }
+    void reset() { if (s_) { (void)hipStreamSynchronize(s_); (void)hipStreamDestroy(s_); } s_ = nullptr; }
+    void create() { reset(); ck(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking), "hipStreamCreate"); }
+};
+
 // What a solver keeps per (device, stream): one T per pair, made on first use. A stream's owner calls forget_stream (below) before it
 // destroys the stream: the key is the handle's value, and a later stream with the same value must not inherit another one's state.
 // An entry is destroyed with its device current. (Space: only the device switch is taken from it.)

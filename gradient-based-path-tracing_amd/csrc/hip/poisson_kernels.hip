@@ -559,6 +559,7 @@ struct DctTables {
     std::mutex mu;
     std::vector<std::unique_ptr<DctPlan>> plans;
     std::vector<std::pair<int, DeviceBuffer<double>>> lap_y;
+    int num_cus = 0;                  // compute units of the device, asked once (0 = not asked yet)
 };
 struct DctWorkspace {
     rocblas_handle handle = nullptr;
@@ -647,7 +648,7 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
         rb(rocblas_set_stream(ws.handle, stream), "rocblas_set_stream");
     }
     const double *Cw, *Ch, *lap_x, *lap_y, *Ew[2], *EhT[2];
-    int ld_ew, ld_eht;
+    int ld_ew, ld_eht, num_cus;
     {
         DctTables &t = device_tables(dev);
         std::lock_guard<std::mutex> lk(t.mu);
@@ -656,6 +657,11 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
         const DctPlan &ph = get_plan(t, h);
         Ch = ph.d_mat; EhT[0] = ph.d_et[0]; EhT[1] = ph.d_et[1]; ld_eht = ph.ld_et;
         lap_y = get_lap_y(t, h);
+        if (t.num_cus == 0) {                                    // (not per solve: the query costs more than a launch)
+            hipDeviceProp_t prop;
+            t.num_cus = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
+        }
+        num_cus = t.num_cus;
     }
     gp::Geo g{w, h, w * h * 3, w * 3};
     const size_t plane = (size_t)w * h;
@@ -696,8 +702,6 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
         const int qw = (w + 1) / 2, qh = (h + 1) / 2;           // outputs of the even parity along the folded dimension
         const dim3 block(gp::kGemmThreads);
         const long long pl = (long long)plane;
-        int num_cus = 256;
-        { hipDeviceProp_t prop; if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) num_cus = prop.multiProcessorCount; }
         // The shape follows the grid (dct_fold_gemm_f64): with 64-row tiles, at most one block per CU -> 32-row tiles (twice the
         // blocks, two of them resident per CU) with deep prefetch; at most two per CU -> 64 rows, deep prefetch; more -> 64 rows, the
         // small-footprint shape. Test knobs dct_bk / dct_bm force a shape.

@@ -41,6 +41,9 @@ inline bool is_persistent(Route r) { return r <= Route::WAVEFRONT_GENERAL || r >
 inline bool is_wavefront(Route r) { return r == Route::WAVEFRONT_LAMBERT || r == Route::WAVEFRONT_GENERAL; }
 inline bool needs_bounce_log(Route r) { return r >= Route::TWOSIDED_LDS && r <= Route::TWOSIDED_HBM_GLASS; }
 inline bool is_stamped(Route r) { return r >= Route::LAMBERT_STAMPED_LDS_PLAIN && r <= Route::LAMBERT_STAMPED_HBM; }
+// the one-sided lane machine (gdpt_render_phases) in its product builds: its launch touches nothing but the scene, its partials,
+// queue head and counters, so it may run beside the previous frame's tail (capi_device.hip: begin_launch)
+inline bool can_overlap(Route r) { return r <= Route::GENERAL_HBM && !is_stamped(r); }
 // the only kernels that walk the LDS copy in its BVH2 form; every other route walks a BVH4 (or the HBM tree)
 inline bool walks_bvh2(Route r) { return r == Route::LAMBERT_LDS_BVH2 || r == Route::GENERAL_LDS_BVH2; }
 
@@ -93,6 +96,10 @@ struct RenderLaunch {
     int replay_per_step;           // two-sided lane machine (render_twosided.h), 0 = default
     double *partials;              // device, >= 16 doubles per work item (partial sums)
     unsigned long long *queue_head;// device, work-queue head
+    // overlapped launch (can_overlap routes only; nullptr = everything on the caller's stream): the queue reset and the render kernel
+    // go on kernel_stream, kernel_done is recorded behind them and the caller's stream waits for it before gdpt_reduce_partials
+    hipStream_t kernel_stream;
+    hipEvent_t kernel_done;
 };
 bool scene_fits_lds(int num_nodes, int num_prims, int num_tris, int num_materials, int num_lights, int bvh_depth);
 bool scene_fits_lds_wide(int num_nodes4, int num_prims, int num_tris, int num_materials, int num_lights, int wide_stack_need);

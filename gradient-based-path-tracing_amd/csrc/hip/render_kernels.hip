@@ -203,6 +203,9 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
 
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream) {
     const Route r = rl.route;
+    // an overlapped launch (rl.kernel_stream): queue reset and render kernel on that stream; what writes the images stays on `stream`
+    if (rl.kernel_stream && (!can_overlap(r) || !rl.kernel_done)) throw std::runtime_error("launch_render: this route does not overlap");
+    const hipStream_t ks = rl.kernel_stream ? rl.kernel_stream : stream;
     gd::KernelArgs a{};
     a.spp = rl.spp; a.stream_spp = rl.stream_spp; a.first_sample = rl.first_sample; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
     a.img = rl.img; a.cx0 = rl.cx0; a.cy0 = rl.cy0; a.cx1 = rl.cx1; a.cy1 = rl.cy1; a.counters = rl.counters;
@@ -221,30 +224,30 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
         a.stack_levels = rl.wide_stack_need > 0 ? rl.wide_stack_need : GDPT_BVH_MAX_DEPTH;
         a.replay_per_step = rl.replay_per_step >= 1 ? rl.replay_per_step : 4;       // render_twosided.h: kReplayPerStep
         if (a.stack_levels > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("launch_render: traversal stack bound exceeds the builder's maximum");
-        grid = start_queue(a, rl, W, stream);
+        grid = start_queue(a, rl, W, ks);
     }
     if (needs_bounce_log(r) && (!rl.bounce_log || rl.bounce_log_bytes < twosided_log_bytes(grid.x))) throw std::runtime_error("launch_render: bounce log missing");
     if (is_wavefront(r) && (!rl.wf_state || !rl.wf_live || !rl.wf_counters || !rl.wf_host || !rl.wf_aux || rl.wf_slots <= 0))
         throw std::runtime_error("launch_render: wavefront buffers missing");
     set_route(r);
     switch (r) {
-    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, stream); break;
-    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, stream); break;
-    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, stream); break;
-    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, stream); break;
-    case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, stream); break;
-    case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, stream); break;
-    case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, stream); break;
+    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, ks); break;
+    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, ks); break;
+    case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, ks); break;
+    case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, ks); break;
+    case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, ks); break;
     case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, stream); break;
     case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, stream); break;
     case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, stream); break;
-    case Route::GENERAL_SET_A_DISNEY_DIFFUSE: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_DIFFUSE, stream); break;
-    case Route::GENERAL_SET_A_DISNEY_METAL: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_METAL, stream); break;
-    case Route::GENERAL_SET_B_DISNEY_CLEARCOAT: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_CLEARCOAT, stream); break;
-    case Route::GENERAL_SET_B_DISNEY_SHEEN: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_SHEEN, stream); break;
-    case Route::GENERAL_LDS_WIDE: launch_phases_general(sv, a, grid, true, true, stream); break;
-    case Route::GENERAL_LDS_BVH2: launch_phases_general(sv, a, grid, true, false, stream); break;
-    case Route::GENERAL_HBM: launch_phases_general(sv, a, grid, false, false, stream); break;
+    case Route::GENERAL_SET_A_DISNEY_DIFFUSE: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_DIFFUSE, ks); break;
+    case Route::GENERAL_SET_A_DISNEY_METAL: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_METAL, ks); break;
+    case Route::GENERAL_SET_B_DISNEY_CLEARCOAT: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_CLEARCOAT, ks); break;
+    case Route::GENERAL_SET_B_DISNEY_SHEEN: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_SHEEN, ks); break;
+    case Route::GENERAL_LDS_WIDE: launch_phases_general(sv, a, grid, true, true, ks); break;
+    case Route::GENERAL_LDS_BVH2: launch_phases_general(sv, a, grid, true, false, ks); break;
+    case Route::GENERAL_HBM: launch_phases_general(sv, a, grid, false, false, ks); break;
     case Route::TWOSIDED_LDS: launch_phases_twosided(sv, a, grid, true, rl.bounce_log, stream); break;
     case Route::TWOSIDED_HBM: launch_phases_twosided(sv, a, grid, false, rl.bounce_log, stream); break;
     case Route::TWOSIDED_HBM_GLASS: launch_phases_twosided_glass(sv, a, grid, rl.bounce_log, stream); break;
@@ -269,6 +272,10 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
     case Route::PATH_PERSISTENT_HBM_GENERAL: launch_path_persistent(sv, a, grid, false, false, false, false, stream); break;
     case Route::PATH_PERSISTENT_HBM_GENERAL_ENV: launch_path_persistent(sv, a, grid, false, false, true, false, stream); break;
     case Route::COUNT: throw std::runtime_error("launch_render: no route");
+    }
+    if (rl.kernel_stream) {
+        if (hipEventRecord(rl.kernel_done, ks) != hipSuccess || hipStreamWaitEvent(stream, rl.kernel_done, 0) != hipSuccess)
+            throw std::runtime_error("launch_render: joining the render stream failed");
     }
     if (is_persistent(r) && !is_path(r)) launch_reduce_partials(sv, a, stream);
     hipError_t e = hipGetLastError();

@@ -12,6 +12,17 @@
 #include <string>
 #include <vector>
 
+// What one launch of a persistent render kernel owns while it is in flight. A handle has two (GdptScene::scratch): consecutive
+// overlapped launches alternate between them, so frame k + 1's kernel can run while frame k's partials wait to be reduced.
+struct GdptLaunchScratch {
+    gdpt::DeviceBuffer<double> partials;              // work-item partial sums of the persistent render kernel
+    gdpt::DeviceBuffer<unsigned long long> queue;     // work-queue head
+    gdpt::DeviceBuffer<gdpt::RenderCounters> counters;
+    gdpt::Event rendered;    // behind the render kernel, on the set's render stream
+    gdpt::Event released;    // behind the last reader or writer of the set on a caller's stream (gdpt_reduce_partials; an in-stream launch)
+    bool used = false;       // `released` has been recorded
+};
+
 struct GdptScene {
     int device = 0;
     DevSceneView view{};
@@ -27,11 +38,21 @@ struct GdptScene {
     std::vector<gdpt::DeviceBuffer<unsigned char>> allocations;   // the uploaded scene tables `view` points into
     // cached output/work buffers for the host-pointer entry points
     gdpt::DeviceBuffer<double> d_buf[9];
-    gdpt::DeviceBuffer<gdpt::RenderCounters> d_counters;
+    gdpt::RenderCounters *d_counters = nullptr;       // the counters block of the last launch (scratch[k].counters)
     gdpt::PinnedBuffer<gdpt::RenderCounters> h_counters;
     gdpt::DeviceBuffer<unsigned char> d_bounce_log;   // per-lane bounce log of the two-sided lane machine
-    gdpt::DeviceBuffer<double> d_partials;            // work-item partial sums of the persistent render kernel
-    gdpt::DeviceBuffer<unsigned long long> d_queue;
+    // Launch scratch and render streams (capi_device.hip: begin_launch). An in-stream launch runs wholly on the caller's stream with
+    // scratch[0]. An overlapped launch k runs its queue reset and render kernel on render_stream[k % 2] with scratch[k % 2]; only
+    // gdpt_reduce_partials, which writes the images, stays on the caller's stream. scratch[1] is allocated by the second such launch.
+    GdptLaunchScratch scratch[2];
+    gdpt::Stream render_stream[2];
+    gdpt::Event ev_entry[2];              // recorded on the caller's stream at the start of every launch call, alternating
+    unsigned long long calls = 0;         // launch calls so far
+    unsigned long long overlapped = 0;    // overlapped launches so far
+    bool in_flight = false;               // a render stream may hold work the host has not waited for
+    bool need_fence = true;               // the next overlapped launch makes both render streams wait for the caller's stream as it is at that call
+    bool have_caller = false;
+    hipStream_t last_caller = nullptr;    // the caller's stream of the last launch
     // wavefront pipeline (render_wavefront.h): path state, live list (one entry per slot), generation counters
     gdpt::DeviceBuffer<unsigned long long> d_wf_state;
     gdpt::DeviceBuffer<unsigned> d_wf_live, d_wf_counters;
@@ -45,7 +66,17 @@ struct GdptScene {
     void ensure_buffers(size_t elems) {
         for (auto &b : d_buf) b.grow(elems, "hipMalloc(image buffers)");
     }
-    ~GdptScene() { hipSetDevice(device); }      // the members free themselves on it
+    // Waits on the host for everything the render streams hold. (What a caller's stream still holds is that caller's, as before.)
+    void join() {
+        if (!in_flight) return;
+        for (auto &st : render_stream) if (st) gdpt::ck(hipStreamSynchronize(st), "hipStreamSynchronize(render stream)");
+        in_flight = false;
+    }
+    ~GdptScene() {                              // the members free themselves on the device: streams join and go before the buffers
+        hipSetDevice(device);
+        for (auto &st : render_stream) st.reset();
+        for (auto &ss : scratch) if (ss.used) (void)hipEventSynchronize(ss.released);      // a caller's stream may still reduce from the set
+    }
 };
 
 

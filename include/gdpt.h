@@ -228,10 +228,19 @@ int gdpt_render(GdptScene *scene, const GdptRenderParams *params,
 /* ---- hot path, device buffers (hipMalloc'd / torch CUDA tensors; data stays in HBM) ----
  * `stream` is a hipStream_t passed as void* (NULL = default stream). Asynchronous w.r.t. the host
  * unless `stats` is non-NULL (then it synchronises to read the counters).
- * A GdptScene owns ONE set of launch scratch (work queue, per-item partial sums, counters, bounce log): at most one
- * render of a given scene handle may be in flight at a time. Renders issued on the same stream are ordered by it;
- * to overlap renders on different streams (or devices) upload one scene handle per stream — the scene tables are
- * a few MB. The reference's render() is likewise called once, synchronously (src/main.cpp:40). */
+ * Calls on one scene handle come from one host thread at a time. The output buffers are written only by work on `stream`,
+ * in call order, so consecutive renders on one stream behave as ordered by it. Internally an enqueue-only render
+ * (stats == NULL) of a scene with one-sided lobes runs its render kernel on one of two streams the handle owns, with one
+ * of two sets of launch scratch (work queue, per-item partial sums, counters; the second set, the size of the first, is
+ * allocated by the second such call): the previous frame's reduction and whatever the caller enqueued behind it (its solve)
+ * then run while this frame's kernel drains, where most of the chip would idle. The kernel reads only the scene, so it does
+ * not wait for the caller's stream as it is at this call, only as it was at the previous one; what it needs beyond that
+ * (scratch reuse two frames apart, another caller stream, growth) is ordered by events. Every other render (stats requested, two-sided or rough lobes, GDPT_RNG_TILE, GDPT_SHIFT_RECONNECT,
+ * Integrator::Path, a stream that is being captured into a graph) runs wholly on `stream` after waiting for the handle's
+ * own streams. A captured launch uses the first scratch set and leaves no event of the handle's in the graph: replays of such a
+ * graph must not be mixed with direct enqueue-only renders of the same handle unless the caller orders them (a device or stream
+ * synchronise between the two kinds). gdpt_scene_free waits for what the handle has in flight. To render on several devices upload one scene
+ * handle per device. The reference's render() is called once, synchronously (src/main.cpp:40). */
 int gdpt_render_device(GdptScene *scene, const GdptRenderParams *params,
                        double *d_img, double *d_cx0, double *d_cy0, double *d_cx1, double *d_cy1,
                        void *stream, GdptRenderStats *stats /* nullable */);

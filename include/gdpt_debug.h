@@ -35,6 +35,7 @@
  *   dct_bk (16 / 32), dct_bm (32 / 64)   GDPT_SOLVER_DCT_MFMA: force a shape of the folded GEMM (default: by grid size)
  *   replay_per_step (n >= 1)    two-sided lane machine: replay iterations of an offset per wave step (default 4; 1 = one per step)
  *   no_plain_kernel (0/1)       one-sided lane machine: the kernel with sphere and texture code even for a triangles-only, constant-texture scene
+ *   no_render_overlap (0/1)     one-sided lane machine: every launch wholly on the caller's stream, none on the handle's render streams
  *   full_material_switch (0/1)  lane machines: the kernel with the full material switch even when the scene fits a small set
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
@@ -80,6 +81,10 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
 /* Route of the last gdpt_render / gdpt_path_render (and their _device forms) made by the CALLING thread: one of the
  * names above, "" before the first one (or after a render that failed before its launch). The string is static. */
 const char *gdpt_debug_last_route(void);
+/* Renders of this handle so far whose kernel went on one of the handle's own render streams (include/gdpt.h: gdpt_render_device);
+ * -1 for a null handle. Lets a test see that the overlapped path was taken. */
+struct GdptScene;
+long long gdpt_debug_overlapped_launches(const struct GdptScene *scene);
 /* Every name gdpt_debug_last_route can return: fills out[0..n) and returns n, or -1 if `capacity` < n; out == NULL
  * returns n alone. */
 int gdpt_debug_route_names(const char **out, int capacity);
