@@ -129,6 +129,7 @@ def lib():
         L.gdpt_debug_last_route.restype = C.c_char_p
         L.gdpt_debug_overlapped_launches.argtypes = [vp]
         L.gdpt_debug_overlapped_launches.restype = C.c_longlong
+        L.gdpt_debug_leaf_histogram.argtypes = [vp, C.POINTER(C.c_int32)]
         L.gdpt_debug_route_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
         _LIB = L
     return _LIB
@@ -282,6 +283,12 @@ class Scene:
         buf = (C.c_double * T)()
         _check(lib().gdpt_tile_row_costs(self.handle, int(spp), buf, T))
         return [float(x) for x in buf]
+
+    def leaf_histogram(self):
+        """Leaves of the uploaded tree by size: [leaves of 1, 2, 3, 4 primitive records] (include/gdpt_debug.h)."""
+        h = (C.c_int32 * 4)()
+        _check(lib().gdpt_debug_leaf_histogram(self.handle, h))
+        return list(h)
 
     def overlapped_launches(self):
         """Renders so far whose kernel ran on one of the handle's own render streams (include/gdpt_debug.h)."""
@@ -890,7 +897,7 @@ class debug_knobs:
         """GDPT_FORCE_EAGER=1 -> force_eager=1 ... for the manual sweep scripts (tests/sweep_*.py, tune_render.py)."""
         environ = os.environ if environ is None else environ
         names = ("force_eager", "log2k", "keep_frac", "search_frac", "blocks_per_cu", "no_lds_scene", "lds_wide",
-                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap")
+                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips")
         lib().gdpt_debug_knobs_reset()
         for n in names:
             v = environ.get("GDPT_" + n.upper())

@@ -71,6 +71,13 @@ struct DevBvh4QNode {
 #ifndef GDPT_HBM_Q4
 #define GDPT_HBM_Q4 1              // scenes walked from HBM use DevBvh4QNode (0: the fp32 DevBvh4Node, A/B builds)
 #endif
+#ifndef GDPT_LDS_LEAF_K
+#define GDPT_LDS_LEAF_K 2          // one-sided lane machine on an LDS-resident scene: primitive records tested per leaf trip, the cursor kept
+#endif                             // in the leaf reference (leaf_cursor.h); 0: whole leaves, four tests in a row (A/B builds: 0, 1, 2)
+#ifndef GDPT_LDS_LEAF_FLAT
+#define GDPT_LDS_LEAF_FLAT 1       // ... with the branch-free triangle test (0: tri_hit's early-outs; A/B builds)
+#endif                             // cbox, same-box A/B against whole leaves: K = 2 branch-free -4.3 %, K = 2 branching -2.6 %, K = 1
+                                   // branch-free 0, K = 1 branching +3 % (profiles/leaf_cursor_times.txt)
 
 // Traversal record of one primitive, 48 B, in BVH leaf order.
 // Triangle: v0, e1 = fl(v1-v0), e2 = fl(v2-v0) in fp32; gid = global triangle id (index into DevTriShade).

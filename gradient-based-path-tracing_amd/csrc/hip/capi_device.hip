@@ -173,6 +173,8 @@ void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
     std::vector<DevPrim> prims(bvh.order.size());
     for (size_t i = 0; i < bvh.order.size(); i++) prims[i] = prim_in[ref_prim[bvh.order[i]]];
     sc->bvh_depth = bvh.depth;
+    for (const DevBvhNode &n : bvh.nodes)
+        for (int32_t ch : {n.left, n.right}) if (ch < 0 && ch != GDPT_CHILD_EMPTY) sc->leaf_hist[~(unsigned)ch & 3u]++;
     if (bvh.depth > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("gdpt_scene_upload: BVH deeper than the traversal stack (builder bug)");
 
     // ---- textures: fp64 mip chains exactly as make_mipmap builds them (src/mipmap.h:27-48) ----
@@ -531,9 +533,10 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     in.force_eager = knob("force_eager", 0) != 0; in.no_lds_scene = knob("no_lds_scene", 0) != 0; in.lds_wide = knob("lds_wide", 1) != 0;
     in.no_twosided_machine = knob("no_twosided_machine", 0) != 0; in.wavefront = knob("wavefront", kWavefrontDefault) != 0;
     in.stamps = knob("stamps", 0) != 0; in.no_plain_kernel = knob("no_plain_kernel", 0) != 0;
-    in.full_material_switch = knob("full_material_switch", 0) != 0;
+    in.full_material_switch = knob("full_material_switch", 0) != 0; in.whole_leaf_trips = knob("whole_leaf_trips", 0) != 0;
     gdpt::RenderLaunch rl{};
     rl.route = gdpt::choose_route(in);
+    rl.whole_leaf_trips = in.whole_leaf_trips;
     rl.spp = b.spp; rl.stream_spp = b.stream_spp; rl.first_sample = b.first_sample; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
     rl.count_traversal = stats && stats->nodes_visited == ~0ull;   // request flag: caller presets nodes_visited = UINT64_MAX
     rl.force_log2k = knob("log2k", -1);
@@ -732,6 +735,12 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
 // include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: launch_render)
 const char *gdpt_debug_last_route(void) { return gdpt::last_route(); }
 long long gdpt_debug_overlapped_launches(const GdptScene *scene) { return scene ? (long long)scene->overlapped : -1; }
+int gdpt_debug_leaf_histogram(const GdptScene *scene, int32_t hist[4]) {
+    return gdpt::guarded([&]() {
+        if (!scene || !hist) throw std::runtime_error("gdpt_debug_leaf_histogram: null argument");
+        for (int i = 0; i < 4; i++) hist[i] = scene->leaf_hist[i];
+    });
+}
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
 
 int gdpt_scene_upload(const GdptSceneDesc *desc, int device, GdptScene **out_scene) {

@@ -33,6 +33,7 @@
 #pragma once
 #include "render_kernels.h"
 #include "device_trace.h"
+#include "../leaf_cursor.h"
 
 namespace gd {
 
@@ -352,6 +353,36 @@ GD void test_leaf(const DevSceneView &sv, const TraceCtx &tx, int cur, const flo
     }
 }
 
+// The same leaf taken K records per step (K = 1, 2), the cursor kept in the leaf reference itself (leaf_cursor.h): a step fetches and
+// tests records first .. first + K - 1 (indices clamped to the leaf) and turns `cur` into the leaf of the records that remain;
+// it returns true when none remain and the caller pops. A lane that holds a partly consumed leaf is simply a lane that holds a leaf:
+// it is not searching in the while-while node loop, the walk's resumable state stays (cur, sp, best), and trace_pending may leave
+// with such a lane unfinished. The records are tested in the order test_leaf tests them and no node is visited in between, so
+// `best` goes through the same values: same hit, same nodes visited, same records tested, bit for bit.
+// Termination: the step lowers the count in THIS lane's `cur` by K (leaf_advance; checked exhaustively on the host by
+// tests/leaf_cursor_check.cpp) and reads nothing of any other lane, and every trip of trav_run's outer loop that a lane enters with a
+// leaf runs one step for it — the node loop in front of it does not wait for lanes that hold leaves. A lane therefore leaves a
+// leaf of `count` records after ceil(count / K) <= count of the trips it takes part in, whatever the other lanes do.
+// FLAT: the branch-free triangle test (a lone triangle per lane gains little from tri_hit's early-outs).
+template <int K, bool FLAT, bool SPHERES = true>
+GD bool leaf_step(const DevSceneView &sv, const TraceCtx &tx, int &cur, const float o[3], const float d[3], float tnear, float tfar,
+                  Hit &best, TraceCounters &tc) {
+    static_assert(K == 1 || K == 2, "leaf_step: one or two records per step");
+    const unsigned packed = ~(unsigned)cur;
+    const unsigned first = packed >> 2, last = packed & 3u;      // last = count - 1
+    const DevPrim p0 = tx.prims[first];
+    const DevPrim p1 = tx.prims[first + (K > 1 ? min(1u, last) : 0u)];      // (K = 1: p0 again, folded away)
+    if (tx.count) { tc.prims += leaf_step_records(cur, K); if (wave_leader()) tc.leaf_trips++; }
+    if (!FLAT || (SPHERES && ((p0.gid | p1.gid) & GDPT_SPHERE_FLAG))) {
+        test_prim<SPHERES>(sv, p0, o, d, tnear, tfar, best);
+        if (K > 1 && last >= 1u) test_prim<SPHERES>(sv, p1, o, d, tnear, tfar, best);
+    } else {
+        test_tri_flat(p0, o, d, tnear, tfar, true, best);
+        if (K > 1) test_tri_flat(p1, o, d, tnear, tfar, last >= 1u, best);
+    }
+    return !leaf_advance(cur, K);
+}
+
 // Resumable closest-hit traversal (definition of "closest": device_trace.h). The walk's whole state is (cur, sp, best)
 // plus the lane's stack column in LDS, so a wave can leave the loop while some rays are unfinished, shade and re-arm the
 // lanes that are done, and come back: `stop_below` = number of unfinished rays at or below which the loop is left
@@ -441,7 +472,12 @@ GD void trav_node(const TraceCtx &tx, const float oi[3], const float inv[3], flo
 }
 // Compile-time traversal configuration of a kernel: loop order, tree form, leaf test style.
 // SPEC (while-while order only): a lane that reaches a leaf sets it aside and goes on looking for its next one.
-template <bool WW_, bool WIDE_, bool FLAT_, bool SPHERES_ = true, bool SPEC_ = false> struct TraceCfg { static constexpr bool WW = WW_, WIDE = WIDE_, FLAT = FLAT_, SPHERES = SPHERES_, SPEC = SPEC_ || GDPT_SPEC_LEAF; };
+// LEAF_K: 0 = a leaf trip tests the whole leaf (test_leaf), 1 / 2 = that many records per trip (leaf_step).
+template <bool WW_, bool WIDE_, bool FLAT_, bool SPHERES_ = true, bool SPEC_ = false, int LEAF_K_ = 0> struct TraceCfg {
+    static constexpr bool WW = WW_, WIDE = WIDE_, FLAT = FLAT_, SPHERES = SPHERES_, SPEC = SPEC_ || GDPT_SPEC_LEAF;
+    static constexpr int LEAF_K = LEAF_K_;
+    static constexpr bool LEAF_FLAT = FLAT_ || GDPT_LDS_LEAF_FLAT;      // test style of leaf_step; read nowhere else, so without meaning when LEAF_K == 0 (test_leaf goes by FLAT)
+};
 using TraceHbm = TraceCfg<true, true, true>;       // scenes walked from HBM
 
 // Called by the lanes whose ray is unfinished (tv.cur != kTravDone); the others of the wave sit it out.
@@ -468,6 +504,9 @@ GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, flo
             // (waiting for the last lane costs ~ln(64) mean search lengths); those lanes sit out the leaf tests.
             const int few = (live * search_frac) >> 8;
             if (TC::SPEC) {
+                // (A leaf set aside is taken whole: a shortened leaf would have to go back on the stack beside what the lane found
+                // meanwhile, one slot more than the tree's stack bound allows for. The cursor is for the plain orders below.)
+                static_assert(!(TC::SPEC && TC::LEAF_K > 0), "the speculative leaf hold takes whole leaves");
                 // A lane that reaches a leaf sets it aside and goes on looking for its next one while the others are still
                 // searching (the nodes it visits meanwhile are tested against the hit distance it had before the leaf: a
                 // few more visits, never a different hit); the leaf set aside is intersected when the node loop is left, so
@@ -498,8 +537,12 @@ GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, flo
                     }
                 }
                 if (cur < 0 && cur != kTravDone) {
-                    test_leaf<TC::FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc);
-                    trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+                    if constexpr (TC::LEAF_K > 0) {
+                        if (leaf_step<TC::LEAF_K, TC::LEAF_FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc)) trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+                    } else {
+                        test_leaf<TC::FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc);
+                        trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+                    }
                     if (any_hit && best.gid >= 0) cur = kTravDone;
                 }
             }
@@ -507,8 +550,12 @@ GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, flo
             if (tx.count) { tc.nodes++; if (wave_leader()) tc.node_trips++; }
             trav_node<TC::WIDE, TC::FLAT>(tx, oi, inv, tnear, best.t, cur, sp, tv.ovf);
         } else if (cur != kTravDone) {
-            test_leaf<TC::FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc);
-            trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+            if constexpr (TC::LEAF_K > 0) {
+                if (leaf_step<TC::LEAF_K, TC::LEAF_FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc)) trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+            } else {
+                test_leaf<TC::FLAT, TC::SPHERES>(sv, tx, cur, o, d, tnear, tfar, best, tc);
+                trav_pop<kOvf>(tx, cur, sp, tv.ovf);
+            }
             if (any_hit && best.gid >= 0) cur = kTravDone;
         }
     }
@@ -974,7 +1021,9 @@ struct WaveQueue {
 // that finishes early picks up the next item instead of idling behind the longest path of its wave. Per-item sums go
 // to `partials` ([15][items], one writer per slot) and are merged per pixel in chunk order by gdpt_reduce_partials,
 // so the result does not depend on which lane processed what, or when.
-template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0>
+// LEAF_K (TraceCfg): the kernels that walk the LDS copy take their leaves GDPT_LDS_LEAF_K records per trip; 0 = whole leaves (the
+// kernels that walk the tree from HBM; the LDS kernels under the test knob whole_leaf_trips).
+template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE && !GDPT_SPEC_LEAF ? GDPT_LDS_LEAF_K : 0)>
 __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv, KernelArgs a) {
     // LDS-resident scenes: fixed 12-slot stack + the scene copy. Scenes walked from HBM: dynamic LDS = a.stack_levels stack
     // slots per lane (the tree's own bound, not the builder's maximum of 32).
@@ -1051,7 +1100,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             stamps.mark(SEG_QUEUE);
         }
         // ---- (T) the wave's unfinished pending rays, then (S, first half) the lanes whose ray is done consume their hit
-        trace_pending<TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE>>(sv, tx, L, tv, a.thresh_a, a.thresh_c, tc);
+        trace_pending<TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE, LEAF_K>>(sv, tx, L, tv, a.thresh_a, a.thresh_c, tc);
         stamps.mark(SEG_TRACE);
         stamps.tick(SEG_STEPS);
         act = ACT_NONE;
@@ -1313,11 +1362,12 @@ __global__ __launch_bounds__(64) void gdpt_render_tile_stream_eager(DevSceneView
 namespace gdpt {
 // host launchers, one translation unit per kernel family (parallel compilation); each launches the kernel its arguments name
 // (render_kernels.hip: launch_render calls one per route)
-void launch_phases_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, hipStream_t stream);
-void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, hipStream_t stream);   // triangles only (and constant textures)
-void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, hipStream_t stream);   // diagnostic build
+// whole_leaf (knob whole_leaf_trips): the LDS kernels in their LEAF_K = 0 form; the kernels that walk the tree from HBM have no other
+void launch_phases_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, bool whole_leaf, hipStream_t stream);
+void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, bool whole_leaf, hipStream_t stream);   // triangles only (and constant textures)
+void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, bool whole_leaf, hipStream_t stream);   // diagnostic build
 void launch_reduce_partials(const DevSceneView &sv, const gd::KernelArgs &a, hipStream_t stream);
-void launch_phases_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, hipStream_t stream);
+void launch_phases_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, bool whole_leaf, hipStream_t stream);
 // kernels built for {Lambertian, `lobe`} (render_phases_general_sets_*.hip): GDPT_MAT_DISNEY_DIFFUSE / _METAL (a), _CLEARCOAT / _SHEEN (b)
 void launch_phases_general_set_a(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int lobe, hipStream_t stream);
 void launch_phases_general_set_b(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, int lobe, hipStream_t stream);

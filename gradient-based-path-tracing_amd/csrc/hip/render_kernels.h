@@ -62,6 +62,9 @@ struct RouteInputs {
     bool fits_lds_wide;            // scene_fits_lds_wide: the same for the BVH4 form
     // knob overrides (defaults: the product path)
     bool force_eager, no_lds_scene, lds_wide, no_twosided_machine, wavefront, stamps, no_plain_kernel, full_material_switch;
+    // knob whole_leaf_trips: picks no other route — the LDS-resident one-sided lane machines run their LEAF_K = 0 instantiation (a leaf
+    // trip tests the whole leaf) under the route name they always have; launch_render takes it from RenderLaunch::whole_leaf_trips
+    bool whole_leaf_trips;
 };
 // Pure: no HIP call, no knob read. Throws std::runtime_error for an rng_scheme / shift_mode pair no kernel serves.
 Route choose_route(const RouteInputs &in);
@@ -94,6 +97,7 @@ struct RenderLaunch {
     hipEvent_t wf_event;
     int wf_slots;
     int replay_per_step;           // two-sided lane machine (render_twosided.h), 0 = default
+    bool whole_leaf_trips;         // RouteInputs::whole_leaf_trips
     double *partials;              // device, >= 16 doubles per work item (partial sums)
     unsigned long long *queue_head;// device, work-queue head
     // overlapped launch (can_overlap routes only; nullptr = everything on the caller's stream): the queue reset and the render kernel

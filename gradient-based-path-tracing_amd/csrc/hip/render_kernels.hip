@@ -230,24 +230,25 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
     if (is_wavefront(r) && (!rl.wf_state || !rl.wf_live || !rl.wf_counters || !rl.wf_host || !rl.wf_aux || rl.wf_slots <= 0))
         throw std::runtime_error("launch_render: wavefront buffers missing");
     set_route(r);
+    const bool wl = rl.whole_leaf_trips;       // (knob; read by the LDS-resident one-sided lane machines only)
     switch (r) {
-    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, ks); break;
-    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, ks); break;
-    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, ks); break;
-    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, ks); break;
-    case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, ks); break;
-    case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, ks); break;
-    case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, ks); break;
-    case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, stream); break;
-    case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, stream); break;
-    case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, stream); break;
+    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, wl, ks); break;
+    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, wl, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, wl, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, wl, ks); break;
+    case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, wl, ks); break;
+    case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, wl, ks); break;
+    case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, wl, ks); break;
+    case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, wl, stream); break;
+    case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, wl, stream); break;
+    case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, wl, stream); break;
     case Route::GENERAL_SET_A_DISNEY_DIFFUSE: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_DIFFUSE, ks); break;
     case Route::GENERAL_SET_A_DISNEY_METAL: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_METAL, ks); break;
     case Route::GENERAL_SET_B_DISNEY_CLEARCOAT: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_CLEARCOAT, ks); break;
     case Route::GENERAL_SET_B_DISNEY_SHEEN: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_SHEEN, ks); break;
-    case Route::GENERAL_LDS_WIDE: launch_phases_general(sv, a, grid, true, true, ks); break;
-    case Route::GENERAL_LDS_BVH2: launch_phases_general(sv, a, grid, true, false, ks); break;
-    case Route::GENERAL_HBM: launch_phases_general(sv, a, grid, false, false, ks); break;
+    case Route::GENERAL_LDS_WIDE: launch_phases_general(sv, a, grid, true, true, wl, ks); break;
+    case Route::GENERAL_LDS_BVH2: launch_phases_general(sv, a, grid, true, false, wl, ks); break;
+    case Route::GENERAL_HBM: launch_phases_general(sv, a, grid, false, false, wl, ks); break;
     case Route::TWOSIDED_LDS: launch_phases_twosided(sv, a, grid, true, rl.bounce_log, stream); break;
     case Route::TWOSIDED_HBM: launch_phases_twosided(sv, a, grid, false, rl.bounce_log, stream); break;
     case Route::TWOSIDED_HBM_GLASS: launch_phases_twosided_glass(sv, a, grid, rl.bounce_log, stream); break;

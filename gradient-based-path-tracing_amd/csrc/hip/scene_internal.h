@@ -27,6 +27,7 @@ struct GdptScene {
     int device = 0;
     DevSceneView view{};
     int bvh_depth = 0;
+    int leaf_hist[4] = {0, 0, 0, 0};   // leaves of 1..4 primitive records (gdpt_debug_leaf_histogram)
     int wide_stack_need = 0;       // stack bound of the BVH4 (LDS-resident scenes)
     int wide8_stack_need = 0;      // stack bound of the BVH8 (scenes walked from HBM)
     bool has_envmap = false;

@@ -37,6 +37,8 @@
  *   no_plain_kernel (0/1)       one-sided lane machine: the kernel with sphere and texture code even for a triangles-only, constant-texture scene
  *   no_render_overlap (0/1)     one-sided lane machine: every launch wholly on the caller's stream, none on the handle's render streams
  *   full_material_switch (0/1)  lane machines: the kernel with the full material switch even when the scene fits a small set
+ *   whole_leaf_trips (0/1)      one-sided lane machine on an LDS-resident scene: the kernel whose leaf trips test the whole leaf (four
+ *                               tests in a row) instead of two records per trip with the cursor in the leaf reference; same route name
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
  *
@@ -85,6 +87,11 @@ const char *gdpt_debug_last_route(void);
  * -1 for a null handle. Lets a test see that the overlapped path was taken. */
 struct GdptScene;
 long long gdpt_debug_overlapped_launches(const struct GdptScene *scene);
+/* Leaves of the binary BVH the upload built, by size: hist[k] = leaves of k + 1 primitive records. The wide forms the kernels walk
+ * (BVH4, quantised BVH4, BVH8) are collapsed from that tree and keep its leaves as they are, so these are the leaves every kernel
+ * meets. The root is an inner node whenever the scene has a primitive (a scene of one leaf hangs it under the root); a scene without
+ * primitives gives zeros. Returns 0, or non-zero for a null argument. */
+int gdpt_debug_leaf_histogram(const struct GdptScene *scene, int32_t hist[4]);
 /* Every name gdpt_debug_last_route can return: fills out[0..n) and returns n, or -1 if `capacity` < n; out == NULL
  * returns n alone. */
 int gdpt_debug_route_names(const char **out, int capacity);
