@@ -131,6 +131,7 @@ def lib():
         L.gdpt_debug_overlapped_launches.restype = C.c_longlong
         L.gdpt_debug_leaf_histogram.argtypes = [vp, C.POINTER(C.c_int32)]
         L.gdpt_debug_route_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
+        L.gdpt_debug_prepare_scene.argtypes = [C.POINTER(defs.GdptSceneDesc), C.POINTER(defs.GdptPreparedInfo), dp, dp, C.c_int]
         _LIB = L
     return _LIB
 
@@ -891,6 +892,22 @@ class debug_knobs:
         if lib().gdpt_debug_route_names(buf, n) != n:
             raise GdptError("gdpt_debug_route_names: capacity")
         return [x.decode() for x in buf]
+
+    @staticmethod
+    def prepare_scene(scene_desc):
+        """The host half of an upload of `scene_desc`, on the CPU (include/gdpt_debug.h: gdpt_debug_prepare_scene): a dict of the
+        traits and scalars, `count` and `digest` by table name, and the emitter selection table `light_pmf`, `light_cdf`."""
+        n = scene_desc.desc.num_lights
+        info = defs.GdptPreparedInfo()
+        pmf, cdf = np.zeros(n + 1), np.zeros(n + 1)
+        _check(lib().gdpt_debug_prepare_scene(scene_desc.ptr, C.byref(info), _dp(pmf), _dp(cdf), n + 1))
+        d = {k: getattr(info, k) for k, _ in defs.GdptPreparedInfo._fields_ if k not in ("count", "digest", "bounds", "leaf_hist")}
+        d["bounds"], d["leaf_hist"] = list(info.bounds), list(info.leaf_hist)
+        d["count"] = dict(zip(defs.PREPARED_TABLES, info.count))
+        d["digest"] = dict(zip(defs.PREPARED_TABLES, info.digest))
+        have = d["count"]["light_pmf"]                   # (a scene without emitters has no table)
+        d["light_pmf"], d["light_cdf"] = pmf[:have], cdf[:have + 1 if have else 0]
+        return d
 
     @staticmethod
     def from_env(environ=None):

@@ -146,3 +146,17 @@ class GdptMultiStats(C.Structure):
                 ("row_begin", C.c_int32 * GDPT_MULTI_MAX_DEVICES), ("row_end", C.c_int32 * GDPT_MULTI_MAX_DEVICES),
                 ("render_ms", C.c_double * GDPT_MULTI_MAX_DEVICES), ("render_ms_max", C.c_double),
                 ("exchange_ms", C.c_double), ("solve_ms", C.c_double), ("wall_ms", C.c_double)]
+
+
+# include/gdpt_debug.h: gdpt_debug_prepare_scene
+PREPARED_TABLES = ("nodes", "nodes4", "nodes8", "nodes4q", "prims", "tris", "spheres", "materials", "light_intensity", "images", "texels",
+                   "lights", "light_pmf", "light_cdf", "light_tri_cdf", "light_tri_pos", "light_tri_nrm", "env_cdf_rows", "env_pdf_rows",
+                   "env_cdf_marginals", "env_pdf_marginals")
+
+
+class GdptPreparedInfo(C.Structure):
+    _fields_ = [("count", C.c_int64 * len(PREPARED_TABLES)), ("digest", C.c_uint64 * len(PREPARED_TABLES)), ("isect_eps", C.c_double),
+                ("bounds", C.c_float * 6), ("bvh_depth", C.c_int32), ("leaf_hist", C.c_int32 * 4), ("wide_stack_need", C.c_int32),
+                ("wide8_stack_need", C.c_int32), ("one_sided", C.c_int32), ("lambert_only", C.c_int32), ("has_rough", C.c_int32),
+                ("plan_take_pct", C.c_int32), ("material_mask", C.c_uint32), ("has_envmap", C.c_int32), ("env_w", C.c_int32),
+                ("env_h", C.c_int32), ("all_textures_constant", C.c_int32)]

@@ -5,6 +5,7 @@
 #include "host/bvh.h"
 #include "host/image_io.h"
 #include "host/scene_loader.h"
+#include "host/scene_prepare.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -66,6 +67,41 @@ void gdpt_debug_get_stamps(double out[16]) {
 void gdpt_debug_knobs_reset(void) {
     std::lock_guard<std::mutex> lk(gdpt::g_knob_mu);
     gdpt::g_knobs.clear();
+}
+
+int gdpt_debug_prepare_scene(const GdptSceneDesc *desc, GdptPreparedInfo *info, double *light_pmf, double *light_cdf, int capacity) {
+    return gdpt::guarded([&]() {
+        if (!desc || !info) throw std::runtime_error("gdpt_debug_prepare_scene: null argument");
+        const gdpt::PreparedScene ps = gdpt::prepare_scene(*desc, gdpt::PrepareOptions{});
+        if ((light_pmf || light_cdf) && (size_t)std::max(capacity, 0) < ps.light_cdf.size()) throw std::runtime_error("gdpt_debug_prepare_scene: capacity < num_lights + 1");
+        std::memset(info, 0, sizeof(*info));
+        auto table = [&](int k, const auto &v) {
+            uint64_t h = 0xcbf29ce484222325ull;      // FNV-1a, 64 bits
+            const unsigned char *p = (const unsigned char *)v.data();
+            for (size_t i = 0; i < v.size() * sizeof(v[0]); i++) { h ^= p[i]; h *= 0x100000001b3ull; }
+            info->count[k] = (int64_t)v.size(); info->digest[k] = h;
+        };
+        table(GDPT_PREPARED_NODES, ps.nodes); table(GDPT_PREPARED_NODES4, ps.nodes4); table(GDPT_PREPARED_NODES8, ps.nodes8);
+        table(GDPT_PREPARED_NODES4Q, ps.nodes4q); table(GDPT_PREPARED_PRIMS, ps.prims); table(GDPT_PREPARED_TRIS, ps.tris);
+        table(GDPT_PREPARED_SPHERES, ps.spheres); table(GDPT_PREPARED_MATERIALS, ps.materials);
+        table(GDPT_PREPARED_LIGHT_INTENSITY, ps.light_intensity); table(GDPT_PREPARED_IMAGES, ps.images); table(GDPT_PREPARED_TEXELS, ps.texels);
+        table(GDPT_PREPARED_LIGHTS, ps.lights); table(GDPT_PREPARED_LIGHT_PMF, ps.light_pmf); table(GDPT_PREPARED_LIGHT_CDF, ps.light_cdf);
+        table(GDPT_PREPARED_LIGHT_TRI_CDF, ps.light_tri_cdf); table(GDPT_PREPARED_LIGHT_TRI_POS, ps.light_tri_pos);
+        table(GDPT_PREPARED_LIGHT_TRI_NRM, ps.light_tri_nrm); table(GDPT_PREPARED_ENV_CDF_ROWS, ps.env_cdf_rows);
+        table(GDPT_PREPARED_ENV_PDF_ROWS, ps.env_pdf_rows); table(GDPT_PREPARED_ENV_CDF_MARGINALS, ps.env_cdf_marginals);
+        table(GDPT_PREPARED_ENV_PDF_MARGINALS, ps.env_pdf_marginals);
+        const gdpt::SceneTraits &t = ps.traits;
+        info->isect_eps = ps.view.isect_eps;
+        for (int k = 0; k < 6; k++) info->bounds[k] = t.bounds[k];
+        info->bvh_depth = t.bvh_depth; info->wide_stack_need = t.wide_stack_need; info->wide8_stack_need = t.wide8_stack_need;
+        for (int k = 0; k < 4; k++) info->leaf_hist[k] = t.leaf_hist[k];
+        info->one_sided = t.one_sided; info->lambert_only = t.lambert_only; info->has_rough = t.has_rough;
+        info->plan_take_pct = t.plan_take_pct; info->material_mask = t.material_mask;
+        info->has_envmap = ps.view.has_envmap; info->env_w = ps.view.env_w; info->env_h = ps.view.env_h;
+        info->all_textures_constant = ps.view.all_textures_constant;
+        if (light_pmf) std::copy(ps.light_pmf.begin(), ps.light_pmf.end(), light_pmf);
+        if (light_cdf) std::copy(ps.light_cdf.begin(), ps.light_cdf.end(), light_cdf);
+    });
 }
 
 int gdpt_parse_scene(const char *xml_path, GdptSceneDesc **out_desc) { return gdpt_parse_scene_film(xml_path, 0, 0, out_desc); }

@@ -1,10 +1,9 @@
-// capi_device.hip — device-side entry points of include/gdpt.h: scene upload (own BVH2 build + HBM
-// layout), the five-buffer render, gradient assembly, the Poisson solve and the whole GradPath pipeline.
+// capi_device.hip — device-side entry points of include/gdpt.h: scene upload (the tables host/scene_prepare.cpp
+// makes, copied to HBM), the five-buffer render, gradient assembly, the Poisson solve and the whole GradPath pipeline.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "../device_scene.h"
-#include "../host/bvh.h"
-#include "../host/tri_precompute.h"
+#include "../host/scene_prepare.h"
 #include "poisson_kernels.h"
 #include "recon_l1.h"
 #include "recon_weighted.h"
@@ -17,9 +16,10 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <limits>
+#include <exception>
 #include <memory>
 #include <string>
+#include <thread>
 #include <vector>
 
 namespace {
@@ -40,352 +40,59 @@ T *upload(GdptScene *sc, const std::vector<T> &v) {
 } // namespace
 
 static constexpr int kWavefrontDefault = 0;       // HBM scenes: 1 = wavefront pipeline by default, 0 = lane machine
-static constexpr double kSbvhBudget = 1.0;       // extra references / primitives the spatial-split build may add (it adds ~0.1-0.35; knob sbvh overrides)
-static constexpr double kPresplitBudget = 0.0;   // extra references / primitives (GDPT_PRESPLIT overrides)
 
 namespace gdpt {
 
-void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
-    if (!desc) throw std::runtime_error("gdpt_scene_upload: null scene description");
+namespace {
+
+void check_device(int device) {
     int ndev = 0;
     ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
     if (ndev <= 0) throw std::runtime_error("gdpt_scene_upload: no HIP device visible (this library has no CPU fallback)");
     if (device < 0 || device >= ndev) throw std::runtime_error("gdpt_scene_upload: bad device index");
+}
+
+// The host half of an upload with the knobs resolved (host/scene_prepare.h). GDPT_HBM_BVH8 and GDPT_HBM_Q4 are tested here, in a
+// translation unit the A/B builds recompile, and nowhere in a host object.
+PreparedScene prepare(const GdptSceneDesc &desc) {
+    PrepareOptions opt;
+    opt.presplit = debug_knob("presplit", -1.0);
+    opt.sbvh = debug_knob("sbvh", -1.0);
+    opt.with_bvh8 = GDPT_HBM_BVH8 != 0;
+    opt.with_q4 = GDPT_HBM_Q4 != 0;
+    return prepare_scene(desc, opt);
+}
+
+} // namespace
+
+void upload_scene(const PreparedScene &ps, int device, GdptScene *sc) {
+    check_device(device);
     ck(hipSetDevice(device), "hipSetDevice");
     sc->device = device;
-
-    const GdptCamera &cam = desc->camera;
-    if (cam.width <= 0 || cam.height <= 0) throw std::runtime_error("gdpt_scene_upload: empty film");
-    for (int m = 0; m < desc->num_materials; m++) {
-        int t = desc->materials[m].type;
-        if (t < 0 || t > GDPT_MAT_DISNEY_BSDF) throw std::runtime_error("gdpt_scene_upload: unknown material type");
-        for (int k = 0; k < GDPT_MAT_MAX_TEX; k++) {
-            const GdptTexture &tx = desc->materials[m].tex[k];
-            if (tx.type == GDPT_TEX_IMAGE && (tx.image_id < 0 || tx.image_id >= desc->num_images))
-                throw std::runtime_error("gdpt_scene_upload: texture references a missing image");
-        }
-    }
-
-    // ---- flatten primitives: triangles in (shape, triangle) order = global id; spheres after them ----
-    std::vector<DevTriShade> tris;
-    std::vector<DevSphere> spheres;
-    std::vector<DevPrim> prim_in;          // input order (gid order, spheres last)
-    std::vector<gdpt::PrimBounds> bounds;
-    std::vector<float> tri_verts;          // the fp32 triangles the intersection test sees (9 floats each), for presplit
-    float lb[3], ub[3];
-    for (int k = 0; k < 3; k++) { lb[k] = std::numeric_limits<float>::infinity(); ub[k] = -lb[k]; }
-    for (int s = 0; s < desc->num_shapes; s++) {
-        const GdptShape &sh = desc->shapes[s];
-        if (sh.material_id < 0 || sh.material_id >= desc->num_materials) throw std::runtime_error("gdpt_scene_upload: shape without a valid material");
-        if (sh.area_light_id >= desc->num_lights) throw std::runtime_error("gdpt_scene_upload: bad area light id");
-        if (sh.type != GDPT_SHAPE_TRIMESH) continue;
-        if (!sh.positions || !sh.indices) throw std::runtime_error("gdpt_scene_upload: mesh without positions/indices");
-        for (int i = 0; i < sh.num_vertices; i++)
-            for (int k = 0; k < 3; k++) { float p = (float)sh.positions[3 * i + k]; lb[k] = std::min(lb[k], p); ub[k] = std::max(ub[k], p); }
-        for (int t = 0; t < sh.num_triangles; t++) {
-            DevTriShade ts{};
-            DevPrim pr{};
-            gdpt::PrimBounds pb;
-            float v[3][3];
-            double pos64[3][3];
-            for (int k = 0; k < 3; k++) { pb.bmin[k] = std::numeric_limits<float>::infinity(); pb.bmax[k] = -pb.bmin[k]; }
-            for (int i = 0; i < 3; i++) {
-                int vi = sh.indices[3 * t + i];
-                if (vi < 0 || vi >= sh.num_vertices) throw std::runtime_error("gdpt_scene_upload: mesh index out of range");
-                for (int k = 0; k < 3; k++) {
-                    pos64[i][k] = sh.positions[3 * vi + k];
-                    v[i][k] = (float)sh.positions[3 * vi + k];
-                    pb.bmin[k] = std::min(pb.bmin[k], v[i][k]); pb.bmax[k] = std::max(pb.bmax[k], v[i][k]);
-                    if (sh.normals) ts.n[i][k] = sh.normals[3 * vi + k];
-                }
-                if (sh.uvs) { ts.uv[i][0] = sh.uvs[2 * vi]; ts.uv[i][1] = sh.uvs[2 * vi + 1]; }
-            }
-            if (!sh.uvs) { // src/shapes/triangle_mesh.inl:86-90
-                ts.uv[0][0] = 0; ts.uv[0][1] = 0; ts.uv[1][0] = 1; ts.uv[1][1] = 0; ts.uv[2][0] = 1; ts.uv[2][1] = 1;
-            }
-            ts.shape_id = s; ts.prim_id = t; ts.material_id = sh.material_id; ts.light_id = sh.area_light_id;
-            ts.has_normals = sh.normals != nullptr; ts.has_uvs = sh.uvs != nullptr;
-            for (int k = 0; k < 3; k++) { pr.v0[k] = v[0][k]; pr.e1[k] = v[1][k] - v[0][k]; pr.e2[k] = v[2][k] - v[0][k]; }
-            for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) tri_verts.push_back(v[i][k]);
-            gdpt::precompute_tri_constants(pos64, pr.e1, pr.e2, &ts);
-            pr.gid = (uint32_t)tris.size();
-            tris.push_back(ts); prim_in.push_back(pr); bounds.push_back(pb);
-        }
-    }
-    if (tris.size() >= (size_t)GDPT_SPHERE_FLAG / 8) throw std::runtime_error("gdpt_scene_upload: too many triangles");
-    for (int s = 0; s < desc->num_shapes; s++) {
-        const GdptShape &sh = desc->shapes[s];
-        if (sh.type != GDPT_SHAPE_SPHERE) continue;
-        DevSphere sp{};
-        DevPrim pr{};
-        gdpt::PrimBounds pb;
-        for (int k = 0; k < 3; k++) {
-            sp.center[k] = sh.center[k];
-            // scene bounds as Embree sees them: sphere_bounds_func stores double -> float (src/shapes/sphere.inl:1-10)
-            lb[k] = std::min(lb[k], (float)(sh.center[k] - sh.radius)); ub[k] = std::max(ub[k], (float)(sh.center[k] + sh.radius));
-            // BVH bounds: rounded outward so the box always contains the fp64 sphere
-            pb.bmin[k] = std::nextafterf((float)(sh.center[k] - sh.radius), -std::numeric_limits<float>::infinity());
-            pb.bmax[k] = std::nextafterf((float)(sh.center[k] + sh.radius), std::numeric_limits<float>::infinity());
-        }
-        sp.radius = sh.radius; sp.shape_id = s; sp.material_id = sh.material_id; sp.light_id = sh.area_light_id;
-        pr.gid = GDPT_SPHERE_FLAG | (uint32_t)spheres.size();
-        spheres.push_back(sp); prim_in.push_back(pr); bounds.push_back(pb);
-    }
-
-    // large triangles of big meshes are referenced from several smaller boxes (host/presplit.cpp); scenes small enough
-    // for LDS keep one reference per primitive
-    std::vector<gdpt::PrimBounds> refs;
-    std::vector<uint32_t> ref_prim;
-    {
-        double budget = tris.size() >= 4096 ? kPresplitBudget : 0.0;
-        budget = gdpt::debug_knob("presplit", budget);
-        gdpt::presplit_triangles(bounds, tri_verts, budget, &refs, &ref_prim);
-    }
-    // spatial splits inside the SAH build (host/sbvh.cpp) for meshes that are walked from HBM; `sbvh` = extra references allowed
-    // per primitive (test knob; 0 = the plain object-split build)
-    const double sbvh_budget = gdpt::debug_knob("sbvh", tris.size() >= 4096 ? kSbvhBudget : 0.0);
-    gdpt::BvhBuildResult bvh = sbvh_budget > 0 ? gdpt::build_sbvh(bounds, tri_verts, sbvh_budget, &ref_prim) : gdpt::build_bvh(refs);
-    {   // widen every child box: the traversal's slab test then needs no per-test padding (device_trace.h: box_hit)
-        float ext = 0.f;
-        for (int k = 0; k < 3; k++) if (ub[k] >= lb[k]) ext = std::max(ext, std::max(std::fabs(ub[k]), std::fabs(lb[k])));
-        for (auto &sp : spheres) for (int k = 0; k < 3; k++) ext = std::max(ext, (float)(std::fabs(sp.center[k]) + sp.radius));
-        {   // ray origins: surface points (inside the bounds) and the camera position, xform_point(cam_to_world, 0)
-            const double *m = cam.cam_to_world;
-            for (int k = 0; k < 3; k++) ext = std::max(ext, (float)std::fabs(m[4 * k + 3] / m[15]) * 1.0000002f);
-        }
-        const float pad = ext * 1e-6f + 1e-30f;
-        for (auto &n : bvh.nodes)
-            for (int k = 0; k < 3; k++) {
-                if (n.lmin[k] <= n.lmax[k]) { n.lmin[k] -= pad; n.lmax[k] += pad; }
-                if (n.rmin[k] <= n.rmax[k]) { n.rmin[k] -= pad; n.rmax[k] += pad; }
-            }
-    }
-    // wide form for scenes walked from HBM (same padded boxes); narrower nodes if the stack bound would not hold
-    // (the 8-wide quantised form is built, verified and uploaded only by the GDPT_HBM_BVH8 A/B library: a product upload neither
-    // pays for it nor can fail on it)
-    gdpt::WideBvh wide = gdpt::collapse_for_traversal(bvh.nodes, GDPT_HBM_BVH8 != 0);
-    if (wide.stack_need > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("gdpt_scene_upload: BVH deeper than the traversal stack (builder bug)");
-    if (wide.stack_need8 > GDPT_BVH_MAX_DEPTH + GDPT_STACK_OVERFLOW) throw std::runtime_error("gdpt_scene_upload: BVH8 deeper than the traversal stack (builder bug)");
-    static_assert(sizeof(DevBvh8Node) == 128 && sizeof(DevBvh4Node) == 128, "wide BVH nodes are one 128-byte line");
-    const std::vector<DevBvh4Node> &nodes4 = wide.nodes;
-    sc->wide_stack_need = wide.stack_need;
-    sc->wide8_stack_need = wide.stack_need8;
-    std::vector<DevPrim> prims(bvh.order.size());
-    for (size_t i = 0; i < bvh.order.size(); i++) prims[i] = prim_in[ref_prim[bvh.order[i]]];
-    sc->bvh_depth = bvh.depth;
-    for (const DevBvhNode &n : bvh.nodes)
-        for (int32_t ch : {n.left, n.right}) if (ch < 0 && ch != GDPT_CHILD_EMPTY) sc->leaf_hist[~(unsigned)ch & 3u]++;
-    if (bvh.depth > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("gdpt_scene_upload: BVH deeper than the traversal stack (builder bug)");
-
-    // ---- textures: fp64 mip chains exactly as make_mipmap builds them (src/mipmap.h:27-48) ----
-    std::vector<DevImage> images;
-    std::vector<double> texels;
-    for (int i = 0; i < desc->num_images; i++) {
-        const GdptImage &im = desc->images[i];
-        if (im.width <= 0 || im.height <= 0 || (im.channels != 1 && im.channels != 3) || !im.texels)
-            throw std::runtime_error("gdpt_scene_upload: bad image");
-        DevImage di{};
-        di.channels = im.channels;
-        int size = std::max(im.width, im.height);
-        int num_levels = std::min((int)std::ceil(std::log2((double)size) + 1), 8);
-        di.num_levels = num_levels;
-        int pw = im.width, ph = im.height;
-        size_t prev_off = texels.size();
-        di.width[0] = pw; di.height[0] = ph; di.offset[0] = (int64_t)prev_off;
-        texels.insert(texels.end(), im.texels, im.texels + (size_t)pw * ph * im.channels);
-        for (int l = 1; l < num_levels; l++) {
-            int nw = std::max(pw / 2, 1), nh = std::max(ph / 2, 1);
-            size_t off = texels.size();
-            texels.resize(off + (size_t)nw * nh * im.channels);
-            auto P = [&](int x, int y, int c) { x = std::min(x, pw - 1); y = std::min(y, ph - 1); return texels[prev_off + ((size_t)y * pw + x) * im.channels + c]; };
-            for (int y = 0; y < nh; y++) for (int x = 0; x < nw; x++) for (int c = 0; c < im.channels; c++)
-                texels[off + ((size_t)y * nw + x) * im.channels + c] =
-                    (P(2 * x, 2 * y, c) + P(2 * x + 1, 2 * y, c) + P(2 * x, 2 * y + 1, c) + P(2 * x + 1, 2 * y + 1, c)) / 4.0;
-            di.width[l] = nw; di.height[l] = nh; di.offset[l] = (int64_t)off;
-            prev_off = off; pw = nw; ph = nh;
-        }
-        images.push_back(di);
-    }
-
-    std::vector<GdptMaterial> materials(desc->materials, desc->materials + desc->num_materials);
-    std::vector<double> light_intensity;
-    for (int l = 0; l < desc->num_lights; l++) for (int k = 0; k < 3; k++) light_intensity.push_back(desc->lights[l].intensity[k]);
-
-    // ---- Integrator::Path emitter tables (same formulas and operation order as the reference) ----
-    int env_power_slot = -1;
-    std::vector<double> light_power;
-    std::vector<DevLight> dlights;
-    std::vector<double> light_pmf, light_cdf, light_tri_cdf, light_tri_pos, light_tri_nrm;
-    auto table_1d = [](const std::vector<double> &f, std::vector<double> &pmf, std::vector<double> &cdf) {   // src/table_dist.cpp:3-25
-        pmf = f;
-        cdf.assign(f.size() + 1, 0.0);
-        for (size_t i = 0; i < f.size(); i++) cdf[i + 1] = cdf[i] + pmf[i];
-        const double total = cdf.back();
-        if (total > 0) { for (size_t i = 0; i < pmf.size(); i++) { pmf[i] /= total; cdf[i] /= total; } }
-        else {
-            for (size_t i = 0; i < pmf.size(); i++) { pmf[i] = 1.0 / (double)pmf.size(); cdf[i] = (double)i / (double)pmf.size(); }
-            cdf.back() = 1;
-        }
-    };
-    {
-        std::vector<int> sphere_index_of_shape((size_t)desc->num_shapes, -1);
-        { int k = 0; for (int s = 0; s < desc->num_shapes; s++) if (desc->shapes[s].type == GDPT_SHAPE_SPHERE) sphere_index_of_shape[(size_t)s] = k++; }
-        std::vector<double> power;
-        for (int l = 0; l < desc->num_lights; l++) {
-            const GdptLight &lt = desc->lights[l];
-            if (lt.shape_id < 0 && desc->has_envmap && l == desc->envmap.light_id) {      // environment map: power filled in below
-                dlights.push_back(DevLight{});
-                power.push_back(0.0);
-                continue;
-            }
-            if (lt.shape_id < 0 || lt.shape_id >= desc->num_shapes) throw std::runtime_error("gdpt_scene_upload: light without a shape");
-            const GdptShape &sh = desc->shapes[lt.shape_id];
-            DevLight dl{};
-            for (int k = 0; k < 3; k++) dl.intensity[k] = lt.intensity[k];
-            if (sh.type == GDPT_SHAPE_SPHERE) {
-                dl.is_sphere = 1; dl.sphere_index = sphere_index_of_shape[(size_t)lt.shape_id];
-                dl.area = 4 * 3.14159265358979323846 * sh.radius * sh.radius;                 // sphere.inl:207-209
-            } else {
-                dl.tri_first = (int)(light_tri_pos.size() / 9); dl.tri_count = sh.num_triangles;
-                dl.cdf_first = (int)light_tri_cdf.size(); dl.has_normals = sh.normals ? 1 : 0;
-                std::vector<double> areas((size_t)sh.num_triangles), pmf, cdf;
-                double total = 0;
-                for (int t = 0; t < sh.num_triangles; t++) {
-                    const int *ix = sh.indices + 3 * t;
-                    double p[3][3];
-                    for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) { p[i][k] = sh.positions[3 * ix[i] + k]; light_tri_pos.push_back(p[i][k]); }
-                    for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) light_tri_nrm.push_back(sh.normals ? sh.normals[3 * ix[i] + k] : 0.0);
-                    const double e1[3] = {p[1][0] - p[0][0], p[1][1] - p[0][1], p[1][2] - p[0][2]}, e2[3] = {p[2][0] - p[0][0], p[2][1] - p[0][1], p[2][2] - p[0][2]};
-                    const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
-                    areas[(size_t)t] = std::sqrt(cx * cx + cy * cy + cz * cz) / 2;               // triangle_mesh.inl:70
-                    total += areas[(size_t)t];
-                }
-                table_1d(areas, pmf, cdf);
-                light_tri_cdf.insert(light_tri_cdf.end(), cdf.begin(), cdf.end());
-                dl.area = total;
-            }
-            const double lum = lt.intensity[0] * 0.212671 + lt.intensity[1] * 0.715160 + lt.intensity[2] * 0.072169;   // src/spectrum.h:33-35
-            power.push_back(lum * dl.area * 3.14159265358979323846);                              // diffuse_area_light.inl:1-3
-            dlights.push_back(dl);
-        }
-        env_power_slot = desc->has_envmap ? desc->envmap.light_id : -1;
-        light_power = power;
-    }
-
+    sc->traits = ps.traits;
     DevSceneView &v = sc->view;
-    std::memcpy(v.cam.sample_to_cam, cam.sample_to_cam, sizeof(v.cam.sample_to_cam));
-    std::memcpy(v.cam.cam_to_world, cam.cam_to_world, sizeof(v.cam.cam_to_world));
-    {   // xform_point(cam_to_world, (0,0,0)), src/camera.cpp:42
-        const double *m = cam.cam_to_world;
-        double inv_w = 1.0 / m[15];
-        v.cam.org[0] = m[3] * inv_w; v.cam.org[1] = m[7] * inv_w; v.cam.org[2] = m[11] * inv_w;
-    }
-    v.cam.width = cam.width; v.cam.height = cam.height; v.cam.filter_type = cam.filter_type; v.cam.filter_param = cam.filter_param;
-    v.cam.pow2_film = ((cam.width & (cam.width - 1)) == 0 && (cam.height & (cam.height - 1)) == 0) ? 1 : 0;
-    v.cam.inv_width = 1.0 / (double)cam.width; v.cam.inv_height = 1.0 / (double)cam.height;
-    v.nodes = upload(sc, bvh.nodes);
-    v.nodes4 = upload(sc, nodes4);
-    v.nodes8 = upload(sc, wide.nodes8);
-    v.nodes4q = GDPT_HBM_Q4 ? upload(sc, gdpt::quantise_bvh4(nodes4)) : nullptr;
-    v.prims = upload(sc, prims);
-    v.tris = upload(sc, tris);
-    v.spheres = upload(sc, spheres);
-    v.materials = upload(sc, materials);
-    v.light_intensity = upload(sc, light_intensity);
-    v.images = upload(sc, images);
-    v.texels = upload(sc, texels);
-    v.lights = upload(sc, dlights);
-    v.light_tri_cdf = upload(sc, light_tri_cdf);
-    v.light_tri_pos = upload(sc, light_tri_pos); v.light_tri_nrm = upload(sc, light_tri_nrm);
-    sc->has_envmap = desc->has_envmap != 0;
-    v.num_nodes = (int)bvh.nodes.size(); v.num_nodes4 = (int)nodes4.size(); v.num_nodes8 = (int)wide.nodes8.size(); v.num_prims = (int)prims.size();
-    v.num_tris = (int)tris.size(); v.num_spheres = (int)spheres.size();
-    v.num_materials = desc->num_materials; v.num_lights = desc->num_lights; v.num_images = desc->num_images;
-    v.max_depth = desc->max_depth; v.rr_depth = desc->rr_depth;
-    v.all_textures_constant = 1;
-    for (auto &m : materials) for (auto &t : m.tex) if (t.type != GDPT_TEX_CONSTANT) v.all_textures_constant = 0;
-    for (auto &m : materials) {
-        sc->material_mask |= 1u << m.type;
-        if (m.type != GDPT_MAT_LAMBERTIAN) sc->lambert_only = false;
-        if (m.type == GDPT_MAT_ROUGHPLASTIC || m.type == GDPT_MAT_ROUGHDIELECTRIC) sc->has_rough = true;
-        if (m.type == GDPT_MAT_DISNEY_GLASS || m.type == GDPT_MAT_DISNEY_BSDF || m.type == GDPT_MAT_ROUGHDIELECTRIC) sc->one_sided = false;   // two-sided lobes
-    }
-    // scenes with a refractive lobe (DisneyGlass, RoughDielectric): paths through glass are long-tailed, the work items are cut smaller
-    // (render_kernels.hip: make_chunk_plan; disney_glass +9..15 %, matpreview's Integrator::Path +7 %; DisneyBSDF and the opaque scenes are flat)
-    if (sc->material_mask & ((1u << GDPT_MAT_DISNEY_GLASS) | (1u << GDPT_MAT_ROUGHDIELECTRIC))) sc->plan_take_pct = 40;
-    // get_intersection_epsilon (src/scene.h:100-102) from Embree-style fp32 scene bounds (src/scene.cpp:29-33)
-    double dx = (double)ub[0] - (double)lb[0], dy = (double)ub[1] - (double)lb[1], dz = (double)ub[2] - (double)lb[2];
-    double radius = prims.empty() ? 0.0 : std::sqrt(dx * dx + dy * dy + dz * dz) / 2;
-    for (int k = 0; k < 3; k++) { sc->bounds[k] = lb[k]; sc->bounds[3 + k] = ub[k]; }
-    v.isect_eps = std::min(radius * 1e-5, 0.01);
-
-    // ---- environment map (Integrator::Path): TableDist2D over luminance * sin(elevation) of the level-0 image
-    // (init_sampling_dist, src/lights/envmap.inl:66-83; make_table_dist_2d, src/table_dist.cpp:40-112), its power
-    // (envmap.inl:1-5) and only then the light selection table (src/scene.cpp:44-53)
-    v.has_envmap = 0; v.env_light_id = -1;
-    if (desc->has_envmap) {
-        const GdptEnvmap &e = desc->envmap;
-        if (e.image_id < 0 || e.image_id >= desc->num_images || desc->images[e.image_id].channels != 3)
-            throw std::runtime_error("gdpt_scene_upload: environment map without a 3-channel image");
-        const GdptImage &im = desc->images[e.image_id];
-        const int w = im.width, h = im.height;
-        auto texel = [&](int x, int y) { const double *p = im.texels + ((size_t)y * w + x) * 3; return p; };
-        auto modulo = [](int a, int b) { int r = a % b; return r < 0 ? r + b : r; };
-        std::vector<double> f((size_t)w * h);
-        size_t i = 0;
-        for (int y = 0; y < h; y++) {
-            const double vv = (y + 0.5) / (double)h;
-            const double sin_elevation = std::sin(3.14159265358979323846 * vv);
-            for (int x = 0; x < w; x++) {
-                const double uu = (x + 0.5) / (double)w;
-                // lookup(mipmap, u, v, 0): bilinear at level 0 with repeat wrap (src/mipmap.h:51-72)
-                double u = uu * w - 0.5, vq = vv * h - 0.5;
-                int ufi = modulo((int)u, w), vfi = modulo((int)vq, h);
-                int uci = modulo(ufi + 1, w), vci = modulo(vfi + 1, h);
-                double u_off = u - ufi, v_off = vq - vfi;
-                double rgb[3];
-                for (int c = 0; c < 3; c++)
-                    rgb[c] = texel(ufi, vfi)[c] * (1 - u_off) * (1 - v_off) + texel(ufi, vci)[c] * (1 - u_off) * v_off +
-                             texel(uci, vfi)[c] * u_off * (1 - v_off) + texel(uci, vci)[c] * u_off * v_off;
-                f[i++] = (rgb[0] * 0.212671 + rgb[1] * 0.715160 + rgb[2] * 0.072169) * sin_elevation;
-            }
-        }
-        std::vector<double> cdf_rows((size_t)h * (w + 1)), pdf_rows((size_t)h * w), cdf_m((size_t)h + 1), pdf_m((size_t)h);
-        for (int y = 0; y < h; y++) {
-            double *cdf = &cdf_rows[(size_t)y * (w + 1)];
-            cdf[0] = 0;
-            for (int x = 0; x < w; x++) cdf[x + 1] = cdf[x] + f[(size_t)y * w + x];
-            const double integral = cdf[w];
-            if (integral > 0) {
-                for (int x = 0; x < w; x++) cdf[x] /= integral;
-                for (int x = 0; x < w; x++) pdf_rows[(size_t)y * w + x] = f[(size_t)y * w + x] / integral;
-            } else {
-                for (int x = 0; x < w; x++) { pdf_rows[(size_t)y * w + x] = 1.0 / (double)w; cdf[x] = (double)x / (double)w; }
-                cdf[w] = 1;
-            }
-        }
-        cdf_m[0] = 0;
-        for (int y = 0; y < h; y++) cdf_m[(size_t)y + 1] = cdf_m[(size_t)y] + cdf_rows[(size_t)y * (w + 1) + w];
-        const double total_values = cdf_m.back();
-        if (total_values > 0) {
-            for (int y = 0; y < h; y++) cdf_m[(size_t)y] /= total_values;
-            cdf_m[(size_t)h] = 1;
-            for (int y = 0; y < h; y++) pdf_m[(size_t)y] = cdf_rows[(size_t)y * (w + 1) + w] / total_values;
-        } else {
-            for (int y = 0; y < h; y++) { pdf_m[(size_t)y] = 1.0 / (double)h; cdf_m[(size_t)y] = (double)y / (double)h; }
-            cdf_m[(size_t)h] = 1;
-        }
-        for (int y = 0; y < h; y++) cdf_rows[(size_t)y * (w + 1) + w] = 1;
-        v.has_envmap = 1; v.env_light_id = e.light_id; v.env_image_id = e.image_id; v.env_w = w; v.env_h = h; v.env_scale = e.scale;
-        std::memcpy(v.env_to_world, e.to_world, sizeof(v.env_to_world));
-        std::memcpy(v.env_to_local, e.to_local, sizeof(v.env_to_local));
-        v.env_cdf_rows = upload(sc, cdf_rows); v.env_pdf_rows = upload(sc, pdf_rows);
-        v.env_cdf_marginals = upload(sc, cdf_m); v.env_pdf_marginals = upload(sc, pdf_m);
-        if (env_power_slot >= 0 && env_power_slot < (int)light_power.size())
-            light_power[(size_t)env_power_slot] = 3.14159265358979323846 * radius * radius * total_values / ((double)w * (double)h);
-    }
-    if (!light_power.empty()) table_1d(light_power, light_pmf, light_cdf);
-    v.light_pmf = upload(sc, light_pmf); v.light_cdf = upload(sc, light_cdf);
+    v = ps.view;
+    v.nodes = upload(sc, ps.nodes);
+    v.nodes4 = upload(sc, ps.nodes4);
+    v.nodes8 = upload(sc, ps.nodes8);
+    v.nodes4q = upload(sc, ps.nodes4q);
+    v.prims = upload(sc, ps.prims);
+    v.tris = upload(sc, ps.tris);
+    v.spheres = upload(sc, ps.spheres);
+    v.materials = upload(sc, ps.materials);
+    v.light_intensity = upload(sc, ps.light_intensity);
+    v.images = upload(sc, ps.images);
+    v.texels = upload(sc, ps.texels);
+    v.lights = upload(sc, ps.lights);
+    v.light_tri_cdf = upload(sc, ps.light_tri_cdf);
+    v.light_tri_pos = upload(sc, ps.light_tri_pos);
+    v.light_tri_nrm = upload(sc, ps.light_tri_nrm);
+    v.env_cdf_rows = upload(sc, ps.env_cdf_rows);
+    v.env_pdf_rows = upload(sc, ps.env_pdf_rows);
+    v.env_cdf_marginals = upload(sc, ps.env_cdf_marginals);
+    v.env_pdf_marginals = upload(sc, ps.env_pdf_marginals);
+    v.light_pmf = upload(sc, ps.light_pmf);
+    v.light_cdf = upload(sc, ps.light_cdf);
 
     sc->scratch[0].counters.alloc(1, "hipMalloc(counters)");
     sc->scratch[0].queue.alloc(1, "hipMalloc(queue)");
@@ -397,6 +104,35 @@ void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
     sc->h_counters.alloc(1, "hipHostMalloc(counters)");
     sc->ev0.create();
     sc->ev1.create();
+}
+
+void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc) {
+    if (!desc) throw std::runtime_error("gdpt_scene_upload: null scene description");
+    check_device(device);          // (before the description's own checks, and before the seconds a large mesh's tree takes)
+    upload_scene(prepare(*desc), device, sc);
+}
+
+std::vector<std::unique_ptr<GdptScene>> upload_scenes(const GdptSceneDesc *desc, const int32_t *devices, int n) {
+    if (!desc) throw std::runtime_error("gdpt_scene_upload: null scene description");
+    for (int i = 0; i < n; i++) check_device(devices[i]);
+    const PreparedScene ps = prepare(*desc);
+    // every device gets its own copy of the tables; the fp64 texel pool of a textured mesh is hundreds of MB of pageable copy per
+    // device, so the N uploads run side by side instead of one after the other
+    std::vector<std::unique_ptr<GdptScene>> scenes((size_t)n);
+    std::vector<std::exception_ptr> errs((size_t)n);
+    std::vector<std::thread> th;
+    auto one = [&](int i) {
+        try {
+            scenes[(size_t)i].reset(new GdptScene());
+            upload_scene(ps, devices[i], scenes[(size_t)i].get());       // sets the calling thread's device
+            scenes[(size_t)i]->scene_spp = desc->samples_per_pixel;
+        } catch (...) { errs[(size_t)i] = std::current_exception(); }
+    };
+    for (int i = 1; i < n; i++) th.emplace_back(one, i);
+    one(0);
+    for (std::thread &t : th) t.join();
+    for (const std::exception_ptr &e : errs) if (e) std::rethrow_exception(e);
+    return scenes;
 }
 
 } // namespace gdpt
@@ -526,10 +262,10 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     const DevSceneView &v = sc->view;
     gdpt::RouteInputs in{};
     in.path = path; in.rng_scheme = b.rng; in.shift_mode = b.shift; in.max_depth = b.max_depth; in.rr_depth = v.rr_depth;
-    in.one_sided = sc->one_sided; in.has_rough = sc->has_rough; in.lambert_only = sc->lambert_only; in.material_mask = sc->material_mask;
+    in.one_sided = sc->traits.one_sided; in.has_rough = sc->traits.has_rough; in.lambert_only = sc->traits.lambert_only; in.material_mask = sc->traits.material_mask;
     in.has_spheres = v.num_spheres != 0; in.const_textures = v.all_textures_constant != 0; in.has_envmap = v.has_envmap != 0;
-    in.fits_lds = gdpt::scene_fits_lds(v.num_nodes, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->bvh_depth);
-    in.fits_lds_wide = gdpt::scene_fits_lds_wide(v.num_nodes4, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->wide_stack_need);
+    in.fits_lds = gdpt::scene_fits_lds(v.num_nodes, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->traits.bvh_depth);
+    in.fits_lds_wide = gdpt::scene_fits_lds_wide(v.num_nodes4, v.num_prims, v.num_tris, v.num_materials, v.num_lights, sc->traits.wide_stack_need);
     in.force_eager = knob("force_eager", 0) != 0; in.no_lds_scene = knob("no_lds_scene", 0) != 0; in.lds_wide = knob("lds_wide", 1) != 0;
     in.no_twosided_machine = knob("no_twosided_machine", 0) != 0; in.wavefront = knob("wavefront", kWavefrontDefault) != 0;
     in.stamps = knob("stamps", 0) != 0; in.no_plain_kernel = knob("no_plain_kernel", 0) != 0;
@@ -606,9 +342,9 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
     const Band b = resolve_spp(sc, params, scene_spp, "gdpt_render", window);
     if (!img || !cx0 || !cy0 || !cx1 || !cy1) throw std::runtime_error("gdpt_render: null output buffer");
     ScratchClaim claim;
-    RenderLaunch rl = begin_launch(sc, b, false, sc->plan_take_pct, stream, stats, &claim);
+    RenderLaunch rl = begin_launch(sc, b, false, sc->traits.plan_take_pct, stream, stats, &claim);
     rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
-    rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
+    rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->traits.wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->traits.wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
     rl.replay_per_step = debug_knob_int("replay_per_step", 0);
     const long long items = band_slots(sc->view.cam.width, b.row_end - b.row_begin) * rl.plan.n;
     if (needs_bounce_log(rl.route)) {
@@ -625,7 +361,7 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
         if (!sc->h_wf_word) sc->h_wf_word.alloc(1, "hipHostMalloc(wavefront)");
         if (!sc->wf_event) sc->wf_event.create(hipEventDisableTiming);
         rl.wf_aux = sc->d_wf_aux; rl.wf_sort = debug_knob_int("wf_sort", 1);
-        for (int k = 0; k < 6; k++) rl.wf_bounds[k] = sc->bounds[k];
+        for (int k = 0; k < 6; k++) rl.wf_bounds[k] = sc->traits.bounds[k];
         rl.wf_state = sc->d_wf_state; rl.wf_live = sc->d_wf_live; rl.wf_counters = sc->d_wf_counters; rl.wf_host = sc->h_wf_word;
         rl.wf_event = sc->wf_event; rl.wf_slots = slots;       // exactly the slots this band needs (the buffers may be larger)
     }
@@ -738,7 +474,7 @@ long long gdpt_debug_overlapped_launches(const GdptScene *scene) { return scene 
 int gdpt_debug_leaf_histogram(const GdptScene *scene, int32_t hist[4]) {
     return gdpt::guarded([&]() {
         if (!scene || !hist) throw std::runtime_error("gdpt_debug_leaf_histogram: null argument");
-        for (int i = 0; i < 4; i++) hist[i] = scene->leaf_hist[i];
+        for (int i = 0; i < 4; i++) hist[i] = scene->traits.leaf_hist[i];
     });
 }
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
@@ -764,7 +500,7 @@ int gdpt_scene_info(const GdptScene *scene, int32_t *num_nodes, int32_t *num_tri
         if (num_nodes) *num_nodes = scene->view.num_nodes;
         if (num_tris) *num_tris = scene->view.num_tris;
         if (num_spheres) *num_spheres = scene->view.num_spheres;
-        if (bvh_depth) *bvh_depth = scene->bvh_depth;
+        if (bvh_depth) *bvh_depth = scene->traits.bvh_depth;
     });
 }
 

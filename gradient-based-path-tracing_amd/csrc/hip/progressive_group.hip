@@ -227,22 +227,9 @@ int gdpt_progressive_group_create(const GdptSceneDesc *desc, const int32_t *devi
         if (cfg.budget_spp <= 0) throw std::runtime_error("gdpt_progressive_group_create: budget_spp must be > 0");
         std::unique_ptr<GdptProgressiveGroup> g(new GdptProgressiveGroup());
         g->members.resize((size_t)n);
-        {   // every member gets its own copy of the scene; the uploads run side by side (as gdpt_multi_create's do)
-            std::vector<std::exception_ptr> errs((size_t)n);
-            std::vector<std::thread> th;
-            auto one = [&](int i) {
-                try {
-                    Member &m = g->members[(size_t)i];
-                    m.device = devices[i];
-                    m.scene.reset(new GdptScene());
-                    gdpt::build_scene(desc, m.device, m.scene.get());       // sets the calling thread's device
-                    m.scene->scene_spp = desc->samples_per_pixel;
-                } catch (...) { errs[(size_t)i] = std::current_exception(); }
-            };
-            for (int i = 1; i < n; i++) th.emplace_back(one, i);
-            one(0);
-            for (std::thread &t : th) t.join();
-            for (const std::exception_ptr &e : errs) if (e) std::rethrow_exception(e);
+        {   // every member gets its own copy of the scene, made from one prepared scene
+            std::vector<std::unique_ptr<GdptScene>> scenes = gdpt::upload_scenes(desc, devices, n);
+            for (int i = 0; i < n; i++) { g->members[(size_t)i].device = devices[i]; g->members[(size_t)i].scene = std::move(scenes[(size_t)i]); }
         }
         const long long B = cfg.budget_spp;
         for (int i = 0; i < n; i++) {

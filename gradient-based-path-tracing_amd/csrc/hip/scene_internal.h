@@ -3,11 +3,13 @@
 #pragma once
 #include "../../../include/gdpt.h"
 #include "../device_scene.h"
+#include "../host/scene_prepare.h"
 #include "device_mem.h"
 #include "render_kernels.h"
 
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -26,16 +28,8 @@ struct GdptLaunchScratch {
 struct GdptScene {
     int device = 0;
     DevSceneView view{};
-    int bvh_depth = 0;
-    int leaf_hist[4] = {0, 0, 0, 0};   // leaves of 1..4 primitive records (gdpt_debug_leaf_histogram)
-    int wide_stack_need = 0;       // stack bound of the BVH4 (LDS-resident scenes)
-    int wide8_stack_need = 0;      // stack bound of the BVH8 (scenes walked from HBM)
-    bool has_envmap = false;
+    gdpt::SceneTraits traits;      // what chooses a render's route (host/scene_prepare.h), read by begin_launch
     int scene_spp = 0;             // <sampler sampleCount> of the description (default spp)
-    bool one_sided = true, lambert_only = true;
-    unsigned material_mask = 0;    // bit t = a material of type t is present
-    int plan_take_pct = 0;         // work-item plan: share of the unassigned samples a chunk takes (0 = default 55; 40 where a refractive lobe is present)
-    bool has_rough = false;        // RoughPlastic / RoughDielectric present: GradPath uses the evaluator built with those lobes
     std::vector<gdpt::DeviceBuffer<unsigned char>> allocations;   // the uploaded scene tables `view` points into
     // cached output/work buffers for the host-pointer entry points
     gdpt::DeviceBuffer<double> d_buf[9];
@@ -59,7 +53,6 @@ struct GdptScene {
     gdpt::DeviceBuffer<unsigned> d_wf_live, d_wf_counters;
     gdpt::PinnedBuffer<unsigned> h_wf_word;
     gdpt::DeviceBuffer<unsigned char> d_wf_aux;       // ray / hit records, sort keys and histogram, overflow stacks (render_kernels.hip: wf_aux_layout)
-    float bounds[6] = {0, 0, 0, 0, 0, 0};   // fp32 scene bounds (min xyz, max xyz), as get_intersection_epsilon sees them
     gdpt::Event wf_event;
     int num_cus = 256;
     gdpt::Event ev0, ev1;
@@ -82,8 +75,14 @@ struct GdptScene {
 
 
 namespace gdpt {
-// Own BVH build + HBM upload of a flattened scene (replaces Scene::Scene, src/scene.cpp:4-53).
+// A scene upload (replaces Scene::Scene, src/scene.cpp:4-53) is two steps: prepare_scene (host/scene_prepare.h) makes the tables on
+// the host, upload_scene copies them to `device` and creates the handle's scratch, streams and events there.
+void upload_scene(const PreparedScene &ps, int device, GdptScene *sc);
+// Both steps, with the upload knobs (presplit, sbvh) resolved: what gdpt_scene_upload does.
 void build_scene(const GdptSceneDesc *desc, int device, GdptScene *sc);
+// One scene per entry of `devices` (a device may be named twice), each with its scene_spp set: prepared once, uploaded by one thread
+// per device. The first error of any upload is rethrown after all threads have ended.
+std::vector<std::unique_ptr<GdptScene>> upload_scenes(const GdptSceneDesc *desc, const int32_t *devices, int n);
 // Enqueues one five-buffer render of rows [params->row_begin, row_end) on `stream`; waits only when `stats` is given.
 // `window` (nullable): the samples are a window of a larger stream block (include/gdpt.h: GdptSampleWindow).
 void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,

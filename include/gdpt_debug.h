@@ -95,6 +95,29 @@ int gdpt_debug_leaf_histogram(const struct GdptScene *scene, int32_t hist[4]);
 /* Every name gdpt_debug_last_route can return: fills out[0..n) and returns n, or -1 if `capacity` < n; out == NULL
  * returns n alone. */
 int gdpt_debug_route_names(const char **out, int capacity);
+/* The host half of a scene upload (csrc/host/scene_prepare.h: prepare_scene) on `desc`, with the default options of a product upload
+ * and no knob applied; makes no GPU call, so it runs where there is none. `info` receives the table sizes, the traits that choose a
+ * render's route, the intersection epsilon and a 64-bit FNV-1a digest of the bytes of every table (GDPT_PREPARED_* index it; an empty
+ * table digests to the FNV offset basis). light_pmf / light_cdf (either may be NULL) receive the emitter selection table, num_lights
+ * and num_lights + 1 entries; `capacity` = entries each of the two arrays can hold. Returns 0, or non-zero (message in
+ * gdpt_last_error: the one gdpt_scene_upload gives for the same description) on error or when `capacity` is too small. */
+enum { GDPT_PREPARED_NODES, GDPT_PREPARED_NODES4, GDPT_PREPARED_NODES8, GDPT_PREPARED_NODES4Q, GDPT_PREPARED_PRIMS, GDPT_PREPARED_TRIS,
+       GDPT_PREPARED_SPHERES, GDPT_PREPARED_MATERIALS, GDPT_PREPARED_LIGHT_INTENSITY, GDPT_PREPARED_IMAGES, GDPT_PREPARED_TEXELS,
+       GDPT_PREPARED_LIGHTS, GDPT_PREPARED_LIGHT_PMF, GDPT_PREPARED_LIGHT_CDF, GDPT_PREPARED_LIGHT_TRI_CDF, GDPT_PREPARED_LIGHT_TRI_POS,
+       GDPT_PREPARED_LIGHT_TRI_NRM, GDPT_PREPARED_ENV_CDF_ROWS, GDPT_PREPARED_ENV_PDF_ROWS, GDPT_PREPARED_ENV_CDF_MARGINALS,
+       GDPT_PREPARED_ENV_PDF_MARGINALS, GDPT_PREPARED_TABLES };
+typedef struct GdptPreparedInfo {
+    int64_t count[GDPT_PREPARED_TABLES];     /* elements of each table (records, or doubles for the fp64 pools) */
+    uint64_t digest[GDPT_PREPARED_TABLES];
+    double isect_eps;
+    float bounds[6];                         /* fp32 scene bounds: min xyz, max xyz */
+    int32_t bvh_depth, leaf_hist[4], wide_stack_need, wide8_stack_need;
+    int32_t one_sided, lambert_only, has_rough, plan_take_pct;
+    uint32_t material_mask;
+    int32_t has_envmap, env_w, env_h, all_textures_constant;
+} GdptPreparedInfo;
+struct GdptSceneDesc;
+int gdpt_debug_prepare_scene(const struct GdptSceneDesc *desc, GdptPreparedInfo *info, double *light_pmf, double *light_cdf, int capacity);
 /* Removes every override: the library is back on its product path. */
 void gdpt_debug_knobs_reset(void);
 

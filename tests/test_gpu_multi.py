@@ -166,6 +166,41 @@ def test_multi_device_set_equals_single_device(G, scene_tmp, devices, exchange, 
 
 
 @pytest.mark.gpu
+def test_scenes_uploaded_from_one_prepared_scene_are_each_complete(G, scene_tmp):
+    """gdpt_multi_create and gdpt_progressive_group_create prepare the scene once on the host and upload it once per member
+    (csrc/hip/capi_device.hip: upload_scenes). Every member's scene must be a whole one: each band of a two-member device set equals,
+    byte for byte, what a single handle renders for that band with the same plan_rows; and a two-member progressive group, whose
+    members render the whole film over their halves of the sample block, gives the bits of two slice sessions on ONE handle merged
+    in the same order."""
+    xml = scene_variant(scene_tmp, "cbox/cbox_gdpt.xml", width=64, height=64)
+    sd = G.parse_scene(xml)
+    one = G.Scene(sd)
+    ms = G.MultiScene(sd, (0, 0), exchange=G.EXCHANGE_PEER_COPY)
+    _, bufs, _, st = ms.gradient_path_render(4, G.RNG_SAMPLE, return_buffers=True)
+    bands = [(st.row_begin[i], st.row_end[i]) for i in range(2)]
+    assert bands == [(0, 32), (32, 64)]
+    for b0, b1 in bands:
+        want, _ = one.render(4, G.RNG_SAMPLE, rows=(b0, b1), plan_rows=32)
+        for k in BUFS:
+            assert bufs[k][b0:b1].tobytes() == want[k][b0:b1].tobytes(), (k, b0)
+    ms.close()
+    grp = G.ProgressiveGroup(sd, (0, 0), 8)
+    assert grp.run(pass_spp=2)["stop_reason"] == "budget"
+    acc = G.Progressive(one, 8, slice=(0, 0))
+    for first in (0, 4):
+        s = G.Progressive(one, 8, slice=(first, 4))
+        assert s.run(pass_spp=2)["stop_reason"] == "budget"
+        acc.merge(s)
+        s.close()
+    got, want = grp.total.read(), acc.read()
+    for g, w in zip(got, want):                       # means, variances of the mean, assembled variances
+        for k in w:
+            assert g[k].tobytes() == w[k].tobytes(), k
+    acc.close()
+    grp.close()
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("band", [0, 1, 2])
 @pytest.mark.parametrize("stage", [1, 2, 3, 4])
 def test_a_band_that_fails_does_not_hang_the_others(G, scene_tmp, band, stage):
