@@ -209,6 +209,13 @@ void join_scratch(GdptScene *sc) {
 // waiting at all lets a third kernel queue up while the small kernels of two frames (whose GEMMs need LDS the resident render blocks
 // hold) starve behind it: profiles/render_overlap_times.txt has both schemes, measured. Where the handle says so (need_fence) both render streams wait
 // for the caller's stream as it is now.
+// An overlapped launch's resets (counters, queue head) are enqueued here, on the render stream, behind its wait for the set's release
+// and AHEAD of its wait for the previous call: they depend on the set alone, and behind the second wait they were three small fills
+// between the previous frame's solve and this frame's kernel (18-19 us of the 37 us gap, profiles/render_overlap_times.txt). Nothing
+// reads a set's counters between its release and its next launch: their readers are the stats copy of run_launch (an in-stream launch,
+// which joins the render streams first and records `released` behind itself) and the synchronous copy of multi_gpu.hip (through
+// d_counters, after the host has waited for the render, before that host thread's next launch); the queue head is read by the render
+// kernel only, which the render stream orders.
 GdptLaunchScratch &claim_scratch(GdptScene *sc, bool overlap, bool capturing, size_t need, hipStream_t stream) {
     const int k = overlap ? (int)(sc->overlapped & 1) : 0;
     GdptLaunchScratch &ss = sc->scratch[k];
@@ -240,12 +247,15 @@ GdptLaunchScratch &claim_scratch(GdptScene *sc, bool overlap, bool capturing, si
             for (auto &o : sc->scratch) ck(hipStreamWaitEvent(stream, o.rendered, 0), "hipStreamWaitEvent(render stream)");
             sc->need_fence = true;
         }
+        if (ss.used) ck(hipStreamWaitEvent(sc->render_stream[k], ss.released, 0), "hipStreamWaitEvent(launch scratch)");
+        sc->in_flight = true;              // (from here on a render stream may hold work: GdptScene::join)
+        ck(hipMemsetAsync(ss.counters, 0, sizeof(gdpt::RenderCounters), sc->render_stream[k]), "hipMemsetAsync(counters)");
+        ck(hipMemsetAsync(ss.queue, 0, sizeof(unsigned long long), sc->render_stream[k]), "hipMemsetAsync(queue)");
         if (sc->need_fence || !prev_entry) {
             for (auto &st : sc->render_stream) ck(hipStreamWaitEvent(st, entry, 0), "hipStreamWaitEvent(fence)");
             sc->need_fence = false;
         } else
             ck(hipStreamWaitEvent(sc->render_stream[k], prev_entry, 0), "hipStreamWaitEvent(previous call)");
-        if (ss.used) ck(hipStreamWaitEvent(sc->render_stream[k], ss.released, 0), "hipStreamWaitEvent(launch scratch)");
     }
     sc->have_caller = true; sc->last_caller = stream;
     return ss;
@@ -293,17 +303,17 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     GdptLaunchScratch &ss = claim_scratch(sc, overlap, capturing, need, stream);
     rl.counters = ss.counters; sc->d_counters = ss.counters;
     if (gdpt::is_persistent(rl.route)) { rl.partials = ss.partials; rl.queue_head = ss.queue; }
-    if (overlap) { rl.kernel_stream = sc->render_stream[sc->overlapped & 1]; rl.kernel_done = ss.rendered; }
+    if (overlap) { rl.kernel_stream = sc->render_stream[sc->overlapped & 1]; rl.kernel_done = ss.rendered; rl.resets_enqueued = true; }   // (claim_scratch)
     claim->set = &ss; claim->record_release = !capturing;
     return rl;
 }
 
-// Enqueues the counter reset, the launch and, when stats are requested, waits for the render and reports it.
+// Enqueues the counter reset (unless claim_scratch has: an overlapped launch), the launch and, when stats are requested, waits for the render and reports it.
 void run_launch(GdptScene *sc, const gdpt::RenderLaunch &rl, const ScratchClaim &claim, const Band &b, hipStream_t stream, GdptRenderStats *stats) {
     const bool stamped = gdpt::is_stamped(rl.route);
     const hipStream_t ks = rl.kernel_stream ? rl.kernel_stream : stream;       // (begin_launch: an overlapped launch)
     if (rl.kernel_stream) sc->in_flight = true;           // (from here on a render stream may hold work: GdptScene::join)
-    ck(hipMemsetAsync(rl.counters, 0, sizeof(gdpt::RenderCounters), ks), "hipMemsetAsync(counters)");
+    if (!rl.resets_enqueued) ck(hipMemsetAsync(rl.counters, 0, sizeof(gdpt::RenderCounters), ks), "hipMemsetAsync(counters)");
     if (stamped) ck(hipMemsetAsync(&rl.counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), ks), "hipMemsetAsync(stamps)");   // min slots
     if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
     gdpt::launch_render(sc->view, rl, stream);

@@ -247,7 +247,9 @@ GD D2 filter_sample(int type, double param, double rx, double ry) {
     }
     return o;
 }
-GD D3 xform_point(const double *m, D3 p) {
+// (M: const double * or the same in the constant address space, see CamConst)
+template <class M>
+GD D3 xform_point(M m, D3 p) {
     double tx = m[0] * p.x + m[1] * p.y + m[2] * p.z + m[3];
     double ty = m[4] * p.x + m[5] * p.y + m[6] * p.z + m[7];
     double tz = m[8] * p.x + m[9] * p.y + m[10] * p.z + m[11];
@@ -255,7 +257,8 @@ GD D3 xform_point(const double *m, D3 p) {
     double inv_w = 1.0 / tw;
     return mk(tx * inv_w, ty * inv_w, tz * inv_w);
 }
-GD D3 xform_vector(const double *m, D3 v) {
+template <class M>
+GD D3 xform_vector(M m, D3 v) {
     return mk(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[4] * v.x + m[5] * v.y + m[6] * v.z, m[8] * v.x + m[9] * v.y + m[10] * v.z);
 }
 // `cache` (optional): the sub-pixel numbers (dx,dy) and filter offset of the lane's base ray. An offset ray whose
@@ -264,8 +267,11 @@ struct FilterCache { double dx, dy, ox, oy; };
 // PIXEL_SPACE: (sx, sy) are the pixel-space numbers (x + u, y + v) the caller would otherwise divide by the film extent.
 // For power-of-two films that division, the multiplication back (src/camera.cpp:26-27) and the division of the filtered
 // position are exact scalings by 2^-k: the fast path skips them and gets the reference's bits with four fp64 divisions less.
-template <bool PIXEL_SPACE = false>
-GD Ray sample_primary(const DevCamera &cam, double sx, double sy, FilterCache *cache = nullptr, bool store = false) {
+// CAM: DevCamera (a view's by-value copy: the compiler keeps what it reads of it in SGPRs for the whole kernel) or CamConst (the camera
+// where the kernel's arguments lie, read with scalar loads where it is used — the lane machine, render_device.h: camera_here).
+typedef const __attribute__((address_space(4))) DevCamera CamConst;
+template <bool PIXEL_SPACE = false, class CAM = const DevCamera>
+GD Ray sample_primary(CAM &cam, double sx, double sy, FilterCache *cache = nullptr, bool store = false) {
     const bool exact = PIXEL_SPACE && cam.pow2_film != 0;        // wave-uniform
     if (PIXEL_SPACE && !exact) { sx = sx / cam.width; sy = sy / cam.height; }
     double ppx = exact ? sx : sx * cam.width, ppy = exact ? sy : sy * cam.height;
@@ -279,11 +285,11 @@ GD Ray sample_primary(const DevCamera &cam, double sx, double sy, FilterCache *c
     double rx, ry;
     if (exact) { rx = (fx + 0.5 + off.x) * cam.inv_width; ry = (fy + 0.5 + off.y) * cam.inv_height; }
     else { rx = (fx + 0.5 + off.x) / cam.width; ry = (fy + 0.5 + off.y) / cam.height; }
-    D3 pt = xform_point(cam.sample_to_cam, mk(rx, ry, 0.0));
+    D3 pt = xform_point(&cam.sample_to_cam[0], mk(rx, ry, 0.0));
     D3 dir = normalize(pt);
     Ray r;
     r.org = mk(cam.org[0], cam.org[1], cam.org[2]);
-    r.dir = normalize(xform_vector(cam.cam_to_world, dir));
+    r.dir = normalize(xform_vector(&cam.cam_to_world[0], dir));
     r.tnear = 0; r.tfar = __builtin_huge_val();
     return r;
 }

@@ -34,6 +34,7 @@
 #include "render_kernels.h"
 #include "device_trace.h"
 #include "../leaf_cursor.h"
+#include "../item_slice.h"
 
 namespace gd {
 
@@ -747,10 +748,11 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
     // with the base path's bounce-1 numbers (:773-959). One copy of the code, run by both groups together.
     const bool off_valid = (st0 == S_OFFSET) && hit && nv.material_id == L.mat0();                   // :424-443
     const bool off_resample = off_valid && (L.cmode() == C_AFTER_BOUNCE1 || L.cmode() == C_BROKE_BOUNCE2);
-    bool sampled = false;
-    BsdfSample bs; bs.dir_out = splat(0); bs.eta = 0; bs.roughness = 0;
-    D3 f = splat(0);
-    double pdf = 0;
+    bool sampled = false, arm = false;
+    // (bs is read where `sampled`, f and pdf where mat_eval_pdf ran: the Lambertian lobe writes all of them on those paths, and
+    // its kernels do not pay for zeros nothing reads. The full switch keeps them: not every lobe was checked.)
+    BsdfSample bs; D3 f; double pdf;
+    if (!LAMBERT) { bs.dir_out = splat(0); bs.eta = 0; bs.roughness = 0; f = splat(0); pdf = 0; }
     if (act == ACT_BOUNCE || off_resample) {
         D2 ruv; double rw;
         if (act == ACT_BOUNCE) {
@@ -798,28 +800,34 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
                 if (L.num_vertices == 3) { L.kc = C_BROKE_BOUNCE1 << 2; act = ACT_OFFSETS; }           // hit is unobservable
                 else if (L.num_vertices == 4 && L.mat0() == L.mat1()) { L.kc = C_BROKE_BOUNCE2 << 2; act = ACT_OFFSETS; }   // :607-612 passed
                 else { acc_no_offsets(acc, lp.radiance(), L.contrib, L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
-            } else {
-                L.org = nv.position; L.dir = bs.dir_out; L.f = f; L.pdf = pdf; L.st = S_BOUNCE;
-            }
+            } else arm = true;
         }
     }
     stamps.mark(SEG_FINISH);
+    // the bounce ray, written to the lane in one place at the function's top level: set inside the branches above, the pending ray, f
+    // and pdf were copied aside and back at every join the lanes that do not bounce pass (act stays ACT_BOUNCE only here)
+    if (arm) { L.org = nv.position; L.dir = bs.dir_out; L.f = f; L.pdf = pdf; L.st = S_BOUNCE; }
     if (act == ACT_OFFSETS) { L.kc &= ~3; act = ACT_OFFSET_RAY; }
     if (act == ACT_NEXT_SAMPLE) {
         L.s++;
         if (L.s >= L.s_end) L.st = S_DONE; else act = ACT_PRIMARY_RAY;
     }
-    if (L.st == S_BOUNCE && act == ACT_BOUNCE) trav_init(sv, tv, __builtin_huge_val());       // a bounce ray was armed
     return act;
+}
+
+// A step that leaves the lane a fresh pending ray arms the walk for it, in one place behind both halves: ACT_BOUNCE (lane_consume armed a
+// bounce ray), ACT_PRIMARY_RAY / ACT_OFFSET_RAY (lane_camera made a camera ray).
+GD void lane_arm(const DevSceneView &sv, int act, Trav &tv) {
+    if (act == ACT_BOUNCE || act == ACT_PRIMARY_RAY || act == ACT_OFFSET_RAY) trav_init(sv, tv, __builtin_huge_val());
 }
 
 // Second half of a lane's step: the camera ray of the next sample (ACT_PRIMARY_RAY) or of the next offset (ACT_OFFSET_RAY).
 // Separate from lane_consume so that the persistent kernels can hand a NEW ITEM to a lane whose item has just ended in
 // between: its first camera ray is then made in the same step instead of one trace phase later.
-template <bool SERIAL_RNG, class STAMPS = Stamps<false>>
-GD void lane_camera(const DevSceneView &sv, int act, int x, int y, unsigned long long base, Lane &L, Trav &tv, LanePriv &lp, STAMPS *stp = nullptr) {
+// `cam`: sv.cam, or the same camera where it is read at its point of use (camera_here).
+template <bool SERIAL_RNG, class STAMPS = Stamps<false>, class CAM = const DevCamera>
+GD void lane_camera(const DevSceneView &sv, CAM &cam, int act, int x, int y, unsigned long long base, Lane &L, Trav &tv, LanePriv &lp, STAMPS *stp = nullptr) {
     STAMPS none{}; STAMPS &stamps = stp ? *stp : none;
-    const DevCamera &cam = sv.cam;
     if (act == ACT_PRIMARY_RAY || act == ACT_OFFSET_RAY) {
         double rx, ry;
         int ox = 0, oy = 0;
@@ -842,8 +850,7 @@ GD void lane_camera(const DevSceneView &sv, int act, int x, int y, unsigned long
         if (act == ACT_OFFSET_RAY) fc = lp.fc();
         Ray r = sample_primary<true>(cam, (x + ox) + rx, (y + oy) + ry, &fc, act == ACT_PRIMARY_RAY);
         if (act == ACT_PRIMARY_RAY) lp.set_fc(fc);
-        L.org = r.org; L.dir = r.dir;
-        trav_init(sv, tv, __builtin_huge_val());                                    // a fresh pending ray
+        L.org = r.org; L.dir = r.dir;                                               // a fresh pending ray: the caller arms the walk (lane_arm)
     }
     stamps.mark(SEG_CAMERA);
 }
@@ -853,7 +860,8 @@ template <bool LAMBERT, bool SERIAL_RNG, class ACC, class STAMPS = Stamps<false>
 GD void lane_step(const DevSceneView &sv, const TraceCtx &tx, int max_depth, double spp, int x, int y, unsigned long long base,
                   Lane &L, Trav &tv, LanePriv &lp, ACC &acc, LaneCounters &lc, TraceCounters &tc, STAMPS *stp = nullptr) {
     const int act = lane_consume<LAMBERT, SERIAL_RNG, ACC, STAMPS, PLAIN>(sv, tx, max_depth, spp, base, L, tv, lp, acc, lc, tc, stp);
-    lane_camera<SERIAL_RNG, STAMPS>(sv, act, x, y, base, L, tv, lp, stp);
+    lane_camera<SERIAL_RNG, STAMPS>(sv, sv.cam, act, x, y, base, L, tv, lp, stp);
+    lane_arm(sv, act, tv);
 }
 
 // The lane machine's two halves. trace_pending: traversal of the wave's unfinished pending rays, left when at most
@@ -1016,6 +1024,63 @@ struct WaveQueue {
     }
 };
 
+// The same queue for the one-sided lane machine (the two-sided and path machines keep WaveQueue). Same hand-out: the same atomicAdd on
+// the 64-bit head with the same `want`, the same items to the same lanes. What differs is the bookkeeping:
+//   * num_items < 2^32 (render_kernels.hip: start_queue refuses more), so next / end are 32-bit, and the head a wave last saw is `end`
+//     (WaveQueue::seen_head differs from end only once the queue is exhausted, when it is no longer read). A head past num_items (the
+//     other waves' last atomics push it at most waves * 64 further) is clamped to num_items before it is narrowed;
+//   * they are wave-uniform and read from the leader's lane with v_readlane, so they live in SGPRs and cost no vector issue per step;
+//   * the slice's first item is taken apart once per refill (item_slice.h), on those uniform values; a lane's item follows by carry
+//     instead of two 32-bit divisions per started item.
+constexpr unsigned kNoItem = 0xFFFFFFFFu;        // (an item index is < num_items <= 2^32 - 1)
+struct SliceQueue {
+    unsigned next = 0, end = 0, start = 0;       // items [next, end) of the slice that began at `start` are not handed out yet
+    ItemSlice slice = {0, 0, 0, 0};              // `start` taken apart
+    bool exhausted = false;
+    // `item`: kNoItem, or the lane's new item with its parts in `parts`.
+    GD unsigned take(const KernelArgs &a, bool idle, int tid, ItemParts &parts) {
+        unsigned item = kNoItem;
+        const unsigned long long m_idle = __ballot(idle);
+        if (m_idle) {
+            const unsigned num_items = (unsigned)a.num_items, num_slots = (unsigned)a.num_slots, tiles_x = (unsigned)a.tiles_x;
+            if (next >= end && !exhausted) {
+                const unsigned left = num_items - end;
+                const unsigned waves = gridDim.x * (unsigned)(kBlock / 64);
+                const unsigned n_idle_now = (unsigned)__popcll(m_idle);
+                unsigned want = 64;
+                if (left < waves * 64u) { want = left / (waves * 2u); want = want > 64u ? 64u : (want < n_idle_now ? n_idle_now : want); }
+                unsigned long long got = 0;
+                if ((tid & 63) == 0) got = atomicAdd(a.queue_head, (unsigned long long)want);
+                const unsigned got_lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)got, 0);
+                const unsigned got_hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(got >> 32), 0);
+                if (got_hi != 0u || got_lo >= num_items) { exhausted = true; next = end = start = num_items; }
+                else {
+                    next = start = got_lo;
+                    end = (want < num_items - got_lo) ? got_lo + want : num_items;
+                    slice = item_slice_begin(start, num_slots, tiles_x);
+                }
+            }
+            const unsigned avail = end - next;
+            const unsigned rank = (unsigned)__popcll(m_idle & ((1ull << (tid & 63)) - 1ull));
+            if (idle && rank < avail) { item = next + rank; parts = item_slice_at(slice, item - start, num_slots, tiles_x); }
+            const unsigned n_idle = (unsigned)__popcll(m_idle);
+            next += (n_idle < avail) ? n_idle : avail;
+        }
+        return item;
+    }
+};
+
+// The camera of a kernel whose first argument is the DevSceneView, read where that argument lies (the kernel-argument segment, constant
+// address space: scalar loads). The by-value `sv.cam` is loop-invariant to the compiler, which loads the two 4x4 matrices (64 SGPRs) ahead
+// of the lane machine's loop and spills other SGPRs to VGPR lanes around them for the whole kernel. The pointer returned here is opaque to
+// the compiler (an empty asm), so what is read through it is loaded behind the call, where the camera block uses it, and is dead after it.
+static_assert(offsetof(DevSceneView, cam) == 0, "camera_here reads the camera at the start of the kernel's first argument");
+GD CamConst &camera_here() {
+    CamConst *p = (CamConst *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+
 // SAMPLE stream, persistent threads. Every lane repeatedly takes a work item (pixel, chunk of the pixel's samples)
 // from a global queue — fetched 64 at a time per wave with one atomicAdd — and runs the lane machine on it; a lane
 // that finishes early picks up the next item instead of idling behind the longest path of its wave. Per-item sums go
@@ -1053,8 +1118,8 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
     L.org = L.dir = splat(0);
     int x = 0, y = 0;
     unsigned long long base = 0;
-    long long my_item = -1;
-    WaveQueue wq;
+    unsigned my_item = kNoItem;
+    SliceQueue wq;
     __shared__ unsigned long long s_stamps[STAMPED ? (kBlock / 64) * (SEG_COUNT + 1) : 1];
     Stamps<STAMPED> stamps;
     stamps.start(s_stamps + (STAMPED ? (tid >> 6) * (SEG_COUNT + 1) : 0));
@@ -1067,7 +1132,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
     constexpr bool QUEUE_MID = LAMBERT;
     auto hand_out = [&](int &act) __attribute__((always_inline)) {
         const bool idle = (L.st == S_DONE);
-        if (idle && my_item >= 0) {                     // item finished: publish its 15 sums, clear the slot
+        if (idle && my_item != kNoItem) {               // item finished: publish its 15 sums, clear the slot
             Accum r = acc.result();
             // one 128-byte record per item (15 sums + pad), written as eight 16-byte stores: a single HBM line
             typedef double d2 __attribute__((ext_vector_type(2)));
@@ -1075,16 +1140,19 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             dst[0] = d2{r.r.x, r.r.y}; dst[1] = d2{r.r.z, r.dx0.x}; dst[2] = d2{r.dx0.y, r.dx0.z}; dst[3] = d2{r.dy0.x, r.dy0.y};
             dst[4] = d2{r.dy0.z, r.dx1.x}; dst[5] = d2{r.dx1.y, r.dx1.z}; dst[6] = d2{r.dy1.x, r.dy1.y}; dst[7] = d2{r.dy1.z, 0.0};
             acc.init();
-            my_item = -1;
+            my_item = kNoItem;
         }
         stamps.mark(SEG_PUBLISH);
-        const long long got_item = wq.take(a, idle, tid);
+        ItemParts parts;
+        const unsigned got_item = wq.take(a, idle, tid, parts);
         stamps.mark(SEG_TAKE);
         if (STAMPED && wq.exhausted && t_dry == ~0ull) t_dry = __builtin_amdgcn_s_memrealtime();
-        if (got_item >= 0) {
+        if (got_item != kNoItem) {
             my_item = got_item;
-            int s0, s1;
-            const bool inside = item_to_pixel(a, W, (unsigned)my_item, x, y, s0, s1, s_chunks);
+            // item_to_pixel with the parts the queue carried from the slice's first item (no division here)
+            x = (int)(parts.tx * 16u + (parts.pin & 15u)); y = a.row_begin + (int)(parts.ty * 16u + (parts.pin >> 4));
+            const int s0 = s_chunks[parts.c], s1 = s_chunks[parts.c + 1];
+            const bool inside = x < W && y < a.row_end;
             base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;     // (s0, s1 carry the window's first_sample)
             L.s = s0; L.s_end = s1;
             if (inside && s0 < s1) act = ACT_PRIMARY_RAY;       // (an empty slot of a ragged edge tile stays S_DONE and is published as zeros)
@@ -1110,7 +1178,8 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
         }
         if (QUEUE_MID) hand_out(act);
         // ---- (S, second half) camera rays: next sample, next offset, first sample of a new item
-        lane_camera<false, Stamps<STAMPED>>(sv, act, x, y, base, L, tv, lp, &stamps);
+        lane_camera<false, Stamps<STAMPED>>(sv, camera_here(), act, x, y, base, L, tv, lp, &stamps);
+        lane_arm(sv, act, tv);
         if (QUEUE_MID) {
             if (!__any(L.st != S_DONE) && wq.exhausted) break;
             stamps.mark(SEG_QUEUE);

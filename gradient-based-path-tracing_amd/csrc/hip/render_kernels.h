@@ -104,6 +104,9 @@ struct RenderLaunch {
     // go on kernel_stream, kernel_done is recorded behind them and the caller's stream waits for it before gdpt_reduce_partials
     hipStream_t kernel_stream;
     hipEvent_t kernel_done;
+    // an overlapped launch whose counters and queue head were zeroed on kernel_stream when its scratch set was claimed, ahead of the
+    // stream's wait for the previous call (capi_device.hip: claim_scratch): launch_render then enqueues no reset of its own
+    bool resets_enqueued;
 };
 bool scene_fits_lds(int num_nodes, int num_prims, int num_tris, int num_materials, int num_lights, int bvh_depth);
 bool scene_fits_lds_wide(int num_nodes4, int num_prims, int num_tris, int num_materials, int num_lights, int wide_stack_need);

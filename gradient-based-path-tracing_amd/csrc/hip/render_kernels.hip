@@ -119,7 +119,7 @@ static dim3 start_queue(gd::KernelArgs &a, const RenderLaunch &rl, int W, hipStr
     if (a.num_items >= (1LL << 32)) throw std::runtime_error("launch_render: image band too large for the 32-bit work queue");
     a.partials = rl.partials; a.queue_head = rl.queue_head;
     if (!a.partials || !a.queue_head) throw std::runtime_error("launch_render: work-queue buffers missing");
-    if (hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), stream) != hipSuccess) throw std::runtime_error("launch_render: queue reset failed");
+    if (!rl.resets_enqueued && hipMemsetAsync(a.queue_head, 0, sizeof(unsigned long long), stream) != hipSuccess) throw std::runtime_error("launch_render: queue reset failed");
     return dim3(persistent_blocks(rl, a.num_items));
 }
 
@@ -205,6 +205,7 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
     const Route r = rl.route;
     // an overlapped launch (rl.kernel_stream): queue reset and render kernel on that stream; what writes the images stays on `stream`
     if (rl.kernel_stream && (!can_overlap(r) || !rl.kernel_done)) throw std::runtime_error("launch_render: this route does not overlap");
+    if (rl.resets_enqueued && !rl.kernel_stream) throw std::runtime_error("launch_render: resets enqueued ahead of a launch that does not overlap");
     const hipStream_t ks = rl.kernel_stream ? rl.kernel_stream : stream;
     gd::KernelArgs a{};
     a.spp = rl.spp; a.stream_spp = rl.stream_spp; a.first_sample = rl.first_sample; a.row_begin = rl.row_begin; a.row_end = rl.row_end; a.max_depth = rl.max_depth;
