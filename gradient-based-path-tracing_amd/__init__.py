@@ -84,6 +84,12 @@ def lib():
         L.gdpt_progressive_group_reconstruct_error.argtypes = [vp, grp, C.c_int, vp, vp, vp, sst, C.POINTER(defs.GdptReconStats)]
         L.gdpt_progressive_group_run_recon.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.c_int, grp,
                                                        C.POINTER(defs.GdptProgressiveStatus), sst]
+        nlp, nls = C.POINTER(defs.GdptNlmParams), C.POINTER(defs.GdptNlmStats)
+        L.gdpt_nlm_default_params.argtypes = [nlp]
+        L.gdpt_nlm_default_params.restype = None
+        L.gdpt_denoise_nlm_device.argtypes = [C.c_int, C.c_int, vp, vp, nlp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm.argtypes = [C.c_int, C.c_int, vp, vp, nlp, vp, vp, nls]
+        L.gdpt_progressive_denoise.argtypes = [vp, nlp, C.c_int, vp, vp, nls]
         L.gdpt_assemble_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gdpt_poisson_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         L.gdpt_poisson_solve_ex.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, C.c_int, C.c_double, C.c_int,
@@ -423,6 +429,20 @@ class Progressive:
                                                            _ptr_table([a.ctypes.data for a in planes] if confidence else None), C.byref(st)))
         return (out, np.stack(planes, axis=2), st) if confidence else (out, st)
 
+    def denoise(self, out_ptr=None, var_out_ptr=None, **params):
+        """The non-local-means filter on buffer 0 (gdpt_progressive_denoise; from 2 passes on): the running mean of the image of a Path
+        session, or of the primal of a GradPath session, with the variance of that mean (`params`: the keywords of nlm_params).
+        Returns (HxWx3 filtered mean, HxWx3 variance of it, GdptNlmStats); with `out_ptr` (and `var_out_ptr`) everything stays in
+        device memory and the stats alone are returned."""
+        p, st = nlm_params(**params), defs.GdptNlmStats()
+        if out_ptr is not None:
+            _check(lib().gdpt_progressive_denoise(self.handle, C.byref(p), 1, C.c_void_p(int(out_ptr)),
+                                                  C.c_void_p(int(var_out_ptr)) if var_out_ptr else None, C.byref(st)))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        _check(lib().gdpt_progressive_denoise(self.handle, C.byref(p), 0, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.byref(st)))
+        return out, var_out, st
+
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
         <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
@@ -622,6 +642,52 @@ def recon_spread_device(width, height, image_ptrs, weights, total_ptr=None, radi
     opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
     _check(lib().gdpt_recon_spread_device(int(width), int(height), n, tab, _dp(w), opt(total_ptr), int(radius), opt(var_ptr), opt(map_ptr),
                                           opt(stream), C.byref(st)))
+    return st
+
+
+def nlm_params(window_radius=None, patch_radius=None, k=None, alpha=None, epsilon=None):
+    """GdptNlmParams (include/gdpt.h): the library's defaults (gdpt_nlm_default_params: window radius 10, patch radius 3, k 0.45,
+    alpha 1, epsilon 1e-10) with the keywords given in their places, taken literally."""
+    p = defs.GdptNlmParams()
+    lib().gdpt_nlm_default_params(C.byref(p))
+    if window_radius is not None:
+        p.window_radius = int(window_radius)
+    if patch_radius is not None:
+        p.patch_radius = int(patch_radius)
+    if k is not None:
+        p.k = float(k)
+    if alpha is not None:
+        p.alpha = float(alpha)
+    if epsilon is not None:
+        p.epsilon = float(epsilon)
+    return p
+
+
+def denoise_nlm(img, var, **params):
+    """Non-local means with variance-cancelling patch distances on the GPU (gdpt_denoise_nlm): `img` a mean and `var` the variance of
+    that mean, HxWx3 float64 (what Progressive.read() returns); `params`: the keywords of nlm_params. Returns (HxWx3 filtered image,
+    HxWx3 variance of it with the weights taken as fixed, GdptNlmStats). Pixels with a non-finite value or a negative variance are
+    returned unchanged and counted in stats.pixels_left_out."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm: img and var must be HxWx3 arrays of one shape")
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = nlm_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_nlm(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data), C.byref(p),
+                                  C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_nlm_device(width, height, img_ptr, var_ptr, out_ptr, var_out_ptr=None, stream=None, stats=True, params=None, **kw):
+    """denoise_nlm() on device addresses (gdpt_denoise_nlm_device); `var_out_ptr` may be None. `params`: a GdptNlmParams taken as it
+    is (else the keywords of nlm_params). Returns GdptNlmStats after waiting for `stream`; with `stats=False` the call only enqueues
+    and returns None."""
+    p = params if params is not None else nlm_params(**kw)
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_device(int(width), int(height), opt(img_ptr), opt(var_ptr), C.byref(p), opt(out_ptr), opt(var_out_ptr),
+                                         opt(stream), C.byref(st) if stats else None))
     return st
 
 
@@ -914,7 +980,7 @@ class debug_knobs:
         """GDPT_FORCE_EAGER=1 -> force_eager=1 ... for the manual sweep scripts (tests/sweep_*.py, tune_render.py)."""
         environ = os.environ if environ is None else environ
         names = ("force_eager", "log2k", "keep_frac", "search_frac", "blocks_per_cu", "no_lds_scene", "lds_wide",
-                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips")
+                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct")
         lib().gdpt_debug_knobs_reset()
         for n in names:
             v = environ.get("GDPT_" + n.upper())

@@ -127,6 +127,17 @@ class GdptReconSpreadStats(C.Structure):
                 ("sum_sq", C.c_double), ("pixels_left_out", C.c_uint64), ("spread_ms", C.c_double)]
 
 
+class GdptNlmParams(C.Structure):
+    _fields_ = [("window_radius", C.c_int32), ("patch_radius", C.c_int32), ("k", C.c_double), ("alpha", C.c_double), ("epsilon", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
+class GdptNlmStats(C.Structure):
+    _fields_ = [("pixels_left_out", C.c_uint64), ("sum_var_in", C.c_double), ("sum_sq_in", C.c_double), ("sum_var_out", C.c_double),
+                ("sum_sq_out", C.c_double), ("error_in", C.c_double), ("error_out", C.c_double), ("filter_ms", C.c_double),
+                ("window_radius", C.c_int32), ("patch_radius", C.c_int32)]
+
+
 class GdptGroupReconParams(C.Structure):
     _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
                 ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]

@@ -1,0 +1,413 @@
+// denoise_nlm.hip — non-local means with variance-cancelling patch distances on (mean, variance of the mean), for gfx950
+// (include/gdpt.h: gdpt_denoise_nlm*, where the definition stands; Rousselle, Knaus, Zwicker 2012, sections 4-5).
+//
+// Kernels: two forms of the one definition, chosen by the test knob nlm_direct (include/gdpt_debug.h). Both loop over 16 x 16 tiles
+// as box_kernel (recon_spread.hip) does, a thread on a pixel of the tile, and both leave block partials through prg::block_sum for
+// prg's finish_kernel: a fixed order, the same bits every time.
+//   direct_kernel   the literal definition: the loops over the window offsets o and the patch taps n read global memory, every
+//                   pair distance e_o(p + n) is computed where it is used, (2r+1)^2 (2f+1)^2 of them per pixel.
+//   tiled_kernel    the tile with a halo of r + f pixels staged in LDS, plane by plane (three u, three v, a validity flag; out-of-film
+//                   and invalid entries are u = v = 0, flag 0), sized by the call's r and f: (16 + 2(r+f))^2 entries of 52 bytes,
+//                   42 x 42 = 91.7 KB at r = 10, f = 3. Per window offset: e_o and its count on the (16 + 2f)^2 points the tile's
+//                   patches touch, into LDS; row sums of 2f + 1 taps; column sums of the row sums (the separable box of box_kernel);
+//                   exp, and the three numerators, the weight sum and the three w^2 v sums accumulate in registers. (16 + 2f)^2
+//                   pair distances per offset and tile instead of 256 (2f+1)^2: 484 against 12544 at f = 3.
+//                   LDS banking: every plane is a plane of doubles or of ints, so consecutive lanes read consecutive elements. In the
+//                   row pass a half-wave covers two rows of 16 outputs; the e plane's pitch is 16 (f = 0) or 48 doubles, = 16 mod 32,
+//                   which puts the second row's 16 doubles on the other half of the 64 banks. In the column pass a half-wave reads 32
+//                   consecutive doubles of the row sums (pitch 16).
+#include "../../../include/gdpt.h"
+#include "../capi_common.h"
+#include "progressive_internal.h"
+#include "denoise_nlm.h"
+
+#include <algorithm>
+#include <cmath>
+#include <mutex>
+#include <vector>
+
+namespace nlm {
+
+constexpr int kBlock = prg::kBlock, kMaxBlocks = prg::kMaxBlocks;
+constexpr int kTile = 16;
+constexpr int kMaxR = GDPT_NLM_MAX_WINDOW_RADIUS, kMaxF = GDPT_NLM_MAX_PATCH_RADIUS;
+static_assert(kTile * kTile == kBlock, "one thread per tile pixel");
+static_assert((kTile + 2 * kMaxF) * (kTile + 2 * kMaxF) <= 2 * kBlock, "a thread computes at most two pair distances per offset");
+
+struct Args {
+    int w, h, tiles_x, tiles, r, f;
+    double k2, alpha, eps;
+    const double *img, *var;
+    double *out, *var_out;       // var_out nullable
+    double *partials;            // [0] sum var in, [1] sum u^2 in, [2] pixels left out, [3] sum var out, [4] sum u^2 out, [5] = [2]; gridDim.x doubles each
+};
+
+// pitch of the e plane for patches of ew = 16 + 2f points a row
+__host__ __device__ inline int e_pitch(int f) { return f == 0 ? kTile : 48; }
+// doubles, then ints, of the tiled kernel's LDS
+__host__ __device__ inline int lds_doubles(int r, int f) {
+    const int sw = kTile + 2 * (r + f), ew = kTile + 2 * f;
+    return 6 * sw * sw + e_pitch(f) * ew + kTile * ew;
+}
+__host__ __device__ inline int lds_ints(int r, int f) {
+    const int sw = kTile + 2 * (r + f), ew = kTile + 2 * f;
+    return sw * sw + e_pitch(f) * ew + kTile * ew;
+}
+
+__device__ __forceinline__ bool valid_triples(const double u[3], const double v[3]) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < 3; c++) ok = ok && isfinite(u[c]) && isfinite(v[c]) && v[c] >= 0.0;
+    return ok;
+}
+
+// e_o(x) of two valid pixels a = x, b = x + o
+__device__ __forceinline__ double pair_distance(const double ua[3], const double va[3], const double ub[3], const double vb[3], double k2,
+                                                double alpha, double eps) {
+    double t[3];
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double d = ua[c] - ub[c];
+        t[c] = (d * d - alpha * (va[c] + fmin(vb[c], va[c]))) / (eps + k2 * (va[c] + vb[c]));
+    }
+    return ((t[0] + t[1]) + t[2]) / 3.0;
+}
+
+struct Accum {
+    double num[3] = {0.0, 0.0, 0.0}, vnum[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
+    __device__ __forceinline__ void add(double S, int C, const double u[3], const double v[3]) {
+        double D = S / (double)C;
+        D = D > 0.0 ? D : 0.0;
+        const double wgt = exp(-D);
+        wsum += wgt;
+#pragma unroll
+        for (int c = 0; c < 3; c++) { num[c] += wgt * u[c]; vnum[c] += (wgt * wgt) * v[c]; }
+    }
+};
+
+struct Sums {
+    double var_in = 0.0, sq_in = 0.0, var_out = 0.0, sq_out = 0.0, left_out = 0.0;
+};
+
+// the pixel's outputs and its terms of the film sums; u, v: its valid input triples
+__device__ __forceinline__ void finish_pixel(const Args &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
+    double o[3], vo[3];
+    const double w2 = acc.wsum * acc.wsum;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        o[c] = acc.num[c] / acc.wsum;
+        vo[c] = acc.vnum[c] / w2;
+        a.out[i + c] = o[c];
+        if (a.var_out) a.var_out[i + c] = vo[c];
+    }
+    s.var_in += (v[0] + v[1]) + v[2];
+    s.sq_in += (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+    s.var_out += (vo[0] + vo[1]) + vo[2];
+    s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+}
+
+__device__ __forceinline__ void keep_pixel(const Args &a, size_t i, const double u[3], const double v[3], Sums &s) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        a.out[i + c] = u[c];
+        if (a.var_out) a.var_out[i + c] = v[c];
+    }
+    s.left_out += 1.0;
+}
+
+__device__ __forceinline__ void leave_partials(const Args &a, const Sums &s, double *red) {
+    const int nb = gridDim.x;
+    double r;
+    r = prg::block_sum(s.var_in, red); if (threadIdx.x == 0) a.partials[0 * nb + blockIdx.x] = r;
+    r = prg::block_sum(s.sq_in, red); if (threadIdx.x == 0) a.partials[1 * nb + blockIdx.x] = r;
+    r = prg::block_sum(s.left_out, red); if (threadIdx.x == 0) { a.partials[2 * nb + blockIdx.x] = r; a.partials[5 * nb + blockIdx.x] = r; }
+    r = prg::block_sum(s.var_out, red); if (threadIdx.x == 0) a.partials[3 * nb + blockIdx.x] = r;
+    r = prg::block_sum(s.sq_out, red); if (threadIdx.x == 0) a.partials[4 * nb + blockIdx.x] = r;
+}
+
+// the triples of film pixel (x, y), which is inside the film; returns whether it is valid
+__device__ __forceinline__ bool load_pixel(const Args &a, int x, int y, double u[3], double v[3]) {
+    const size_t i = ((size_t)y * a.w + x) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++) { u[c] = a.img[i + c]; v[c] = a.var[i + c]; }
+    return valid_triples(u, v);
+}
+
+__global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
+    __shared__ double red[kBlock / 64];
+    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x / kTile;
+    const int r = a.r, f = a.f;
+    Sums s;
+    for (int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+        const int x = tx * kTile + lx, y = ty * kTile + ly;
+        if (x >= a.w || y >= a.h) continue;
+        const size_t i = ((size_t)y * a.w + x) * 3;
+        double u[3], v[3];
+        if (!load_pixel(a, x, y, u, v)) { keep_pixel(a, i, u, v, s); continue; }
+        Accum acc;
+        for (int oy = -r; oy <= r; oy++)
+            for (int ox = -r; ox <= r; ox++) {
+                const int qx = x + ox, qy = y + oy;
+                if (qx < 0 || qy < 0 || qx >= a.w || qy >= a.h) continue;
+                double uq[3], vq[3];
+                if (!load_pixel(a, qx, qy, uq, vq)) continue;
+                double S = 0.0;
+                int C = 0;
+                for (int ny = -f; ny <= f; ny++)
+                    for (int nx = -f; nx <= f; nx++) {
+                        const int ax = x + nx, ay = y + ny, bx = ax + ox, by = ay + oy;
+                        if (ax < 0 || ay < 0 || ax >= a.w || ay >= a.h || bx < 0 || by < 0 || bx >= a.w || by >= a.h) continue;
+                        double ua[3], va[3], ub[3], vb[3];
+                        const bool oka = load_pixel(a, ax, ay, ua, va), okb = load_pixel(a, bx, by, ub, vb);
+                        if (!oka || !okb) continue;
+                        S += pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
+                        C++;
+                    }
+                acc.add(S, C, uq, vq);      // (C >= 1: the tap n = 0 counts)
+            }
+        finish_pixel(a, i, u, v, acc, s);
+    }
+    leave_partials(a, s, red);
+}
+
+__global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
+    extern __shared__ double lds[];
+    __shared__ double red[kBlock / 64];
+    const int r = a.r, f = a.f, halo = r + f;
+    const int sw = kTile + 2 * halo, sn = sw * sw;      // the stage: the tile and its halo
+    const int ew = kTile + 2 * f, en = ew * ew;         // the points the tile's patches touch
+    const int ep = e_pitch(f), taps = 2 * f + 1;
+    double *const su = lds, *const sv = lds + 3 * sn;   // plane c at su + c sn, sv + c sn
+    double *const pe = lds + 6 * sn;                    // e_o of the current offset, pitch ep
+    double *const ph = pe + ep * ew;                    // its row sums, pitch 16
+    int *const sflag = (int *)(ph + kTile * ew);
+    int *const ce = sflag + sn, *const ch = ce + ep * ew;
+    const int tid = threadIdx.x, lx = tid & (kTile - 1), ly = tid / kTile;
+    // the (at most two) pair distances and row sums of an offset that fall to this thread
+    int ia[2], ie[2], jrow[2];
+    for (int k = 0; k < 2; k++) {
+        const int q = tid + k * kBlock;
+        const int qy = q / ew, qx = q - qy * ew;
+        ia[k] = q < en ? (qy + r) * sw + qx + r : -1;
+        ie[k] = qy * ep + qx;
+        jrow[k] = q < kTile * ew ? (q / kTile) * ep + (q & (kTile - 1)) : -1;
+    }
+    const int pc = (ly + halo) * sw + lx + halo;        // the thread's own pixel in the stage
+    Sums s;
+    for (int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
+        const int x0 = tx * kTile, y0 = ty * kTile;
+        __syncthreads();                                // the previous tile's stage has been read
+        for (int k = tid; k < sn; k += kBlock) {
+            const int ry = k / sw, rx = k - ry * sw;
+            const int gx = x0 - halo + rx, gy = y0 - halo + ry;
+            double u[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+            bool ok = false;
+            if (gx >= 0 && gy >= 0 && gx < a.w && gy < a.h) ok = load_pixel(a, gx, gy, u, v);
+#pragma unroll
+            for (int c = 0; c < 3; c++) { su[c * sn + k] = ok ? u[c] : 0.0; sv[c * sn + k] = ok ? v[c] : 0.0; }
+            sflag[k] = ok ? 1 : 0;
+        }
+        __syncthreads();
+        const int x = x0 + lx, y = y0 + ly;
+        const bool inside = x < a.w && y < a.h;
+        const bool okp = inside && sflag[pc] != 0;
+        Accum acc;
+        for (int oy = -r; oy <= r; oy++)
+            for (int ox = -r; ox <= r; ox++) {
+                const int shift = oy * sw + ox;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    if (ia[k] < 0) continue;
+                    const int i0 = ia[k], i1 = i0 + shift;
+                    const int both = sflag[i0] & sflag[i1];
+                    double e = 0.0;
+                    if (both) {
+                        double ua[3], va[3], ub[3], vb[3];
+#pragma unroll
+                        for (int c = 0; c < 3; c++) { ua[c] = su[c * sn + i0]; va[c] = sv[c * sn + i0]; ub[c] = su[c * sn + i1]; vb[c] = sv[c * sn + i1]; }
+                        e = pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
+                    }
+                    pe[ie[k]] = e; ce[ie[k]] = both;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    if (jrow[k] < 0) continue;
+                    double S = 0.0;
+                    int C = 0;
+                    for (int n = 0; n < taps; n++) { S += pe[jrow[k] + n]; C += ce[jrow[k] + n]; }
+                    ph[tid + k * kBlock] = S; ch[tid + k * kBlock] = C;
+                }
+                __syncthreads();
+                const int iq = pc + shift;
+                if (okp && sflag[iq] != 0) {
+                    double S = 0.0;
+                    int C = 0;
+                    for (int n = 0; n < taps; n++) { S += ph[tid + n * kTile]; C += ch[tid + n * kTile]; }
+                    const double uq[3] = {su[iq], su[sn + iq], su[2 * sn + iq]}, vq[3] = {sv[iq], sv[sn + iq], sv[2 * sn + iq]};
+                    acc.add(S, C, uq, vq);
+                }
+            }
+        if (!inside) continue;
+        const size_t i = ((size_t)y * a.w + x) * 3;
+        if (okp) {
+            const double u[3] = {su[pc], su[sn + pc], su[2 * sn + pc]}, v[3] = {sv[pc], sv[sn + pc], sv[2 * sn + pc]};
+            finish_pixel(a, i, u, v, acc, s);
+        } else {
+            double u[3], v[3];
+            load_pixel(a, x, y, u, v);                  // (the stage holds zeros in its place)
+            keep_pixel(a, i, u, v, s);
+        }
+    }
+    leave_partials(a, s, red);
+}
+
+} // namespace nlm
+
+namespace gdpt {
+
+namespace {
+
+struct NlmWorkspace {
+    std::mutex mu;                    // held while a call runs on this (device, stream) pair
+    DeviceBuffer<double> partials;
+    DeviceBuffer<prg::Estimate> d_est;      // [0] sum var in, sum u^2 in, left out; [1] sum var out, sum u^2 out, left out
+    PinnedBuffer<prg::Estimate> h_est;
+    Event ev[2];
+};
+
+// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip)
+PerStream<NlmWorkspace> &g_workspaces = *new PerStream<NlmWorkspace>();
+
+// Device pointers on the current device; the arguments have been checked. Enqueued on `stream`; waits for it if `stats` is asked for.
+void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, const GdptNlmParams &p, double *d_out, double *d_var_out,
+                        hipStream_t stream, GdptNlmStats *stats) {
+    int dev = 0;
+    ck(hipGetDevice(&dev), "hipGetDevice");
+    NlmWorkspace &ws = g_workspaces.get(dev, stream);
+    std::lock_guard<std::mutex> lk(ws.mu);
+    if (!ws.partials) ws.partials.alloc(6 * nlm::kMaxBlocks, "hipMalloc(nlm partials)");
+    if (!ws.d_est) ws.d_est.alloc(2, "hipMalloc(nlm sums)");
+    if (!ws.h_est) ws.h_est.alloc(2, "hipHostMalloc(nlm sums)");
+    for (auto &e : ws.ev) if (!e) e.create();
+
+    nlm::Args a{};
+    a.w = w; a.h = h; a.r = p.window_radius; a.f = p.patch_radius;
+    a.tiles_x = (w + nlm::kTile - 1) / nlm::kTile; a.tiles = a.tiles_x * ((h + nlm::kTile - 1) / nlm::kTile);
+    a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
+    a.img = d_img; a.var = d_var; a.out = d_out; a.var_out = d_var_out; a.partials = ws.partials;
+    const int nb = std::min(a.tiles, nlm::kMaxBlocks);
+    if (stats) ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
+    if (debug_knob("nlm_direct", 0) != 0) {
+        hipLaunchKernelGGL(nlm::direct_kernel, dim3(nb), dim3(nlm::kBlock), 0, stream, a);
+    } else {
+        const size_t lds = (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
+        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+           "hipFuncSetAttribute(nlm stage)");
+        hipLaunchKernelGGL(nlm::tiled_kernel, dim3(nb), dim3(nlm::kBlock), lds, stream, a);
+    }
+    ck(hipGetLastError(), "nlm launch");
+    if (!stats) return;
+    prg::launch_finish(nb, ws.partials, ws.d_est, stream);
+    prg::launch_finish(nb, ws.partials.data() + 3 * nb, ws.d_est.data() + 1, stream);
+    ck(hipGetLastError(), "nlm reduction launch");
+    ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
+    ck(hipMemcpyAsync(ws.h_est, ws.d_est, 2 * sizeof(prg::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(nlm sums)");
+    ck(hipStreamSynchronize(stream), "hipStreamSynchronize(nlm)");
+    *stats = GdptNlmStats{};
+    const prg::Estimate &in = ws.h_est.data()[0], &out = ws.h_est.data()[1];
+    stats->pixels_left_out = (uint64_t)in.left_out;
+    stats->sum_var_in = in.sum_var; stats->sum_sq_in = in.sum_mean2;
+    stats->sum_var_out = out.sum_var; stats->sum_sq_out = out.sum_mean2;
+    stats->error_in = std::sqrt(in.sum_var / in.sum_mean2);
+    stats->error_out = std::sqrt(out.sum_var / out.sum_mean2);
+    { float ms = 0; ck(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]), "hipEventElapsedTime"); stats->filter_ms = ms; }
+    stats->window_radius = p.window_radius; stats->patch_radius = p.patch_radius;
+}
+
+} // namespace
+
+void denoise_nlm_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
+
+void nlm_check_params(const std::string &who, const GdptNlmParams &p) {
+    if (p.window_radius < 0 || p.window_radius > nlm::kMaxR)
+        throw std::runtime_error(who + ": window_radius must be in [0, " + std::to_string(nlm::kMaxR) + "]");
+    if (p.patch_radius < 0 || p.patch_radius > nlm::kMaxF)
+        throw std::runtime_error(who + ": patch_radius must be in [0, " + std::to_string(nlm::kMaxF) + "]");
+    if (!std::isfinite(p.k) || !(p.k > 0)) throw std::runtime_error(who + ": k must be finite and > 0");
+    if (!std::isfinite(p.alpha) || !(p.alpha >= 0)) throw std::runtime_error(who + ": alpha must be finite and >= 0");
+    if (!std::isfinite(p.epsilon) || !(p.epsilon > 0)) throw std::runtime_error(who + ": epsilon must be finite and > 0");
+    if (p.reserved[0] != 0 || p.reserved[1] != 0) throw std::runtime_error(who + ": reserved must be 0");
+}
+
+} // namespace gdpt
+
+namespace {
+
+using gdpt::ck;
+
+// what both entry points refuse; `who` names the caller. Returns the parameters in force.
+GdptNlmParams check_arguments(const std::string &who, int width, int height, const double *img, const double *var, const GdptNlmParams *params,
+                              const double *out, const double *var_out) {
+    if (!img) throw std::runtime_error(who + ": img is null");
+    if (!var) throw std::runtime_error(who + ": var is null");
+    if (!out) throw std::runtime_error(who + ": out is null");
+    if (out == img || out == var) throw std::runtime_error(who + ": out must not alias an input");
+    if (var_out && (var_out == img || var_out == var || var_out == out)) throw std::runtime_error(who + ": var_out must not alias an input or out");
+    if (width < 1 || height < 1) throw std::runtime_error(who + ": width and height must be >= 1");
+    if ((long long)width * height > (1LL << 29)) throw std::runtime_error(who + ": width * height: film too large");
+    GdptNlmParams p;
+    if (params) p = *params;
+    else gdpt_nlm_default_params(&p);
+    gdpt::nlm_check_params(who, p);
+    return p;
+}
+
+void need_a_device(const std::string &who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
+    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
+}
+
+} // namespace
+
+extern "C" {
+
+void gdpt_nlm_default_params(GdptNlmParams *p) {
+    if (!p) return;
+    *p = GdptNlmParams{};
+    p->window_radius = GDPT_NLM_MAX_WINDOW_RADIUS; p->patch_radius = GDPT_NLM_MAX_PATCH_RADIUS;
+    p->k = 0.45; p->alpha = 1.0; p->epsilon = 1e-10;
+}
+
+int gdpt_denoise_nlm_device(int width, int height, const double *d_img, const double *d_var, const GdptNlmParams *params, double *d_out,
+                            double *d_var_out, void *stream, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm_device";
+        const GdptNlmParams p = check_arguments(who, width, height, d_img, d_var, params, d_out, d_var_out);
+        need_a_device(who);
+        gdpt::denoise_nlm_launch(width, height, d_img, d_var, p, d_out, d_var_out, (hipStream_t)stream, stats);
+    });
+}
+
+int gdpt_denoise_nlm(int width, int height, const double *img, const double *var, const GdptNlmParams *params, double *out, double *var_out,
+                     GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm";
+        const GdptNlmParams p = check_arguments(who, width, height, img, var, params, out, var_out);
+        need_a_device(who);
+        const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
+        gdpt::DeviceBuffer<double> d_img, d_var, d_out, d_var_out;
+        d_img.alloc(elems, "hipMalloc(nlm io)"); d_var.alloc(elems, "hipMalloc(nlm io)"); d_out.alloc(elems, "hipMalloc(nlm io)");
+        if (var_out) d_var_out.alloc(elems, "hipMalloc(nlm io)");
+        ck(hipMemcpy(d_img, img, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        ck(hipMemcpy(d_var, var, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        gdpt::denoise_nlm_launch(width, height, d_img, d_var, p, d_out, d_var_out, nullptr, stats);
+        ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+    });
+}
+
+} // extern "C"

@@ -21,6 +21,7 @@
 #include "device_mem.h"
 #include "recon_l1.h"
 #include "recon_spread.h"
+#include "denoise_nlm.h"
 #include "../capi_common.h"
 #include "../../../include/gdpt.h"
 
@@ -744,6 +745,7 @@ void forget_stream(int dev, hipStream_t stream) {
     g_streams.forget(dev, stream);         // scratch buffers, rocBLAS handle, timing events
     recon_l1_forget_stream(dev, stream);
     recon_spread_forget_stream(dev, stream);
+    denoise_nlm_forget_stream(dev, stream);
 }
 
 void poisson_release_workspace() {

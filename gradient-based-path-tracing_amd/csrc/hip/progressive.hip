@@ -26,6 +26,7 @@
 #include "../capi_common.h"
 #include "poisson_kernels.h"
 #include "progressive_internal.h"
+#include "denoise_nlm.h"
 
 #include <algorithm>
 #include <cmath>
@@ -493,6 +494,32 @@ int gdpt_progressive_reconstruct_weighted(GdptProgressive *session, double dataC
         prg::reconstruct_weighted(s, dataCost, params, confidence, stats);
         copy_out(s, out, s.asm_buf[3], on_device);
         ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive reconstruct)");
+    });
+}
+
+int gdpt_progressive_denoise(GdptProgressive *session, const GdptNlmParams *params, int on_device, double *out, double *var_out, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        if (params) gdpt::nlm_check_params(who, *params);
+        GdptProgressive &s = *session;
+        if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        compute_variances(s);
+        double *d_out = out, *d_var_out = var_out;
+        if (!on_device) {                 // through planes of the session's on the way to host memory
+            for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+            d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+        }
+        GdptNlmStats st{};                // (asked for always: the call is blocking)
+        if (gdpt_denoise_nlm_device(s.w, s.h, s.mean[0], s.var[0], params, d_out, d_var_out, s.stream, &st) != 0) throw std::runtime_error(gdpt_last_error());
+        if (!on_device) {
+            copy_out(s, out, d_out, 0);
+            copy_out(s, var_out, d_var_out, 0);
+            ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+        }
+        if (stats) *stats = st;
     });
 }
 

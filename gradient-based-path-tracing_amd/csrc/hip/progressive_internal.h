@@ -46,6 +46,7 @@ struct GdptProgressive {
     gdpt::DeviceBuffer<double> stage[10];      // mean / M2 planes of a merge source on another device, allocated by the first such merge
     gdpt::DeviceBuffer<double> var[7];         // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
     gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
+    gdpt::DeviceBuffer<double> nlm_buf[2];     // filtered mean and its variance on their way to host memory: allocated by the first denoise
     gdpt::DeviceBuffer<double> partials;
     gdpt::DeviceBuffer<prg::Estimate> d_est;
     gdpt::PinnedBuffer<prg::Estimate> h_est;

@@ -33,6 +33,10 @@
 //                 taken from the spread of the members' own reconstructions (gdpt_progressive_group_run_recon); --error-map FILE
 //                 writes that estimate's per-pixel variance map (all three channels), --error-radius R (0..8) averages it over a
 //                 (2R+1)^2 window. They need two or more entries (0,0 is fine on one GPU): one session has no independent halves
+//   --denoised FILE   also writes the session's primal mean (buffer 0: the image of an Integrator::Path scene, the primal of a GradPath
+//                 scene) filtered by non-local means on its per-pixel variance (gdpt_progressive_denoise); -o receives what it
+//                 receives without the flag. --nlm-window R (0..10, default 10), --nlm-patch F (0..3, default 3), --nlm-k K (default
+//                 0.45). Needs --pass-spp: the filter is driven by the variance of the mean, and no variance exists without passes
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -56,6 +60,10 @@ int main(int argc, char *argv[]) {
     std::string error_map_file = "";
     std::string variance_file = "", confidence_file = "";
     bool weighted = false;
+    std::string denoised_file = "";
+    GdptNlmParams nlm{};
+    gdpt_nlm_default_params(&nlm);
+    bool nlm_option = false;
     double conf_floor = 0.0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
     std::vector<int32_t> sample_devices;      // --sample-devices: a progressive group
@@ -121,6 +129,10 @@ int main(int argc, char *argv[]) {
         else if (a == "--error-map") error_map_file = next();
         else if (a == "--error-radius") { error_radius = std::stoi(next()); error_radius_set = true; }
         else if (a == "--variance") variance_file = next();
+        else if (a == "--denoised") denoised_file = next();
+        else if (a == "--nlm-window") { nlm.window_radius = std::stoi(next()); nlm_option = true; }
+        else if (a == "--nlm-patch") { nlm.patch_radius = std::stoi(next()); nlm_option = true; }
+        else if (a == "--nlm-k") { nlm.k = std::stod(next()); nlm_option = true; }
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
         else if (a == "--shift") {        // extension: "reconnect" = GDPT_SHIFT_RECONNECT (include/gdpt.h); default = the reference's offsets
             std::string v = next();
@@ -158,6 +170,11 @@ int main(int argc, char *argv[]) {
     if (pass_spp > 0 && multi.num_devices > 0) { std::cerr << "--pass-spp is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
     if (pass_spp > 0 && rng == GDPT_RNG_TILE) { std::cerr << "--pass-spp needs --rng sample (the tile streams have no sample window)" << std::endl; return 2; }
     if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
+    if (!denoised_file.empty() && pass_spp <= 0) {
+        std::cerr << "--denoised needs --pass-spp: the filter is driven by the variance of the mean, and no variance exists without passes" << std::endl;
+        return 2;
+    }
+    if (nlm_option && denoised_file.empty()) { std::cerr << "--nlm-window, --nlm-patch and --nlm-k need --denoised" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
     const bool recon_error = target_recon_error != 0.0 || !error_map_file.empty();
@@ -215,6 +232,7 @@ int main(int argc, char *argv[]) {
         int rc;
         GdptProgressiveStatus prog{};
         GdptReconSpreadStats spread{};
+        GdptNlmStats nlm_stats{};
         GdptGroupReconParams gp{};        // the reconstruction the estimate of --target-recon-error / --error-map goes through
         gp.dataCost = alpha; gp.weighted = weighted ? 1 : 0; gp.map_radius = error_radius;
         gp.recon = recon; gp.wrecon.recon = recon; gp.wrecon.conf_floor = conf_floor;
@@ -264,6 +282,11 @@ int main(int argc, char *argv[]) {
                 rc = gdpt_progressive_read(session, 0, nullptr, vars, nullptr);
                 if (rc == 0) rc = gdpt_imwrite(variance_file.c_str(), w, h, variance.data());
             }
+            if (rc == 0 && !denoised_file.empty()) {
+                std::vector<double> filtered((size_t)w * h * 3);
+                rc = gdpt_progressive_denoise(session, &nlm, 0, filtered.data(), nullptr, &nlm_stats);
+                if (rc == 0) rc = gdpt_imwrite(denoised_file.c_str(), w, h, filtered.data());
+            }
             std::string err = rc != 0 ? gdpt_last_error() : "";
             if (!grouped) gdpt_progressive_free(session);
             if (rc != 0) { std::cerr << "terminate: " << err << std::endl; return 134; }
@@ -308,6 +331,10 @@ int main(int argc, char *argv[]) {
             std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << budget
                       << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
                       << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
+            if (!denoised_file.empty())
+                std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
+                          << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
+                          << ", filter_ms " << nlm_stats.filter_ms << ", written to " << denoised_file << std::endl;
             if (recon_error)
                 std::cout << "[gdpt] reconstruction: error estimate " << spread.error_estimate << " from the spread of " << spread.members
                           << " members (" << spread.pixels_left_out << " pixels left out), map radius " << spread.radius << ", spread "

@@ -651,6 +651,44 @@ int gdpt_progressive_group_run_recon(GdptProgressiveGroup *group, double target_
                                      const GdptGroupReconParams *params, GdptProgressiveStatus *status,
                                      GdptReconSpreadStats *spread_stats /* nullable */);
 
+/* ---- a variance-driven non-local-means filter for a mean and the variance of that mean (not part of the reference) ----
+ * What a progressive session yields per pixel, a running mean u and the variance v of that mean, is what non-local means with
+ * variance-cancelling patch distances takes (Rousselle, Knaus, Zwicker, "Adaptive rendering with non-local means filtering",
+ * SIGGRAPH Asia 2012, sections 4-5). img, var: W*H*3 doubles, interleaved like every film here. Window radius r, patch radius f,
+ * k > 0, alpha >= 0, epsilon > 0. A pixel is VALID if its three img and its three var values are finite and the var values >= 0.
+ *   e_o(x) = (1/3) sum_c [ (u_c(x) - u_c(x+o))^2 - alpha (v_c(x) + min(v_c(x+o), v_c(x))) ] / [ epsilon + k^2 (v_c(x) + v_c(x+o)) ]
+ *            for x and x+o both in the film and valid (such an x counts 1); otherwise 0, counting 0
+ *   S_o(p) = sum of e_o(p+n) over |n|_inf <= f, C_o(p) the same sum of the counts;   D_o(p) = max(0, S_o(p) / C_o(p))
+ *   w_o(p) = exp(-D_o(p)) if C_o(p) > 0 and p, p+o are both in the film and valid, else 0   (w_0(p) = 1)
+ *   out_c(p) = sum_o w_o(p) u_c(p+o) / sum_o w_o(p),   var_out_c(p) = sum_o w_o(p)^2 v_c(p+o) / (sum_o w_o(p))^2
+ * with the sums over |o|_inf <= r in row-major order of o. An invalid p keeps its input triples in out and var_out, bit for bit,
+ * and is counted in pixels_left_out. r = 0 returns the input; f = 0 gives pixel-wise distances. 0 <= r <= 10, 0 <= f <= 3 (the
+ * paper's defaults are the caps). The film sums run over the valid pixels and are reduced in a fixed order: the same call gives the
+ * same bits. error_in = sqrt(sum_var_in / sum_sq_in) is the session's own error estimate restricted to the valid pixels;
+ * error_out = sqrt(sum_var_out / sum_sq_out) treats the weights as fixed and independent of the data and ignores the filter's
+ * bias: it is the variance the weighted average would have if its weights were given, not the error of the filtered image. */
+typedef struct GdptNlmParams { int32_t window_radius, patch_radius; double k, alpha, epsilon; int32_t reserved[2]; } GdptNlmParams;
+typedef struct GdptNlmStats  { uint64_t pixels_left_out; double sum_var_in, sum_sq_in, sum_var_out, sum_sq_out, error_in, error_out, filter_ms;
+                               int32_t window_radius, patch_radius; } GdptNlmStats;
+#define GDPT_NLM_MAX_WINDOW_RADIUS 10
+#define GDPT_NLM_MAX_PATCH_RADIUS 3
+void gdpt_nlm_default_params(GdptNlmParams *p);            /* 10, 3, 0.45, 1.0, 1e-10; every field of a passed struct is taken literally */
+/* Device pointers on the current device. Refused, with a message that names the field, before any device call: NULL d_img, d_var or
+ * d_out; d_out or d_var_out aliasing an input or each other; width or height < 1; radii outside the caps; a non-finite k, alpha or
+ * epsilon, k <= 0, alpha < 0, epsilon <= 0; non-zero reserved. Enqueued on `stream`; with stats it waits for the stream (the sums
+ * and filter_ms, HIP events, come back), with stats == NULL it only enqueues. Scratch (the block partials of the sums) per
+ * (device, stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_denoise_nlm_device(int width, int height, const double *d_img, const double *d_var, const GdptNlmParams *params /* NULL: defaults */,
+                            double *d_out, double *d_var_out /* nullable */, void *stream, GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm(int width, int height, const double *img, const double *var, const GdptNlmParams *params /* NULL: defaults */,
+                     double *out, double *var_out /* nullable */, GdptNlmStats *stats /* nullable */);
+/* The filter on a session's buffer 0: its running mean with the variance of that mean, the image of an Integrator::Path session and
+ * the primal of a GradPath session (a group's total included). Needs at least 2 passes (no variance is defined before). `out` and
+ * `var_out` (nullable) are host memory, or device memory with on_device != 0. Blocking. */
+int gdpt_progressive_denoise(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */, int on_device, double *out,
+                             double *var_out /* nullable */, GdptNlmStats *stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);

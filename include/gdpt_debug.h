@@ -39,6 +39,9 @@
  *   full_material_switch (0/1)  lane machines: the kernel with the full material switch even when the scene fits a small set
  *   whole_leaf_trips (0/1)      one-sided lane machine on an LDS-resident scene: the kernel whose leaf trips test the whole leaf (four
  *                               tests in a row) instead of two records per trip with the cursor in the leaf reference; same route name
+ *   nlm_direct (0/1)            gdpt_denoise_nlm*: the direct form of the filter (one thread per pixel, every patch distance summed
+ *                               from global memory: the literal definition) instead of the tiled form (a block's tile and halo
+ *                               staged in LDS, separable patch sums)
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
  *
