@@ -137,6 +137,7 @@ def lib():
         L.gdpt_debug_overlapped_launches.restype = C.c_longlong
         L.gdpt_debug_leaf_histogram.argtypes = [vp, C.POINTER(C.c_int32)]
         L.gdpt_debug_route_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
+        L.gdpt_debug_image_grid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         L.gdpt_debug_prepare_scene.argtypes = [C.POINTER(defs.GdptSceneDesc), C.POINTER(defs.GdptPreparedInfo), dp, dp, C.c_int]
         _LIB = L
     return _LIB
@@ -958,6 +959,14 @@ class debug_knobs:
         if lib().gdpt_debug_route_names(buf, n) != n:
             raise GdptError("gdpt_debug_route_names: capacity")
         return [x.decode() for x in buf]
+
+    @staticmethod
+    def image_grid(kernel, width, height):
+        """(blocks launched, units of work they stride over) of an image-space launch on a width x height film, as the launch
+        computes them (include/gdpt_debug.h: gdpt_debug_image_grid). No GPU call."""
+        out = (C.c_int32 * 2)()
+        _check(lib().gdpt_debug_image_grid(kernel.encode(), int(width), int(height), out))
+        return int(out[0]), int(out[1])
 
     @staticmethod
     def prepare_scene(scene_desc):

@@ -4,8 +4,12 @@
 #include "../capi_common.h"
 #include "../device_scene.h"
 #include "../host/scene_prepare.h"
+#include "denoise_nlm.h"
 #include "poisson_kernels.h"
+#include "progressive_internal.h"
 #include "recon_l1.h"
+#include "recon_pcg.h"
+#include "recon_spread.h"
 #include "recon_weighted.h"
 #include "render_kernels.h"
 #include "scene_internal.h"
@@ -488,6 +492,26 @@ int gdpt_debug_leaf_histogram(const GdptScene *scene, int32_t hist[4]) {
     });
 }
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
+
+// include/gdpt_debug.h: the grid of an image-space launch, from the helpers the launches themselves call (no GPU needed)
+int gdpt_debug_image_grid(const char *kernel, int width, int height, int32_t out[2]) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_debug_image_grid";
+        if (!kernel || !out) throw std::runtime_error(who + ": null argument");
+        if (width < 1 || height < 1 || (long long)width * height > (1LL << 29)) throw std::runtime_error(who + ": width and height must be >= 1, the film at most 2^29 pixels");
+        const std::string k(kernel);
+        const size_t npix = (size_t)width * height;
+        if (k == "fold") { out[0] = prg::fold_blocks((int)npix); out[1] = prg::groups(npix); }
+        else if (k == "variance") { out[0] = prg::variance_blocks(3 * npix); out[1] = prg::groups(3 * npix); }
+        else if (k == "spread") { const gdpt::SpreadGrid g = gdpt::spread_grid(width, height); out[0] = g.blocks; out[1] = g.groups; }
+        else if (k == "box") { const gdpt::BoxGrid g = gdpt::box_grid(width, height); out[0] = g.blocks; out[1] = g.tiles; }
+        else if (k == "nlm") { const gdpt::NlmGrid g = gdpt::nlm_grid(width, height); out[0] = g.blocks; out[1] = g.tiles; }
+        else if (k == "recon_tiles") { const rl1::Geo g = gdpt::recon_geo(width, height); out[0] = gdpt::recon_blocks(g); out[1] = g.tiles; }
+        else if (k == "recon_pixels") { const rl1::Geo g = gdpt::recon_geo(width, height); out[0] = gdpt::recon_blocks(g); out[1] = gdpt::recon_pixel_groups(g); }
+        else if (k == "cg") { out[0] = gdpt::poisson_blocks((int)(3 * npix)); out[1] = gdpt::poisson_groups((int)(3 * npix)); }
+        else throw std::runtime_error(who + ": unknown kernel '" + k + "' (fold, variance, spread, box, nlm, recon_tiles, recon_pixels, cg)");
+    });
+}
 
 int gdpt_scene_upload(const GdptSceneDesc *desc, int device, GdptScene **out_scene) {
     return gdpt::guarded([&]() {

@@ -295,10 +295,11 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
 
     nlm::Args a{};
     a.w = w; a.h = h; a.r = p.window_radius; a.f = p.patch_radius;
-    a.tiles_x = (w + nlm::kTile - 1) / nlm::kTile; a.tiles = a.tiles_x * ((h + nlm::kTile - 1) / nlm::kTile);
+    const NlmGrid ng = nlm_grid(w, h);
+    a.tiles_x = ng.tiles_x; a.tiles = ng.tiles;
     a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
     a.img = d_img; a.var = d_var; a.out = d_out; a.var_out = d_var_out; a.partials = ws.partials;
-    const int nb = std::min(a.tiles, nlm::kMaxBlocks);
+    const int nb = ng.blocks;
     if (stats) ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     if (debug_knob("nlm_direct", 0) != 0) {
         hipLaunchKernelGGL(nlm::direct_kernel, dim3(nb), dim3(nlm::kBlock), 0, stream, a);
@@ -330,6 +331,13 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
 } // namespace
 
 void denoise_nlm_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
+
+NlmGrid nlm_grid(int w, int h) {
+    NlmGrid g{(w + nlm::kTile - 1) / nlm::kTile, 0, 0};
+    g.tiles = g.tiles_x * ((h + nlm::kTile - 1) / nlm::kTile);
+    g.blocks = std::min(g.tiles, nlm::kMaxBlocks);
+    return g;
+}
 
 void nlm_check_params(const std::string &who, const GdptNlmParams &p) {
     if (p.window_radius < 0 || p.window_radius > nlm::kMaxR)

@@ -516,6 +516,9 @@ __global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_
 
 namespace gdpt {
 
+int poisson_groups(int n3) { return (n3 + gp::kBlock - 1) / gp::kBlock; }
+int poisson_blocks(int n3) { return std::min(gp::kMaxBlocks, poisson_groups(n3)); }
+
 namespace {
 
 struct Workspace {
@@ -668,7 +671,7 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
     const size_t plane = (size_t)w * h;
     for (auto &b : ws.buf) b.grow(3 * plane, stream, "hipMalloc(dct buffers)");   // (earlier solves may still use the old buffers)
     if (!ws.partials) ws.partials.alloc(3 * gp::kMaxBlocks, "hipMalloc(dct partials)");
-    const int nb = std::min(gp::kMaxBlocks, (g.n3 + gp::kBlock - 1) / gp::kBlock);
+    const int nb = poisson_blocks(g.n3);
     if (timed) {
         for (auto &e : ws.ev) if (!e) e.create();
         ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
@@ -810,7 +813,7 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
     gp::Geo g{w, h, w * h * 3, w * 3};
     ss.cg.ensure((size_t)g.n3, stream);
     Workspace &ws = ss.cg;
-    const int nb = std::min(gp::kMaxBlocks, (g.n3 + gp::kBlock - 1) / gp::kBlock);
+    const int nb = poisson_blocks(g.n3);
     // init layout: 8 slots of nb doubles (slot 0 = <r,r>, reused as part_rr); <p,q> partials live in slot 8
     double *part_rr = ws.partials, *part_pq = ws.partials + 8 * (size_t)nb;
     hipEvent_t e0 = ws.ev[0], e1 = ws.ev[1];

@@ -160,7 +160,7 @@ namespace {
 
 using gdpt::ck;
 
-int fold_blocks(int npix) { return std::max(1, std::min(prg::kMaxBlocks, (npix + prg::kBlock - 1) / prg::kBlock)); }
+using prg::fold_blocks;
 
 void add_totals(GdptRenderStats &t, const GdptRenderStats &rs) {
     t.samples += rs.samples; t.rays += rs.rays; t.bounces += rs.bounces;
@@ -329,7 +329,7 @@ void compute_variances(GdptProgressive &s) {
     for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
     vp.vcx = s.var[5]; vp.vcy = s.var[6];
     const double norm = (double)(s.passes - 1) * (double)s.done;
-    const int nb = std::max(1, std::min(4 * prg::kMaxBlocks, (int)((s.elems + prg::kBlock - 1) / prg::kBlock)));
+    const int nb = prg::variance_blocks(s.elems);
     if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
     else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
     ck(hipGetLastError(), "progressive variance launch");

@@ -3,6 +3,7 @@
 #pragma once
 #include "scene_internal.h"
 
+#include <algorithm>
 #include <utility>
 #include <vector>
 
@@ -25,6 +26,13 @@ __device__ __forceinline__ double block_sum(double v, double *red) {
     for (int k = 1; k < kBlock / 64; k++) s += red[k];
     return s;
 }
+
+// Launch geometry of the kernels in which a thread owns a pixel (fold_kernel, merge_kernel, recon_spread.hip's spread_kernel) or an
+// element (variance_kernel): groups of kBlock consecutive pixels / elements, and the blocks that stride over them. The launches and
+// gdpt_debug_image_grid (include/gdpt_debug.h) both take them from here.
+inline int groups(size_t n) { return (int)((n + kBlock - 1) / kBlock); }
+inline int fold_blocks(int npix) { return std::max(1, std::min(kMaxBlocks, groups((size_t)npix))); }
+inline int variance_blocks(size_t elems) { return std::max(1, std::min(4 * kMaxBlocks, groups(elems))); }
 } // namespace prg
 
 struct GdptProgressive {

@@ -76,6 +76,8 @@ ReconWorkspace &recon_workspace(int dev, hipStream_t stream);
 
 rl1::Geo recon_geo(int w, int h);
 inline int recon_blocks(const rl1::Geo &g) { return g.tiles < rl1::kMaxBlocks ? g.tiles : rl1::kMaxBlocks; }
+// pcg_step_b runs on the same grid, a thread per pixel: the groups of kBlock consecutive pixels its blocks stride over
+inline int recon_pixel_groups(const rl1::Geo &g) { return (int)(((size_t)g.w * g.h + rl1::kBlock - 1) / rl1::kBlock); }
 
 // round_init_kernel after a weights pass over `nb` blocks: the round's scalars (reset == 0: only the energy)
 void recon_round_init(ReconWorkspace &ws, int nb, double tol, int reset, hipStream_t stream);

@@ -19,6 +19,13 @@ struct ReconSpreadResult {
 ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *d_images, const double *weights, const double *d_total,
                                       int radius, double *d_var, double *d_map, hipStream_t stream);
 
+// Launch geometry (gdpt_debug_image_grid reads it too). spread_kernel: groups of 256 consecutive pixels and the blocks that stride over
+// them; box_kernel: 32 x 8 tiles and the blocks that stride over them.
+struct SpreadGrid { int groups, blocks; };
+struct BoxGrid { int tiles_x, tiles, blocks; };
+SpreadGrid spread_grid(int w, int h);
+BoxGrid box_grid(int w, int h);
+
 // members, radius, the sums, error_estimate = sqrt(sum_var / sum_sq), the count and the device time into *st (nullable)
 void fill_spread_stats(GdptReconSpreadStats *st, int n, int radius, const ReconSpreadResult &r);
 

@@ -151,6 +151,14 @@ PerStream<SpreadWorkspace> &g_workspaces = *new PerStream<SpreadWorkspace>();
 
 void recon_spread_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
 
+SpreadGrid spread_grid(int w, int h) { return {prg::groups((size_t)w * h), prg::fold_blocks(w * h)}; }
+BoxGrid box_grid(int w, int h) {
+    BoxGrid g{(w + rsp::kTileW - 1) / rsp::kTileW, 0, 0};
+    g.tiles = g.tiles_x * ((h + rsp::kTileH - 1) / rsp::kTileH);
+    g.blocks = std::min(g.tiles, rsp::kMaxBlocks);
+    return g;
+}
+
 ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *d_images, const double *weights, const double *d_total,
                                       int radius, double *d_var, double *d_map, hipStream_t stream) {
     int dev = 0;
@@ -172,7 +180,7 @@ ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *
         m.img[i] = d_images[i]; m.w[i] = weights[i]; m.frac[i] = weights[i] / wsum;
     }
     const double norm = (double)(n - 1) * wsum;
-    const int nb = std::max(1, std::min(rsp::kMaxBlocks, (npix + rsp::kBlock - 1) / rsp::kBlock));
+    const int nb = spread_grid(w, h).blocks;
     ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     hipLaunchKernelGGL(rsp::spread_kernel, dim3(nb), dim3(rsp::kBlock), 0, stream, m, n, npix, norm, d_total, d_var,
                        windowed ? ws.pixsum.data() : d_map, ws.partials.data());
@@ -180,8 +188,8 @@ ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *
     prg::launch_finish(nb, ws.partials, ws.d_est, stream);
     ck(hipGetLastError(), "spread reduction launch");
     if (windowed) {
-        const int tiles_x = (w + rsp::kTileW - 1) / rsp::kTileW, tiles = tiles_x * ((h + rsp::kTileH - 1) / rsp::kTileH);
-        hipLaunchKernelGGL(rsp::box_kernel, dim3(std::min(tiles, rsp::kMaxBlocks)), dim3(rsp::kBlock), 0, stream, w, h, tiles_x, tiles, radius,
+        const BoxGrid bg = box_grid(w, h);
+        hipLaunchKernelGGL(rsp::box_kernel, dim3(bg.blocks), dim3(rsp::kBlock), 0, stream, w, h, bg.tiles_x, bg.tiles, radius,
                            ws.pixsum.data(), d_map);
         ck(hipGetLastError(), "spread window launch");
     }

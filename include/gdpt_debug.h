@@ -98,6 +98,15 @@ int gdpt_debug_leaf_histogram(const struct GdptScene *scene, int32_t hist[4]);
 /* Every name gdpt_debug_last_route can return: fills out[0..n) and returns n, or -1 if `capacity` < n; out == NULL
  * returns n alone. */
 int gdpt_debug_route_names(const char **out, int capacity);
+/* The grid of an image-space launch on a film of width x height, as the launch itself computes it: out[0] = blocks launched (256
+ * threads each), out[1] = units of work those blocks stride over (tiles, or groups of 256 consecutive pixels / elements). A block takes
+ * a second trip of its work loop where out[1] > out[0]; the reduction of the per-block partials takes one where out[0] > 256. Names,
+ * one per grid rule: "fold" (fold_kernel, merge_kernel: pixels), "variance" (variance_kernel: the 3 W H elements), "spread"
+ * (spread_kernel: pixels), "box" (box_kernel: 32 x 8 tiles), "nlm" (both forms of the filter: 16 x 16 tiles), "recon_tiles" (the tile
+ * kernels of the L1 and the variance-weighted reconstruction: 32 x 8 tiles), "recon_pixels" (pcg_step_b: pixels, on the grid of the
+ * tile kernels), "cg" (the Poisson CG: the 3 W H elements). Makes no GPU call. Returns 0, or non-zero (message in gdpt_last_error)
+ * for an unknown name, a null argument or an empty film. */
+int gdpt_debug_image_grid(const char *kernel, int width, int height, int32_t out[2]);
 /* The host half of a scene upload (csrc/host/scene_prepare.h: prepare_scene) on `desc`, with the default options of a product upload
  * and no knob applied; makes no GPU call, so it runs where there is none. `info` receives the table sizes, the traits that choose a
  * render's route, the intersection epsilon and a 64-bit FNV-1a digest of the bytes of every table (GDPT_PREPARED_* index it; an empty

@@ -97,6 +97,35 @@ def test_no_environment_variable_reaches_the_kernels(G):
     G.debug_knobs.reset()
 
 
+def test_image_grid_of_the_image_space_launches(G):
+    """gdpt_debug_image_grid (host only): (blocks launched, units they stride over) per grid rule. 512 x 512 is the last film on
+    which no block takes a second trip; 1025 x 345, 33 x 8201 and 513 x 171 are the films of
+    tests/test_gpu_films_past_the_block_cap.py, with the tile counts worked out by hand. An unknown name is an error."""
+    import pytest
+    grid = G.debug_knobs.image_grid
+    for name in ("fold", "spread", "box", "recon_tiles", "recon_pixels"):
+        assert grid(name, 512, 512) == (1024, 1024), name
+    assert grid("nlm", 512, 512) == (1024, 1024) and grid("variance", 512, 512) == (3072, 3072) and grid("cg", 512, 512) == (1024, 3072)
+    assert grid("fold", 1025, 345) == grid("spread", 1025, 345) == (1024, 1382)          # 353 625 pixels
+    assert grid("variance", 1025, 345) == (4096, 4145) and grid("cg", 1025, 345) == (1024, 4145)
+    assert grid("box", 1025, 345) == grid("recon_tiles", 1025, 345) == (1024, 33 * 44)
+    assert grid("recon_pixels", 1025, 345) == (1024, 1382)
+    assert grid("nlm", 1025, 345) == (1024, 65 * 22)
+    assert grid("box", 33, 8201) == grid("recon_tiles", 33, 8201) == (1024, 2 * 1026)
+    assert grid("recon_pixels", 33, 8201) == grid("fold", 33, 8201) == (1024, 1058)      # 270 633 pixels
+    assert grid("nlm", 33, 8201) == (1024, 3 * 513)
+    assert grid("cg", 513, 171) == (1024, 1029) and grid("cg", 257, 64) == (193, 193)
+    assert grid("fold", 96, 72) == (27, 27) and grid("variance", 96, 72) == (81, 81) and grid("recon_tiles", 128, 96) == (48, 48)
+    assert grid("recon_pixels", 17, 9) == (2, 1)             # pcg_step_b runs on the grid of the tile kernels
+    for name in ("fold", "variance", "spread", "box", "nlm", "recon_tiles", "recon_pixels", "cg"):
+        assert grid(name, 1, 1) == (1, 1), name
+    with pytest.raises(G.GdptError, match="unknown kernel 'finish'"):
+        grid("finish", 4, 4)
+    with pytest.raises(G.GdptError):
+        grid("fold", 0, 4)
+    assert G.lib().gdpt_debug_image_grid(None, 4, 4, None) != 0
+
+
 def test_work_item_plan_invariants(G):
     """The persistent kernels cut a pixel's samples into chunks that shrink along the queue and end in single samples
     (so a launch drains one sample, not one long item); every sample is covered exactly once, at most 64 chunks, small
