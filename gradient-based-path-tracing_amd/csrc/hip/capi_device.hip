@@ -5,6 +5,7 @@
 #include "../device_scene.h"
 #include "../host/scene_prepare.h"
 #include "denoise_nlm.h"
+#include "image_kernels.h"
 #include "poisson_kernels.h"
 #include "progressive_internal.h"
 #include "recon_l1.h"
@@ -493,7 +494,21 @@ int gdpt_debug_leaf_histogram(const GdptScene *scene, int32_t hist[4]) {
 }
 int gdpt_debug_route_names(const char **out, int capacity) { return gdpt::route_names(out, capacity); }
 
-// include/gdpt_debug.h: the grid of an image-space launch, from the helpers the launches themselves call (no GPU needed)
+// include/gdpt_debug.h: the grid of an image-space launch, from the two rules the launches themselves call (image_kernels.h; no GPU
+// needed). A stride rule counts `per_pixel` elements a pixel under `cap` blocks, at least `floor`; a tile rule has tw x th pixel tiles
+// and reports the tiles, or with `pixel_groups` the groups of 256 pixels the same blocks stride over (pcg_step_b).
+struct ImageGridRule { const char *name; int tw, th; bool pixel_groups; int per_pixel, cap, floor; };
+const ImageGridRule kImageGridRules[] = {
+    {"fold", 0, 0, false, 1, film::kMaxBlocks, 1},
+    {"variance", 0, 0, false, 3, 4 * film::kMaxBlocks, 1},
+    {"spread", 0, 0, false, 1, film::kMaxBlocks, 1},
+    {"box", gdpt::kSpreadTileW, gdpt::kSpreadTileH, false, 0, 0, 0},
+    {"nlm", gdpt::kNlmTile, gdpt::kNlmTile, false, 0, 0, 0},
+    {"recon_tiles", rl1::kTileW, rl1::kTileH, false, 0, 0, 0},
+    {"recon_pixels", rl1::kTileW, rl1::kTileH, true, 0, 0, 0},
+    {"cg", 0, 0, false, 3, film::kMaxBlocks, 0},
+};
+
 int gdpt_debug_image_grid(const char *kernel, int width, int height, int32_t out[2]) {
     return gdpt::guarded([&]() {
         const std::string who = "gdpt_debug_image_grid";
@@ -501,15 +516,18 @@ int gdpt_debug_image_grid(const char *kernel, int width, int height, int32_t out
         if (width < 1 || height < 1 || (long long)width * height > (1LL << 29)) throw std::runtime_error(who + ": width and height must be >= 1, the film at most 2^29 pixels");
         const std::string k(kernel);
         const size_t npix = (size_t)width * height;
-        if (k == "fold") { out[0] = prg::fold_blocks((int)npix); out[1] = prg::groups(npix); }
-        else if (k == "variance") { out[0] = prg::variance_blocks(3 * npix); out[1] = prg::groups(3 * npix); }
-        else if (k == "spread") { const gdpt::SpreadGrid g = gdpt::spread_grid(width, height); out[0] = g.blocks; out[1] = g.groups; }
-        else if (k == "box") { const gdpt::BoxGrid g = gdpt::box_grid(width, height); out[0] = g.blocks; out[1] = g.tiles; }
-        else if (k == "nlm") { const gdpt::NlmGrid g = gdpt::nlm_grid(width, height); out[0] = g.blocks; out[1] = g.tiles; }
-        else if (k == "recon_tiles") { const rl1::Geo g = gdpt::recon_geo(width, height); out[0] = gdpt::recon_blocks(g); out[1] = g.tiles; }
-        else if (k == "recon_pixels") { const rl1::Geo g = gdpt::recon_geo(width, height); out[0] = gdpt::recon_blocks(g); out[1] = gdpt::recon_pixel_groups(g); }
-        else if (k == "cg") { out[0] = gdpt::poisson_blocks((int)(3 * npix)); out[1] = gdpt::poisson_groups((int)(3 * npix)); }
-        else throw std::runtime_error(who + ": unknown kernel '" + k + "' (fold, variance, spread, box, nlm, recon_tiles, recon_pixels, cg)");
+        for (const ImageGridRule &r : kImageGridRules) {
+            if (k != r.name) continue;
+            if (r.tw == 0) { const film::StrideGrid g = film::stride_grid(r.per_pixel * npix, r.cap, r.floor); out[0] = g.blocks; out[1] = g.groups; }
+            else {
+                const film::TileGrid g = film::tile_grid(width, height, r.tw, r.th);
+                out[0] = g.blocks; out[1] = r.pixel_groups ? film::stride_grid(npix, g.blocks).groups : g.tiles;
+            }
+            return;
+        }
+        std::string names;
+        for (const ImageGridRule &r : kImageGridRules) names += std::string(names.empty() ? "" : ", ") + r.name;
+        throw std::runtime_error(who + ": unknown kernel '" + k + "' (" + names + ")");
     });
 }
 

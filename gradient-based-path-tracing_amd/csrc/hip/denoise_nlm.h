@@ -10,11 +10,8 @@ namespace gdpt {
 // What every entry point refuses in a parameter block; the message names the field. `who` names the caller. Host only.
 void nlm_check_params(const std::string &who, const GdptNlmParams &p);
 
-// Launch geometry of both kernel forms (gdpt_debug_image_grid reads it too): 16 x 16 tiles and the blocks that stride over them.
-struct NlmGrid { int tiles_x, tiles, blocks; };
-NlmGrid nlm_grid(int w, int h);
-
-// Drops the (device, stream) pair's scratch; forget_stream (device_mem.h) calls it.
-void denoise_nlm_forget_stream(int dev, hipStream_t stream);
+// Launch geometry of both kernel forms: film::tile_grid (image_kernels.h) over tiles of kNlmTile x kNlmTile pixels. The filter's
+// scratch is kept per (device, stream), and dropped by forget_stream (device_mem.h).
+constexpr int kNlmTile = 16;
 
 } // namespace gdpt

@@ -2,8 +2,8 @@
 // (include/gdpt.h: gdpt_denoise_nlm*, where the definition stands; Rousselle, Knaus, Zwicker 2012, sections 4-5).
 //
 // Kernels: two forms of the one definition, chosen by the test knob nlm_direct (include/gdpt_debug.h). Both loop over 16 x 16 tiles
-// as box_kernel (recon_spread.hip) does, a thread on a pixel of the tile, and both leave block partials through prg::block_sum for
-// prg's finish_kernel: a fixed order, the same bits every time.
+// as box_kernel (recon_spread.hip) does, a thread on a pixel of the tile, and both leave block partials through leave_block_sum for
+// finish_kernel (image_kernels.h): a fixed order, the same bits every time.
 //   direct_kernel   the literal definition: the loops over the window offsets o and the patch taps n read global memory, every
 //                   pair distance e_o(p + n) is computed where it is used, (2r+1)^2 (2f+1)^2 of them per pixel.
 //   tiled_kernel    the tile with a halo of r + f pixels staged in LDS, plane by plane (three u, three v, a validity flag; out-of-film
@@ -18,7 +18,7 @@
 //                   consecutive doubles of the row sums (pitch 16).
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
-#include "progressive_internal.h"
+#include "image_kernels.h"
 #include "denoise_nlm.h"
 
 #include <algorithm>
@@ -28,14 +28,16 @@
 
 namespace nlm {
 
-constexpr int kBlock = prg::kBlock, kMaxBlocks = prg::kMaxBlocks;
-constexpr int kTile = 16;
+using namespace film;             // kBlock, kMaxBlocks, TileGrid, leave_block_sum
+
+constexpr int kTile = gdpt::kNlmTile;
 constexpr int kMaxR = GDPT_NLM_MAX_WINDOW_RADIUS, kMaxF = GDPT_NLM_MAX_PATCH_RADIUS;
 static_assert(kTile * kTile == kBlock, "one thread per tile pixel");
 static_assert((kTile + 2 * kMaxF) * (kTile + 2 * kMaxF) <= 2 * kBlock, "a thread computes at most two pair distances per offset");
 
 struct Args {
-    int w, h, tiles_x, tiles, r, f;
+    TileGrid g;                  // 16 x 16 tiles
+    int r, f;
     double k2, alpha, eps;
     const double *img, *var;
     double *out, *var_out;       // var_out nullable
@@ -116,18 +118,17 @@ __device__ __forceinline__ void keep_pixel(const Args &a, size_t i, const double
 }
 
 __device__ __forceinline__ void leave_partials(const Args &a, const Sums &s, double *red) {
-    const int nb = gridDim.x;
-    double r;
-    r = prg::block_sum(s.var_in, red); if (threadIdx.x == 0) a.partials[0 * nb + blockIdx.x] = r;
-    r = prg::block_sum(s.sq_in, red); if (threadIdx.x == 0) a.partials[1 * nb + blockIdx.x] = r;
-    r = prg::block_sum(s.left_out, red); if (threadIdx.x == 0) { a.partials[2 * nb + blockIdx.x] = r; a.partials[5 * nb + blockIdx.x] = r; }
-    r = prg::block_sum(s.var_out, red); if (threadIdx.x == 0) a.partials[3 * nb + blockIdx.x] = r;
-    r = prg::block_sum(s.sq_out, red); if (threadIdx.x == 0) a.partials[4 * nb + blockIdx.x] = r;
+    leave_block_sum(a.partials, 0, s.var_in, red);
+    leave_block_sum(a.partials, 1, s.sq_in, red);
+    const double out = block_sum(s.left_out, red);      // (one sum, left for both reductions)
+    if (threadIdx.x == 0) { a.partials[2 * gridDim.x + blockIdx.x] = out; a.partials[5 * gridDim.x + blockIdx.x] = out; }
+    leave_block_sum(a.partials, 3, s.var_out, red);
+    leave_block_sum(a.partials, 4, s.sq_out, red);
 }
 
 // the triples of film pixel (x, y), which is inside the film; returns whether it is valid
 __device__ __forceinline__ bool load_pixel(const Args &a, int x, int y, double u[3], double v[3]) {
-    const size_t i = ((size_t)y * a.w + x) * 3;
+    const size_t i = ((size_t)y * a.g.w + x) * 3;
 #pragma unroll
     for (int c = 0; c < 3; c++) { u[c] = a.img[i + c]; v[c] = a.var[i + c]; }
     return valid_triples(u, v);
@@ -135,21 +136,20 @@ __device__ __forceinline__ bool load_pixel(const Args &a, int x, int y, double u
 
 __global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
     __shared__ double red[kBlock / 64];
-    const int lx = threadIdx.x & (kTile - 1), ly = threadIdx.x / kTile;
     const int r = a.r, f = a.f;
     Sums s;
-    for (int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
-        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-        const int x = tx * kTile + lx, y = ty * kTile + ly;
-        if (x >= a.w || y >= a.h) continue;
-        const size_t i = ((size_t)y * a.w + x) * 3;
+    for (int t = blockIdx.x; t < a.g.tiles; t += gridDim.x) {
+        const TilePixel tp = tile_pixel<kTile, kTile>(a.g, t);
+        const int x = tp.x, y = tp.y;
+        if (x >= a.g.w || y >= a.g.h) continue;
+        const size_t i = ((size_t)y * a.g.w + x) * 3;
         double u[3], v[3];
         if (!load_pixel(a, x, y, u, v)) { keep_pixel(a, i, u, v, s); continue; }
         Accum acc;
         for (int oy = -r; oy <= r; oy++)
             for (int ox = -r; ox <= r; ox++) {
                 const int qx = x + ox, qy = y + oy;
-                if (qx < 0 || qy < 0 || qx >= a.w || qy >= a.h) continue;
+                if (qx < 0 || qy < 0 || qx >= a.g.w || qy >= a.g.h) continue;
                 double uq[3], vq[3];
                 if (!load_pixel(a, qx, qy, uq, vq)) continue;
                 double S = 0.0;
@@ -157,7 +157,7 @@ __global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
                 for (int ny = -f; ny <= f; ny++)
                     for (int nx = -f; nx <= f; nx++) {
                         const int ax = x + nx, ay = y + ny, bx = ax + ox, by = ay + oy;
-                        if (ax < 0 || ay < 0 || ax >= a.w || ay >= a.h || bx < 0 || by < 0 || bx >= a.w || by >= a.h) continue;
+                        if (ax < 0 || ay < 0 || ax >= a.g.w || ay >= a.g.h || bx < 0 || by < 0 || bx >= a.g.w || by >= a.g.h) continue;
                         double ua[3], va[3], ub[3], vb[3];
                         const bool oka = load_pixel(a, ax, ay, ua, va), okb = load_pixel(a, bx, by, ub, vb);
                         if (!oka || !okb) continue;
@@ -195,23 +195,23 @@ __global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
     }
     const int pc = (ly + halo) * sw + lx + halo;        // the thread's own pixel in the stage
     Sums s;
-    for (int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
-        const int ty = t / a.tiles_x, tx = t - ty * a.tiles_x;
-        const int x0 = tx * kTile, y0 = ty * kTile;
+    for (int t = blockIdx.x; t < a.g.tiles; t += gridDim.x) {
+        const TilePixel tp = tile_pixel<kTile, kTile>(a.g, t);
+        const int x0 = tp.x0, y0 = tp.y0;
         __syncthreads();                                // the previous tile's stage has been read
         for (int k = tid; k < sn; k += kBlock) {
             const int ry = k / sw, rx = k - ry * sw;
             const int gx = x0 - halo + rx, gy = y0 - halo + ry;
             double u[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
             bool ok = false;
-            if (gx >= 0 && gy >= 0 && gx < a.w && gy < a.h) ok = load_pixel(a, gx, gy, u, v);
+            if (gx >= 0 && gy >= 0 && gx < a.g.w && gy < a.g.h) ok = load_pixel(a, gx, gy, u, v);
 #pragma unroll
             for (int c = 0; c < 3; c++) { su[c * sn + k] = ok ? u[c] : 0.0; sv[c * sn + k] = ok ? v[c] : 0.0; }
             sflag[k] = ok ? 1 : 0;
         }
         __syncthreads();
-        const int x = x0 + lx, y = y0 + ly;
-        const bool inside = x < a.w && y < a.h;
+        const int x = tp.x, y = tp.y;
+        const bool inside = x < a.g.w && y < a.g.h;
         const bool okp = inside && sflag[pc] != 0;
         Accum acc;
         for (int oy = -r; oy <= r; oy++)
@@ -251,7 +251,7 @@ __global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
                 }
             }
         if (!inside) continue;
-        const size_t i = ((size_t)y * a.w + x) * 3;
+        const size_t i = ((size_t)y * a.g.w + x) * 3;
         if (okp) {
             const double u[3] = {su[pc], su[sn + pc], su[2 * sn + pc]}, v[3] = {sv[pc], sv[sn + pc], sv[2 * sn + pc]};
             finish_pixel(a, i, u, v, acc, s);
@@ -273,12 +273,13 @@ namespace {
 struct NlmWorkspace {
     std::mutex mu;                    // held while a call runs on this (device, stream) pair
     DeviceBuffer<double> partials;
-    DeviceBuffer<prg::Estimate> d_est;      // [0] sum var in, sum u^2 in, left out; [1] sum var out, sum u^2 out, left out
-    PinnedBuffer<prg::Estimate> h_est;
+    DeviceBuffer<film::Estimate> d_est;     // [0] sum var in, sum u^2 in, left out; [1] sum var out, sum u^2 out, left out
+    PinnedBuffer<film::Estimate> h_est;
     Event ev[2];
 };
 
-// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip)
+// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip); a pair's entry
+// goes with forget_stream (device_mem.h)
 PerStream<NlmWorkspace> &g_workspaces = *new PerStream<NlmWorkspace>();
 
 // Device pointers on the current device; the arguments have been checked. Enqueued on `stream`; waits for it if `stats` is asked for.
@@ -288,37 +289,35 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
     ck(hipGetDevice(&dev), "hipGetDevice");
     NlmWorkspace &ws = g_workspaces.get(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
-    if (!ws.partials) ws.partials.alloc(6 * nlm::kMaxBlocks, "hipMalloc(nlm partials)");
+    if (!ws.partials) ws.partials.alloc(6 * film::kMaxBlocks, "hipMalloc(nlm partials)");
     if (!ws.d_est) ws.d_est.alloc(2, "hipMalloc(nlm sums)");
     if (!ws.h_est) ws.h_est.alloc(2, "hipHostMalloc(nlm sums)");
     for (auto &e : ws.ev) if (!e) e.create();
 
     nlm::Args a{};
-    a.w = w; a.h = h; a.r = p.window_radius; a.f = p.patch_radius;
-    const NlmGrid ng = nlm_grid(w, h);
-    a.tiles_x = ng.tiles_x; a.tiles = ng.tiles;
+    a.g = film::tile_grid(w, h, kNlmTile, kNlmTile); a.r = p.window_radius; a.f = p.patch_radius;
     a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
     a.img = d_img; a.var = d_var; a.out = d_out; a.var_out = d_var_out; a.partials = ws.partials;
-    const int nb = ng.blocks;
+    const int nb = a.g.blocks;
     if (stats) ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     if (debug_knob("nlm_direct", 0) != 0) {
-        hipLaunchKernelGGL(nlm::direct_kernel, dim3(nb), dim3(nlm::kBlock), 0, stream, a);
+        hipLaunchKernelGGL(nlm::direct_kernel, dim3(nb), dim3(film::kBlock), 0, stream, a);
     } else {
         const size_t lds = (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
         ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
            "hipFuncSetAttribute(nlm stage)");
-        hipLaunchKernelGGL(nlm::tiled_kernel, dim3(nb), dim3(nlm::kBlock), lds, stream, a);
+        hipLaunchKernelGGL(nlm::tiled_kernel, dim3(nb), dim3(film::kBlock), lds, stream, a);
     }
     ck(hipGetLastError(), "nlm launch");
     if (!stats) return;
-    prg::launch_finish(nb, ws.partials, ws.d_est, stream);
-    prg::launch_finish(nb, ws.partials.data() + 3 * nb, ws.d_est.data() + 1, stream);
+    film::launch_finish(nb, ws.partials, ws.d_est, stream);
+    film::launch_finish(nb, ws.partials.data() + 3 * nb, ws.d_est.data() + 1, stream);
     ck(hipGetLastError(), "nlm reduction launch");
     ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
-    ck(hipMemcpyAsync(ws.h_est, ws.d_est, 2 * sizeof(prg::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(nlm sums)");
+    ck(hipMemcpyAsync(ws.h_est, ws.d_est, 2 * sizeof(film::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(nlm sums)");
     ck(hipStreamSynchronize(stream), "hipStreamSynchronize(nlm)");
     *stats = GdptNlmStats{};
-    const prg::Estimate &in = ws.h_est.data()[0], &out = ws.h_est.data()[1];
+    const film::Estimate &in = ws.h_est.data()[0], &out = ws.h_est.data()[1];
     stats->pixels_left_out = (uint64_t)in.left_out;
     stats->sum_var_in = in.sum_var; stats->sum_sq_in = in.sum_mean2;
     stats->sum_var_out = out.sum_var; stats->sum_sq_out = out.sum_mean2;
@@ -329,15 +328,6 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
 }
 
 } // namespace
-
-void denoise_nlm_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
-
-NlmGrid nlm_grid(int w, int h) {
-    NlmGrid g{(w + nlm::kTile - 1) / nlm::kTile, 0, 0};
-    g.tiles = g.tiles_x * ((h + nlm::kTile - 1) / nlm::kTile);
-    g.blocks = std::min(g.tiles, nlm::kMaxBlocks);
-    return g;
-}
 
 void nlm_check_params(const std::string &who, const GdptNlmParams &p) {
     if (p.window_radius < 0 || p.window_radius > nlm::kMaxR)

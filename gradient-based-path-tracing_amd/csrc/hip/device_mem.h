@@ -1,10 +1,12 @@
 // device_mem.h — who owns device memory on the host side: a move-only Buffer for device and pinned memory, an Event, and the
-// registry of what a solver keeps per (device, stream). Every handle (GdptScene, GdptProgressive, the solvers' workspaces, the ranks
-// of GdptMulti) holds these as members, so a handle's destructor names no field, and a buffer's size cannot disagree with its
-// pointer: after a failed allocation the buffer is empty and the next call allocates again.
+// registries of what the solvers keep per (device, stream), which enrol themselves so that forget_stream reaches all of them. Every
+// handle (GdptScene, GdptProgressive, the solvers' workspaces, the ranks of GdptMulti) holds these as members, so a handle's
+// destructor names no field, and a buffer's size cannot disagree with its pointer: after a failed allocation the buffer is empty
+// and the next call allocates again.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 #include <map>
 #include <memory>
@@ -12,6 +14,7 @@
 #include <stdexcept>
 #include <string>
 #include <utility>
+#include <vector>
 
 namespace gdpt {
 
@@ -106,11 +109,36 @@ public:
     void create() { reset(); ck(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking), "hipStreamCreate"); }
 };
 
-// What a solver keeps per (device, stream): one T per pair, made on first use. A stream's owner calls forget_stream (below) before it
-// destroys the stream: the key is the handle's value, and a later stream with the same value must not inherit another one's state.
+// Every registry of per-(device, stream) state in the process, so that a stream's owner can drop all of it in one call without
+// knowing who keeps any: a registry enrols itself when it is made and leaves when it goes. The list and its mutex are leaked like the
+// registries of the solvers themselves, so no static destructor touches them.
+inline void forget_stream(int dev, hipStream_t stream);
+class PerStreamBase {
+public:
+    // Drops what the registry keeps for the pair, if anything. The caller guarantees that nothing of the pair is in flight.
+    virtual void forget(int dev, hipStream_t stream) = 0;
+    PerStreamBase(const PerStreamBase &) = delete;
+    PerStreamBase &operator=(const PerStreamBase &) = delete;
+protected:
+    PerStreamBase() { std::lock_guard<std::mutex> lk(all().mu); all().list.push_back(this); }
+    ~PerStreamBase() { std::lock_guard<std::mutex> lk(all().mu); auto &l = all().list; l.erase(std::find(l.begin(), l.end(), this)); }
+private:
+    struct All { std::mutex mu; std::vector<PerStreamBase *> list; };
+    static All &all() { static All &a = *new All(); return a; }
+    friend void forget_stream(int dev, hipStream_t stream);
+};
+
+// Drops everything any registry keeps for the pair. A stream's owner calls it before it destroys the stream: the key is the handle's
+// value, and a later stream with the same value must not inherit another one's state.
+inline void forget_stream(int dev, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(PerStreamBase::all().mu);
+    for (PerStreamBase *r : PerStreamBase::all().list) r->forget(dev, stream);
+}
+
+// What a solver keeps per (device, stream): one T per pair, made on first use, dropped by forget_stream (above).
 // An entry is destroyed with its device current. (Space: only the device switch is taken from it.)
 template <class T, class Space = DeviceSpace>
-class PerStream {
+class PerStream : public PerStreamBase {
     std::mutex mu_;
     std::map<std::pair<int, hipStream_t>, std::unique_ptr<T>> map_;
 public:
@@ -120,8 +148,7 @@ public:
         if (!slot) slot.reset(new T());
         return *slot;
     }
-    // The caller guarantees that nothing of the pair is in flight.
-    void forget(int dev, hipStream_t stream) {
+    void forget(int dev, hipStream_t stream) override {
         std::unique_ptr<T> gone;
         {
             std::lock_guard<std::mutex> lk(mu_);
@@ -144,8 +171,5 @@ public:
         map_.clear();
     }
 };
-
-// Drops everything the solvers keep for the pair: the Poisson solvers' and the reconstructions' scratch (poisson_kernels.hip).
-void forget_stream(int dev, hipStream_t stream);
 
 } // namespace gdpt

@@ -25,13 +25,7 @@ PoissonResult assemble_solve_device(int w, int h, const double *img, const doubl
                                     hipStream_t stream, bool timed);
 
 // Launch geometry of the element-wise kernels (the CG's cg_*, the DCT solvers' right-hand side, scaling and final pass) over the
-// n3 = 3 W H doubles of a film: groups of 256 consecutive elements and the blocks that stride over them (gdpt_debug_image_grid
-// reads them too).
-int poisson_groups(int n3);
-int poisson_blocks(int n3);
-
-// Drops every pair's scratch state and every device's tables (nothing in flight). One pair alone, before its stream is destroyed:
-// forget_stream (device_mem.h).
-void poisson_release_workspace();
+// n3 = 3 W H doubles of a film: film::stride_grid(n3, film::kMaxBlocks) (image_kernels.h). A pair's scratch goes, before its stream
+// is destroyed, with forget_stream (device_mem.h).
 
 } // namespace gdpt

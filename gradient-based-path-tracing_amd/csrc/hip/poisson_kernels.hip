@@ -16,12 +16,10 @@
 // Per iteration two kernels and no host round trip:
 //   cg_step_a: p' = r + beta p (recomputed on the 5 taps, p double-buffered), q = A p', partial <p',q>
 //   cg_step_b: x += a p', r -= a q, partial <r,r>
-// Scalars are reduced from per-block partials by every block in the same fixed order (deterministic).
+// Scalars are reduced from per-block partials by every block in the same fixed order (image_kernels.h: deterministic).
 #include "poisson_kernels.h"
 #include "device_mem.h"
-#include "recon_l1.h"
-#include "recon_spread.h"
-#include "denoise_nlm.h"
+#include "image_kernels.h"
 #include "../capi_common.h"
 #include "../../../include/gdpt.h"
 
@@ -38,8 +36,7 @@
 
 namespace gp {
 
-constexpr int kBlock = 256;
-constexpr int kMaxBlocks = 1024;
+using namespace film;      // kBlock, block_sum, reduce_partials, leave_block_sum
 
 struct CgState {
     double rr[2];         // <r,r> ping-pong by iteration parity
@@ -49,25 +46,6 @@ struct CgState {
     int iters;
     int converged;
 };
-
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    // fixed-order: xor tree inside each wave, then the 4 wave totals in index order
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / 64; k++) s += red[k];
-    return s;
-}
-__device__ __forceinline__ double reduce_partials(const double *part, int n, double *red) {
-    double v = 0;
-    for (int i = threadIdx.x; i < n; i += kBlock) v += part[i];
-    return block_sum(v, red);
-}
 
 struct Geo { int w, h, n3, row; };   // row = 3*w doubles per image row
 
@@ -122,14 +100,12 @@ __global__ __launch_bounds__(kBlock) void cg_init_kernel(Geo g, double alpha, co
 #pragma unroll
         for (int k = 0; k < 3; k++) if (ch == k) { s_wu[k] += wgt * ui; s_wh[k] += wgt * hv; }
     }
-    const int nb = gridDim.x;
-    double v;
-    v = block_sum(s_rr, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
-    v = block_sum(s_bb, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
+    leave_block_sum(partials, 0, s_rr, red);
+    leave_block_sum(partials, 1, s_bb, red);
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-        v = block_sum(s_wu[k], red); if (threadIdx.x == 0) partials[(2 + k) * nb + blockIdx.x] = v;
-        v = block_sum(s_wh[k], red); if (threadIdx.x == 0) partials[(5 + k) * nb + blockIdx.x] = v;
+        leave_block_sum(partials, 2 + k, s_wu[k], red);
+        leave_block_sum(partials, 5 + k, s_wh[k], red);
     }
 }
 
@@ -168,8 +144,7 @@ __global__ __launch_bounds__(kBlock) void cg_step_a(Geo g, double alpha, int it,
         p_out[i] = pi; q[i] = qi;
         s += pi * qi;
     }
-    double v = block_sum(s, red);
-    if (threadIdx.x == 0) part_pq[blockIdx.x] = v;
+    leave_block_sum(part_pq, 0, s, red);
 }
 
 __global__ __launch_bounds__(kBlock) void cg_step_b(Geo g, int it, const double *p, const double *q, double *x, double *r,
@@ -186,11 +161,8 @@ __global__ __launch_bounds__(kBlock) void cg_step_b(Geo g, int it, const double 
         r[i] = ri;
         s += ri * ri;
     }
-    double v = block_sum(s, red);
-    if (threadIdx.x == 0) {
-        part_rr[blockIdx.x] = v;
-        if (blockIdx.x == 0) st->iters = it + 1;
-    }
+    leave_block_sum(part_rr, 0, s, red);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->iters = it + 1;
 }
 
 // out = x + (sum(w u) - sum(w h)/alpha) / (4 (W-1)(H-1)) per channel  (the DC override, src/render.cpp:239)
@@ -235,9 +207,8 @@ __global__ __launch_bounds__(kBlock) void dct_rhs_kernel(Geo g, double alpha, co
 #pragma unroll
         for (int k = 0; k < 3; k++) if (ch == k) s_wu[k] += wgt * ui;
     }
-    const int nb = gridDim.x;
 #pragma unroll
-    for (int k = 0; k < 3; k++) { double v = block_sum(s_wu[k], red); if (threadIdx.x == 0) partials[k * nb + blockIdx.x] = v; }
+    for (int k = 0; k < 3; k++) leave_block_sum(partials, k, s_wu[k], red);
 }
 // assemble_kernel + dct_rhs_kernel in one pass over the film (whole images on one device): the five rendered buffers are read
 // once, c / cx / cy written once and not read back — every value by the expression the two kernels use, so the bits are theirs.
@@ -260,9 +231,8 @@ __global__ __launch_bounds__(kBlock) void assemble_rhs_kernel(Geo g, double alph
 #pragma unroll
         for (int k = 0; k < 3; k++) if (ch == k) s_wu[k] += wgt * ui;
     }
-    const int nb = gridDim.x;
 #pragma unroll
-    for (int k = 0; k < 3; k++) { double v = block_sum(s_wu[k], red); if (threadIdx.x == 0) partials[k * nb + blockIdx.x] = v; }
+    for (int k = 0; k < 3; k++) leave_block_sum(partials, k, s_wu[k], red);
 }
 // F^ = H^ / (alpha - (float)(lapY[y] + lapX[x]))  (:229-235)
 __global__ __launch_bounds__(kBlock) void dct_scale_kernel(Geo g, double alpha, const double *lap_x, const double *lap_y, double *hhat) {
@@ -486,6 +456,8 @@ __global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_
         // (red[] has one slot per wave of a 256-thread block: the first four waves reduce, all eight pass the barriers)
         double v = 0;
         if (tid < kBlock) for (int i = tid; i < e.dc_nb; i += kBlock) v += e.dc_partials[(size_t)ch * e.dc_nb + i];
+        // (wave_sum's tree written out: with the call in its place the compiler reorders this block's epilogue, and the whole 512 x 512
+        // solve measured 0.2 - 1.1 us above the parent's 86.4 us in three sessions: profiles/image_kernels_times.txt)
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
         if (lane == 0 && wave < kBlock / 64) red[wave] = v;
@@ -516,9 +488,6 @@ __global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_
 
 namespace gdpt {
 
-int poisson_groups(int n3) { return (n3 + gp::kBlock - 1) / gp::kBlock; }
-int poisson_blocks(int n3) { return std::min(gp::kMaxBlocks, poisson_groups(n3)); }
-
 namespace {
 
 struct Workspace {
@@ -532,7 +501,7 @@ struct Workspace {
     void ensure(size_t n3, hipStream_t stream) {
         for (auto *b : {&x, &r, &q, &p0, &p1}) b->grow(n3, stream, "hipMalloc(poisson workspace)");
         if (ev[2]) return;                            // the rest has one size, and is made once
-        partials.alloc(10 * gp::kMaxBlocks, "hipMalloc(partials)");
+        partials.alloc(10 * film::kMaxBlocks, "hipMalloc(partials)");
         rel.alloc(1, "hipMalloc(rel)");
         state.alloc(1, "hipMalloc(state)");
         h_state.alloc(1, "hipHostMalloc");
@@ -578,7 +547,8 @@ struct StreamState {                  // everything a solve on one (device, stre
     DctWorkspace dct;
 };
 // Both registries are leaked on purpose: what is never forgotten stays until the process ends, and no HIP or rocBLAS call is made
-// from a static destructor (the runtime libraries may already be gone by then).
+// from a static destructor (the runtime libraries may already be gone by then). forget_stream (device_mem.h) drops a pair's
+// StreamState: scratch buffers, rocBLAS handle, timing events.
 PerStream<StreamState> &g_streams = *new PerStream<StreamState>();
 std::mutex g_tables_mu;
 std::map<int, std::unique_ptr<DctTables>> &g_tables = *new std::map<int, std::unique_ptr<DctTables>>();
@@ -670,16 +640,16 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
     gp::Geo g{w, h, w * h * 3, w * 3};
     const size_t plane = (size_t)w * h;
     for (auto &b : ws.buf) b.grow(3 * plane, stream, "hipMalloc(dct buffers)");   // (earlier solves may still use the old buffers)
-    if (!ws.partials) ws.partials.alloc(3 * gp::kMaxBlocks, "hipMalloc(dct partials)");
-    const int nb = poisson_blocks(g.n3);
+    if (!ws.partials) ws.partials.alloc(3 * film::kMaxBlocks, "hipMalloc(dct partials)");
+    const int nb = film::stride_grid((size_t)g.n3, film::kMaxBlocks).blocks;
     if (timed) {
         for (auto &e : ws.ev) if (!e) e.create();
         ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     }
     double *A = ws.buf[0], *B = ws.buf[1];
-    if (raw) hipLaunchKernelGGL(gp::assemble_rhs_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, raw[0], raw[1], raw[2], raw[3], raw[4],
+    if (raw) hipLaunchKernelGGL(gp::assemble_rhs_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, raw[0], raw[1], raw[2], raw[3], raw[4],
                                 const_cast<double *>(d_c), const_cast<double *>(d_gx), const_cast<double *>(d_gy), A, ws.partials);
-    else hipLaunchKernelGGL(gp::dct_rhs_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, d_c, d_gx, d_gy, A, ws.partials);
+    else hipLaunchKernelGGL(gp::dct_rhs_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, d_c, d_gx, d_gy, A, ws.partials);
     const double one = 1.0, zero = 0.0;
     // Row-major X (h x w) is the column-major matrix X^T (w x h, ld = w). Row transform T = X * Cw  <=>  T^T = Cw^T * X^T:
     // the row-major buffer of Cw read column-major IS Cw^T, so (N, N). Column transform Y = Ch^T * T  <=>  Y^T = T^T * Ch:
@@ -692,10 +662,10 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
     };
     if (library_gemm) {                                      // GDPT_SOLVER_DCT: the two 1-D passes as rocBLAS dgemm_strided_batched
         transform(A, B, A);                                  // A = DCT2D(h)
-        hipLaunchKernelGGL(gp::dct_scale_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, lap_x, lap_y, A);
-        hipLaunchKernelGGL(gp::dct_dc_kernel, dim3(1), dim3(gp::kBlock), 0, stream, g, A, ws.partials, nb);
+        hipLaunchKernelGGL(gp::dct_scale_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, lap_x, lap_y, A);
+        hipLaunchKernelGGL(gp::dct_dc_kernel, dim3(1), dim3(film::kBlock), 0, stream, g, A, ws.partials, nb);
         transform(A, B, A);                                  // A = DCT2D(F^)
-        hipLaunchKernelGGL(gp::dct_finalize_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, A, d_out);
+        hipLaunchKernelGGL(gp::dct_finalize_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, A, d_out);
     } else {
         // GDPT_SOLVER_DCT_MFMA: own folded fp64 MFMA GEMMs, per (channel, output parity) plane:  T = X * Cw  (rows),
         // Y = Ch^T * T  (columns); spectral division + DC override ride on the second product, the final scaling +
@@ -743,25 +713,6 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
 
 } // namespace
 
-// Owners of a stream call it before destroying the stream (device_mem.h). The caller guarantees no solve is in flight on the pair.
-void forget_stream(int dev, hipStream_t stream) {
-    g_streams.forget(dev, stream);         // scratch buffers, rocBLAS handle, timing events
-    recon_l1_forget_stream(dev, stream);
-    recon_spread_forget_stream(dev, stream);
-    denoise_nlm_forget_stream(dev, stream);
-}
-
-void poisson_release_workspace() {
-    g_streams.clear();
-    std::lock_guard<std::mutex> lk(g_tables_mu);
-    for (auto &kv : g_tables) {
-        const int cur = DeviceSpace::set_device(kv.first);
-        kv.second.reset();
-        DeviceSpace::set_device(cur);
-    }
-    g_tables.clear();
-}
-
 void launch_assemble(int w, int h, int row_begin, int row_end, const double *img, const double *cx0, const double *cy0, const double *cx1,
                      const double *cy1, double *c, double *cx, double *cy, hipStream_t stream) {
     if (w <= 0 || h <= 0) throw std::runtime_error("assemble: empty image");
@@ -769,8 +720,8 @@ void launch_assemble(int w, int h, int row_begin, int row_end, const double *img
     if (row_begin < 0 || row_end > h || row_begin >= row_end) throw std::runtime_error("assemble: bad row band");
     gp::Geo g{w, h, w * h * 3, w * 3};
     const int n = (row_end - row_begin) * g.row;
-    int nb = std::min(gp::kMaxBlocks * 2, (n + gp::kBlock - 1) / gp::kBlock);
-    hipLaunchKernelGGL(gp::assemble_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, row_begin, row_end, img, cx0, cy0, cx1, cy1, c, cx, cy);
+    const int nb = film::stride_grid((size_t)n, 2 * film::kMaxBlocks).blocks;
+    hipLaunchKernelGGL(gp::assemble_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, row_begin, row_end, img, cx0, cy0, cx1, cy1, c, cx, cy);
     ck(hipGetLastError(), "assemble kernel launch");
 }
 
@@ -813,13 +764,13 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
     gp::Geo g{w, h, w * h * 3, w * 3};
     ss.cg.ensure((size_t)g.n3, stream);
     Workspace &ws = ss.cg;
-    const int nb = poisson_blocks(g.n3);
+    const int nb = film::stride_grid((size_t)g.n3, film::kMaxBlocks).blocks;
     // init layout: 8 slots of nb doubles (slot 0 = <r,r>, reused as part_rr); <p,q> partials live in slot 8
     double *part_rr = ws.partials, *part_pq = ws.partials + 8 * (size_t)nb;
     hipEvent_t e0 = ws.ev[0], e1 = ws.ev[1];
     ck(hipEventRecord(e0, stream), "hipEventRecord");
-    hipLaunchKernelGGL(gp::cg_init_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, d_c, d_gx, d_gy, ws.x, ws.r, ws.p0, ws.p1, ws.partials);
-    hipLaunchKernelGGL(gp::cg_init_reduce_kernel, dim3(1), dim3(gp::kBlock), 0, stream, nb, ws.partials, ws.state, tol);
+    hipLaunchKernelGGL(gp::cg_init_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, d_c, d_gx, d_gy, ws.x, ws.r, ws.p0, ws.p1, ws.partials);
+    hipLaunchKernelGGL(gp::cg_init_reduce_kernel, dim3(1), dim3(film::kBlock), 0, stream, nb, ws.partials, ws.state, tol);
     ck(hipGetLastError(), "cg init launch");
     const int chunk = 32;          // even, so buffer parity is chunk-invariant
     int launched = 0;
@@ -830,8 +781,8 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
             int it = launched + k;
             const double *pin = (it & 1) ? ws.p1 : ws.p0;
             double *pout = (it & 1) ? ws.p0 : ws.p1;
-            hipLaunchKernelGGL(gp::cg_step_a, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, it, ws.r, pin, pout, ws.q, part_rr, part_pq, ws.state);
-            hipLaunchKernelGGL(gp::cg_step_b, dim3(nb), dim3(gp::kBlock), 0, stream, g, it, pout, ws.q, ws.x, ws.r, part_pq, part_rr, ws.state);
+            hipLaunchKernelGGL(gp::cg_step_a, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, it, ws.r, pin, pout, ws.q, part_rr, part_pq, ws.state);
+            hipLaunchKernelGGL(gp::cg_step_b, dim3(nb), dim3(film::kBlock), 0, stream, g, it, pout, ws.q, ws.x, ws.r, part_pq, part_rr, ws.state);
         }
         launched += chunk;
         ck(hipGetLastError(), "cg chunk launch");
@@ -846,7 +797,7 @@ PoissonResult poisson_solve_device(int w, int h, const double *d_c, const double
         ck(hipEventSynchronize(chunk_ev), "hipEventSynchronize");
         if (ws.h_state->converged || !more) done = true;
     }
-    hipLaunchKernelGGL(gp::cg_finalize_kernel, dim3(nb), dim3(gp::kBlock), 0, stream, g, alpha, ws.x, d_out, part_rr, nb, ws.state, ws.rel);
+    hipLaunchKernelGGL(gp::cg_finalize_kernel, dim3(nb), dim3(film::kBlock), 0, stream, g, alpha, ws.x, d_out, part_rr, nb, ws.state, ws.rel);
     ck(hipGetLastError(), "cg finalize launch");
     ck(hipMemcpyAsync(ws.h_state, ws.state, sizeof(gp::CgState), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(state)");
     ck(hipMemcpyAsync(ws.h_rel, ws.rel, sizeof(double), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(rel)");

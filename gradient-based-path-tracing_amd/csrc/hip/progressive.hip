@@ -12,8 +12,8 @@
 // threads read consecutive 24-byte triples and a wave covers 1536 contiguous bytes per plane).
 //   fold_kernel      one pass over the film for all buffers: reads pass, mean, M2, writes mean, M2 (the first pass reads no
 //                    mean / M2: they start at 0), and leaves the block partials of the two sums and of the left-out count.
-//   finish_kernel    one block: the partials reduced in a fixed order (xor tree in a wave, waves in index order, blocks strided
-//                    in index order), so that the same session gives the same bits and the same stopping pass.
+//   finish_kernel    (image_kernels.hip) one block: the partials reduced in a fixed order (xor tree in a wave, waves in index order,
+//                    blocks strided in index order), so that the same session gives the same bits and the same stopping pass.
 //   variance_kernel  read-out: M2 / ((K-1) W) per buffer and the variances of the assembled cx, cy.
 //   merge_kernel     the fold's sibling for two sessions: dst takes in src's (mean, M2) by the pairwise update below.
 // The fold is memory bound: 5 doubles of traffic per component (3 read, 2 written), 40 bytes x 15 components per GradPath pixel.
@@ -35,6 +35,8 @@
 #include <memory>
 
 namespace prg {
+
+using namespace film;             // kBlock, kMaxBlocks, leave_block_sum
 
 struct Planes {
     const double *pass[5];
@@ -73,11 +75,9 @@ __global__ __launch_bounds__(kBlock) void fold_kernel(Planes p, int npix, double
             }
         }
     }
-    const int nb = gridDim.x;
-    double v;
-    v = block_sum(s_var, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
-    v = block_sum(s_m2, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
-    v = block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
+    leave_block_sum(partials, 0, s_var, red);
+    leave_block_sum(partials, 1, s_m2, red);
+    leave_block_sum(partials, 2, s_out, red);
 }
 
 // dst (mean, m2) takes in src (smean, sm2): f = Wb / W, g = Wa Wb / W for dst's Wa, src's Wb, W = Wa + Wb; norm = (K - 1) W of the
@@ -118,22 +118,9 @@ __global__ __launch_bounds__(kBlock) void merge_kernel(MergePlanes p, int npix, 
             }
         }
     }
-    const int nb = gridDim.x;
-    double v;
-    v = block_sum(s_var, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
-    v = block_sum(s_m2, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
-    v = block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
-}
-
-__global__ __launch_bounds__(kBlock) void finish_kernel(int nb, const double *partials, Estimate *est) {
-    __shared__ double red[kBlock / 64];
-    double r[3];
-    for (int k = 0; k < 3; k++) {
-        double v = 0;
-        for (int i = threadIdx.x; i < nb; i += kBlock) v += partials[k * nb + i];
-        r[k] = block_sum(v, red);
-    }
-    if (threadIdx.x == 0) { est->sum_var = r[0]; est->sum_mean2 = r[1]; est->left_out = r[2]; }
+    leave_block_sum(partials, 0, s_var, red);
+    leave_block_sum(partials, 1, s_m2, red);
+    leave_block_sum(partials, 2, s_out, red);
 }
 
 // var[b] = M2[b] / norm for b < NBUF; NBUF == 5: vcx(x,y) = var cx0(x,y) + var cx1(x-1,y), vcy(x,y) = var cy0(x,y) + var cy1(x,y-1),
@@ -160,8 +147,6 @@ namespace {
 
 using gdpt::ck;
 
-using prg::fold_blocks;
-
 void add_totals(GdptRenderStats &t, const GdptRenderStats &rs) {
     t.samples += rs.samples; t.rays += rs.rays; t.bounces += rs.bounces;
     t.nodes_visited += rs.nodes_visited; t.tris_tested += rs.tris_tested; t.nonfinite_samples += rs.nonfinite_samples;
@@ -172,10 +157,10 @@ void add_totals(GdptRenderStats &t, const GdptRenderStats &rs) {
 
 // the reduction of the partials a fold or merge launch left, the estimate to the host, the launches' device time; waits for the stream
 void finish_estimate(GdptProgressive &s, int nb, const char *what) {
-    prg::launch_finish(nb, s.partials, s.d_est, s.stream);
+    film::launch_finish(nb, s.partials, s.d_est, s.stream);
     ck(hipGetLastError(), what);
     ck(hipEventRecord(s.ev[1], s.stream), "hipEventRecord");
-    ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
+    ck(hipMemcpyAsync(s.h_est, s.d_est, sizeof(film::Estimate), hipMemcpyDeviceToHost, s.stream), "hipMemcpyAsync(estimate)");
     ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(fold)");
     s.est = *s.h_est;
     { float ms = 0; ck(hipEventElapsedTime(&ms, s.ev[0], s.ev[1]), "hipEventElapsedTime"); s.fold_ms = ms; }
@@ -191,10 +176,6 @@ std::vector<std::pair<int, int>> intervals_held(const GdptProgressive &s) {
 } // namespace
 
 namespace prg {
-
-void launch_finish(int nb, const double *partials, Estimate *est, hipStream_t stream) {
-    hipLaunchKernelGGL(finish_kernel, dim3(1), dim3(kBlock), 0, stream, nb, partials, est);
-}
 
 double error_estimate(const GdptProgressive &s) {
     if (s.passes < 2) return std::numeric_limits<double>::quiet_NaN();
@@ -228,9 +209,9 @@ void add_pass(GdptProgressive &s, int spp, GdptRenderStats *stats) {
 
     prg::Planes pl{};
     for (int k = 0; k < s.nbuf; k++) { pl.pass[k] = s.pass[k]; pl.mean[k] = s.mean[k]; pl.m2[k] = s.m2[k]; }
-    const int npix = s.w * s.h, nb = fold_blocks(npix), K = s.passes + 1;
+    const int npix = s.w * s.h, nb = film::stride_grid((size_t)npix, film::kMaxBlocks, 1).blocks, K = s.passes + 1;
     const double n = (double)spp, w_new = (double)(s.done + spp), norm = (double)(K - 1) * w_new;
-    const dim3 grid(nb), block(prg::kBlock);
+    const dim3 grid(nb), block(film::kBlock);
     const bool first = s.passes == 0;
     ck(hipEventRecord(s.ev[0], s.stream), "hipEventRecord");
     if (s.nbuf == 5) {
@@ -284,10 +265,10 @@ void merge(GdptProgressive &dst, const GdptProgressive &src) {
     } else
         for (int k = 0; k < dst.nbuf; k++) { pl.smean[k] = src.mean[k]; pl.sm2[k] = src.m2[k]; }
     for (int k = 0; k < dst.nbuf; k++) { pl.mean[k] = dst.mean[k]; pl.m2[k] = dst.m2[k]; }
-    const int npix = dst.w * dst.h, nb = fold_blocks(npix), K = dst.passes + src.passes;
+    const int npix = dst.w * dst.h, nb = film::stride_grid((size_t)npix, film::kMaxBlocks, 1).blocks, K = dst.passes + src.passes;
     const double wa = (double)dst.done, wb = (double)src.done, w = wa + wb;
     const double f = wb / w, g = wa * wb / w, norm = (double)(K - 1) * w;
-    const dim3 grid(nb), block(prg::kBlock);
+    const dim3 grid(nb), block(film::kBlock);
     const bool first = dst.passes == 0;
     ck(hipEventRecord(dst.ev[0], dst.stream), "hipEventRecord");
     if (dst.nbuf == 5) {
@@ -306,7 +287,7 @@ void merge(GdptProgressive &dst, const GdptProgressive &src) {
 void reset(GdptProgressive &s) {
     s.own_done = 0; s.merged = 0; s.done = 0; s.passes = 0; s.stop_reason = GDPT_STOP_NONE;
     s.merged_intervals.clear();
-    s.est = prg::Estimate{}; s.fold_ms = 0; s.totals = GdptRenderStats{};
+    s.est = film::Estimate{}; s.fold_ms = 0; s.totals = GdptRenderStats{};
 }
 
 } // namespace prg
@@ -329,9 +310,9 @@ void compute_variances(GdptProgressive &s) {
     for (int k = 0; k < s.nbuf; k++) { vp.m2[k] = s.m2[k]; vp.var[k] = s.var[k]; }
     vp.vcx = s.var[5]; vp.vcy = s.var[6];
     const double norm = (double)(s.passes - 1) * (double)s.done;
-    const int nb = prg::variance_blocks(s.elems);
-    if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
-    else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(prg::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+    const int nb = film::stride_grid(s.elems, 4 * film::kMaxBlocks, 1).blocks;
+    if (s.nbuf == 5) hipLaunchKernelGGL(prg::variance_kernel<5>, dim3(nb), dim3(film::kBlock), 0, s.stream, vp, s.w, s.h, norm);
+    else hipLaunchKernelGGL(prg::variance_kernel<1>, dim3(nb), dim3(film::kBlock), 0, s.stream, vp, s.w, s.h, norm);
     ck(hipGetLastError(), "progressive variance launch");
 }
 
@@ -369,7 +350,7 @@ void create_session(const char *fn, GdptScene *scene, const GdptProgressiveConfi
         if (set == s->pass && num == 0) continue;        // an accumulator renders nothing
         for (int k = 0; k < s->nbuf; k++) set[k].alloc(s->elems, "hipMalloc(progressive planes)");
     }
-    s->partials.alloc(3 * prg::kMaxBlocks, "hipMalloc(progressive partials)");
+    s->partials.alloc(3 * film::kMaxBlocks, "hipMalloc(progressive partials)");
     s->d_est.alloc(1, "hipMalloc(progressive estimate)");
     s->h_est.alloc(1, "hipHostMalloc(progressive estimate)");
     for (auto &e : s->ev) e.create();

@@ -1,39 +1,12 @@
 // progressive_internal.h — the progressive session handle and the entry points shared by progressive.hip (sessions, the merge of
 // sessions) and progressive_group.hip (one slice session per device, a merged total).
 #pragma once
+#include "image_kernels.h"
 #include "scene_internal.h"
 
 #include <algorithm>
 #include <utility>
 #include <vector>
-
-namespace prg {
-struct Estimate { double sum_var, sum_mean2, left_out; };
-
-constexpr int kBlock = 256, kMaxBlocks = 1024;
-
-// What every kernel that leaves block partials for finish_kernel (progressive.hip) reduces its block with.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-    // fixed order: xor tree inside each wave, then the wave totals in index order
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[wave] = v;
-    __syncthreads();
-    double s = red[0];
-#pragma unroll
-    for (int k = 1; k < kBlock / 64; k++) s += red[k];
-    return s;
-}
-
-// Launch geometry of the kernels in which a thread owns a pixel (fold_kernel, merge_kernel, recon_spread.hip's spread_kernel) or an
-// element (variance_kernel): groups of kBlock consecutive pixels / elements, and the blocks that stride over them. The launches and
-// gdpt_debug_image_grid (include/gdpt_debug.h) both take them from here.
-inline int groups(size_t n) { return (int)((n + kBlock - 1) / kBlock); }
-inline int fold_blocks(int npix) { return std::max(1, std::min(kMaxBlocks, groups((size_t)npix))); }
-inline int variance_blocks(size_t elems) { return std::max(1, std::min(4 * kMaxBlocks, groups(elems))); }
-} // namespace prg
 
 struct GdptProgressive {
     GdptScene *scene = nullptr;
@@ -56,9 +29,9 @@ struct GdptProgressive {
     gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
     gdpt::DeviceBuffer<double> nlm_buf[2];     // filtered mean and its variance on their way to host memory: allocated by the first denoise
     gdpt::DeviceBuffer<double> partials;
-    gdpt::DeviceBuffer<prg::Estimate> d_est;
-    gdpt::PinnedBuffer<prg::Estimate> h_est;
-    prg::Estimate est{};             // of the last fold or merge (valid from 2 passes)
+    gdpt::DeviceBuffer<film::Estimate> d_est;
+    gdpt::PinnedBuffer<film::Estimate> h_est;
+    film::Estimate est{};             // of the last fold or merge (valid from 2 passes)
     gdpt::Event ev[2];               // around the fold / merge launches
     double fold_ms = 0;              // device time of the last fold (fold_kernel + finish_kernel) or merge (merge_kernel + finish_kernel)
     GdptRenderStats totals{};
@@ -73,8 +46,6 @@ void merge(GdptProgressive &dst, const GdptProgressive &src);
 // Back to the state of a fresh accumulator: nothing held (the planes keep their bytes: the next merge overwrites them).
 void reset(GdptProgressive &s);
 double error_estimate(const GdptProgressive &s);
-// finish_kernel on `stream`: three runs of nb block partials (as fold_kernel leaves them) reduced in a fixed order into *est
-void launch_finish(int nb, const double *partials, Estimate *est, hipStream_t stream);
 // What gdpt_progressive_reconstruct / _reconstruct_weighted do up to the copy-out: the image is left in s.asm_buf[3], enqueued on the
 // session's stream (the weighted kinds and L1 have waited for it). They throw what the entry points report.
 void reconstruct(GdptProgressive &s, double dataCost, const GdptReconParams *recon, GdptReconStats *stats);

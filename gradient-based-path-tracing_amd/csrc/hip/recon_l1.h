@@ -9,11 +9,8 @@ struct ReconL1Result { int irls_rounds, cg_iters_total, cg_iters_last; double en
 
 // L1 reconstruction by IRLS over a weighted, Jacobi-preconditioned CG (include/gdpt.h: gdpt_reconstruct) on device buffers
 // (W*H*3 doubles, interleaved RGB). d_out is the iterate itself and must not alias an input. Synchronises `stream`:
-// convergence of every inner solve is checked on the host, one chunk of iterations behind. Scratch is kept per (device, stream).
+// convergence of every inner solve is checked on the host, one chunk of iterations behind. Scratch is kept per (device, stream), and dropped by forget_stream (device_mem.h).
 ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, double alpha,
                               const ReconL1Params &p, double *d_out, hipStream_t stream);
-
-// Drops the (device, stream) pair's scratch; forget_stream (device_mem.h) calls it, and is what a stream's owner calls.
-void recon_l1_forget_stream(int dev, hipStream_t stream);
 
 } // namespace gdpt

@@ -13,7 +13,7 @@
 // warm-started from f_{k-1} (round 0: from u), until |r| <= cg_tol |b| or cg_max_iters. Energy E(f) = sum over rows of |r|_2.
 //
 // Kernels. A thread owns a PIXEL (its three channels), so every weight is loaded once for three unknowns.
-//   weights_kernel   one pass over f, u, gx, gy per round: the two edge-weight planes wx(x,y) (edge x-1|x; 0 at x = 0) and
+//   weights_kernel   (recon_pcg.h, with the positional row policy) one pass over f, u, gx, gy per round: the two edge-weight planes wx(x,y) (edge x-1|x; 0 at x = 0) and
 //                    wy(x,y), the diagonal alpha w_d + sum of the four edge weights (the Jacobi preconditioner AND the
 //                    centre tap: w_d itself is never needed again, so it is not stored), the initial residual b - A f
 //                    (formed from the residual rows, not as a difference of two large numbers) and the block partials of
@@ -25,8 +25,7 @@
 // Two launches per iteration and no host round trip: scalars are reduced from per-block partials by every block in the
 // same fixed order, so the same inputs give the same bits. The host reads the convergence flag one chunk of iterations
 // behind the launches, as the CG of poisson_kernels.hip does; kernels of a converged solve return at once.
-// Grid: one block of 256 threads per tile, at most kMaxBlocks blocks striding over the tiles (so that the partial arrays
-// every block re-reduces stay short); 8 KB of LDS, 50 VGPRs and no scratch, i.e. occupancy is bound by neither.
+// Grid: film::tile_grid (image_kernels.h), one block of 256 threads per tile, at most kMaxBlocks blocks striding over the tiles; 8 KB of LDS, 50 VGPRs and no scratch, i.e. occupancy is bound by neither.
 #include "recon_l1.h"
 #include "recon_pcg.h"
 #include "../capi_common.h"
@@ -39,59 +38,7 @@
 
 namespace rl1 {
 
-// partials layout: slot s of gridDim.x doubles: [0] <r,z>, [1] <r,r>, [2] <b,b>, [3] energy, [4] <p,q>
-// unit != 0: all weights 1 (round 0). x_init (nullable): receives a copy of f (round 0: the iterate starts at u).
-// WRITE = false: only the energy partials (the energy of the last iterate).
-template <bool WRITE>
-__global__ __launch_bounds__(kBlock) void weights_kernel(Geo g, double alpha, double eps, int unit, const double *f, const double *u,
-                                                         const double *gx, const double *gy, double *x_init, double *wx, double *wy,
-                                                         double *diag, double *r, double *partials) {
-    __shared__ double red[kBlock / 64];
-    const int row = 3 * g.w;
-    double s_rz = 0, s_rr = 0, s_bb = 0, s_e = 0;
-    for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
-        const int ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
-        const int x = tx * kTileW + (threadIdx.x & (kTileW - 1)), y = ty * kTileH + (threadIdx.x / kTileW);
-        if (x >= g.w || y >= g.h) continue;
-        const int pix = y * g.w + x, i = 3 * pix;
-        const bool has_l = x > 0, has_u = y > 0, has_r = x + 1 < g.w, has_d = y + 1 < g.h;
-        double fc[3], uc[3], d[3], el[3] = {0, 0, 0}, er[3] = {0, 0, 0}, eu[3] = {0, 0, 0}, ed[3] = {0, 0, 0};
-        double gl[3] = {0, 0, 0}, gr[3] = {0, 0, 0}, gu[3] = {0, 0, 0}, gd[3] = {0, 0, 0};
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            fc[c] = f[i + c]; uc[c] = u[i + c]; d[c] = fc[c] - uc[c];
-            if (has_l) { gl[c] = gx[i + c]; el[c] = (fc[c] - f[i - 3 + c]) - gl[c]; }
-            if (has_r) { gr[c] = gx[i + 3 + c]; er[c] = (f[i + 3 + c] - fc[c]) - gr[c]; }
-            if (has_u) { gu[c] = gy[i + c]; eu[c] = (fc[c] - f[i - row + c]) - gu[c]; }
-            if (has_d) { gd[c] = gy[i + row + c]; ed[c] = (f[i + row + c] - fc[c]) - gd[c]; }
-        }
-        const double n_d = sqrt(alpha) * norm3(d), n_l = norm3(el), n_u = norm3(eu);
-        s_e += n_d + (has_l ? n_l : 0.0) + (has_u ? n_u : 0.0);      // every row once: its data row and the two edges it owns
-        if (!WRITE) continue;
-        const double w_d = unit ? 1.0 : 1.0 / (eps + n_d);
-        const double w_l = has_l ? (unit ? 1.0 : 1.0 / (eps + n_l)) : 0.0;
-        const double w_u = has_u ? (unit ? 1.0 : 1.0 / (eps + n_u)) : 0.0;
-        const double w_r = has_r ? (unit ? 1.0 : 1.0 / (eps + norm3(er))) : 0.0;
-        const double w_dn = has_d ? (unit ? 1.0 : 1.0 / (eps + norm3(ed))) : 0.0;
-        const double dg = alpha * w_d + ((w_l + w_r) + (w_u + w_dn));
-        wx[pix] = w_l; wy[pix] = w_u; diag[pix] = dg;
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const double b = alpha * w_d * uc[c] + ((w_l * gl[c] - w_r * gr[c]) + (w_u * gu[c] - w_dn * gd[c]));
-            const double ri = -(alpha * w_d * d[c] + ((w_l * el[c] - w_r * er[c]) + (w_u * eu[c] - w_dn * ed[c])));     // b - A f
-            r[i + c] = ri;
-            if (x_init) x_init[i + c] = fc[c];
-            s_rr += ri * ri; s_rz += ri * ri / dg; s_bb += b * b;
-        }
-    }
-    const int nb = gridDim.x;
-    double v;
-    v = block_sum(s_e, red); if (threadIdx.x == 0) partials[3 * nb + blockIdx.x] = v;
-    if (!WRITE) return;
-    v = block_sum(s_rz, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = v;
-    v = block_sum(s_rr, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = v;
-    v = block_sum(s_bb, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = v;
-}
+// partials layout (recon_pcg.h: weights_kernel): slot s of gridDim.x doubles: [0] <r,z>, [1] <r,r>, [2] <b,b>, [3] energy, [4] <p,q>
 
 // one block, after a weights pass: the round's scalars. reset == 0: only the energy (after weights_kernel<false>).
 __global__ __launch_bounds__(kBlock) void round_init_kernel(int nb, const double *partials, State *st, double tol, int reset) {
@@ -106,7 +53,7 @@ __global__ __launch_bounds__(kBlock) void round_init_kernel(int nb, const double
 }
 
 // iteration `it` of a round (parity selects the p buffers; it == 0 reads no p_in): p_out = z + beta p_in, q = A p_out, partial <p_out,q>
-__global__ __launch_bounds__(kBlock) void pcg_step_a(Geo g, int it, const double *r, const double *p_in, double *p_out, double *q,
+__global__ __launch_bounds__(kBlock) void pcg_step_a(TileGrid g, int it, const double *r, const double *p_in, double *p_out, double *q,
                                                      const double *wx, const double *wy, const double *diag,
                                                      const double *part_rz, const double *part_rr, double *part_pq, State *st) {
     __shared__ double sp[3][kTileH + 2][kPitch];
@@ -136,8 +83,8 @@ __global__ __launch_bounds__(kBlock) void pcg_step_a(Geo g, int it, const double
     const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
     double s = 0;
     for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
-        const int ty = t / g.tiles_x, tx = t - ty * g.tiles_x;
-        const int x0 = tx * kTileW, y0 = ty * kTileH, x = x0 + lx, y = y0 + ly;
+        const TilePixel tp = tile_pixel<kTileW, kTileH>(g, t);
+        const int x0 = tp.x0, y0 = tp.y0, x = tp.x, y = tp.y;
         double pv[3], dg;
         direction(x, y, pv, dg);
         __syncthreads();                                   // the previous tile's taps have been read
@@ -168,8 +115,7 @@ __global__ __launch_bounds__(kBlock) void pcg_step_a(Geo g, int it, const double
             }
         }
     }
-    const double v = block_sum(s, red);
-    if (threadIdx.x == 0) part_pq[blockIdx.x] = v;
+    leave_block_sum(part_pq, 0, s, red);
 }
 
 __global__ __launch_bounds__(kBlock) void pcg_step_b(int npix, int it, const double *p, const double *q, const double *diag, double *x, double *r,
@@ -191,13 +137,9 @@ __global__ __launch_bounds__(kBlock) void pcg_step_b(int npix, int it, const dou
             s_rr += ri * ri; s_rz += ri * ri / dg;
         }
     }
-    double v = block_sum(s_rz, red);
-    if (threadIdx.x == 0) part_rz[blockIdx.x] = v;
-    v = block_sum(s_rr, red);
-    if (threadIdx.x == 0) {
-        part_rr[blockIdx.x] = v;
-        if (blockIdx.x == 0) st->iters = it + 1;
-    }
+    leave_block_sum(part_rz, 0, s_rz, red);
+    leave_block_sum(part_rr, 0, s_rr, red);
+    if (blockIdx.x == 0 && threadIdx.x == 0) st->iters = it + 1;
 }
 
 // one block, at the end of a round: |r| / |b| of the iterate as it stands
@@ -213,7 +155,8 @@ namespace gdpt {
 
 namespace {
 
-// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip)
+// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip); a pair's entry
+// goes with forget_stream (device_mem.h)
 PerStream<ReconWorkspace> &g_workspaces = *new PerStream<ReconWorkspace>();
 
 } // namespace
@@ -222,7 +165,7 @@ void ReconWorkspace::ensure(size_t npix, hipStream_t stream) {
     for (auto *b : {&r, &q, &p0, &p1}) b->grow(3 * npix, stream, "hipMalloc(recon workspace)");
     for (auto *b : {&wx, &wy, &diag}) b->grow(npix, stream, "hipMalloc(recon weights)");
     if (ev[2]) return;                    // the rest has one size, and is made once
-    partials.alloc(5 * rl1::kMaxBlocks, "hipMalloc(recon partials)");
+    partials.alloc(5 * film::kMaxBlocks, "hipMalloc(recon partials)");
     state.alloc(1, "hipMalloc(recon state)");
     h_state.alloc(1, "hipHostMalloc");
     for (auto &e : ev) e.create();
@@ -230,21 +173,15 @@ void ReconWorkspace::ensure(size_t npix, hipStream_t stream) {
 void ReconWorkspace::ensure_confidence(size_t npix, hipStream_t stream) {
     for (auto &b : var) b.grow(npix, stream, "hipMalloc(recon row variances)");
     for (auto &b : conf) b.grow(npix, stream, "hipMalloc(recon confidences)");
-    if (!conf_partials) conf_partials.alloc(kConfSlots * rl1::kMaxBlocks, "hipMalloc(recon confidence partials)");
+    if (!conf_partials) conf_partials.alloc(kConfSlots * film::kMaxBlocks, "hipMalloc(recon confidence partials)");
     if (!conf_stats) conf_stats.alloc(1, "hipMalloc(recon confidence scalars)");
     if (!h_conf_stats) h_conf_stats.alloc(1, "hipHostMalloc");
 }
 
 ReconWorkspace &recon_workspace(int dev, hipStream_t stream) { return g_workspaces.get(dev, stream); }
 
-rl1::Geo recon_geo(int w, int h) {
-    rl1::Geo g{w, h, (w + rl1::kTileW - 1) / rl1::kTileW, 0};
-    g.tiles = g.tiles_x * ((h + rl1::kTileH - 1) / rl1::kTileH);
-    return g;
-}
-
 void recon_round_init(ReconWorkspace &ws, int nb, double tol, int reset, hipStream_t stream) {
-    hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), dim3(rl1::kBlock), 0, stream, nb, ws.partials, ws.state, tol, reset);
+    hipLaunchKernelGGL(rl1::round_init_kernel, dim3(1), dim3(film::kBlock), 0, stream, nb, ws.partials, ws.state, tol, reset);
 }
 
 void recon_read_state(ReconWorkspace &ws, hipStream_t stream) {
@@ -252,10 +189,11 @@ void recon_read_state(ReconWorkspace &ws, hipStream_t stream) {
     ck(hipEventRecord(ws.ev[2], stream), "hipEventRecord");
 }
 
-void recon_pcg_round(ReconWorkspace &ws, const rl1::Geo &g, int nb, double *d_out, const ReconL1Params &p, hipStream_t stream, int k,
+void recon_pcg_round(ReconWorkspace &ws, const film::TileGrid &g, double *d_out, const ReconL1Params &p, hipStream_t stream, int k,
                      ReconL1Result &res) {
+    const int nb = g.blocks;
     double *part_rz = ws.partials, *part_rr = ws.partials + nb, *part_pq = ws.partials + 4 * (size_t)nb;
-    const dim3 grid(nb), block(rl1::kBlock);
+    const dim3 grid(nb), block(film::kBlock);
     const int npix = g.w * g.h, chunk = 32;
     int launched = 0;
     auto enqueue_chunk = [&]() {
@@ -289,8 +227,6 @@ void recon_pcg_round(ReconWorkspace &ws, const rl1::Geo &g, int nb, double *d_ou
     res.irls_rounds = k + 1;
 }
 
-void recon_l1_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
-
 ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_gx, const double *d_gy, double alpha,
                               const ReconL1Params &p, double *d_out, hipStream_t stream) {
     if (w < 2 || h < 2) throw std::runtime_error("reconstruct: width and height must be >= 2");
@@ -302,21 +238,22 @@ ReconL1Result recon_l1_device(int w, int h, const double *d_c, const double *d_g
     ReconWorkspace &ws = recon_workspace(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
     ws.ensure((size_t)w * h, stream);
-    const rl1::Geo g = recon_geo(w, h);
-    const int nb = recon_blocks(g);
-    const dim3 grid(nb), block(rl1::kBlock);
+    const film::TileGrid g = film::tile_grid(w, h, rl1::kTileW, rl1::kTileH);
+    const int nb = g.blocks;
+    const dim3 grid(nb), block(film::kBlock);
     ReconL1Result res{};
     ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
     for (int k = 0; k <= p.irls_iters; k++) {
         const double eps = k == 0 ? 0.0 : std::max(p.eps_init * std::pow(p.eps_decay, k - 1), p.eps_floor);
-        hipLaunchKernelGGL(rl1::weights_kernel<true>, grid, block, 0, stream, g, alpha, eps, k == 0 ? 1 : 0, k == 0 ? d_c : (const double *)d_out, d_c, d_gx, d_gy,
-                           k == 0 ? d_out : (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
+        hipLaunchKernelGGL((rl1::weights_kernel<rl1::PositionalRows, true>), grid, block, 0, stream, g, alpha, eps, k == 0 ? 1 : 0,
+                           k == 0 ? d_c : (const double *)d_out, d_c, d_gx, d_gy, rl1::PositionalRows::Planes{}, k == 0 ? d_out : (double *)nullptr,
+                           ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
         recon_round_init(ws, nb, p.cg_tol, 1, stream);
         ck(hipGetLastError(), "recon round launch");
-        recon_pcg_round(ws, g, nb, d_out, p, stream, k, res);
+        recon_pcg_round(ws, g, d_out, p, stream, k, res);
     }
-    hipLaunchKernelGGL(rl1::weights_kernel<false>, grid, block, 0, stream, g, alpha, 0.0, 1, (const double *)d_out, d_c, d_gx, d_gy,
-                       (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
+    hipLaunchKernelGGL((rl1::weights_kernel<rl1::PositionalRows, false>), grid, block, 0, stream, g, alpha, 0.0, 1, (const double *)d_out, d_c, d_gx, d_gy,
+                       rl1::PositionalRows::Planes{}, (double *)nullptr, ws.wx, ws.wy, ws.diag, ws.r, ws.partials);
     recon_round_init(ws, nb, p.cg_tol, 0, stream);
     ck(hipGetLastError(), "recon energy launch");
     recon_read_state(ws, stream);

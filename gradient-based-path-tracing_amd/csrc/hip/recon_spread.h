@@ -15,21 +15,15 @@ struct ReconSpreadResult {
 // Device pointers on the current device, W*H*3 doubles each (d_map: W*H). weights[i] > 0; 2 <= n <= GDPT_MULTI_MAX_DEVICES;
 // 0 <= radius <= 8; d_total == nullptr: the weighted mean takes its place; d_var, d_map nullable. The arguments are the caller's to
 // check (gdpt_recon_spread_device does). Enqueued on `stream`, and waits for it (the sums come back to the host). Scratch is kept
-// per (device, stream); the same call gives the same bits.
+// per (device, stream), and dropped by forget_stream (device_mem.h); the same call gives the same bits.
 ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *d_images, const double *weights, const double *d_total,
                                       int radius, double *d_var, double *d_map, hipStream_t stream);
 
-// Launch geometry (gdpt_debug_image_grid reads it too). spread_kernel: groups of 256 consecutive pixels and the blocks that stride over
-// them; box_kernel: 32 x 8 tiles and the blocks that stride over them.
-struct SpreadGrid { int groups, blocks; };
-struct BoxGrid { int tiles_x, tiles, blocks; };
-SpreadGrid spread_grid(int w, int h);
-BoxGrid box_grid(int w, int h);
+// Launch geometry (image_kernels.h). spread_kernel: film::stride_grid(W H, film::kMaxBlocks, 1), as the fold it mirrors; box_kernel:
+// film::tile_grid over tiles of kSpreadTileW x kSpreadTileH pixels.
+constexpr int kSpreadTileW = 32, kSpreadTileH = 8;
 
 // members, radius, the sums, error_estimate = sqrt(sum_var / sum_sq), the count and the device time into *st (nullable)
 void fill_spread_stats(GdptReconSpreadStats *st, int n, int radius, const ReconSpreadResult &r);
-
-// Drops the (device, stream) pair's scratch; forget_stream (device_mem.h) calls it.
-void recon_spread_forget_stream(int dev, hipStream_t stream);
 
 } // namespace gdpt

@@ -11,7 +11,7 @@
 //   spread_kernel   a thread owns a PIXEL (consecutive threads on consecutive 24-byte triples, as fold_kernel): the running
 //                   (mean, M2) of its three channels stay in registers while the N images stream by; the image pointers and
 //                   weights come by value in the kernel arguments. Memory bound: (N + 1) x 24 bytes read, 32 written per pixel.
-//                   Block partials through prg::block_sum, then prg's finish_kernel: a fixed order, the same bits every time.
+//                   Block partials through leave_block_sum, then finish_kernel (image_kernels.h): a fixed order, the same bits every time.
 //   box_kernel      the map's window mean for radius r >= 1: 32 x 8 pixel tiles with an r-wide halo staged in LDS (48 x 24 doubles
 //                   at r = 8), staged as pcg_step_a stages its tile; a finite count travels beside every sum; separable inside the
 //                   tile: row sums of 2r + 1 taps, then column sums of the row sums. Out-of-film and non-finite entries count 0.
@@ -19,7 +19,7 @@
 //                   the 64-dword bank row once) in both passes, whatever the pitch: no padding is needed for the 8-byte reads.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
-#include "progressive_internal.h"
+#include "image_kernels.h"
 #include "recon_spread.h"
 
 #include <algorithm>
@@ -29,9 +29,10 @@
 
 namespace rsp {
 
-constexpr int kBlock = prg::kBlock, kMaxBlocks = prg::kMaxBlocks;
+using namespace film;             // kBlock, kMaxBlocks, TileGrid, leave_block_sum
+
 constexpr int kMaxN = GDPT_MULTI_MAX_DEVICES, kMaxRadius = 8;
-constexpr int kTileW = 32, kTileH = 8;
+constexpr int kTileW = gdpt::kSpreadTileW, kTileH = gdpt::kSpreadTileH;
 constexpr int kStageW = kTileW + 2 * kMaxRadius, kStageH = kTileH + 2 * kMaxRadius;      // 48 x 24
 static_assert(kTileW * kTileH == kBlock, "one thread per tile pixel");
 
@@ -81,25 +82,24 @@ __global__ __launch_bounds__(kBlock) void spread_kernel(Members m, int n, int np
             s_sq += (t[0] * t[0] + t[1] * t[1]) + t[2] * t[2];
         } else s_out += 1.0;
     }
-    const int nb = gridDim.x;
-    double r;
-    r = prg::block_sum(s_var, red); if (threadIdx.x == 0) partials[0 * nb + blockIdx.x] = r;
-    r = prg::block_sum(s_sq, red); if (threadIdx.x == 0) partials[1 * nb + blockIdx.x] = r;
-    r = prg::block_sum(s_out, red); if (threadIdx.x == 0) partials[2 * nb + blockIdx.x] = r;
+    leave_block_sum(partials, 0, s_var, red);
+    leave_block_sum(partials, 1, s_sq, red);
+    leave_block_sum(partials, 2, s_out, red);
 }
 
 // out(x, y) = mean of the finite entries of `in` in the window [x - r, x + r] x [y - r, y + r] clipped to the film; NaN without one.
 // 1 <= r <= kMaxRadius.
-__global__ __launch_bounds__(kBlock) void box_kernel(int w, int h, int tiles_x, int tiles, int r, const double *in, double *out) {
+__global__ __launch_bounds__(kBlock) void box_kernel(TileGrid g, int r, const double *in, double *out) {
     __shared__ double sv[kStageH][kStageW];      // the tile and its halo: the value, 0 where it does not count
     __shared__ int sc[kStageH][kStageW];         // ... 1 where it counts
     __shared__ double hv[kStageH][kTileW];       // row sums of 2r + 1 taps
     __shared__ int hc[kStageH][kTileW];
     const int lx = threadIdx.x & (kTileW - 1), ly = threadIdx.x / kTileW;
     const int sw = kTileW + 2 * r, sh = kTileH + 2 * r, taps = 2 * r + 1;
-    for (int t = blockIdx.x; t < tiles; t += gridDim.x) {
-        const int ty = t / tiles_x, tx = t - ty * tiles_x;
-        const int x0 = tx * kTileW, y0 = ty * kTileH;
+    const int w = g.w, h = g.h;
+    for (int t = blockIdx.x; t < g.tiles; t += gridDim.x) {
+        const TilePixel tp = tile_pixel<kTileW, kTileH>(g, t);
+        const int x0 = tp.x0, y0 = tp.y0;
         __syncthreads();                                   // the previous tile's sums have been read
         for (int k = threadIdx.x; k < sw * sh; k += kBlock) {
             const int ry = k / sw, rx = k - ry * sw;
@@ -120,7 +120,7 @@ __global__ __launch_bounds__(kBlock) void box_kernel(int w, int h, int tiles_x, 
             hv[row][lx] = s; hc[row][lx] = c;
         }
         __syncthreads();
-        const int x = x0 + lx, y = y0 + ly;
+        const int x = tp.x, y = tp.y;
         if (x < w && y < h) {
             double s = 0.0;
             int c = 0;
@@ -139,25 +139,16 @@ namespace {
 struct SpreadWorkspace {
     std::mutex mu;                    // held while a call runs on this (device, stream) pair
     DeviceBuffer<double> partials, pixsum;
-    DeviceBuffer<prg::Estimate> d_est;
-    PinnedBuffer<prg::Estimate> h_est;
+    DeviceBuffer<film::Estimate> d_est;
+    PinnedBuffer<film::Estimate> h_est;
     Event ev[2];
 };
 
-// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip)
+// leaked on purpose: no HIP call is made from a static destructor (as the solver's registry, poisson_kernels.hip); a pair's entry
+// goes with forget_stream (device_mem.h)
 PerStream<SpreadWorkspace> &g_workspaces = *new PerStream<SpreadWorkspace>();
 
 } // namespace
-
-void recon_spread_forget_stream(int dev, hipStream_t stream) { g_workspaces.forget(dev, stream); }
-
-SpreadGrid spread_grid(int w, int h) { return {prg::groups((size_t)w * h), prg::fold_blocks(w * h)}; }
-BoxGrid box_grid(int w, int h) {
-    BoxGrid g{(w + rsp::kTileW - 1) / rsp::kTileW, 0, 0};
-    g.tiles = g.tiles_x * ((h + rsp::kTileH - 1) / rsp::kTileH);
-    g.blocks = std::min(g.tiles, rsp::kMaxBlocks);
-    return g;
-}
 
 ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *d_images, const double *weights, const double *d_total,
                                       int radius, double *d_var, double *d_map, hipStream_t stream) {
@@ -166,7 +157,7 @@ ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *
     SpreadWorkspace &ws = g_workspaces.get(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
     const int npix = w * h;
-    if (!ws.partials) ws.partials.alloc(3 * rsp::kMaxBlocks, "hipMalloc(spread partials)");
+    if (!ws.partials) ws.partials.alloc(3 * film::kMaxBlocks, "hipMalloc(spread partials)");
     if (!ws.d_est) ws.d_est.alloc(1, "hipMalloc(spread sums)");
     if (!ws.h_est) ws.h_est.alloc(1, "hipHostMalloc(spread sums)");
     for (auto &e : ws.ev) if (!e) e.create();
@@ -180,21 +171,20 @@ ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *
         m.img[i] = d_images[i]; m.w[i] = weights[i]; m.frac[i] = weights[i] / wsum;
     }
     const double norm = (double)(n - 1) * wsum;
-    const int nb = spread_grid(w, h).blocks;
+    const int nb = film::stride_grid((size_t)npix, film::kMaxBlocks, 1).blocks;
     ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
-    hipLaunchKernelGGL(rsp::spread_kernel, dim3(nb), dim3(rsp::kBlock), 0, stream, m, n, npix, norm, d_total, d_var,
+    hipLaunchKernelGGL(rsp::spread_kernel, dim3(nb), dim3(film::kBlock), 0, stream, m, n, npix, norm, d_total, d_var,
                        windowed ? ws.pixsum.data() : d_map, ws.partials.data());
     ck(hipGetLastError(), "spread launch");
-    prg::launch_finish(nb, ws.partials, ws.d_est, stream);
+    film::launch_finish(nb, ws.partials, ws.d_est, stream);
     ck(hipGetLastError(), "spread reduction launch");
     if (windowed) {
-        const BoxGrid bg = box_grid(w, h);
-        hipLaunchKernelGGL(rsp::box_kernel, dim3(bg.blocks), dim3(rsp::kBlock), 0, stream, w, h, bg.tiles_x, bg.tiles, radius,
-                           ws.pixsum.data(), d_map);
+        const film::TileGrid bg = film::tile_grid(w, h, kSpreadTileW, kSpreadTileH);
+        hipLaunchKernelGGL(rsp::box_kernel, dim3(bg.blocks), dim3(film::kBlock), 0, stream, bg, radius, ws.pixsum.data(), d_map);
         ck(hipGetLastError(), "spread window launch");
     }
     ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
-    ck(hipMemcpyAsync(ws.h_est, ws.d_est, sizeof(prg::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(spread sums)");
+    ck(hipMemcpyAsync(ws.h_est, ws.d_est, sizeof(film::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(spread sums)");
     ck(hipStreamSynchronize(stream), "hipStreamSynchronize(spread)");
     ReconSpreadResult res;
     res.sum_var = ws.h_est->sum_var; res.sum_sq = ws.h_est->sum_mean2; res.left_out = ws.h_est->left_out;

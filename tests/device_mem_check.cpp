@@ -1,6 +1,7 @@
 // device_mem_check.cpp — the invariants of csrc/hip/device_mem.h on the CPU (tests/test_device_mem_host.py builds this with the host
 // compiler under AddressSanitizer + UBSan and runs it): Buffer over a malloc / free space that counts live blocks and can be told to
-// fail the n-th allocation, and PerStream over a plain struct with the device switch a no-op. Needs no GPU and links no HIP.
+// fail the n-th allocation, and PerStream over plain structs with the device switch a no-op,
+// forget_stream over two such registries included. Needs no GPU and links no HIP.
 #include "../gradient-based-path-tracing_amd/csrc/hip/device_mem.h"
 
 #include <cstdio>
@@ -145,12 +146,55 @@ void registry() {
     CHECK(reg.get(0, s1).value == 0 && Plain::made == 5);
 }
 
+// (e) forget_stream reaches every registry alive, whatever it keeps: the pair goes from both, other pairs and devices stay
+struct Other {
+    static int made, gone;
+    Buf a, b;
+    Other() { made++; }
+    ~Other() { gone++; }
+};
+int Other::made = 0, Other::gone = 0;
+
+void forget_stream_reaches_every_registry() {
+    const hipStream_t s1 = reinterpret_cast<hipStream_t>(0x10), s2 = reinterpret_cast<hipStream_t>(0x20);
+    const int plain_made = Plain::made, plain_gone = Plain::gone;
+    gdpt::forget_stream(0, s1);                              // the registry of registry() has left the list: nothing to visit
+    CHECK(Plain::gone == plain_gone && Other::gone == 0);
+    {
+        gdpt::PerStream<Plain, TestSpace> plains;
+        gdpt::PerStream<Other, TestSpace> others;
+        for (int dev = 0; dev < 2; dev++)
+            for (hipStream_t s : {s1, s2}) {
+                plains.get(dev, s).value = 10 * dev + (s == s1 ? 1 : 2);
+                plains.get(dev, s).scratch.alloc(4, "alloc");
+                others.get(dev, s).a.alloc(2, "alloc");
+            }
+        CHECK(Plain::made == plain_made + 4 && Other::made == 4 && TestSpace::live == 8);
+        const int switches = TestSpace::switches;
+        gdpt::forget_stream(0, s1);
+        CHECK(Plain::gone == plain_gone + 1 && Other::gone == 1 && TestSpace::live == 6);
+        CHECK(TestSpace::switches == switches + 4);          // each entry destroyed with its device current, then back
+        CHECK(plains.get(0, s2).value == 2 && plains.get(1, s1).value == 11 && plains.get(1, s2).value == 12);   // the others: untouched
+        CHECK(others.get(0, s2).a.size() == 2 && others.get(1, s1).a.size() == 2 && others.get(1, s2).a.size() == 2);
+        CHECK(Plain::made == plain_made + 4 && Other::made == 4);
+        gdpt::forget_stream(0, s1);                          // again: a no-op
+        gdpt::forget_stream(2, s1); gdpt::forget_stream(0, nullptr);      // pairs nobody keeps
+        CHECK(Plain::gone == plain_gone + 1 && Other::gone == 1 && TestSpace::live == 6 && TestSpace::switches == switches + 4);
+        CHECK(plains.get(0, s1).value == 0 && others.get(0, s1).a.size() == 0);      // a later stream of the same value starts fresh
+        CHECK(Plain::made == plain_made + 5 && Other::made == 5);
+    }
+    CHECK(Plain::gone == plain_gone + 5 && Other::gone == 5 && TestSpace::live == 0);
+    gdpt::forget_stream(1, s2);                              // both registries have left the list
+    CHECK(Plain::gone == plain_gone + 5 && Other::gone == 5);
+}
+
 } // namespace
 
 int main() {
     failed_allocations();
     moves();
     registry();
+    forget_stream_reaches_every_registry();
     CHECK(TestSpace::live == 0);       // (the registry of registry() has gone with its entry)
     if (g_failures) { std::printf("%d check(s) failed\n", g_failures); return 1; }
     std::printf("device_mem_check ok\n");
