@@ -139,6 +139,9 @@ def lib():
         L.gdpt_debug_route_names.argtypes = [C.POINTER(C.c_char_p), C.c_int]
         L.gdpt_debug_image_grid.argtypes = [C.c_char_p, C.c_int, C.c_int, C.POINTER(C.c_int32)]
         L.gdpt_debug_prepare_scene.argtypes = [C.POINTER(defs.GdptSceneDesc), C.POINTER(defs.GdptPreparedInfo), dp, dp, C.c_int]
+        L.gdpt_debug_kat_variants.argtypes = [C.c_char_p, C.POINTER(defs.GdptKatVariant), C.c_int]
+        for family, (query, result) in defs.KAT_STRUCTS.items():
+            getattr(L, "gdpt_debug_kat_" + family).argtypes = [vp, C.c_int, C.c_int, C.POINTER(query), C.POINTER(result)]
         _LIB = L
     return _LIB
 
@@ -983,6 +986,28 @@ class debug_knobs:
         have = d["count"]["light_pmf"]                   # (a scene without emitters has no table)
         d["light_pmf"], d["light_cdf"] = pmf[:have], cdf[:have + 1 if have else 0]
         return d
+
+    @staticmethod
+    def kat_variants(family):
+        """The family's table of variants (include/gdpt_debug.h: gdpt_debug_kat_variants): a list of dicts, in the order the
+        `variant` argument of kat() indexes. No GPU call."""
+        n = lib().gdpt_debug_kat_variants(family.encode(), None, 0)
+        if n < 0:
+            raise GdptError(lib().gdpt_last_error().decode("utf-8", "replace"))
+        rows = (defs.GdptKatVariant * n)()
+        if lib().gdpt_debug_kat_variants(family.encode(), rows, n) != n:
+            raise GdptError(lib().gdpt_last_error().decode("utf-8", "replace"))
+        return [{"name": r.name.decode(), "mask": int(r.mask), "rough": bool(r.rough), "twosided": bool(r.twosided),
+                 "inline_lambert": bool(r.inline_lambert), "plain": int(r.plain)} for r in rows]
+
+    @staticmethod
+    def kat(scene, family, variant, queries):
+        """Runs one device function family on an array of cases (include/gdpt_debug.h: gdpt_debug_kat_<family>). `queries`: a ctypes
+        array of the family's query struct (defs.KAT_STRUCTS); returns the ctypes array of results."""
+        result = defs.KAT_STRUCTS[family][1]
+        out = (result * max(1, len(queries)))()
+        _check(getattr(lib(), "gdpt_debug_kat_" + family)(scene.handle, int(variant), len(queries), queries, out))
+        return out
 
     @staticmethod
     def from_env(environ=None):

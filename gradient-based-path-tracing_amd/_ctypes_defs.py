@@ -171,3 +171,73 @@ class GdptPreparedInfo(C.Structure):
                 ("wide8_stack_need", C.c_int32), ("one_sided", C.c_int32), ("lambert_only", C.c_int32), ("has_rough", C.c_int32),
                 ("plan_take_pct", C.c_int32), ("material_mask", C.c_uint32), ("has_envmap", C.c_int32), ("env_w", C.c_int32),
                 ("env_h", C.c_int32), ("all_textures_constant", C.c_int32)]
+
+
+# include/gdpt_debug.h: gdpt_debug_kat_* (the per-vertex device functions on arrays of cases)
+KAT_FAMILIES = ("bsdf", "texture", "filter", "primary", "shading", "light")
+
+
+class GdptKatVariant(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("mask", C.c_uint32), ("rough", C.c_int32), ("twosided", C.c_int32), ("inline_lambert", C.c_int32),
+                ("plain", C.c_int32)]
+
+
+class GdptKatVertex(C.Structure):
+    _fields_ = [("gn", C.c_double * 3), ("fx", C.c_double * 3), ("fy", C.c_double * 3), ("fn", C.c_double * 3), ("uv", C.c_double * 2),
+                ("uv_screen_size", C.c_double)]
+
+
+class GdptKatBsdfQuery(C.Structure):
+    _fields_ = [("material_id", C.c_int32), ("pad", C.c_int32), ("vertex", GdptKatVertex), ("dir_in", C.c_double * 3),
+                ("dir_out2", C.c_double * 3), ("ruv", C.c_double * 2), ("rw", C.c_double)]
+
+
+class GdptKatBsdfResult(C.Structure):
+    _fields_ = [("sample_valid", C.c_int32), ("pad", C.c_int32), ("s_dir", C.c_double * 3), ("s_eta", C.c_double), ("s_rough", C.c_double),
+                ("f", (C.c_double * 3) * 2), ("pdf", C.c_double * 2), ("fused_f", (C.c_double * 3) * 2), ("fused_pdf", C.c_double * 2)]
+
+
+class GdptKatTextureQuery(C.Structure):
+    _fields_ = [("material_id", C.c_int32), ("slot", C.c_int32), ("uv", C.c_double * 2), ("uv_screen_size", C.c_double)]
+
+
+class GdptKatTextureResult(C.Structure):
+    _fields_ = [("tex3", C.c_double * 3), ("tex1", C.c_double)]
+
+
+class GdptKatFilterQuery(C.Structure):
+    _fields_ = [("type", C.c_int32), ("pad", C.c_int32), ("param", C.c_double), ("u", C.c_double * 2)]
+
+
+class GdptKatFilterResult(C.Structure):
+    _fields_ = [("out", C.c_double * 2)]
+
+
+class GdptKatPrimaryQuery(C.Structure):
+    _fields_ = [("s", C.c_double * 2)]
+
+
+class GdptKatPrimaryResult(C.Structure):
+    _fields_ = [("org", C.c_double * 3), ("dir", C.c_double * 3)]
+
+
+class GdptKatShadingQuery(C.Structure):
+    _fields_ = [("is_sphere", C.c_int32), ("index", C.c_int32), ("need_uv", C.c_int32), ("pad", C.c_int32), ("st", C.c_double * 2),
+                ("gn", C.c_double * 3)]
+
+
+class GdptKatShadingResult(C.Structure):
+    _fields_ = [("uv", C.c_double * 2), ("fx", C.c_double * 3), ("fy", C.c_double * 3), ("fn", C.c_double * 3), ("inv_uv_size", C.c_double)]
+
+
+class GdptKatLightQuery(C.Structure):
+    _fields_ = [("light_id", C.c_int32), ("pad", C.c_int32), ("ref", C.c_double * 3), ("uv", C.c_double * 2), ("w", C.c_double)]
+
+
+class GdptKatLightResult(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("normal", C.c_double * 3), ("pdf", C.c_double)]
+
+
+KAT_STRUCTS = {"bsdf": (GdptKatBsdfQuery, GdptKatBsdfResult), "texture": (GdptKatTextureQuery, GdptKatTextureResult),
+               "filter": (GdptKatFilterQuery, GdptKatFilterResult), "primary": (GdptKatPrimaryQuery, GdptKatPrimaryResult),
+               "shading": (GdptKatShadingQuery, GdptKatShadingResult), "light": (GdptKatLightQuery, GdptKatLightResult)}

@@ -114,7 +114,10 @@ GD D3 sample_visible_normals(D3 local_in, double ax, double ay, D2 rnd) { // src
 }
 GD D3 sample_clearcoat_normal(double alpha, D2 rnd) { // src/microfacet.h:164-177
     double a2 = alpha * alpha;
-    double pw = pow(a2, 1 - rnd.x);
+    // An exponent of exactly 1 (rnd.x = 0, one draw in 2^32) gives a2 itself, as the reference's pow does; the device library's pow
+    // is an ulp off there, which the square root of pw - a2 below turns into 2e-9 of the sampled direction.
+    double ex = 1 - rnd.x;
+    double pw = ex == 1.0 ? a2 : pow(a2, ex);
     double sin_e = sqrt((pw - a2) / (1 - a2));
     double cos_e = sqrt((1 - pw) / (1 - a2));
     double s, c;

@@ -12,4 +12,7 @@ inline void launch_phases_set(const DevSceneView &sv, const gd::KernelArgs &a, d
     hipLaunchKernelGGL((gd::gdpt_render_phases<false, false, true, true, false, P>), grid, dim3(gd::kBlock), gd::hbm_dynamic_lds(a), stream, sv, a);
 }
 constexpr unsigned kSetLambert = 1u << GDPT_MAT_LAMBERTIAN;
+// the four sets a kernel is built for (render_phases_general_sets_{a,b}.hip)
+constexpr unsigned kSetDisneyDiffuse = kSetLambert | 1u << GDPT_MAT_DISNEY_DIFFUSE, kSetDisneyMetal = kSetLambert | 1u << GDPT_MAT_DISNEY_METAL;
+constexpr unsigned kSetDisneyClearcoat = kSetLambert | 1u << GDPT_MAT_DISNEY_CLEARCOAT, kSetDisneySheen = kSetLambert | 1u << GDPT_MAT_DISNEY_SHEEN;
 } // namespace gdpt

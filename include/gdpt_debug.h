@@ -130,6 +130,58 @@ typedef struct GdptPreparedInfo {
 } GdptPreparedInfo;
 struct GdptSceneDesc;
 int gdpt_debug_prepare_scene(const struct GdptSceneDesc *desc, GdptPreparedInfo *info, double *light_pmf, double *light_cdf, int capacity);
+/* ---- The per-vertex device functions on arrays of cases (csrc/hip/debug_kat.hip) ------------------------------------------------
+ * What the render kernels call at a vertex (the BSDF trio of device_bsdf.h and its fused eval_pdf, the inline Lambertian of
+ * render_device.h, texture lookups, the pixel filter and the camera, the shading info of a hit, emitter sampling) is otherwise
+ * observable only summed into an image. Each family below is one kernel that calls the product's functions as they are, one thread
+ * per case (256-thread blocks, no LDS scene, no traversal), and one entry point
+ *     gdpt_debug_kat_<family>(scene, variant, n, in, out)
+ * with host arrays of n queries and n results. The entry runs on the scene's first render stream and has waited for it when it
+ * returns. Before the launch the host checks `variant` against the family's table and every index a query carries against the table
+ * sizes of the uploaded scene; a bad argument is refused (non-zero, message in gdpt_last_error) and never reaches the kernel.
+ *
+ * gdpt_debug_kat_variants(family, out, capacity): the family's table of variants, one row each, in the order `variant` indexes; returns
+ * their number (out == NULL: the number alone), -1 for an unknown family or a capacity too small. Families: "bsdf", "texture",
+ * "filter", "primary", "shading", "light". The bsdf rows:
+ *   - one per <ROUGH, TWOSIDED, MASK> triple of bsdf_sample / bsdf_eval / bsdf_pdf / bsdf_eval_pdf that a product kernel instantiates,
+ *     the triple taken from the product's own constants (kAllMaterials, kSetGlass, the sets of render_phases_general_sets.h); `mask` bit
+ *     t = material type t is in the kernel's set, `rough` / `twosided` = the RoughPlastic / RoughDielectric and the DisneyGlass /
+ *     DisneyBSDF arms are compiled in;
+ *   - two with inline_lambert = 1: mat_sample / mat_eval_pdf / mat_pdf with LAMBERT = true (Lambertian materials only), plain = the
+ *     PLAIN flag of mat_eval_pdf (0, or kPlainConstTex = 2: constant reflectances only). That path has no separate eval: f[] is NaN.
+ * "primary": variant 0 takes s = the screen position in [0, 1)^2, variant 1 the pixel-space numbers (x + u, y + v) (PIXEL_SPACE).
+ * The other families have one variant.
+ *
+ * bsdf results: [0] = at the direction bsdf_sample returned (zeros when sample_valid == 0), [1] = at dir_out2; f/pdf from the
+ * separate bsdf_eval and bsdf_pdf, fused_f/fused_pdf from bsdf_eval_pdf. texture: tex3 / tex1 of texture `slot` of a material.
+ * shading: shading_info_tri of global triangle `index` (need_uv as given) or shading_info_sphere of sphere `index`. light:
+ * sample_point_on_light and pdf_point_on_light of that point, for area emitter `light_id`. */
+typedef struct GdptKatVariant { const char *name; uint32_t mask; int32_t rough, twosided, inline_lambert, plain; } GdptKatVariant;
+typedef struct GdptKatVertex { double gn[3], fx[3], fy[3], fn[3], uv[2], uv_screen_size; } GdptKatVertex;   /* what the lobes read of gd::Vertex */
+typedef struct GdptKatBsdfQuery { int32_t material_id, pad; GdptKatVertex vertex; double dir_in[3], dir_out2[3], ruv[2], rw; } GdptKatBsdfQuery;
+typedef struct GdptKatBsdfResult {
+    int32_t sample_valid, pad;
+    double s_dir[3], s_eta, s_rough;
+    double f[2][3], pdf[2];
+    double fused_f[2][3], fused_pdf[2];
+} GdptKatBsdfResult;
+typedef struct GdptKatTextureQuery { int32_t material_id, slot; double uv[2], uv_screen_size; } GdptKatTextureQuery;
+typedef struct GdptKatTextureResult { double tex3[3], tex1; } GdptKatTextureResult;
+typedef struct GdptKatFilterQuery { int32_t type, pad; double param, u[2]; } GdptKatFilterQuery;
+typedef struct GdptKatFilterResult { double out[2]; } GdptKatFilterResult;
+typedef struct GdptKatPrimaryQuery { double s[2]; } GdptKatPrimaryQuery;
+typedef struct GdptKatPrimaryResult { double org[3], dir[3]; } GdptKatPrimaryResult;
+typedef struct GdptKatShadingQuery { int32_t is_sphere, index, need_uv, pad; double st[2], gn[3]; } GdptKatShadingQuery;
+typedef struct GdptKatShadingResult { double uv[2], fx[3], fy[3], fn[3], inv_uv_size; } GdptKatShadingResult;
+typedef struct GdptKatLightQuery { int32_t light_id, pad; double ref[3], uv[2], w; } GdptKatLightQuery;
+typedef struct GdptKatLightResult { double position[3], normal[3], pdf; } GdptKatLightResult;
+int gdpt_debug_kat_variants(const char *family, GdptKatVariant *out, int capacity);
+int gdpt_debug_kat_bsdf(const struct GdptScene *scene, int variant, int n, const GdptKatBsdfQuery *in, GdptKatBsdfResult *out);
+int gdpt_debug_kat_texture(const struct GdptScene *scene, int variant, int n, const GdptKatTextureQuery *in, GdptKatTextureResult *out);
+int gdpt_debug_kat_filter(const struct GdptScene *scene, int variant, int n, const GdptKatFilterQuery *in, GdptKatFilterResult *out);
+int gdpt_debug_kat_primary(const struct GdptScene *scene, int variant, int n, const GdptKatPrimaryQuery *in, GdptKatPrimaryResult *out);
+int gdpt_debug_kat_shading(const struct GdptScene *scene, int variant, int n, const GdptKatShadingQuery *in, GdptKatShadingResult *out);
+int gdpt_debug_kat_light(const struct GdptScene *scene, int variant, int n, const GdptKatLightQuery *in, GdptKatLightResult *out);
 /* Removes every override: the library is back on its product path. */
 void gdpt_debug_knobs_reset(void);
 

@@ -43,6 +43,46 @@ def test_struct_layouts_match_the_header(G, tmp_path):
         assert int(sizes[s]) == C.sizeof(getattr(G, s)), s
 
 
+def test_kat_struct_layouts_match_the_header(G, tmp_path):
+    """Query / Result / variant structs of gdpt_debug_kat_* (include/gdpt_debug.h): plain doubles and int32, the size and the offset of
+    every field as the C compiler lays them out; and the tables of variants, which need no GPU."""
+    structs = {"GdptKatVariant": G.GdptKatVariant, "GdptKatVertex": G.GdptKatVertex}
+    for family in G.KAT_FAMILIES:
+        for s in G.KAT_STRUCTS[family]:
+            structs[s.__name__] = s
+    assert len(structs) == 14
+    lines = []
+    for name, s in structs.items():
+        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        for field, _ in s._fields_:
+            lines.append(f'printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
+    src = tmp_path / "kat.c"
+    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/gdpt_debug.h"\nint main(){{{" ".join(lines)} return 0;}}\n')
+    exe = tmp_path / "kat"
+    subprocess.check_call(["gcc", "-std=c99", "-o", str(exe), str(src)])
+    seen = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    for name, s in structs.items():
+        assert int(seen[name]) == C.sizeof(s), name
+        for field, ftype in s._fields_:
+            assert int(seen[f"{name}.{field}"]) == getattr(s, field).offset, (name, field)
+            if name != "GdptKatVariant":
+                base = ftype
+                while hasattr(base, "_type_") and not isinstance(base._type_, str):
+                    base = base._type_
+                assert base in (C.c_double, C.c_int32, G.GdptKatVertex), (name, field)
+    assert C.sizeof(G.GdptKatBsdfQuery) == 200 and C.sizeof(G.GdptKatBsdfResult) == 176 and C.sizeof(G.GdptKatVertex) == 120
+    rows = G.debug_knobs.kat_variants("bsdf")
+    names = [r["name"] for r in rows]
+    assert len(set(names)) == len(names) and names[0] == "full" and rows[0]["mask"] == 0x1FF and rows[0]["rough"] and rows[0]["twosided"]
+    assert sum(r["inline_lambert"] for r in rows) == 2 and sorted(r["plain"] for r in rows if r["inline_lambert"]) == [0, 2]
+    assert all(r["mask"] & 1 for r in rows)                      # every kernel's set holds the Lambertian
+    for family in G.KAT_FAMILIES:
+        assert len(G.debug_knobs.kat_variants(family)) >= 1
+    import pytest
+    with pytest.raises(G.GdptError, match="unknown family 'bvh'"):
+        G.debug_knobs.kat_variants("bvh")
+
+
 def test_compute_entry_points_fail_loudly_without_a_gpu_or_with_bad_arguments(G):
     import numpy as np
     import torch
