@@ -142,6 +142,8 @@ def lib():
         L.gdpt_debug_kat_variants.argtypes = [C.c_char_p, C.POINTER(defs.GdptKatVariant), C.c_int]
         for family, (query, result) in defs.KAT_STRUCTS.items():
             getattr(L, "gdpt_debug_kat_" + family).argtypes = [vp, C.c_int, C.c_int, C.POINTER(query), C.POINTER(result)]
+        L.gdpt_debug_kat_trace_variants.argtypes = [C.POINTER(defs.GdptKatTraceVariant), C.c_int]
+        L.gdpt_debug_kat_trace.argtypes = [vp, C.c_int, C.c_int, C.POINTER(defs.GdptKatTraceQuery), C.POINTER(defs.GdptKatTraceResult)]
         _LIB = L
     return _LIB
 
@@ -1007,6 +1009,24 @@ class debug_knobs:
         result = defs.KAT_STRUCTS[family][1]
         out = (result * max(1, len(queries)))()
         _check(getattr(lib(), "gdpt_debug_kat_" + family)(scene.handle, int(variant), len(queries), queries, out))
+        return out
+
+    @staticmethod
+    def kat_trace_variants():
+        """The rows of the "trace" family (include/gdpt_debug.h: gdpt_debug_kat_trace_variants): a list of dicts, in the order the
+        `variant` argument of kat_trace() indexes. No GPU call."""
+        n = lib().gdpt_debug_kat_trace_variants(None, 0)
+        rows = (defs.GdptKatTraceVariant * max(1, n))()
+        if n < 0 or lib().gdpt_debug_kat_trace_variants(rows, n) != n:
+            raise GdptError(lib().gdpt_last_error().decode("utf-8", "replace"))
+        return [{"name": r.name.decode(), **{k: int(getattr(r, k)) for k, _ in defs.GdptKatTraceVariant._fields_[1:]}} for r in rows[:n]]
+
+    @staticmethod
+    def kat_trace(scene, variant, queries):
+        """Walks one row of the "trace" family over a ctypes array of GdptKatTraceQuery (include/gdpt_debug.h: gdpt_debug_kat_trace);
+        returns the ctypes array of GdptKatTraceResult."""
+        out = (defs.GdptKatTraceResult * max(1, len(queries)))()
+        _check(lib().gdpt_debug_kat_trace(scene.handle, int(variant), len(queries), queries, out))
         return out
 
     @staticmethod

@@ -238,6 +238,20 @@ class GdptKatLightResult(C.Structure):
     _fields_ = [("position", C.c_double * 3), ("normal", C.c_double * 3), ("pdf", C.c_double)]
 
 
+class GdptKatTraceVariant(C.Structure):
+    _fields_ = [("name", C.c_char_p)] + [(k, C.c_int32) for k in ("ww", "wide", "flat", "spheres", "spec", "leaf_k", "lds_scene", "wavefront",
+                                                                  "lds_stack_levels")]
+
+
+class GdptKatTraceQuery(C.Structure):
+    _fields_ = [("org", C.c_double * 3), ("dir", C.c_double * 3), ("tnear", C.c_double), ("tfar", C.c_double), ("any_hit", C.c_int32),
+                ("pad", C.c_int32)]
+
+
+class GdptKatTraceResult(C.Structure):
+    _fields_ = [("gid", C.c_int32), ("t", C.c_float), ("u", C.c_float), ("v", C.c_float), ("ng", C.c_float * 3)]
+
+
 KAT_STRUCTS = {"bsdf": (GdptKatBsdfQuery, GdptKatBsdfResult), "texture": (GdptKatTextureQuery, GdptKatTextureResult),
                "filter": (GdptKatFilterQuery, GdptKatFilterResult), "primary": (GdptKatPrimaryQuery, GdptKatPrimaryResult),
                "shading": (GdptKatShadingQuery, GdptKatShadingResult), "light": (GdptKatLightQuery, GdptKatLightResult)}

@@ -1,7 +1,7 @@
 // debug_kat.hip — test instrument (include/gdpt_debug.h: gdpt_debug_kat_*): the per-vertex device functions of the render kernels
 // run on arrays of cases, one thread per case, so that a test can compare each of them with a known answer. The kernels include the
-// product headers and call their functions as they are; no LDS scene, no traversal. Nothing in lajolla, in bench.py's timed region or
-// in the library calls these entry points.
+// product headers and call their functions as they are; no LDS scene, no traversal (the walks have a family of their own,
+// debug_kat_trace.hip). Nothing in lajolla, in bench.py's timed region or in the library calls these entry points.
 #include "../../../include/gdpt_debug.h"
 #include "../capi_common.h"
 #include "render_path.h"
@@ -9,6 +9,7 @@
 #include "render_twosided.h"
 #include "scene_internal.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <string>
@@ -198,6 +199,12 @@ int family_variants(const std::string &family, std::vector<GdptKatVariant> &rows
     if (family == "bsdf") { for (const BsdfVariant &b : kBsdfVariants) rows.push_back(b.row); return 0; }
     if (family == "primary") { rows.assign(kPrimaryVariants, kPrimaryVariants + 2); return 0; }
     if (family == "texture" || family == "filter" || family == "shading" || family == "light") { rows.assign(kOneVariant, kOneVariant + 1); return 0; }
+    if (family == "trace") {       // (the table itself: debug_kat_trace.hip)
+        std::vector<GdptKatTraceVariant> t((size_t)std::max(0, gdpt_debug_kat_trace_variants(nullptr, 0)));
+        if (gdpt_debug_kat_trace_variants(t.data(), (int)t.size()) != (int)t.size()) return 1;
+        for (const GdptKatTraceVariant &r : t) rows.push_back(GdptKatVariant{r.name, 0, 0, 0, 0, 0});
+        return 0;
+    }
     return 1;
 }
 
@@ -248,7 +255,7 @@ int gdpt_debug_kat_variants(const char *family, GdptKatVariant *out, int capacit
     const int rc = gdpt::guarded([&]() {
         if (!family) throw std::runtime_error("gdpt_debug_kat_variants: null family");
         std::vector<GdptKatVariant> rows;
-        if (family_variants(family, rows)) throw std::runtime_error(std::string("gdpt_debug_kat_variants: unknown family '") + family + "' (bsdf, texture, filter, primary, shading, light)");
+        if (family_variants(family, rows)) throw std::runtime_error(std::string("gdpt_debug_kat_variants: unknown family '") + family + "' (bsdf, texture, filter, primary, shading, light, trace)");
         if (out) {
             if (capacity < (int)rows.size()) throw std::runtime_error("gdpt_debug_kat_variants: capacity too small");
             for (size_t i = 0; i < rows.size(); i++) out[i] = rows[i];

@@ -131,7 +131,10 @@ GD void test_tri_flat(const DevPrim &tr, const float o[3], const float d[3], flo
 // computed distance is off by at most e (2|t| + |o/d|) = e (2|bound-o| + |o|)/|d| <= 5 e E/|d| = 3e-7 E/|d|, less than
 // the P/|d| by which the padding moved the plane. The computed interval therefore always contains the true interval
 // of the unpadded box, and no relative slack is needed: a box holding a primitive that reports t <= tbest is never
-// rejected. Axes with d = 0 (or 1/d overflowing) produce NaN and drop out of fmin/fmax.
+// rejected. That argument needs every intermediate to be finite. An axis with d = 0, with 1/d overflowing (a denormal d), with o/d
+// overflowing (1/d may still be finite, and fma(bound, 1/d, -inf) would be -inf for both planes) or with (org - o)/d of a quantised
+// node overflowing is given NaN for both 1/d and o/d by the ray set-up (render_device.h: trav_run and kSlabInvMax; gdpt_wf_trace) and
+// drops out of fmin/fmax: the box is then decided by the other axes.
 GD bool box_hit(const float *mn, const float *mx, const float oi[3], const float inv[3], float tnear, float tbest, float &tin) {
     float t0 = tnear, t1 = tbest;
 #pragma unroll

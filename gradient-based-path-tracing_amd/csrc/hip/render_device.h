@@ -481,6 +481,7 @@ template <bool WW_, bool WIDE_, bool FLAT_, bool SPHERES_ = true, bool SPEC_ = f
 };
 using TraceHbm = TraceCfg<true, true, true>;       // scenes walked from HBM
 
+constexpr float kSlabInvMax = 0x1p64f;        // |d| <= 5.4e-20 of a unit direction: parallel to the slab as far as the box tests go (trav_run)
 // Called by the lanes whose ray is unfinished (tv.cur != kTravDone); the others of the wave sit it out.
 template <class TC>
 GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, float tnear, float tfar, Trav &tv, int stop_below, int search_frac, TraceCounters &tc,
@@ -489,11 +490,15 @@ GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, flo
     const float d[3] = {(float)dir.x, (float)dir.y, (float)dir.z};
     float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
     float oi[3] = {o[0] * inv[0], o[1] * inv[1], o[2] * inv[2]};
-    // a zero direction component gives inv = inf and o*inv = inf or NaN: the slab then drops out of fmin/fmax only if
-    // the product is NaN, so force it (the ray is parallel to that slab; the padded box contains the origin's
-    // coordinate or the other axes reject)
+    // An axis along which the ray is as good as parallel to the slab has no usable slab distances: d = 0 (inv = inf, o*inv = inf or
+    // NaN), a denormal d (1/d overflows), a d so small that o/d overflows while 1/d stays finite (fma(bound, inv, -inf) is -inf for
+    // BOTH planes), or one where an intermediate of a node test overflows although 1/d and o/d are finite (the quantised nodes form
+    // (org - o)/d with the node's origin: -2 and 1.6 at d = -1e-38 give 3.6e38). The box would be rejected although the ray lies
+    // inside its slab. From |1/d| = kSlabInvMax on, inv and oi are therefore NaN, which drops the slab out of fmin/fmax: that only
+    // ever admits a box, and the primitive test decides. Below it every product of a coordinate (< 1.8e19) and 1/d is finite.
 #pragma unroll
-    for (int k = 0; k < 3; k++) if (d[k] == 0.0f) { inv[k] = __builtin_nanf(""); oi[k] = __builtin_nanf(""); }
+    for (int k = 0; k < 3; k++)
+        if (!(fabsf(inv[k]) < kSlabInvMax && fabsf(oi[k]) < __builtin_huge_valf())) { inv[k] = __builtin_nanf(""); oi[k] = __builtin_nanf(""); }
     constexpr bool kOvf = TC::WIDE && TC::FLAT && GDPT_HBM_BVH8;
     int cur = tv.cur, sp = tv.sp;
     Hit best = tv.best;
@@ -1088,7 +1093,12 @@ GD CamConst &camera_here() {
 // so the result does not depend on which lane processed what, or when.
 // LEAF_K (TraceCfg): the kernels that walk the LDS copy take their leaves GDPT_LDS_LEAF_K records per trip; 0 = whole leaves (the
 // kernels that walk the tree from HBM; the LDS kernels under the test knob whole_leaf_trips).
-template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE && !GDPT_SPEC_LEAF ? GDPT_LDS_LEAF_K : 0)>
+// (The kernel's traversal configuration and the leaf trips of its LDS forms under names of their own: the test instrument,
+// debug_kat_trace.hip, walks with the same ones.)
+constexpr int kPhasesLdsLeafK = GDPT_SPEC_LEAF ? 0 : GDPT_LDS_LEAF_K;
+template <bool LDS_SCENE, bool WIDE, bool WW, int PLAIN, int LEAF_K>
+using PhasesTraceCfg = TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE, LEAF_K>;
+template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE ? kPhasesLdsLeafK : 0)>
 __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv, KernelArgs a) {
     // LDS-resident scenes: fixed 12-slot stack + the scene copy. Scenes walked from HBM: dynamic LDS = a.stack_levels stack
     // slots per lane (the tree's own bound, not the builder's maximum of 32).
@@ -1168,7 +1178,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             stamps.mark(SEG_QUEUE);
         }
         // ---- (T) the wave's unfinished pending rays, then (S, first half) the lanes whose ray is done consume their hit
-        trace_pending<TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE, LEAF_K>>(sv, tx, L, tv, a.thresh_a, a.thresh_c, tc);
+        trace_pending<PhasesTraceCfg<LDS_SCENE, WIDE, WW, PLAIN, LEAF_K>>(sv, tx, L, tv, a.thresh_a, a.thresh_c, tc);
         stamps.mark(SEG_TRACE);
         stamps.tick(SEG_STEPS);
         act = ACT_NONE;

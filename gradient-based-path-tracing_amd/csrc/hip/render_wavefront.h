@@ -411,7 +411,8 @@ __global__ __launch_bounds__(kWfTraceBlock, COUNT ? 4 : kWfTraceWaves) void gdpt
         float inv[3] = {1.0f / d[0], 1.0f / d[1], 1.0f / d[2]};
         float oi[3] = {o[0] * inv[0], o[1] * inv[1], o[2] * inv[2]};
 #pragma unroll
-        for (int k = 0; k < 3; k++) if (d[k] == 0.0f) { inv[k] = __builtin_nanf(""); oi[k] = __builtin_nanf(""); }     // trav_run: the slab drops out
+        for (int k = 0; k < 3; k++)     // trav_run: an axis the ray is as good as parallel to drops out
+            if (!(fabsf(inv[k]) < kSlabInvMax && fabsf(oi[k]) < __builtin_huge_valf())) { inv[k] = __builtin_nanf(""); oi[k] = __builtin_nanf(""); }
         auto pop = [&]() {
             if (spa >= 1024u) { spa -= 1024u; cur = ((spa >> 10) < (unsigned)kWfLdsLevels) ? lds(spa) : ovf(spa); }
             else cur = kTravDone;

@@ -142,7 +142,7 @@ int gdpt_debug_prepare_scene(const struct GdptSceneDesc *desc, GdptPreparedInfo 
  *
  * gdpt_debug_kat_variants(family, out, capacity): the family's table of variants, one row each, in the order `variant` indexes; returns
  * their number (out == NULL: the number alone), -1 for an unknown family or a capacity too small. Families: "bsdf", "texture",
- * "filter", "primary", "shading", "light". The bsdf rows:
+ * "filter", "primary", "shading", "light", "trace" (its rows carry the name alone: gdpt_debug_kat_trace_variants). The bsdf rows:
  *   - one per <ROUGH, TWOSIDED, MASK> triple of bsdf_sample / bsdf_eval / bsdf_pdf / bsdf_eval_pdf that a product kernel instantiates,
  *     the triple taken from the product's own constants (kAllMaterials, kSetGlass, the sets of render_phases_general_sets.h); `mask` bit
  *     t = material type t is in the kernel's set, `rough` / `twosided` = the RoughPlastic / RoughDielectric and the DisneyGlass /
@@ -182,6 +182,25 @@ int gdpt_debug_kat_filter(const struct GdptScene *scene, int variant, int n, con
 int gdpt_debug_kat_primary(const struct GdptScene *scene, int variant, int n, const GdptKatPrimaryQuery *in, GdptKatPrimaryResult *out);
 int gdpt_debug_kat_shading(const struct GdptScene *scene, int variant, int n, const GdptKatShadingQuery *in, GdptKatShadingResult *out);
 int gdpt_debug_kat_light(const struct GdptScene *scene, int variant, int n, const GdptKatLightQuery *in, GdptKatLightResult *out);
+/* ---- The BVH walks on arrays of rays (csrc/hip/debug_kat_trace.hip) -----------------------------------------------------------------
+ * Family "trace": closest hit (device_trace.h: smallest fp32 t in [tnear, tfar), lowest primitive id on ties) or, with any_hit, whether
+ * any primitive accepts the ray, by one of the walks the render kernels make. One thread per ray in 256-thread blocks, the lanes past n
+ * finished from the start. The kernels call setup_trace, trav_init and trav_run as the product does, re-entering the walk as
+ * trace_pending does (stop_below = pending * keep_frac >> 8; knobs keep_frac and search_frac, the product's defaults when unset).
+ * gdpt_debug_kat_trace_variants: the table, one row per distinct (TraceCfg, residency) that a product kernel instantiates, then two
+ * rows that run the wavefront pipeline's own trace kernel (launch_wf_trace) on a ray queue written as its step kernel writes it.
+ * ww / wide / flat / spheres / spec / leaf_k: the TraceCfg (render_device.h); lds_scene: the walk reads the block's LDS copy of the scene;
+ * lds_stack_levels: stack slots per lane in LDS, 0 = the tree's own bound (dynamic LDS; scenes walked from HBM), the wavefront rows
+ * keep deeper levels in HBM. gdpt_debug_kat_variants("trace") gives the same rows by name alone.
+ * Result: gid = -1 for a miss (t, u, v are then without meaning); ng is set for a sphere hit only. With any_hit only gid >= 0 counts.
+ * Refused on the host, before any launch: an unknown variant; an lds_scene row for a scene that does not fit the LDS copy of that form;
+ * a spheres = 0 row on a scene with spheres; a wavefront row with a finite tfar or any_hit; a number that is not finite (tfar may be
+ * +infinity) or does not stay finite in fp32; a direction that is zero in fp32; tnear < 0; tfar < tnear; n above 2^20. */
+typedef struct GdptKatTraceVariant { const char *name; int32_t ww, wide, flat, spheres, spec, leaf_k, lds_scene, wavefront, lds_stack_levels; } GdptKatTraceVariant;
+typedef struct GdptKatTraceQuery { double org[3], dir[3], tnear, tfar; int32_t any_hit, pad; } GdptKatTraceQuery;
+typedef struct GdptKatTraceResult { int32_t gid; float t, u, v, ng[3]; } GdptKatTraceResult;
+int gdpt_debug_kat_trace_variants(GdptKatTraceVariant *out, int capacity);
+int gdpt_debug_kat_trace(const struct GdptScene *scene, int variant, int n, const GdptKatTraceQuery *in, GdptKatTraceResult *out);
 /* Removes every override: the library is back on its product path. */
 void gdpt_debug_knobs_reset(void);
 

@@ -233,7 +233,10 @@ inline bool box_hit(const float mn[3], const float mx[3], const float o[3], cons
     float t0 = tnear, t1 = tbest;
     for (int k = 0; k < 3; k++) {
         float a = (mn[k] - o[k]) * inv[k], b = (mx[k] - o[k]) * inv[k];
-        float lo = std::fmin(a, b), hi = std::fmax(a, b); // fmin/fmax drop NaNs (0*inf on flat boxes)
+        // 0 * inf: the origin lies in a bounding plane of an axis along which 1/d overflows. fmin/fmax would keep the other plane's
+        // infinity as both ends of the slab and reject a box whose boundary the ray runs in; the slab decides nothing instead.
+        if (a != a || b != b) continue;
+        float lo = std::fmin(a, b), hi = std::fmax(a, b);
         lo = lo - std::fabs(lo) * 4e-7f; hi = hi + std::fabs(hi) * 4e-7f; // widen by ~3 ulp
         t0 = std::fmax(t0, lo); t1 = std::fmin(t1, hi);
     }
@@ -1503,6 +1506,17 @@ OracleScene *oracle_scene_create(const GdptSceneDesc *desc, int use_bvh) {
             for (int k = 0; k < 3; k++) cent[3 * g + k] = 0.5f * (bb[6 * g + k] + bb[6 * g + 3 + k]);
         }
         if (n > 0) build_node(*sc, ids, 0, n, cent, bb);
+        // Every box is widened by 1e-6 of the largest coordinate of the bounds and the camera position (every possible ray origin), as
+        // the product's upload widens its own: the slab distances of a box and the t of a primitive inside it round differently, by
+        // more than box_hit's few ulps where the box is flat or the window [tnear, tfar) is an ulp wide, and a ray that runs IN the
+        // plane of a flat box (one direction component too small to move it in fp32) is still hit by the fp32 primitive test.
+        if (n > 0) {
+            float E = 0;
+            for (int k = 0; k < 3; k++) E = std::max(E, std::max(std::fabs(sc->nodes[0].mn[k]), std::fabs(sc->nodes[0].mx[k])));
+            for (int k = 0; k < 3; k++) E = std::max(E, (float)std::fabs(desc->camera.cam_to_world[4 * k + 3]));
+            const float P = 1e-6f * E;
+            for (BNode &nd : sc->nodes) for (int k = 0; k < 3; k++) { nd.mn[k] -= P; nd.mx[k] += P; }
+        }
     }
     // emitter sampling tables (Integrator::Path): init_sampling_dist per emitter mesh, then the light power table
     sc->mesh_tables.resize((size_t)desc->num_shapes);
@@ -1593,6 +1607,17 @@ int oracle_intersect(const OracleScene *s, const double org[3], const double dir
     if (!intersect(*s, r, ray_diff ? ray_diff[0] : 0, ray_diff ? ray_diff[1] : 0, &v)) return 0;
     to_c(v, out);
     return 1;
+}
+void oracle_closest_hits(const OracleScene *s, int n, const double *rays, int32_t *gid, float *tuvng) {
+    for (int i = 0; i < n; i++) {
+        const double *r = rays + 8 * (size_t)i;
+        float o[3] = {(float)r[0], (float)r[1], (float)r[2]};           // (intersect, occluded)
+        float d[3] = {(float)r[3], (float)r[4], (float)r[5]};
+        Hit h = closest_hit(*s, o, d, (float)r[6], (float)r[7]);
+        float *out = tuvng + 6 * (size_t)i;
+        gid[i] = h.valid ? h.gid : -1;
+        out[0] = h.t; out[1] = h.u; out[2] = h.v; out[3] = h.ng[0]; out[4] = h.ng[1]; out[5] = h.ng[2];
+    }
 }
 void oracle_shading_info_tri(const OracleScene *s, int gid, const double st[2], const double gn[3], double out[13]) {
     const Tri &t = s->tris[gid];

@@ -57,6 +57,10 @@ void oracle_filter_sample(int filter_type, double param, double u0, double u1, d
 /* intersect, src/intersection.cpp:7-65. ray_diff: {radius, spread}. Returns 1 on hit. */
 int oracle_intersect(const OracleScene *s, const double org[3], const double dir[3], double tnear, double tfar,
                      const double ray_diff[2], OracleVertex *out);
+/* The hit record under intersect() and occluded(), for n rays at once: rays = n x {org[3], dir[3], tnear, tfar}, converted to fp32 as
+ * those two do. gid[i] = the primitive (triangles first, then spheres; -1: none accepts the ray, i.e. not occluded), tuvng[6 i ..] =
+ * fp32 t, u, v and the unnormalised fp32 geometric normal. */
+void oracle_closest_hits(const OracleScene *s, int n, const double *rays, int32_t *gid, float *tuvng);
 /* compute_shading_info for triangle `gid` at barycentrics st given a (normalised) geometric normal.
  * out: uv[2], frame_x[3], frame_y[3], frame_n[3], mean_curvature, inv_uv_size  (12 doubles) */
 void oracle_shading_info_tri(const OracleScene *s, int gid, const double st[2], const double gn[3], double out[13]);

@@ -67,6 +67,8 @@ def lib():
         L.oracle_filter_sample.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, dp]
         L.oracle_intersect.restype = C.c_int
         L.oracle_intersect.argtypes = [C.c_void_p, dp, dp, C.c_double, C.c_double, dp, C.POINTER(OracleVertex)]
+        L.oracle_closest_hits.argtypes = [C.c_void_p, C.c_int, dp, C.POINTER(C.c_int32), C.POINTER(C.c_float)]
+        L.oracle_closest_hits.restype = None
         L.oracle_shading_info_tri.argtypes = [C.c_void_p, C.c_int, dp, dp, dp]
         L.oracle_bsdf_eval.argtypes = [C.c_void_p, C.c_void_p, dp, dp, C.POINTER(OracleVertex), dp]
         L.oracle_bsdf_pdf.restype = C.c_double
@@ -138,6 +140,14 @@ class OracleScene:
         v = OracleVertex()
         hit = lib().oracle_intersect(self.handle, _vec(org), _vec(dirv), tnear, tfar, _vec(ray_diff), C.byref(v))
         return v if hit else None
+
+    def closest_hits(self, rays):
+        """The hit records under intersect() and occluded() for an n x 8 array of rays (org, dir, tnear, tfar): (gid int32[n], -1 = no
+        primitive accepts the ray; float32[n, 6] = t, u, v, unnormalised geometric normal)."""
+        rays = np.ascontiguousarray(rays, dtype=np.float64).reshape(-1, 8)
+        gid, out = np.full(len(rays), -1, dtype=np.int32), np.zeros((len(rays), 6), dtype=np.float32)
+        lib().oracle_closest_hits(self.handle, len(rays), _dp(rays), gid.ctypes.data_as(C.POINTER(C.c_int32)), out.ctypes.data_as(C.POINTER(C.c_float)))
+        return gid, out
 
     def shading_info_tri(self, gid, st, gn):
         out = (C.c_double * 13)()

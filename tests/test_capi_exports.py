@@ -190,3 +190,37 @@ def test_work_item_plan_invariants(G):
     assert max(b2 - b1 for b1, b2 in zip(small, small[1:])) <= 4 and len(small) - 1 <= 64   # (the 64-chunk limit wins here: 8 copies of a plan of at most 8 chunks for 16 samples)
     eq = G.debug_knobs.chunk_plan(16, 512 * 512, force_log2k=2)
     assert eq == [0, 4, 8, 12, 16]
+
+
+def test_trace_kat_struct_layouts_and_table_match_the_header(G, tmp_path):
+    """The structs of gdpt_debug_kat_trace (include/gdpt_debug.h), as the C compiler lays them out, and its table of rows (no GPU)."""
+    structs = {"GdptKatTraceVariant": G.GdptKatTraceVariant, "GdptKatTraceQuery": G.GdptKatTraceQuery, "GdptKatTraceResult": G.GdptKatTraceResult}
+    lines = []
+    for name, s in structs.items():
+        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        for field, _ in s._fields_:
+            lines.append(f'printf("{name}.{field} %zu\\n", offsetof({name}, {field}));')
+    src = tmp_path / "kat_trace.c"
+    src.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{ROOT}/include/gdpt_debug.h"\nint main(){{{" ".join(lines)} return 0;}}\n')
+    exe = tmp_path / "kat_trace"
+    subprocess.check_call(["gcc", "-std=c99", "-o", str(exe), str(src)])
+    seen = dict(line.split() for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    for name, s in structs.items():
+        assert int(seen[name]) == C.sizeof(s), name
+        for field, _ in s._fields_:
+            assert int(seen[f"{name}.{field}"]) == getattr(s, field).offset, (name, field)
+    assert C.sizeof(G.GdptKatTraceQuery) == 72 and C.sizeof(G.GdptKatTraceResult) == 28
+    rows = G.debug_knobs.kat_trace_variants()
+    names = [r["name"] for r in rows]
+    assert len(set(names)) == len(names) == 11
+    assert [r["name"] for r in G.debug_knobs.kat_variants("trace")] == names            # the family is known to gdpt_debug_kat_variants
+    # one row per distinct (TraceCfg, residency), then the wavefront pipeline's trace kernel with and without sphere code
+    # (the product build: with GDPT_SPEC_LEAF or GDPT_LDS_LEAF_K = 0, A/B builds, the cursor rows fall together with the whole-leaf rows)
+    cfgs = [tuple(r[k] for k in ("ww", "wide", "flat", "spheres", "spec", "leaf_k", "lds_scene")) for r in rows if not r["wavefront"]]
+    assert len(set(cfgs)) == len(cfgs) == 9
+    assert [(r["spheres"], r["lds_stack_levels"]) for r in rows if r["wavefront"]] == [(1, 16), (0, 16)] and not any(r["wavefront"] for r in rows[:9])
+    for r in rows[:9]:
+        assert r["lds_stack_levels"] == (12 if r["lds_scene"] else 0)
+        assert r["flat"] == (not r["lds_scene"]) and (not r["spec"] or (r["ww"] and r["leaf_k"] == 0)) and (r["wide"] or not r["ww"])
+    for fn in ("gdpt_debug_kat_trace", "gdpt_debug_kat_trace_variants"):
+        assert hasattr(G.lib(), fn)

@@ -7,8 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import DescBuilder, scene_variant
-from test_gpu_route_matrix import Built, room
+from helpers import Built, DescBuilder, odd_room_builder, room, scene_variant
 
 BUFS = ("img", "cx0", "cy0", "cx1", "cy1")
 FILM, SPP = (48, 32), 6
@@ -68,14 +67,7 @@ def test_bit_identical_to_whole_leaf_trips(G, scene_tmp, kind, route):
 
 
 def odd_room(G):
-    """The Lambertian room of test_gpu_route_matrix plus a fan of three triangles on the floor and two lone triangles on a wall and the
-    ceiling: 31 triangles that do not pair up, so the builder at its default leaf factor makes leaves of every size up to bvh_leaf_max
-    (histograms [31], [3, 14], [1, 12, 2], [1, 10, 2, 1]). cbox, 19 quads, never yields a three-record leaf."""
-    b = room(G, "lambert", *FILM, -1, 5)
-    m = b.material(G.MAT_LAMBERTIAN, [DescBuilder.const_tex(G, 0.5)])
-    b.mesh([0.9, -2.0, 0.2, 1.7, -2.0, 0.4, 1.2, -1.0, 0.3, 0.6, -1.0, 0.5, 0.4, -2.0, 0.6], [0, 1, 2, 0, 2, 3, 0, 3, 4], m)
-    b.mesh([-1.9, 1.0, 0.5, -1.9, 1.6, 0.9, -1.9, 1.2, 1.4], [0, 1, 2], m)
-    b.mesh([1.0, 1.9, -1.0, 1.6, 1.9, -0.6, 1.2, 1.9, -0.2], [0, 1, 2], m)
+    b = odd_room_builder(G, FILM)
     return Built(b.finish(), *FILM, b)
 
 

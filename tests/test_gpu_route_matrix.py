@@ -15,7 +15,7 @@ import re
 import numpy as np
 import pytest
 
-from helpers import DescBuilder, rel_l2, scene_variant
+from helpers import Built, DescBuilder, _box, _camera, _quad, rel_l2, room, scene_variant  # noqa: F401 (other modules import them from here)
 
 BUFS = ("img", "cx0", "cy0", "cx1", "cy1")
 THREADS = min(16, os.cpu_count() or 1)
@@ -104,102 +104,7 @@ CASES = _cases()
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------
-def _camera(G, cam, w, h, pos=(0.0, 0.0, 1.6), fov=60.0):
-    """Perspective camera at `pos` looking down -z (the loader's maths for fovAxis x, as test_gpu_render_parity.py)."""
-    cam.width, cam.height, cam.filter_type, cam.filter_param = w, h, G.FILTER_BOX, 1.0
-    c2w = np.eye(4)
-    c2w[:3, 0], c2w[:3, 1], c2w[:3, 2], c2w[:3, 3] = [-1, 0, 0], [0, 1, 0], [0, 0, -1], pos
-    aspect = w / h
-    cot = 1.0 / math.tan(math.radians(fov / 2))
-    persp = np.array([[cot, 0, 0, 0], [0, cot, 0, 0], [0, 0, 1, -1], [0, 0, 1, 0]], dtype=float)
-    c2s = np.diag([-0.5, -0.5 * aspect, 1, 1]) @ np.array([[1, 0, 0, -1], [0, 1, 0, -1 / aspect], [0, 0, 1, 0], [0, 0, 0, 1]], dtype=float) @ persp
-    s2c = np.linalg.inv(c2s)
-    for i in range(16):
-        cam.sample_to_cam[i] = s2c.ravel()[i]
-        cam.cam_to_world[i] = c2w.ravel()[i]
-
-
-def _quad(b, pts, material, toward, light=None, uvs=None):
-    """Two triangles over pts[0..3], wound so that the geometric normal faces the point `toward`."""
-    p = np.asarray(pts, dtype=float)
-    n = np.cross(p[1] - p[0], p[2] - p[0])
-    idx = [0, 1, 2, 0, 2, 3] if np.dot(n, np.asarray(toward, float) - p[0]) > 0 else [0, 2, 1, 0, 3, 2]
-    return b.mesh(list(p.ravel()), idx, material, uvs=uvs, light=light)
-
-
-def _box(b, lo, hi, material, faces_in, lights=None):
-    """Axis-aligned box of six quads (face 2 * axis + side, side 1 = the high one); faces_in: normals point inside (a
-    room) or outside (a block); lights: {face: intensity} makes those faces emitters."""
-    c = [(lo[k] + hi[k]) / 2 for k in range(3)]
-    for axis in range(3):
-        for side in (lo[axis], hi[axis]):
-            u, v = [k for k in range(3) if k != axis]
-            pts = []
-            for a, bb in ((0, 0), (1, 0), (1, 1), (0, 1)):
-                q = [0.0] * 3
-                q[axis], q[u], q[v] = side, (lo[u], hi[u])[a], (lo[v], hi[v])[bb]
-                pts.append(q)
-            face = axis * 2 + (side == hi[axis])
-            mat = material[face] if isinstance(material, list) else material
-            outward = [c[k] + (2 * (side - c[k]) if k == axis else 0.0) for k in range(3)]
-            _quad(b, pts, mat, c if faces_in else outward, light=(lights or {}).get(face))
-
-
-def room(G, kind, w, h, max_depth, rr_depth):
-    """Closed 4x4x4 room seen from inside: Lambertian walls, an emitter on the back wall in the camera's line of sight
-    and glowing walls, a block and the floor made of the lobe under test; `kind` picks that lobe."""
-    b = DescBuilder(G)
-    ct = lambda v: DescBuilder.const_tex(G, v)
-    lam = lambda c: b.material(G.MAT_LAMBERTIAN, [ct(c)])
-    if kind == "metal_box":
-        # every wall, the emitting one included, of one material: DisneyMetal, base colour 1, low roughness -> throughput
-        # stays near 1, paths in the closed box run to maxDepth and no offset fails the replay's material test. (A
-        # metallic DisneyBSDF would not do: the reference samples its glass lobe a quarter of the time, whatever the
-        # weights, and the refracted path leaves the box.) The small glass sphere makes the scene two-sided.
-        m = b.material(G.MAT_DISNEY_METAL, [ct(1.0), ct(0.1), ct(0.0)])
-        _box(b, (-2, -2, -2), (2, 2, 2), m, True, lights={4: (1.0, 0.8, 0.6)})       # the back wall emits
-        b.sphere((1.8, 1.8, -1.8), 0.1, b.material(G.MAT_DISNEY_GLASS, [ct(1.0), ct(0.2), ct(0.0)], eta=1.5))
-        _camera(G, b.desc.camera, w, h)
-        b.desc.max_depth, b.desc.rr_depth = max_depth, rr_depth
-        return b
-    white, red, green, dark = lam((0.7, 0.7, 0.7)), lam((0.7, 0.15, 0.1)), lam((0.1, 0.6, 0.2)), lam(0.0)
-    lobe = {
-        "disney_diffuse": lambda: b.material(G.MAT_DISNEY_DIFFUSE, [ct((0.8, 0.6, 0.3)), ct(0.6), ct(0.4)]),
-        "disney_metal": lambda: b.material(G.MAT_DISNEY_METAL, [ct((0.9, 0.7, 0.5)), ct(0.3), ct(0.25)]),
-        "disney_clearcoat": lambda: b.material(G.MAT_DISNEY_CLEARCOAT, [ct(0.6)]),
-        "disney_sheen": lambda: b.material(G.MAT_DISNEY_SHEEN, [ct((0.8, 0.5, 0.6)), ct(0.5)]),
-        "bsdf": lambda: b.material(G.MAT_DISNEY_BSDF, [ct((0.8, 0.4, 0.3))] + [ct(v) for v in (0.4, 0.3, 0.2, 0.5, 0.35, 0.2, 0.3, 0.4, 0.5, 0.3, 0.6)], eta=1.4),
-        "glass": lambda: b.material(G.MAT_DISNEY_GLASS, [ct((0.9, 0.85, 0.8)), ct(0.25), ct(0.3)], eta=1.5),
-        "rough": lambda: b.material(G.MAT_ROUGHPLASTIC, [ct((0.6, 0.4, 0.3)), ct(0.5), ct(0.2)], eta=1.5),
-    }
-    if kind in lobe:
-        floor = block = lobe[kind]()
-    elif kind == "general_mix":
-        floor, block = lobe["disney_diffuse"](), lobe["disney_metal"]()
-    elif kind == "lambert_tex":
-        rng = np.random.default_rng(7)
-        floor = b.material(G.MAT_LAMBERTIAN, [b.image_tex(list(0.2 + 0.6 * rng.random(16 * 8 * 3)), 16, 8, 3, 2.0, 3.0, 0.1, 0.3)])
-        block = lam((0.5, 0.5, 0.6))
-    else:
-        floor, block = white, lam((0.5, 0.5, 0.6))
-    # walls: -x, +x, -y (floor), +y, -z (back), +z (behind the camera)
-    # every wall glows a little: a sample whose primary ray meets a wall sees emission at any depth, so an all-zero
-    # image would mean the film saw nothing but the block
-    _box(b, (-2, -2, -2), (2, 2, 2), [red, green, floor, white, white, white], True, lights={f: (0.3, 0.3, 0.3) for f in range(6)})
-    _box(b, (-1.7, -2.0, -1.3), (-0.7, -0.7, -0.3), block, False)
-    _quad(b, [[-0.8, -0.8, -1.95], [0.8, -0.8, -1.95], [0.8, 0.8, -1.95], [-0.8, 0.8, -1.95]], dark, (0, 0, 0), light=(6.0, 5.0, 4.0))
-    if kind == "lambert_sphere":
-        b.sphere((1.0, -1.4, -0.8), 0.6, lam((0.6, 0.6, 0.3)))
-    _camera(G, b.desc.camera, w, h)
-    b.desc.max_depth, b.desc.rr_depth = max_depth, rr_depth
-    return b
-
-
-class Built:
-    """Duck-typed SceneDesc (ptr, width, height) over a DescBuilder or a parsed scene file."""
-
-    def __init__(self, ptr, w, h, owner):
-        self.ptr, self.width, self.height, self.owner = ptr, w, h, owner
+# (the room and its parts: tests/helpers.py)
 
 
 def make_scene(G, tmp, kind, film, depth):
