@@ -90,6 +90,16 @@ def lib():
         L.gdpt_denoise_nlm_device.argtypes = [C.c_int, C.c_int, vp, vp, nlp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm.argtypes = [C.c_int, C.c_int, vp, vp, nlp, vp, vp, nls]
         L.gdpt_progressive_denoise.argtypes = [vp, nlp, C.c_int, vp, vp, nls]
+        ngp = C.POINTER(defs.GdptNlmGuide)
+        L.gdpt_nlm_default_guide.argtypes = [ngp]
+        L.gdpt_nlm_default_guide.restype = None
+        L.gdpt_denoise_nlm_guided_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm_guided.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, nls]
+        L.gdpt_progressive_denoise_guided.argtypes = [vp, nlp, ngp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        L.gdpt_features_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp, vp,
+                                                  C.POINTER(defs.GdptRenderStats)]
+        L.gdpt_features_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp,
+                                           C.POINTER(defs.GdptRenderStats)]
         L.gdpt_assemble_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.gdpt_poisson_solve.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         L.gdpt_poisson_solve_ex.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp, C.c_int, C.c_double, C.c_int,
@@ -290,6 +300,36 @@ class Scene:
                                                          C.byref(rs), C.byref(ps)))
         return (out, bufs, rs, ps) if return_buffers else out
 
+    def features(self, spp, window=None, rows=None, out=None, want_stats=False):
+        """First-hit feature buffers of the film (gdpt_features_render): two (8, H, W) float64 arrays, the per-pixel means over `spp`
+        samples and the variances of those means; planes 0-2 albedo, 3-5 shading normal, 6 depth, 7 coverage. The camera rays are the
+        render's own: `window` = (stream_spp, first_sample) as in render_device. `rows` = (begin, end) renders that band alone and
+        leaves the other rows of `out` = (mean, var) as they are (zeros without `out`). With `want_stats` the GdptRenderStats follow."""
+        shape = (defs.FEATURE_CHANNELS, self.height, self.width)
+        if out is None:
+            mean, var = np.zeros(shape, dtype=np.float64), np.zeros(shape, dtype=np.float64)
+        else:
+            mean, var = out
+            if any(a.shape != shape or a.dtype != np.float64 or not a.flags.c_contiguous for a in (mean, var)):
+                raise GdptError("features: out must be two C-contiguous float64 arrays of shape (8, H, W)")
+        st = defs.GdptRenderStats()
+        p = _params(spp, defs.RNG_SAMPLE, rows if rows is not None else (0, 0))
+        win = defs.GdptSampleWindow(int(window[0]), int(window[1])) if window is not None else None
+        _check(lib().gdpt_features_render(self.handle, C.byref(p), C.byref(win) if win is not None else None, C.c_void_p(mean.ctypes.data),
+                                          C.c_void_p(var.ctypes.data), C.byref(st)))
+        return (mean, var, st) if want_stats else (mean, var)
+
+    def features_device(self, mean_ptr, var_ptr, spp, window=None, rows=None, stream=None, want_stats=False):
+        """features() into device memory (gdpt_features_render_device): two device addresses of 8 H W doubles each. Enqueue-only
+        unless `want_stats`."""
+        st = defs.GdptRenderStats() if want_stats else None
+        p = _params(spp, defs.RNG_SAMPLE, rows if rows is not None else (0, 0))
+        win = defs.GdptSampleWindow(int(window[0]), int(window[1])) if window is not None else None
+        _check(lib().gdpt_features_render_device(self.handle, C.byref(p), C.byref(win) if win is not None else None,
+                                                 C.c_void_p(int(mean_ptr)) if mean_ptr else None, C.c_void_p(int(var_ptr)) if var_ptr else None,
+                                                 C.c_void_p(int(stream) if stream else 0), C.byref(st) if st is not None else None))
+        return st
+
     def tile_row_costs(self, spp=1):
         """Rays of a pilot render of every 16-pixel tile row (gdpt_tile_row_costs): what sharding.bands_weighted balances by."""
         T = (self.height + 15) // 16
@@ -448,6 +488,29 @@ class Progressive:
         out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
         _check(lib().gdpt_progressive_denoise(self.handle, C.byref(p), 0, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.byref(st)))
         return out, var_out, st
+
+    def denoise_guided(self, feature_spp, guide=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
+        """The feature-guided non-local-means filter on buffer 0 (gdpt_progressive_denoise_guided; from 2 passes on): the session
+        renders `feature_spp` samples of first-hit features along the camera rays of its own first samples and lets them cap the
+        colour weights. `guide`: a GdptNlmGuide (nlm_guide(...)), None = the library's default; `params`: the keywords of nlm_params.
+        Returns (HxWx3 filtered mean, HxWx3 variance of it, GdptNlmStats), with `features=True` also the two (8, H, W) feature arrays
+        before the stats; with `out_ptr` (and `var_out_ptr`, `features_ptrs` = 2 device addresses) everything stays in device memory
+        and the stats alone are returned."""
+        p, st = nlm_params(**params), defs.GdptNlmStats()
+        g = guide if guide is not None else nlm_guide()
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            _check(lib().gdpt_progressive_denoise_guided(self.handle, C.byref(p), C.byref(g), int(feature_spp), 1, opt(out_ptr), opt(var_out_ptr),
+                                                         opt(fp[0]), opt(fp[1]), C.byref(st)))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        _check(lib().gdpt_progressive_denoise_guided(self.handle, C.byref(p), C.byref(g), int(feature_spp), 0, C.c_void_p(out.ctypes.data),
+                                                     C.c_void_p(var_out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
+                                                     C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
+        return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
@@ -694,6 +757,72 @@ def denoise_nlm_device(width, height, img_ptr, var_ptr, out_ptr, var_out_ptr=Non
     opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
     _check(lib().gdpt_denoise_nlm_device(int(width), int(height), opt(img_ptr), opt(var_ptr), C.byref(p), opt(out_ptr), opt(var_out_ptr),
                                          opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def nlm_guide(num_channels=None, groups=None, k_f=None, alpha_f=None):
+    """GdptNlmGuide (include/gdpt.h): the library's defaults (gdpt_nlm_default_guide: the 8 planes of a feature render, an albedo
+    group (0, 3, 1e-3) and a normal group (3, 3, 1e-3), k_f 0.6, alpha_f 1) with the keywords given in their places, taken literally.
+    `groups`: a list of (first_channel, num_channels, tau), at most 4."""
+    g = defs.GdptNlmGuide()
+    lib().gdpt_nlm_default_guide(C.byref(g))
+    if num_channels is not None:
+        g.num_channels = int(num_channels)
+    if groups is not None:
+        groups = list(groups)
+        if len(groups) > defs.NLM_MAX_GROUPS:
+            raise GdptError(f"nlm_guide: at most {defs.NLM_MAX_GROUPS} groups")
+        g.num_groups = len(groups)
+        for j in range(defs.NLM_MAX_GROUPS):
+            first, count, tau = groups[j] if j < len(groups) else (0, 0, 0.0)
+            g.groups[j] = defs.GdptNlmFeatureGroup(int(first), int(count), float(tau))
+    if k_f is not None:
+        g.k_f = float(k_f)
+    if alpha_f is not None:
+        g.alpha_f = float(alpha_f)
+    return g
+
+
+def _feature_planes(feat, feat_var, shape, guide):
+    """The two planar feature arrays as C-contiguous (num_channels, H, W) float64, or (None, None)."""
+    if feat is None or feat_var is None:
+        return None, None
+    f = np.ascontiguousarray(feat, dtype=np.float64)
+    fv = np.ascontiguousarray(feat_var, dtype=np.float64)
+    if f.ndim != 3 or f.shape != fv.shape or f.shape[1:] != tuple(shape[:2]) or f.shape[0] != guide.num_channels:
+        raise GdptError("denoise_nlm_guided: feat and feat_var must be (num_channels, H, W) arrays of one shape")
+    return f, fv
+
+
+def denoise_nlm_guided(img, var, feat, feat_var, guide=None, **params):
+    """denoise_nlm() with a feature distance capping the colour weights (gdpt_denoise_nlm_guided): `feat`, `feat_var` are planar
+    (num_channels, H, W) float64 arrays, a feature and the variance of it per plane (what Scene.features() returns, or any other);
+    `guide`: a GdptNlmGuide (nlm_guide(...)), None = the library's default. Returns (HxWx3 filtered image, HxWx3 variance of it,
+    GdptNlmStats). Pixels at which a used feature channel is not finite or has a negative variance are left out as well."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm_guided: img and var must be HxWx3 arrays of one shape")
+    g = guide if guide is not None else nlm_guide()
+    f, fv = _feature_planes(feat, feat_var, a.shape, g)
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = nlm_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_nlm_guided(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                         C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                         C.byref(p), C.byref(g), C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_nlm_guided_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_ptr, out_ptr, var_out_ptr=None, guide=None, stream=None,
+                              stats=True, params=None, **kw):
+    """denoise_nlm_guided() on device addresses (gdpt_denoise_nlm_guided_device); arguments as denoise_nlm_device, with the two planar
+    feature arrays and `guide` (None = the library's default)."""
+    p = params if params is not None else nlm_params(**kw)
+    g = guide if guide is not None else nlm_guide()
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_guided_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
+                                                C.byref(g), opt(out_ptr), opt(var_out_ptr), opt(stream), C.byref(st) if stats else None))
     return st
 
 

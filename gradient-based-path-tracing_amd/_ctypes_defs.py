@@ -138,6 +138,19 @@ class GdptNlmStats(C.Structure):
                 ("window_radius", C.c_int32), ("patch_radius", C.c_int32)]
 
 
+FEATURE_CHANNELS = 8             # planes of a feature render: 0-2 albedo, 3-5 shading normal, 6 depth, 7 coverage
+NLM_MAX_GROUPS, NLM_MAX_CHANNELS = 4, 16
+
+
+class GdptNlmFeatureGroup(C.Structure):
+    _fields_ = [("first_channel", C.c_int32), ("num_channels", C.c_int32), ("tau", C.c_double)]
+
+
+class GdptNlmGuide(C.Structure):
+    _fields_ = [("num_channels", C.c_int32), ("num_groups", C.c_int32), ("groups", GdptNlmFeatureGroup * NLM_MAX_GROUPS),
+                ("k_f", C.c_double), ("alpha_f", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class GdptGroupReconParams(C.Structure):
     _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
                 ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]

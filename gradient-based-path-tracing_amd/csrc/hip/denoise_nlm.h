@@ -10,6 +10,14 @@ namespace gdpt {
 // What every entry point refuses in a parameter block; the message names the field. `who` names the caller. Host only.
 void nlm_check_params(const std::string &who, const GdptNlmParams &p);
 
+// The same for the guide of the guided entry points (gdpt_denoise_nlm_guided*).
+void nlm_check_guide(const std::string &who, const GdptNlmGuide &g);
+// The guided filter on device pointers of the current device, every argument checked (the session's entry point). Enqueued on
+// `stream`; waits for it if `stats` is asked for.
+void denoise_nlm_guided_launch(int w, int h, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                               const GdptNlmParams &p, const GdptNlmGuide &g, double *d_out, double *d_var_out, hipStream_t stream,
+                               GdptNlmStats *stats);
+
 // Launch geometry of both kernel forms: film::tile_grid (image_kernels.h) over tiles of kNlmTile x kNlmTile pixels. The filter's
 // scratch is kept per (device, stream), and dropped by forget_stream (device_mem.h).
 constexpr int kNlmTile = 16;

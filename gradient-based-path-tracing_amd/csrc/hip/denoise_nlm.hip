@@ -16,6 +16,12 @@
 //                   row pass a half-wave covers two rows of 16 outputs; the e plane's pitch is 16 (f = 0) or 48 doubles, = 16 mod 32,
 //                   which puts the second row's 16 doubles on the other half of the 64 banks. In the column pass a half-wave reads 32
 //                   consecutive doubles of the row sums (pitch 16).
+// Both are templates on GUIDED (gdpt_denoise_nlm_guided*): the unguided instantiations are the kernels above as they were, argument
+// block included. A guided kernel adds the feature planes to a pixel's validity and caps the colour weight of a pair (p, p+o) with the
+// pair's feature distance. The thread keeps its own pixel's feature values and variances in registers (the loops over groups and
+// channels are unrolled to the caps, so every index is static) and reads those of p+o from global memory: the planes are planar, a
+// wave's read of one plane is four 128-byte rows, served from L1 / L2. The stage gets no feature planes: at (r, f) = (10, 3) it
+// already takes 108 624 of the 163 840 bytes a workgroup may declare, and 2 x 6 planes of (16 + 2r)^2 doubles would be another 124 KB.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "image_kernels.h"
@@ -24,6 +30,7 @@
 #include <algorithm>
 #include <cmath>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 namespace nlm {
@@ -32,16 +39,31 @@ using namespace film;             // kBlock, kMaxBlocks, TileGrid, leave_block_s
 
 constexpr int kTile = gdpt::kNlmTile;
 constexpr int kMaxR = GDPT_NLM_MAX_WINDOW_RADIUS, kMaxF = GDPT_NLM_MAX_PATCH_RADIUS;
+constexpr int kMaxGroups = GDPT_NLM_MAX_GROUPS, kMaxChannels = GDPT_NLM_MAX_CHANNELS;
 static_assert(kTile * kTile == kBlock, "one thread per tile pixel");
 static_assert((kTile + 2 * kMaxF) * (kTile + 2 * kMaxF) <= 2 * kBlock, "a thread computes at most two pair distances per offset");
 
 struct Args {
+    static constexpr bool kGuided = false;
     TileGrid g;                  // 16 x 16 tiles
     int r, f;
     double k2, alpha, eps;
     const double *img, *var;
     double *out, *var_out;       // var_out nullable
     double *partials;            // [0] sum var in, [1] sum u^2 in, [2] pixels left out, [3] sum var out, [4] sum u^2 out, [5] = [2]; gridDim.x doubles each
+};
+
+// the guide of a guided call: planes `feat`, `fvar` of `plane` doubles each; group j compares channels [first[j], first[j] + count[j])
+struct Guide {
+    const double *feat, *fvar;
+    size_t plane;
+    int groups, first[kMaxGroups], count[kMaxGroups];
+    unsigned used;               // bit c: some group names channel c
+    double tau[kMaxGroups], kf2, alpha_f;
+};
+struct GuidedArgs : Args {
+    static constexpr bool kGuided = true;
+    Guide gd;
 };
 
 // pitch of the e plane for patches of ew = 16 + 2f points a row
@@ -77,9 +99,12 @@ __device__ __forceinline__ double pair_distance(const double ua[3], const double
 
 struct Accum {
     double num[3] = {0.0, 0.0, 0.0}, vnum[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
-    __device__ __forceinline__ void add(double S, int C, const double u[3], const double v[3]) {
+    // Df (guided kernels): the pair's feature distance, >= 0
+    template <bool GUIDED = false>
+    __device__ __forceinline__ void add(double S, int C, const double u[3], const double v[3], double Df = 0.0) {
         double D = S / (double)C;
         D = D > 0.0 ? D : 0.0;
+        if (GUIDED) D = fmax(D, Df);
         const double wgt = exp(-D);
         wsum += wgt;
 #pragma unroll
@@ -92,7 +117,8 @@ struct Sums {
 };
 
 // the pixel's outputs and its terms of the film sums; u, v: its valid input triples
-__device__ __forceinline__ void finish_pixel(const Args &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
+template <class A>
+__device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
     double o[3], vo[3];
     const double w2 = acc.wsum * acc.wsum;
 #pragma unroll
@@ -108,7 +134,8 @@ __device__ __forceinline__ void finish_pixel(const Args &a, size_t i, const doub
     s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
 }
 
-__device__ __forceinline__ void keep_pixel(const Args &a, size_t i, const double u[3], const double v[3], Sums &s) {
+template <class A>
+__device__ __forceinline__ void keep_pixel(const A &a, size_t i, const double u[3], const double v[3], Sums &s) {
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         a.out[i + c] = u[c];
@@ -117,7 +144,8 @@ __device__ __forceinline__ void keep_pixel(const Args &a, size_t i, const double
     s.left_out += 1.0;
 }
 
-__device__ __forceinline__ void leave_partials(const Args &a, const Sums &s, double *red) {
+template <class A>
+__device__ __forceinline__ void leave_partials(const A &a, const Sums &s, double *red) {
     leave_block_sum(a.partials, 0, s.var_in, red);
     leave_block_sum(a.partials, 1, s.sq_in, red);
     const double out = block_sum(s.left_out, red);      // (one sum, left for both reductions)
@@ -126,15 +154,62 @@ __device__ __forceinline__ void leave_partials(const Args &a, const Sums &s, dou
     leave_block_sum(a.partials, 4, s.sq_out, red);
 }
 
+// whether every feature channel some group names is finite at pixel i, with variance >= 0
+__device__ __forceinline__ bool valid_features(const Guide &gd, size_t i) {
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < kMaxChannels; c++)
+        if (gd.used >> c & 1u) {
+            const double g = gd.feat[c * gd.plane + i], s = gd.fvar[c * gd.plane + i];
+            ok = ok && isfinite(g) && isfinite(s) && s >= 0.0;
+        }
+    return ok;
+}
+
 // the triples of film pixel (x, y), which is inside the film; returns whether it is valid
-__device__ __forceinline__ bool load_pixel(const Args &a, int x, int y, double u[3], double v[3]) {
+template <class A>
+__device__ __forceinline__ bool load_pixel(const A &a, int x, int y, double u[3], double v[3]) {
     const size_t i = ((size_t)y * a.g.w + x) * 3;
 #pragma unroll
     for (int c = 0; c < 3; c++) { u[c] = a.img[i + c]; v[c] = a.var[i + c]; }
-    return valid_triples(u, v);
+    bool ok = valid_triples(u, v);
+    if constexpr (A::kGuided) ok = ok && valid_features(a.gd, (size_t)y * a.g.w + x);
+    return ok;
 }
 
-__global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
+// A thread's own pixel in registers: the feature values and variances of the channels in use (0 elsewhere). Every loop over groups and
+// channels below runs to the caps with static indices, under wave-uniform conditions.
+struct OwnFeatures {
+    double g[kMaxChannels], s[kMaxChannels];
+    __device__ __forceinline__ void load(const Guide &gd, size_t i) {
+#pragma unroll
+        for (int c = 0; c < kMaxChannels; c++) {
+            g[c] = 0.0; s[c] = 0.0;
+            if (gd.used >> c & 1u) { g[c] = gd.feat[c * gd.plane + i]; s[c] = gd.fvar[c * gd.plane + i]; }
+        }
+    }
+    // D^f of the pair (own pixel, valid pixel iq)
+    __device__ __forceinline__ double distance(const Guide &gd, size_t iq) const {
+        double Df = 0.0;
+#pragma unroll
+        for (int j = 0; j < kMaxGroups; j++) {
+            if (j >= gd.groups) continue;
+            double phi = 0.0;
+#pragma unroll
+            for (int c = 0; c < kMaxChannels; c++) {
+                if (c < gd.first[j] || c >= gd.first[j] + gd.count[j]) continue;
+                const double gq = gd.feat[c * gd.plane + iq], sq = gd.fvar[c * gd.plane + iq];
+                const double d = g[c] - gq;
+                phi += (d * d - gd.alpha_f * (s[c] + fmin(sq, s[c]))) / (gd.kf2 * fmax(gd.tau[j], s[c] + sq));
+            }
+            Df = fmax(Df, phi / (double)gd.count[j]);
+        }
+        return Df;
+    }
+};
+
+template <bool GUIDED>
+__global__ __launch_bounds__(kBlock) void direct_kernel(typename std::conditional<GUIDED, GuidedArgs, Args>::type a) {
     __shared__ double red[kBlock / 64];
     const int r = a.r, f = a.f;
     Sums s;
@@ -145,6 +220,8 @@ __global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
         const size_t i = ((size_t)y * a.g.w + x) * 3;
         double u[3], v[3];
         if (!load_pixel(a, x, y, u, v)) { keep_pixel(a, i, u, v, s); continue; }
+        OwnFeatures own;
+        if constexpr (GUIDED) own.load(a.gd, (size_t)y * a.g.w + x);
         Accum acc;
         for (int oy = -r; oy <= r; oy++)
             for (int ox = -r; ox <= r; ox++) {
@@ -164,14 +241,16 @@ __global__ __launch_bounds__(kBlock) void direct_kernel(Args a) {
                         S += pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
                         C++;
                     }
-                acc.add(S, C, uq, vq);      // (C >= 1: the tap n = 0 counts)
+                if constexpr (GUIDED) acc.template add<true>(S, C, uq, vq, own.distance(a.gd, (size_t)qy * a.g.w + qx));
+                else acc.add(S, C, uq, vq);      // (C >= 1: the tap n = 0 counts)
             }
         finish_pixel(a, i, u, v, acc, s);
     }
     leave_partials(a, s, red);
 }
 
-__global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
+template <bool GUIDED>
+__global__ __launch_bounds__(kBlock) void tiled_kernel(typename std::conditional<GUIDED, GuidedArgs, Args>::type a) {
     extern __shared__ double lds[];
     __shared__ double red[kBlock / 64];
     const int r = a.r, f = a.f, halo = r + f;
@@ -213,6 +292,8 @@ __global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
         const int x = tp.x, y = tp.y;
         const bool inside = x < a.g.w && y < a.g.h;
         const bool okp = inside && sflag[pc] != 0;
+        OwnFeatures own;
+        if constexpr (GUIDED) { if (okp) own.load(a.gd, (size_t)y * a.g.w + x); }
         Accum acc;
         for (int oy = -r; oy <= r; oy++)
             for (int ox = -r; ox <= r; ox++) {
@@ -247,7 +328,8 @@ __global__ __launch_bounds__(kBlock) void tiled_kernel(Args a) {
                     int C = 0;
                     for (int n = 0; n < taps; n++) { S += ph[tid + n * kTile]; C += ch[tid + n * kTile]; }
                     const double uq[3] = {su[iq], su[sn + iq], su[2 * sn + iq]}, vq[3] = {sv[iq], sv[sn + iq], sv[2 * sn + iq]};
-                    acc.add(S, C, uq, vq);
+                    if constexpr (GUIDED) acc.template add<true>(S, C, uq, vq, own.distance(a.gd, (size_t)(y + oy) * a.g.w + (x + ox)));
+                    else acc.add(S, C, uq, vq);
                 }
             }
         if (!inside) continue;
@@ -283,8 +365,10 @@ struct NlmWorkspace {
 PerStream<NlmWorkspace> &g_workspaces = *new PerStream<NlmWorkspace>();
 
 // Device pointers on the current device; the arguments have been checked. Enqueued on `stream`; waits for it if `stats` is asked for.
+// `guide` (nullable): the guided kernels, on `d_feat`, `d_feat_var`.
 void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, const GdptNlmParams &p, double *d_out, double *d_var_out,
-                        hipStream_t stream, GdptNlmStats *stats) {
+                        hipStream_t stream, GdptNlmStats *stats, const GdptNlmGuide *guide = nullptr, const double *d_feat = nullptr,
+                        const double *d_feat_var = nullptr) {
     int dev = 0;
     ck(hipGetDevice(&dev), "hipGetDevice");
     NlmWorkspace &ws = g_workspaces.get(dev, stream);
@@ -294,19 +378,36 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
     if (!ws.h_est) ws.h_est.alloc(2, "hipHostMalloc(nlm sums)");
     for (auto &e : ws.ev) if (!e) e.create();
 
-    nlm::Args a{};
+    nlm::GuidedArgs a{};
     a.g = film::tile_grid(w, h, kNlmTile, kNlmTile); a.r = p.window_radius; a.f = p.patch_radius;
     a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
     a.img = d_img; a.var = d_var; a.out = d_out; a.var_out = d_var_out; a.partials = ws.partials;
     const int nb = a.g.blocks;
     if (stats) ck(hipEventRecord(ws.ev[0], stream), "hipEventRecord");
-    if (debug_knob("nlm_direct", 0) != 0) {
-        hipLaunchKernelGGL(nlm::direct_kernel, dim3(nb), dim3(film::kBlock), 0, stream, a);
-    } else {
-        const size_t lds = (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
-        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+    if (guide) {
+        nlm::Guide &gd = a.gd;
+        gd.feat = d_feat; gd.fvar = d_feat_var; gd.plane = (size_t)w * h;
+        gd.groups = guide->num_groups; gd.kf2 = guide->k_f * guide->k_f; gd.alpha_f = guide->alpha_f;
+        for (int j = 0; j < guide->num_groups; j++) {
+            const GdptNlmFeatureGroup &grp = guide->groups[j];
+            gd.first[j] = grp.first_channel; gd.count[j] = grp.num_channels; gd.tau[j] = grp.tau;
+            for (int c = grp.first_channel; c < grp.first_channel + grp.num_channels; c++) gd.used |= 1u << c;
+        }
+    }
+    const nlm::Args &plain = a;       // (the unguided kernels take the argument block they always took)
+    const bool direct = debug_knob("nlm_direct", 0) != 0;
+    const size_t lds = direct ? 0 : (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
+    if (direct) {
+        if (guide) hipLaunchKernelGGL(nlm::direct_kernel<true>, dim3(nb), dim3(film::kBlock), 0, stream, a);
+        else hipLaunchKernelGGL(nlm::direct_kernel<false>, dim3(nb), dim3(film::kBlock), 0, stream, plain);
+    } else if (guide) {
+        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
            "hipFuncSetAttribute(nlm stage)");
-        hipLaunchKernelGGL(nlm::tiled_kernel, dim3(nb), dim3(film::kBlock), lds, stream, a);
+        hipLaunchKernelGGL(nlm::tiled_kernel<true>, dim3(nb), dim3(film::kBlock), lds, stream, a);
+    } else {
+        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+           "hipFuncSetAttribute(nlm stage)");
+        hipLaunchKernelGGL(nlm::tiled_kernel<false>, dim3(nb), dim3(film::kBlock), lds, stream, plain);
     }
     ck(hipGetLastError(), "nlm launch");
     if (!stats) return;
@@ -340,6 +441,30 @@ void nlm_check_params(const std::string &who, const GdptNlmParams &p) {
     if (p.reserved[0] != 0 || p.reserved[1] != 0) throw std::runtime_error(who + ": reserved must be 0");
 }
 
+void nlm_check_guide(const std::string &who, const GdptNlmGuide &g) {
+    if (g.num_channels < 0 || g.num_channels > nlm::kMaxChannels)
+        throw std::runtime_error(who + ": num_channels must be in [0, " + std::to_string(nlm::kMaxChannels) + "]");
+    if (g.num_groups < 0 || g.num_groups > nlm::kMaxGroups)
+        throw std::runtime_error(who + ": num_groups must be in [0, " + std::to_string(nlm::kMaxGroups) + "]");
+    for (int j = 0; j < g.num_groups; j++) {
+        const GdptNlmFeatureGroup &grp = g.groups[j];
+        const std::string at = who + ": groups[" + std::to_string(j) + "]";
+        if (grp.num_channels < 1) throw std::runtime_error(at + ".num_channels must be >= 1");
+        if (grp.first_channel < 0 || (long long)grp.first_channel + grp.num_channels > (long long)g.num_channels)
+            throw std::runtime_error(at + ".first_channel: the group leaves [0, num_channels)");
+        if (!std::isfinite(grp.tau) || !(grp.tau > 0)) throw std::runtime_error(at + ".tau must be finite and > 0");
+    }
+    if (!std::isfinite(g.k_f) || !(g.k_f > 0)) throw std::runtime_error(who + ": k_f must be finite and > 0");
+    if (!std::isfinite(g.alpha_f) || !(g.alpha_f >= 0)) throw std::runtime_error(who + ": alpha_f must be finite and >= 0");
+    if (g.reserved[0] != 0 || g.reserved[1] != 0) throw std::runtime_error(who + ": guide reserved must be 0");
+}
+
+void denoise_nlm_guided_launch(int w, int h, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                               const GdptNlmParams &p, const GdptNlmGuide &g, double *d_out, double *d_var_out, hipStream_t stream,
+                               GdptNlmStats *stats) {
+    denoise_nlm_launch(w, h, d_img, d_var, p, d_out, d_var_out, stream, stats, &g, d_feat, d_feat_var);
+}
+
 } // namespace gdpt
 
 namespace {
@@ -361,6 +486,22 @@ GdptNlmParams check_arguments(const std::string &who, int width, int height, con
     else gdpt_nlm_default_params(&p);
     gdpt::nlm_check_params(who, p);
     return p;
+}
+
+// ... and what the guided ones refuse beside it. Returns the guide in force.
+GdptNlmGuide check_guided_arguments(const std::string &who, const double *feat, const double *feat_var, const GdptNlmGuide *guide,
+                                    const double *out, const double *var_out) {
+    GdptNlmGuide g;
+    if (guide) g = *guide;
+    else gdpt_nlm_default_guide(&g);
+    gdpt::nlm_check_guide(who, g);
+    if (g.num_groups > 0) {
+        if (!feat) throw std::runtime_error(who + ": feat is null");
+        if (!feat_var) throw std::runtime_error(who + ": feat_var is null");
+    }
+    if (feat && (out == feat || out == feat_var)) throw std::runtime_error(who + ": out must not alias an input");
+    if (var_out && feat && (var_out == feat || var_out == feat_var)) throw std::runtime_error(who + ": var_out must not alias an input or out");
+    return g;
 }
 
 void need_a_device(const std::string &who) {
@@ -387,6 +528,52 @@ int gdpt_denoise_nlm_device(int width, int height, const double *d_img, const do
         const GdptNlmParams p = check_arguments(who, width, height, d_img, d_var, params, d_out, d_var_out);
         need_a_device(who);
         gdpt::denoise_nlm_launch(width, height, d_img, d_var, p, d_out, d_var_out, (hipStream_t)stream, stats);
+    });
+}
+
+void gdpt_nlm_default_guide(GdptNlmGuide *g) {
+    if (!g) return;
+    *g = GdptNlmGuide{};
+    g->num_channels = GDPT_FEATURE_CHANNELS; g->num_groups = 2;
+    g->groups[0] = GdptNlmFeatureGroup{0, 3, 1e-3};      // albedo
+    g->groups[1] = GdptNlmFeatureGroup{3, 3, 1e-3};      // shading normal
+    g->k_f = 0.6; g->alpha_f = 1.0;
+}
+
+int gdpt_denoise_nlm_guided_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                   const GdptNlmParams *params, const GdptNlmGuide *guide, double *d_out, double *d_var_out, void *stream,
+                                   GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm_guided_device";
+        const GdptNlmParams p = check_arguments(who, width, height, d_img, d_var, params, d_out, d_var_out);
+        const GdptNlmGuide g = check_guided_arguments(who, d_feat, d_feat_var, guide, d_out, d_var_out);
+        need_a_device(who);
+        gdpt::denoise_nlm_guided_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, g, d_out, d_var_out, (hipStream_t)stream, stats);
+    });
+}
+
+int gdpt_denoise_nlm_guided(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                            const GdptNlmParams *params, const GdptNlmGuide *guide, double *out, double *var_out, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm_guided";
+        const GdptNlmParams p = check_arguments(who, width, height, img, var, params, out, var_out);
+        const GdptNlmGuide g = check_guided_arguments(who, feat, feat_var, guide, out, var_out);
+        need_a_device(who);
+        const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
+        const size_t felems = g.num_groups > 0 ? (size_t)width * height * g.num_channels : 0, fbytes = felems * sizeof(double);
+        gdpt::DeviceBuffer<double> d_img, d_var, d_out, d_var_out, d_feat, d_feat_var;
+        d_img.alloc(elems, "hipMalloc(nlm io)"); d_var.alloc(elems, "hipMalloc(nlm io)"); d_out.alloc(elems, "hipMalloc(nlm io)");
+        if (var_out) d_var_out.alloc(elems, "hipMalloc(nlm io)");
+        d_feat.alloc(felems, "hipMalloc(nlm features)"); d_feat_var.alloc(felems, "hipMalloc(nlm features)");
+        ck(hipMemcpy(d_img, img, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        ck(hipMemcpy(d_var, var, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        if (felems) {
+            ck(hipMemcpy(d_feat, feat, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+            ck(hipMemcpy(d_feat_var, feat_var, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        }
+        gdpt::denoise_nlm_guided_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, g, d_out, d_var_out, nullptr, stats);
+        ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
     });
 }
 

@@ -504,6 +504,47 @@ int gdpt_progressive_denoise(GdptProgressive *session, const GdptNlmParams *para
     });
 }
 
+int gdpt_progressive_denoise_guided(GdptProgressive *session, const GdptNlmParams *params, const GdptNlmGuide *guide, int feature_spp, int on_device,
+                                    double *out, double *var_out, double *features, double *features_var, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_guided";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        GdptNlmParams p;
+        if (params) p = *params; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        GdptNlmGuide g;
+        if (guide) g = *guide; else gdpt_nlm_default_guide(&g);
+        gdpt::nlm_check_guide(who, g);
+        if (g.num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
+        GdptProgressive &s = *session;
+        if (feature_spp < 2 || feature_spp > s.block) throw std::runtime_error(who + ": feature_spp must be in [2, budget_spp]");
+        if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        compute_variances(s);
+        const size_t felems = (size_t)s.w * s.h * GDPT_FEATURE_CHANNELS;
+        for (auto &b : s.feat_buf) if (!b) b.alloc(felems, "hipMalloc(progressive features)");
+        // the camera rays of the session's own first samples: the window {budget_spp, 0}, on the session's stream
+        GdptRenderParams rp{};
+        rp.spp = feature_spp; rp.rng_scheme = GDPT_RNG_SAMPLE;
+        const GdptSampleWindow win{s.block, 0};
+        gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
+        double *d_out = out, *d_var_out = var_out;
+        if (!on_device) {                 // through planes of the session's on the way to host memory
+            for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+            d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+        }
+        GdptNlmStats st{};                // (asked for always: the call is blocking)
+        gdpt::denoise_nlm_guided_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, g, d_out, d_var_out, s.stream, &st);
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (!on_device) { copy_out(s, out, d_out, 0); copy_out(s, var_out, d_var_out, 0); }
+        if (features) ck(hipMemcpyAsync(features, s.feat_buf[0], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
+        if (features_var) ck(hipMemcpyAsync(features_var, s.feat_buf[1], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
+        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+        if (stats) *stats = st;
+    });
+}
+
 int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass_spp, int max_passes, GdptProgressiveStatus *status) {
     return gdpt::guarded([&]() {
         if (!session) throw std::runtime_error("gdpt_progressive_run: null session");

@@ -28,6 +28,7 @@ struct GdptProgressive {
     gdpt::DeviceBuffer<double> var[7];         // read-out scratch (5 buffers + assembled cx, cy), allocated by the first read
     gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
     gdpt::DeviceBuffer<double> nlm_buf[2];     // filtered mean and its variance on their way to host memory: allocated by the first denoise
+    gdpt::DeviceBuffer<double> feat_buf[2];    // feature planes and their variances of the guided denoise (8 W H doubles each): allocated by the first one
     gdpt::DeviceBuffer<double> partials;
     gdpt::DeviceBuffer<film::Estimate> d_est;
     gdpt::PinnedBuffer<film::Estimate> h_est;

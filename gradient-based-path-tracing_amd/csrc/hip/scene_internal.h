@@ -88,4 +88,8 @@ std::vector<std::unique_ptr<GdptScene>> upload_scenes(const GdptSceneDesc *desc,
 void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene_spp,
                         double *img, double *cx0, double *cy0, double *cx1, double *cy1,
                         hipStream_t stream, GdptRenderStats *stats, const GdptSampleWindow *window = nullptr);
+// The feature render (features.hip; include/gdpt.h: gdpt_features_render_device) on a handle, after the refusals that need no handle:
+// enqueues the kernel on `stream`, with no claim on the handle's launch scratch; waits only when `stats` is given.
+void features_launch(GdptScene *sc, const GdptRenderParams *params, const GdptSampleWindow *window, double *d_mean, double *d_var,
+                     hipStream_t stream, GdptRenderStats *stats);
 } // namespace gdpt

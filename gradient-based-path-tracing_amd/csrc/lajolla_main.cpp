@@ -37,9 +37,18 @@
 //                 scene) filtered by non-local means on its per-pixel variance (gdpt_progressive_denoise); -o receives what it
 //                 receives without the flag. --nlm-window R (0..10, default 10), --nlm-patch F (0..3, default 3), --nlm-k K (default
 //                 0.45). Needs --pass-spp: the filter is driven by the variance of the mean, and no variance exists without passes
+//                 --nlm-guide albedo,normal[,depth] lets first-hit features cap the colour weights (gdpt_progressive_denoise_guided):
+//                 one group per name, rendered with --feature-spp samples along the session's own camera rays. depth needs
+//                 --nlm-depth-tau T, a squared world-space distance (no default: the scale of depth belongs to the scene); --nlm-kf
+//                 sets k_f (default 0.6). With --nlm-guide and no --nlm-k, k is 1.0: features only ever lower a weight, so their
+//                 gain shows once the colour term is loosened. Without --nlm-guide every output file is what it was
+//   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
+//                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
+//                 Single device (not with --gpus / --devices / --sample-devices)
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
+#include <algorithm>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -63,7 +72,10 @@ int main(int argc, char *argv[]) {
     std::string denoised_file = "";
     GdptNlmParams nlm{};
     gdpt_nlm_default_params(&nlm);
-    bool nlm_option = false;
+    bool nlm_option = false, nlm_k_set = false, nlm_guide_option = false;
+    std::string features_prefix = "", nlm_guide_names = "";
+    int feature_spp = 0;
+    double nlm_depth_tau = 0.0, nlm_kf = 0.0;
     double conf_floor = 0.0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
     std::vector<int32_t> sample_devices;      // --sample-devices: a progressive group
@@ -132,7 +144,12 @@ int main(int argc, char *argv[]) {
         else if (a == "--denoised") denoised_file = next();
         else if (a == "--nlm-window") { nlm.window_radius = std::stoi(next()); nlm_option = true; }
         else if (a == "--nlm-patch") { nlm.patch_radius = std::stoi(next()); nlm_option = true; }
-        else if (a == "--nlm-k") { nlm.k = std::stod(next()); nlm_option = true; }
+        else if (a == "--nlm-k") { nlm.k = std::stod(next()); nlm_option = true; nlm_k_set = true; }
+        else if (a == "--nlm-guide") nlm_guide_names = next();
+        else if (a == "--nlm-depth-tau") { nlm_depth_tau = std::stod(next()); nlm_guide_option = true; }
+        else if (a == "--nlm-kf") { nlm_kf = std::stod(next()); nlm_guide_option = true; }
+        else if (a == "--features") features_prefix = next();
+        else if (a == "--feature-spp") { feature_spp = std::stoi(next()); if (feature_spp <= 0) { std::cerr << "--feature-spp must be > 0" << std::endl; return 2; } }
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
         else if (a == "--shift") {        // extension: "reconnect" = GDPT_SHIFT_RECONNECT (include/gdpt.h); default = the reference's offsets
             std::string v = next();
@@ -175,6 +192,37 @@ int main(int argc, char *argv[]) {
         return 2;
     }
     if (nlm_option && denoised_file.empty()) { std::cerr << "--nlm-window, --nlm-patch and --nlm-k need --denoised" << std::endl; return 2; }
+    GdptNlmGuide guide{};
+    gdpt_nlm_default_guide(&guide);
+    const bool guided = !nlm_guide_names.empty();
+    if (guided) {
+        if (denoised_file.empty()) { std::cerr << "--nlm-guide needs --denoised" << std::endl; return 2; }
+        guide.num_groups = 0;
+        bool seen[3] = {false, false, false};
+        size_t at = 0;
+        while (at <= nlm_guide_names.size()) {
+            const size_t comma = std::min(nlm_guide_names.find(',', at), nlm_guide_names.size());
+            const std::string name = nlm_guide_names.substr(at, comma - at);
+            const int which = name == "albedo" ? 0 : name == "normal" ? 1 : name == "depth" ? 2 : -1;
+            if (which < 0 || seen[which]) { std::cerr << "--nlm-guide takes albedo, normal and depth, each once, separated by commas" << std::endl; return 2; }
+            seen[which] = true;
+            if (which == 2 && !(nlm_depth_tau > 0.0)) {
+                std::cerr << "--nlm-guide depth needs --nlm-depth-tau T > 0, a squared world-space distance: the scale of depth belongs to the scene" << std::endl;
+                return 2;
+            }
+            GdptNlmFeatureGroup &grp = guide.groups[guide.num_groups++];
+            grp.first_channel = which == 2 ? 6 : 3 * which; grp.num_channels = which == 2 ? 1 : 3; grp.tau = which == 2 ? nlm_depth_tau : 1e-3;
+            at = comma + 1;
+        }
+        if (nlm_kf != 0.0) guide.k_f = nlm_kf;
+        if (!nlm_k_set) nlm.k = 1.0;
+    } else if (nlm_guide_option) { std::cerr << "--nlm-depth-tau and --nlm-kf need --nlm-guide" << std::endl; return 2; }
+    if (!features_prefix.empty() && (multi.num_devices > 0 || !sample_devices.empty())) {
+        std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
+        return 2;
+    }
+    if (feature_spp > 0 && features_prefix.empty() && !guided) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
     const bool recon_error = target_recon_error != 0.0 || !error_map_file.empty();
@@ -284,7 +332,11 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                rc = gdpt_progressive_denoise(session, &nlm, 0, filtered.data(), nullptr, &nlm_stats);
+                if (guided) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    rc = gdpt_progressive_denoise_guided(session, &nlm, &guide, feature_spp > 0 ? feature_spp : std::min(16, budget), 0, filtered.data(),
+                                                         nullptr, nullptr, nullptr, &nlm_stats);
+                } else rc = gdpt_progressive_denoise(session, &nlm, 0, filtered.data(), nullptr, &nlm_stats);
                 if (rc == 0) rc = gdpt_imwrite(denoised_file.c_str(), w, h, filtered.data());
             }
             std::string err = rc != 0 ? gdpt_last_error() : "";
@@ -302,6 +354,25 @@ int main(int argc, char *argv[]) {
         if (rc != 0) {
             std::cerr << "terminate: " << gdpt_last_error() << std::endl;
             return 134;
+        }
+        if (!features_prefix.empty()) {
+            // the camera rays of the render's own first samples: the window {spp, 0} of every pixel's stream block
+            const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+            GdptRenderParams fp{};
+            fp.spp = feature_spp > 0 ? feature_spp : std::min(16, budget); fp.rng_scheme = GDPT_RNG_SAMPLE;
+            const GdptSampleWindow win{budget, 0};
+            const size_t plane = (size_t)w * h;
+            std::vector<double> fmean(plane * GDPT_FEATURE_CHANNELS), fvar(plane * GDPT_FEATURE_CHANNELS), rgb(plane * 3);
+            GdptRenderStats fs{};
+            rc = gdpt_features_render(scene, &fp, &win, fmean.data(), fvar.data(), &fs);
+            static const char *const suffix[3] = {"_albedo.exr", "_normal.exr", "_depth.pfm"};
+            for (int k = 0; k < 3 && rc == 0; k++) {
+                for (size_t i = 0; i < plane; i++) for (int c = 0; c < 3; c++) rgb[3 * i + c] = fmean[(size_t)(k == 2 ? 6 : 3 * k + c) * plane + i];
+                rc = gdpt_imwrite((features_prefix + suffix[k]).c_str(), w, h, rgb.data());
+            }
+            if (rc != 0) { std::cerr << "terminate: " << gdpt_last_error() << std::endl; return 134; }
+            std::cout << "[gdpt] features: " << fp.spp << " samples per pixel, " << fs.rays << " rays, render " << fs.render_ms << " ms, written to "
+                      << features_prefix << "_albedo.exr, _normal.exr, _depth.pfm" << std::endl;
         }
         // the reference prints one progress line per finished tile and a final 100% line (src/progress_reporter.h:22-29)
         unsigned long long tiles = (unsigned long long)((w + 15) / 16) * ((h + 15) / 16);
@@ -334,7 +405,8 @@ int main(int argc, char *argv[]) {
             if (!denoised_file.empty())
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
-                          << ", filter_ms " << nlm_stats.filter_ms << ", written to " << denoised_file << std::endl;
+                          << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string()) << ", written to " << denoised_file
+                          << std::endl;
             if (recon_error)
                 std::cout << "[gdpt] reconstruction: error estimate " << spread.error_estimate << " from the spread of " << spread.members
                           << " members (" << spread.pixels_left_out << " pixels left out), map radius " << spread.radius << ", spread "

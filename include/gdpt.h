@@ -689,6 +689,81 @@ int gdpt_denoise_nlm(int width, int height, const double *img, const double *var
 int gdpt_progressive_denoise(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */, int on_device, double *out,
                              double *var_out /* nullable */, GdptNlmStats *stats /* nullable */);
 
+/* ---- first-hit feature buffers with per-pixel variances (not part of the reference) ----
+ * Albedo, shading normal, depth and coverage of a render's own base primary rays (Rousselle, Manzi, Zwicker, "Robust denoising using
+ * feature and colour information", Pacific Graphics 2013, section 3): outputs in their own right, and the guide of
+ * gdpt_denoise_nlm_guided below. mean, var: GDPT_FEATURE_CHANNELS planes of W*H doubles each, channel-PLANAR (plane c starts at c W H
+ * and is row-major; the guided filter reads them plane by plane), not interleaved like the films.
+ * GDPT_RNG_SAMPLE is the only scheme. Sample s of pixel (x, y) draws from stream (y W + x) stream_spp + first_sample + s (window ==
+ * NULL: stream_spp = spp, first_sample = 0), takes the stream's first two numbers (rx, ry) as the sub-pixel position and makes the
+ * camera ray of the render's own sample s: sample_primary(camera, (x + rx) / W, (y + ry) / H), with the texture footprint of a
+ * primary ray (ray-differential spread 0.25 / max(W, H)). On a hit its eight values are
+ *     0-2  albedo:   texture slot 0 of the hit's material, evaluated as a spectrum texture at the vertex (reflectance, base_color,
+ *                    the rough lobes' first reflectance); (1, 1, 1) for GDPT_MAT_DISNEY_CLEARCOAT, whose slot 0 is a scalar
+ *     3-5  normal:   the vertex's shading-frame normal, as interpolated (not flipped towards the ray)
+ *     6    depth:    |position - ray origin|
+ *     7    coverage: 1
+ * and on a miss all eight are 0. Emission and environment maps play no part. Per pixel and channel the n = spp values x_1 .. x_n are
+ * folded in sample order, i = 1 .. n:   d = x_i - mean;  mean += d / i;  M2 += d (x_i - mean);   var = M2 / (n (n - 1)), the variance
+ * of the mean (0 for n = 1). A pixel whose samples all return one value has variance exactly 0; a pixel of hits only, or of misses
+ * only, has coverage exactly 1 or 0.
+ * params (NULL: the scene's spp, the whole film): spp (<= 0: the scene's), row_begin / row_end (rows outside the band are left
+ * untouched); max_depth_override and plan_rows are ignored. Refused, with a message that names the field, before any device call:
+ * a NULL scene, mean or var (or the two aliasing); GDPT_RNG_TILE or an unknown rng_scheme; shift_mode != 0; reserved != 0; a bad row
+ * band; a window with stream_spp <= 0, first_sample < 0 or one that leaves [0, stream_spp).
+ * It is not a render route and takes none of the handle's launch scratch: the kernel reads the scene and writes mean and var only,
+ * so it is enqueued on `stream` as it is, beside whatever render of the same handle is in flight. With stats it waits for the stream
+ * (samples, rays and render_ms are filled, the rest is 0); with stats == NULL it only enqueues. No CPU fallback. */
+#define GDPT_FEATURE_CHANNELS 8   /* planes: 0-2 albedo, 3-5 shading normal, 6 depth, 7 coverage */
+int gdpt_features_render_device(GdptScene *scene, const GdptRenderParams *params /* nullable */, const GdptSampleWindow *window /* nullable */,
+                                double *d_mean, double *d_var, void *stream, GdptRenderStats *stats /* nullable */);
+/* Host pointers. Blocking. */
+int gdpt_features_render(GdptScene *scene, const GdptRenderParams *params /* nullable */, const GdptSampleWindow *window /* nullable */,
+                         double *mean, double *var, GdptRenderStats *stats /* nullable */);
+
+/* ---- the non-local-means filter guided by features (not part of the reference) ----
+ * gdpt_denoise_nlm's weights come from colour alone: detail that is small against the noise (a texture, an edge between surfaces of
+ * similar radiance, a crease) is smoothed away. Here a feature distance caps the colour weight (Rousselle, Manzi, Zwicker 2013,
+ * section 4). feat, feat_var: num_channels <= GDPT_NLM_MAX_CHANNELS planes of W*H doubles, channel-planar as above: any planar array
+ * and the variance of it, not only a feature render's. A group j names the channels C_j = [first_channel, first_channel +
+ * num_channels) that are compared together, with a floor tau_j > 0 on the variance in the denominator (a squared feature value:
+ * what counts as "the same" where the feature is noise-free).
+ * The definition extends gdpt_denoise_nlm's. A pixel is VALID if it is valid there and every channel that some group names is finite
+ * at it, with variance >= 0. For valid p and p+o, g the features and s their variances:
+ *   phi_j(p,o) = (1/|C_j|) sum_{c in C_j} [ (g_c(p) - g_c(p+o))^2 - alpha_f (s_c(p) + min(s_c(p+o), s_c(p))) ]
+ *                                          / [ k_f^2 max(tau_j, s_c(p) + s_c(p+o)) ]       (channels summed in index order)
+ *   D^f_o(p)   = max(0, max_j phi_j(p,o))                                                   (0 with no group)
+ *   w_o(p)     = exp(-max(D_o(p), D^f_o(p)))
+ * and e_o, S, C, D_o, out, var_out, the film sums and pixels_left_out are gdpt_denoise_nlm's. The feature term is a term of the pixel
+ * pair (p, p+o), not of a patch. Features only ever lower a weight: num_groups = 0, or features constant over the film with variance
+ * 0, give gdpt_denoise_nlm's result bit for bit; the gain shows once the colour term is loosened (k towards 1). */
+#define GDPT_NLM_MAX_GROUPS 4
+#define GDPT_NLM_MAX_CHANNELS 16
+typedef struct GdptNlmFeatureGroup { int32_t first_channel, num_channels; double tau; } GdptNlmFeatureGroup;
+typedef struct GdptNlmGuide { int32_t num_channels, num_groups; GdptNlmFeatureGroup groups[GDPT_NLM_MAX_GROUPS];
+                              double k_f, alpha_f; int32_t reserved[2]; } GdptNlmGuide;
+void gdpt_nlm_default_guide(GdptNlmGuide *g);   /* 8 channels; groups {0,3,1e-3} albedo, {3,3,1e-3} normal; k_f 0.6; alpha_f 1 */
+/* Device pointers on the current device. What gdpt_denoise_nlm_device refuses is refused, and, naming the field: num_channels outside
+ * [0, 16]; num_groups outside [0, 4]; a group that leaves [0, num_channels) or has fewer than 1 channel; tau <= 0 or non-finite;
+ * k_f <= 0 or non-finite; alpha_f < 0 or non-finite; non-zero reserved; NULL d_feat or d_feat_var when num_groups > 0; an output
+ * aliasing any input. guide == NULL: gdpt_nlm_default_guide. Enqueue-only with stats == NULL; scratch as gdpt_denoise_nlm_device. */
+int gdpt_denoise_nlm_guided_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                   const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                                   double *d_out, double *d_var_out /* nullable */, void *stream, GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm_guided(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                            const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                            double *out, double *var_out /* nullable */, GdptNlmStats *stats /* nullable */);
+/* The guided filter on a session's buffer 0 (as gdpt_progressive_denoise: at least 2 passes, a group's total included), guided by the
+ * features of the session's film: gdpt_features_render_device on the session's stream with feature_spp samples of the window
+ * {stream_spp = budget_spp, first_sample = 0}, the camera rays of the session's own first samples; 2 <= feature_spp <= budget_spp.
+ * guide->num_channels must be GDPT_FEATURE_CHANNELS. features, features_var (nullable): receive the 8 planes. All output pointers
+ * are host memory, or device memory with on_device != 0. Blocking. */
+int gdpt_progressive_denoise_guided(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */,
+                                    const GdptNlmGuide *guide /* NULL: defaults */, int feature_spp, int on_device, double *out,
+                                    double *var_out /* nullable */, double *features /* nullable */, double *features_var /* nullable */,
+                                    GdptNlmStats *stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
