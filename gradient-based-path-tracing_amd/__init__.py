@@ -96,6 +96,12 @@ def lib():
         L.gdpt_denoise_nlm_guided_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_guided.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, nls]
         L.gdpt_progressive_denoise_guided.argtypes = [vp, nlp, ngp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        ndp = C.POINTER(defs.GdptNlmDemod)
+        L.gdpt_nlm_default_demod.argtypes = [ndp]
+        L.gdpt_nlm_default_demod.restype = None
+        L.gdpt_denoise_nlm_demod_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm_demod.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, nls]
+        L.gdpt_progressive_denoise_demod.argtypes = [vp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
         L.gdpt_features_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp, vp,
                                                   C.POINTER(defs.GdptRenderStats)]
         L.gdpt_features_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp,
@@ -512,6 +518,29 @@ class Progressive:
                                                      C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
         return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
+    def denoise_demod(self, feature_spp, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
+        """The albedo-demodulated non-local-means filter on buffer 0 (gdpt_progressive_denoise_demod; from 2 passes on): the session
+        renders `feature_spp` samples of first-hit features along the camera rays of its own first samples, divides its mean by their
+        effective albedo, filters the quotient and multiplies the albedo back. `guide`: a GdptNlmGuide (nlm_guide(...)) over the 8
+        planes, None = NO feature term (not the default guide); `demod`: a GdptNlmDemod (nlm_demod(...)), None = the library's
+        default; `params`: the keywords of nlm_params. Returns and device-memory form as denoise_guided."""
+        p, st = nlm_params(**params), defs.GdptNlmStats()
+        g = C.byref(guide) if guide is not None else None
+        d = demod if demod is not None else nlm_demod()
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            _check(lib().gdpt_progressive_denoise_demod(self.handle, C.byref(p), g, C.byref(d), int(feature_spp), 1, opt(out_ptr), opt(var_out_ptr),
+                                                        opt(fp[0]), opt(fp[1]), C.byref(st)))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        _check(lib().gdpt_progressive_denoise_demod(self.handle, C.byref(p), g, C.byref(d), int(feature_spp), 0, C.c_void_p(out.ctypes.data),
+                                                    C.c_void_p(var_out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
+                                                    C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
+        return (out, var_out, fm, fv, st) if features else (out, var_out, st)
+
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
         <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
@@ -823,6 +852,58 @@ def denoise_nlm_guided_device(width, height, img_ptr, var_ptr, feat_ptr, feat_va
     opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
     _check(lib().gdpt_denoise_nlm_guided_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
                                                 C.byref(g), opt(out_ptr), opt(var_out_ptr), opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def nlm_demod(albedo_channel=None, coverage_channel=None, floor=None):
+    """GdptNlmDemod (include/gdpt.h): the library's defaults (gdpt_nlm_default_demod: albedo planes 0-2, coverage plane 7, floor 1e-3,
+    the layout of a feature render) with the keywords given in their places, taken literally. coverage_channel = -1: none."""
+    d = defs.GdptNlmDemod()
+    lib().gdpt_nlm_default_demod(C.byref(d))
+    if albedo_channel is not None:
+        d.albedo_channel = int(albedo_channel)
+    if coverage_channel is not None:
+        d.coverage_channel = int(coverage_channel)
+    if floor is not None:
+        d.floor = float(floor)
+    return d
+
+
+def denoise_nlm_demod(img, var, feat, feat_var, guide=None, demod=None, **params):
+    """denoise_nlm() on the albedo-demodulated mean (gdpt_denoise_nlm_demod): img / a~ is filtered and a~ multiplied back, a~ the
+    effective albedo max(floor, albedo + (1 - coverage)) taken from the planar (num_channels, H, W) arrays `feat`, `feat_var` (what
+    Scene.features() returns, or any other). `demod`: a GdptNlmDemod (nlm_demod(...)), None = the library's default; `guide`: a
+    GdptNlmGuide over the same planes, None = NO feature term (not the default guide: the albedo is already divided out). Returns
+    (HxWx3 filtered image, HxWx3 variance of it, GdptNlmStats). Pixels whose albedo or coverage is not finite are left out as well."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm_demod: img and var must be HxWx3 arrays of one shape")
+    f = np.ascontiguousarray(feat, dtype=np.float64)
+    fv = np.ascontiguousarray(feat_var, dtype=np.float64)
+    if f.ndim != 3 or f.shape != fv.shape or f.shape[1:] != a.shape[:2]:
+        raise GdptError("denoise_nlm_demod: feat and feat_var must be (num_channels, H, W) arrays of one shape")
+    d = demod if demod is not None else nlm_demod()
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = nlm_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_nlm_demod(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                        C.c_void_p(f.ctypes.data), C.c_void_p(fv.ctypes.data), int(f.shape[0]), C.byref(p),
+                                        C.byref(guide) if guide is not None else None, C.byref(d), C.c_void_p(out.ctypes.data),
+                                        C.c_void_p(var_out.ctypes.data), C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_nlm_demod_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_ptr, num_channels, out_ptr, var_out_ptr=None, guide=None,
+                             demod=None, stream=None, stats=True, params=None, **kw):
+    """denoise_nlm_demod() on device addresses (gdpt_denoise_nlm_demod_device); arguments as denoise_nlm_guided_device, with the number
+    of planes, `demod` (None = the library's default) and `guide` (None = no feature term)."""
+    p = params if params is not None else nlm_params(**kw)
+    d = demod if demod is not None else nlm_demod()
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_demod_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
+                                               C.byref(p), C.byref(guide) if guide is not None else None, C.byref(d), opt(out_ptr), opt(var_out_ptr),
+                                               opt(stream), C.byref(st) if stats else None))
     return st
 
 

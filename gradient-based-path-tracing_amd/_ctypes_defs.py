@@ -151,6 +151,10 @@ class GdptNlmGuide(C.Structure):
                 ("k_f", C.c_double), ("alpha_f", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+class GdptNlmDemod(C.Structure):
+    _fields_ = [("albedo_channel", C.c_int32), ("coverage_channel", C.c_int32), ("floor", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class GdptGroupReconParams(C.Structure):
     _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
                 ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]

@@ -18,6 +18,14 @@ void denoise_nlm_guided_launch(int w, int h, const double *d_img, const double *
                                const GdptNlmParams &p, const GdptNlmGuide &g, double *d_out, double *d_var_out, hipStream_t stream,
                                GdptNlmStats *stats);
 
+// The same for the block of the demodulated entry points (gdpt_denoise_nlm_demod*), whose planes number `num_channels`.
+void nlm_check_demod(const std::string &who, const GdptNlmDemod &d, int num_channels);
+// The demodulated filter on device pointers of the current device, every argument checked (the session's entry point); `g` nullable: no
+// feature term. Enqueued on `stream`; waits for it if `stats` is asked for.
+void denoise_nlm_demod_launch(int w, int h, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                              const GdptNlmParams &p, const GdptNlmGuide *g, const GdptNlmDemod &d, double *d_out, double *d_var_out,
+                              hipStream_t stream, GdptNlmStats *stats);
+
 // Launch geometry of both kernel forms: film::tile_grid (image_kernels.h) over tiles of kNlmTile x kNlmTile pixels. The filter's
 // scratch is kept per (device, stream), and dropped by forget_stream (device_mem.h).
 constexpr int kNlmTile = 16;

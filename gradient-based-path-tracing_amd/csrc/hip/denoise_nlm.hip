@@ -22,6 +22,11 @@
 // channels are unrolled to the caps, so every index is static) and reads those of p+o from global memory: the planes are planar, a
 // wave's read of one plane is four 128-byte rows, served from L1 / L2. The stage gets no feature planes: at (r, f) = (10, 3) it
 // already takes 108 624 of the 163 840 bytes a workgroup may declare, and 2 x 6 planes of (16 + 2r)^2 doubles would be another 124 KB.
+// And on DEMOD (gdpt_denoise_nlm_demod*): the four DEMOD = false instantiations are the kernels above as they were, argument blocks
+// included. A demodulated kernel filters u / a~, v / a~^2 for the effective albedo a~ of include/gdpt.h: load_pixel adds the albedo and
+// coverage planes to a pixel's validity and divides, so the tiled kernel's stage holds the quotients and needs no LDS of its own;
+// finish_pixel multiplies a~ back. A thread recomputes its own a~ from the planar planes there, and reloads its own original triples
+// for the colour-domain sums: (u / a~) a~ is not always u.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "image_kernels.h"
@@ -44,7 +49,7 @@ static_assert(kTile * kTile == kBlock, "one thread per tile pixel");
 static_assert((kTile + 2 * kMaxF) * (kTile + 2 * kMaxF) <= 2 * kBlock, "a thread computes at most two pair distances per offset");
 
 struct Args {
-    static constexpr bool kGuided = false;
+    static constexpr bool kGuided = false, kDemod = false;
     TileGrid g;                  // 16 x 16 tiles
     int r, f;
     double k2, alpha, eps;
@@ -65,6 +70,25 @@ struct GuidedArgs : Args {
     static constexpr bool kGuided = true;
     Guide gd;
 };
+// the divisor of a demodulated call: planes `feat`, `fvar` of `plane` doubles each; the albedo is planes albedo .. albedo + 2, the
+// coverage plane `coverage` (< 0: none)
+struct Demod {
+    const double *feat, *fvar;
+    size_t plane;
+    int albedo, coverage;
+    double floor;
+};
+struct DemodArgs : Args {
+    static constexpr bool kDemod = true;
+    Demod dm;
+};
+struct GuidedDemodArgs : GuidedArgs {
+    static constexpr bool kDemod = true;
+    Demod dm;
+};
+template <bool GUIDED, bool DEMOD>
+using ArgsOf = typename std::conditional<GUIDED, typename std::conditional<DEMOD, GuidedDemodArgs, GuidedArgs>::type,
+                                         typename std::conditional<DEMOD, DemodArgs, Args>::type>::type;
 
 // pitch of the e plane for patches of ew = 16 + 2f points a row
 __host__ __device__ inline int e_pitch(int f) { return f == 0 ? kTile : 48; }
@@ -116,11 +140,48 @@ struct Sums {
     double var_in = 0.0, sq_in = 0.0, var_out = 0.0, sq_out = 0.0, left_out = 0.0;
 };
 
-// the pixel's outputs and its terms of the film sums; u, v: its valid input triples
+// the effective albedo a~ of pixel p (film index y w + x); returns whether its albedo and coverage values are valid
+__device__ __forceinline__ bool effective_albedo(const Demod &dm, size_t p, double al[3]) {
+    bool ok = true;
+    double miss = 0.0;               // 1 - cov; without a coverage plane cov = 1
+    if (dm.coverage >= 0) {
+        const double cov = dm.feat[dm.coverage * dm.plane + p], sc = dm.fvar[dm.coverage * dm.plane + p];
+        ok = isfinite(cov) && isfinite(sc) && sc >= 0.0;
+        miss = 1.0 - cov;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        const double g = dm.feat[(dm.albedo + c) * dm.plane + p], sg = dm.fvar[(dm.albedo + c) * dm.plane + p];
+        ok = ok && isfinite(g) && isfinite(sg) && sg >= 0.0;
+        al[c] = fmax(dm.floor, g + miss);
+    }
+    return ok;
+}
+
+// the pixel's outputs and its terms of the film sums; u, v: its valid input triples (what load_pixel gave). A demodulated kernel
+// multiplies the pixel's own a~ back and takes the sums' input terms from the original triples in global memory.
 template <class A>
 __device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
     double o[3], vo[3];
     const double w2 = acc.wsum * acc.wsum;
+    if constexpr (A::kDemod) {
+        double al[3], uo[3], vi[3];
+        effective_albedo(a.dm, i / 3, al);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double oc = acc.num[c] / acc.wsum, voc = acc.vnum[c] / w2, al2 = al[c] * al[c];
+            o[c] = oc * al[c];
+            vo[c] = voc * al2;
+            a.out[i + c] = o[c];
+            if (a.var_out) a.var_out[i + c] = vo[c];
+            uo[c] = a.img[i + c]; vi[c] = a.var[i + c];
+        }
+        s.var_in += (vi[0] + vi[1]) + vi[2];
+        s.sq_in += (uo[0] * uo[0] + uo[1] * uo[1]) + uo[2] * uo[2];
+        s.var_out += (vo[0] + vo[1]) + vo[2];
+        s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+        return;
+    }
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         o[c] = acc.num[c] / acc.wsum;
@@ -166,7 +227,8 @@ __device__ __forceinline__ bool valid_features(const Guide &gd, size_t i) {
     return ok;
 }
 
-// the triples of film pixel (x, y), which is inside the film; returns whether it is valid
+// the triples of film pixel (x, y), which is inside the film; returns whether it is valid. A demodulated kernel gets the quotients
+// u / a~, v / a~^2 of a valid pixel, and the input bits of an invalid one.
 template <class A>
 __device__ __forceinline__ bool load_pixel(const A &a, int x, int y, double u[3], double v[3]) {
     const size_t i = ((size_t)y * a.g.w + x) * 3;
@@ -174,6 +236,19 @@ __device__ __forceinline__ bool load_pixel(const A &a, int x, int y, double u[3]
     for (int c = 0; c < 3; c++) { u[c] = a.img[i + c]; v[c] = a.var[i + c]; }
     bool ok = valid_triples(u, v);
     if constexpr (A::kGuided) ok = ok && valid_features(a.gd, (size_t)y * a.g.w + x);
+    if constexpr (A::kDemod) {
+        double al[3];
+        const bool oka = effective_albedo(a.dm, (size_t)y * a.g.w + x, al);
+        ok = ok && oka;
+        if (ok) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                const double al2 = al[c] * al[c];
+                u[c] = u[c] / al[c];
+                v[c] = v[c] / al2;
+            }
+        }
+    }
     return ok;
 }
 
@@ -208,8 +283,8 @@ struct OwnFeatures {
     }
 };
 
-template <bool GUIDED>
-__global__ __launch_bounds__(kBlock) void direct_kernel(typename std::conditional<GUIDED, GuidedArgs, Args>::type a) {
+template <bool GUIDED, bool DEMOD>
+__global__ __launch_bounds__(kBlock) void direct_kernel(ArgsOf<GUIDED, DEMOD> a) {
     __shared__ double red[kBlock / 64];
     const int r = a.r, f = a.f;
     Sums s;
@@ -249,8 +324,8 @@ __global__ __launch_bounds__(kBlock) void direct_kernel(typename std::conditiona
     leave_partials(a, s, red);
 }
 
-template <bool GUIDED>
-__global__ __launch_bounds__(kBlock) void tiled_kernel(typename std::conditional<GUIDED, GuidedArgs, Args>::type a) {
+template <bool GUIDED, bool DEMOD>
+__global__ __launch_bounds__(kBlock) void tiled_kernel(ArgsOf<GUIDED, DEMOD> a) {
     extern __shared__ double lds[];
     __shared__ double red[kBlock / 64];
     const int r = a.r, f = a.f, halo = r + f;
@@ -364,11 +439,25 @@ struct NlmWorkspace {
 // goes with forget_stream (device_mem.h)
 PerStream<NlmWorkspace> &g_workspaces = *new PerStream<NlmWorkspace>();
 
+// one form of one instantiation, enqueued on `stream`
+template <bool GUIDED, bool DEMOD>
+void launch_form(const nlm::ArgsOf<GUIDED, DEMOD> &a, bool direct, hipStream_t stream) {
+    const int nb = a.g.blocks;
+    if (direct) {
+        hipLaunchKernelGGL((nlm::direct_kernel<GUIDED, DEMOD>), dim3(nb), dim3(film::kBlock), 0, stream, a);
+        return;
+    }
+    const size_t lds = (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
+    ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel<GUIDED, DEMOD>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
+       "hipFuncSetAttribute(nlm stage)");
+    hipLaunchKernelGGL((nlm::tiled_kernel<GUIDED, DEMOD>), dim3(nb), dim3(film::kBlock), lds, stream, a);
+}
+
 // Device pointers on the current device; the arguments have been checked. Enqueued on `stream`; waits for it if `stats` is asked for.
-// `guide` (nullable): the guided kernels, on `d_feat`, `d_feat_var`.
+// `guide` (nullable): the guided kernels, on `d_feat`, `d_feat_var`. `demod` (nullable): the demodulated kernels, on the same planes.
 void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, const GdptNlmParams &p, double *d_out, double *d_var_out,
                         hipStream_t stream, GdptNlmStats *stats, const GdptNlmGuide *guide = nullptr, const double *d_feat = nullptr,
-                        const double *d_feat_var = nullptr) {
+                        const double *d_feat_var = nullptr, const GdptNlmDemod *demod = nullptr) {
     int dev = 0;
     ck(hipGetDevice(&dev), "hipGetDevice");
     NlmWorkspace &ws = g_workspaces.get(dev, stream);
@@ -396,19 +485,19 @@ void denoise_nlm_launch(int w, int h, const double *d_img, const double *d_var, 
     }
     const nlm::Args &plain = a;       // (the unguided kernels take the argument block they always took)
     const bool direct = debug_knob("nlm_direct", 0) != 0;
-    const size_t lds = direct ? 0 : (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
-    if (direct) {
-        if (guide) hipLaunchKernelGGL(nlm::direct_kernel<true>, dim3(nb), dim3(film::kBlock), 0, stream, a);
-        else hipLaunchKernelGGL(nlm::direct_kernel<false>, dim3(nb), dim3(film::kBlock), 0, stream, plain);
-    } else if (guide) {
-        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-           "hipFuncSetAttribute(nlm stage)");
-        hipLaunchKernelGGL(nlm::tiled_kernel<true>, dim3(nb), dim3(film::kBlock), lds, stream, a);
-    } else {
-        ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlm::tiled_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-           "hipFuncSetAttribute(nlm stage)");
-        hipLaunchKernelGGL(nlm::tiled_kernel<false>, dim3(nb), dim3(film::kBlock), lds, stream, plain);
-    }
+    if (demod) {
+        const nlm::Demod dm{d_feat, d_feat_var, (size_t)w * h, demod->albedo_channel, demod->coverage_channel, demod->floor};
+        if (guide) {
+            nlm::GuidedDemodArgs ad{};
+            static_cast<nlm::GuidedArgs &>(ad) = a; ad.dm = dm;
+            launch_form<true, true>(ad, direct, stream);
+        } else {
+            nlm::DemodArgs ad{};
+            static_cast<nlm::Args &>(ad) = plain; ad.dm = dm;
+            launch_form<false, true>(ad, direct, stream);
+        }
+    } else if (guide) launch_form<true, false>(a, direct, stream);
+    else launch_form<false, false>(plain, direct, stream);
     ck(hipGetLastError(), "nlm launch");
     if (!stats) return;
     film::launch_finish(nb, ws.partials, ws.d_est, stream);
@@ -465,6 +554,25 @@ void denoise_nlm_guided_launch(int w, int h, const double *d_img, const double *
     denoise_nlm_launch(w, h, d_img, d_var, p, d_out, d_var_out, stream, stats, &g, d_feat, d_feat_var);
 }
 
+void nlm_check_demod(const std::string &who, const GdptNlmDemod &d, int num_channels) {
+    if (num_channels < 0 || num_channels > nlm::kMaxChannels)
+        throw std::runtime_error(who + ": num_channels must be in [0, " + std::to_string(nlm::kMaxChannels) + "]");
+    if (d.albedo_channel < 0 || d.albedo_channel > num_channels - 3)
+        throw std::runtime_error(who + ": albedo_channel must be in [0, num_channels - 3]");
+    if (d.coverage_channel < -1 || d.coverage_channel >= num_channels)
+        throw std::runtime_error(who + ": coverage_channel must be in [-1, num_channels)");
+    if (d.coverage_channel >= d.albedo_channel && d.coverage_channel < d.albedo_channel + 3)
+        throw std::runtime_error(who + ": coverage_channel lies inside the albedo triple");
+    if (!std::isfinite(d.floor) || !(d.floor > 0)) throw std::runtime_error(who + ": floor must be finite and > 0");
+    if (d.reserved[0] != 0 || d.reserved[1] != 0) throw std::runtime_error(who + ": demod reserved must be 0");
+}
+
+void denoise_nlm_demod_launch(int w, int h, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                              const GdptNlmParams &p, const GdptNlmGuide *g, const GdptNlmDemod &d, double *d_out, double *d_var_out,
+                              hipStream_t stream, GdptNlmStats *stats) {
+    denoise_nlm_launch(w, h, d_img, d_var, p, d_out, d_var_out, stream, stats, g, d_feat, d_feat_var, &d);
+}
+
 } // namespace gdpt
 
 namespace {
@@ -502,6 +610,24 @@ GdptNlmGuide check_guided_arguments(const std::string &who, const double *feat, 
     if (feat && (out == feat || out == feat_var)) throw std::runtime_error(who + ": out must not alias an input");
     if (var_out && feat && (var_out == feat || var_out == feat_var)) throw std::runtime_error(who + ": var_out must not alias an input or out");
     return g;
+}
+
+// ... and the demodulated ones: the guide (`guided`: whether there is one) and the block in force
+GdptNlmDemod check_demod_arguments(const std::string &who, const double *feat, const double *feat_var, int num_channels, const GdptNlmGuide *guide,
+                                   const GdptNlmDemod *demod, const double *out, const double *var_out) {
+    if (guide) {
+        gdpt::nlm_check_guide(who, *guide);
+        if (guide->num_channels != num_channels) throw std::runtime_error(who + ": guide num_channels must equal num_channels");
+    }
+    GdptNlmDemod d;
+    if (demod) d = *demod;
+    else gdpt_nlm_default_demod(&d);
+    gdpt::nlm_check_demod(who, d, num_channels);
+    if (!feat) throw std::runtime_error(who + ": feat is null");
+    if (!feat_var) throw std::runtime_error(who + ": feat_var is null");
+    if (out == feat || out == feat_var) throw std::runtime_error(who + ": out must not alias an input");
+    if (var_out && (var_out == feat || var_out == feat_var)) throw std::runtime_error(who + ": var_out must not alias an input or out");
+    return d;
 }
 
 void need_a_device(const std::string &who) {
@@ -572,6 +698,48 @@ int gdpt_denoise_nlm_guided(int width, int height, const double *img, const doub
             ck(hipMemcpy(d_feat_var, feat_var, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
         }
         gdpt::denoise_nlm_guided_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, g, d_out, d_var_out, nullptr, stats);
+        ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+    });
+}
+
+void gdpt_nlm_default_demod(GdptNlmDemod *d) {
+    if (!d) return;
+    *d = GdptNlmDemod{};
+    d->albedo_channel = 0; d->coverage_channel = GDPT_FEATURE_CHANNELS - 1; d->floor = 1e-3;
+}
+
+int gdpt_denoise_nlm_demod_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                  int num_channels, const GdptNlmParams *params, const GdptNlmGuide *guide, const GdptNlmDemod *demod, double *d_out,
+                                  double *d_var_out, void *stream, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm_demod_device";
+        const GdptNlmParams p = check_arguments(who, width, height, d_img, d_var, params, d_out, d_var_out);
+        const GdptNlmDemod d = check_demod_arguments(who, d_feat, d_feat_var, num_channels, guide, demod, d_out, d_var_out);
+        need_a_device(who);
+        gdpt::denoise_nlm_demod_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, guide, d, d_out, d_var_out, (hipStream_t)stream, stats);
+    });
+}
+
+int gdpt_denoise_nlm_demod(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var, int num_channels,
+                           const GdptNlmParams *params, const GdptNlmGuide *guide, const GdptNlmDemod *demod, double *out, double *var_out,
+                           GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_denoise_nlm_demod";
+        const GdptNlmParams p = check_arguments(who, width, height, img, var, params, out, var_out);
+        const GdptNlmDemod d = check_demod_arguments(who, feat, feat_var, num_channels, guide, demod, out, var_out);
+        need_a_device(who);
+        const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
+        const size_t felems = (size_t)width * height * num_channels, fbytes = felems * sizeof(double);
+        gdpt::DeviceBuffer<double> d_img, d_var, d_out, d_var_out, d_feat, d_feat_var;
+        d_img.alloc(elems, "hipMalloc(nlm io)"); d_var.alloc(elems, "hipMalloc(nlm io)"); d_out.alloc(elems, "hipMalloc(nlm io)");
+        if (var_out) d_var_out.alloc(elems, "hipMalloc(nlm io)");
+        d_feat.alloc(felems, "hipMalloc(nlm features)"); d_feat_var.alloc(felems, "hipMalloc(nlm features)");
+        ck(hipMemcpy(d_img, img, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        ck(hipMemcpy(d_var, var, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        ck(hipMemcpy(d_feat, feat, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        ck(hipMemcpy(d_feat_var, feat_var, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
+        gdpt::denoise_nlm_demod_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, guide, d, d_out, d_var_out, nullptr, stats);
         ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
         if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
     });

@@ -385,6 +385,38 @@ void reconstruct_weighted(GdptProgressive &s, double dataCost, const GdptWeighte
 
 } // namespace prg
 
+// What the filters that read the session's own features share (gdpt_progressive_denoise_guided, gdpt_progressive_denoise_demod; the
+// parameter blocks have been checked): the variances of buffer 0, the feature render on the session's stream, `filter(s, d_out,
+// d_var_out, stats)` on it, and the copies out. Blocking.
+template <class Filter>
+static void filter_with_features(const std::string &who, GdptProgressive &s, int feature_spp, int on_device, double *out, double *var_out,
+                                 double *features, double *features_var, GdptNlmStats *stats, Filter filter) {
+    if (feature_spp < 2 || feature_spp > s.block) throw std::runtime_error(who + ": feature_spp must be in [2, budget_spp]");
+    if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+    ck(hipSetDevice(s.scene->device), "hipSetDevice");
+    compute_variances(s);
+    const size_t felems = (size_t)s.w * s.h * GDPT_FEATURE_CHANNELS;
+    for (auto &b : s.feat_buf) if (!b) b.alloc(felems, "hipMalloc(progressive features)");
+    // the camera rays of the session's own first samples: the window {budget_spp, 0}, on the session's stream
+    GdptRenderParams rp{};
+    rp.spp = feature_spp; rp.rng_scheme = GDPT_RNG_SAMPLE;
+    const GdptSampleWindow win{s.block, 0};
+    gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
+    double *d_out = out, *d_var_out = var_out;
+    if (!on_device) {                 // through planes of the session's on the way to host memory
+        for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+        d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+    }
+    GdptNlmStats st{};                // (asked for always: the call is blocking)
+    filter(s, d_out, d_var_out, &st);
+    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (!on_device) { copy_out(s, out, d_out, 0); copy_out(s, var_out, d_var_out, 0); }
+    if (features) ck(hipMemcpyAsync(features, s.feat_buf[0], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
+    if (features_var) ck(hipMemcpyAsync(features_var, s.feat_buf[1], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
+    ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+    if (stats) *stats = st;
+}
+
 extern "C" {
 
 int gdpt_progressive_create(GdptScene *scene, const GdptProgressiveConfig *config, void *stream, GdptProgressive **out) {
@@ -517,31 +549,34 @@ int gdpt_progressive_denoise_guided(GdptProgressive *session, const GdptNlmParam
         if (guide) g = *guide; else gdpt_nlm_default_guide(&g);
         gdpt::nlm_check_guide(who, g);
         if (g.num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
-        GdptProgressive &s = *session;
-        if (feature_spp < 2 || feature_spp > s.block) throw std::runtime_error(who + ": feature_spp must be in [2, budget_spp]");
-        if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
-        ck(hipSetDevice(s.scene->device), "hipSetDevice");
-        compute_variances(s);
-        const size_t felems = (size_t)s.w * s.h * GDPT_FEATURE_CHANNELS;
-        for (auto &b : s.feat_buf) if (!b) b.alloc(felems, "hipMalloc(progressive features)");
-        // the camera rays of the session's own first samples: the window {budget_spp, 0}, on the session's stream
-        GdptRenderParams rp{};
-        rp.spp = feature_spp; rp.rng_scheme = GDPT_RNG_SAMPLE;
-        const GdptSampleWindow win{s.block, 0};
-        gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
-        double *d_out = out, *d_var_out = var_out;
-        if (!on_device) {                 // through planes of the session's on the way to host memory
-            for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
-            d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+        filter_with_features(who, *session, feature_spp, on_device, out, var_out, features, features_var, stats,
+                             [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
+                                 gdpt::denoise_nlm_guided_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, g, d_out, d_var_out, s.stream, st);
+                             });
+    });
+}
+
+int gdpt_progressive_denoise_demod(GdptProgressive *session, const GdptNlmParams *params, const GdptNlmGuide *guide, const GdptNlmDemod *demod,
+                                   int feature_spp, int on_device, double *out, double *var_out, double *features, double *features_var,
+                                   GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_demod";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        GdptNlmParams p;
+        if (params) p = *params; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        if (guide) {                      // (NULL: no feature term)
+            gdpt::nlm_check_guide(who, *guide);
+            if (guide->num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
         }
-        GdptNlmStats st{};                // (asked for always: the call is blocking)
-        gdpt::denoise_nlm_guided_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, g, d_out, d_var_out, s.stream, &st);
-        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-        if (!on_device) { copy_out(s, out, d_out, 0); copy_out(s, var_out, d_var_out, 0); }
-        if (features) ck(hipMemcpyAsync(features, s.feat_buf[0], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
-        if (features_var) ck(hipMemcpyAsync(features_var, s.feat_buf[1], felems * sizeof(double), kind, s.stream), "hipMemcpyAsync(progressive features)");
-        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
-        if (stats) *stats = st;
+        GdptNlmDemod d;
+        if (demod) d = *demod; else gdpt_nlm_default_demod(&d);
+        gdpt::nlm_check_demod(who, d, GDPT_FEATURE_CHANNELS);
+        filter_with_features(who, *session, feature_spp, on_device, out, var_out, features, features_var, stats,
+                             [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
+                                 gdpt::denoise_nlm_demod_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, guide, d, d_out, d_var_out, s.stream, st);
+                             });
     });
 }
 

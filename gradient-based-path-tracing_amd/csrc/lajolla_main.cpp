@@ -42,6 +42,11 @@
 //                 --nlm-depth-tau T, a squared world-space distance (no default: the scale of depth belongs to the scene); --nlm-kf
 //                 sets k_f (default 0.6). With --nlm-guide and no --nlm-k, k is 1.0: features only ever lower a weight, so their
 //                 gain shows once the colour term is loosened. Without --nlm-guide every output file is what it was
+//                 --nlm-demodulate filters the illumination, not the colour (gdpt_progressive_denoise_demod): the mean is divided by
+//                 the first-hit albedo (rendered with --feature-spp samples, coverage counted in), the quotient is filtered and the
+//                 albedo multiplied back; --nlm-albedo-floor X is the least divisor (default 1e-3). It combines with --nlm-guide
+//                 normal[,depth], not with a guide that names albedo: the albedo is already divided out, so an albedo group only
+//                 takes samples away. Without --nlm-demodulate every output file is what it was
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -72,7 +77,8 @@ int main(int argc, char *argv[]) {
     std::string denoised_file = "";
     GdptNlmParams nlm{};
     gdpt_nlm_default_params(&nlm);
-    bool nlm_option = false, nlm_k_set = false, nlm_guide_option = false;
+    bool nlm_option = false, nlm_k_set = false, nlm_guide_option = false, nlm_demodulate = false;
+    double nlm_albedo_floor = 0.0;
     std::string features_prefix = "", nlm_guide_names = "";
     int feature_spp = 0;
     double nlm_depth_tau = 0.0, nlm_kf = 0.0;
@@ -148,6 +154,8 @@ int main(int argc, char *argv[]) {
         else if (a == "--nlm-guide") nlm_guide_names = next();
         else if (a == "--nlm-depth-tau") { nlm_depth_tau = std::stod(next()); nlm_guide_option = true; }
         else if (a == "--nlm-kf") { nlm_kf = std::stod(next()); nlm_guide_option = true; }
+        else if (a == "--nlm-demodulate") nlm_demodulate = true;
+        else if (a == "--nlm-albedo-floor") nlm_albedo_floor = std::stod(next());
         else if (a == "--features") features_prefix = next();
         else if (a == "--feature-spp") { feature_spp = std::stoi(next()); if (feature_spp <= 0) { std::cerr << "--feature-spp must be > 0" << std::endl; return 2; } }
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
@@ -217,11 +225,26 @@ int main(int argc, char *argv[]) {
         if (nlm_kf != 0.0) guide.k_f = nlm_kf;
         if (!nlm_k_set) nlm.k = 1.0;
     } else if (nlm_guide_option) { std::cerr << "--nlm-depth-tau and --nlm-kf need --nlm-guide" << std::endl; return 2; }
+    GdptNlmDemod demod{};
+    gdpt_nlm_default_demod(&demod);
+    if (nlm_demodulate) {
+        if (denoised_file.empty()) { std::cerr << "--nlm-demodulate needs --denoised" << std::endl; return 2; }
+        for (int j = 0; j < (guided ? guide.num_groups : 0); j++)
+            if (guide.groups[j].first_channel == 0) {
+                std::cerr << "--nlm-demodulate is not combined with --nlm-guide albedo: the albedo is already divided out of what is filtered, so an albedo group "
+                             "only takes samples away (use --nlm-guide normal[,depth])" << std::endl;
+                return 2;
+            }
+        if (nlm_albedo_floor != 0.0) {
+            if (!(nlm_albedo_floor > 0.0)) { std::cerr << "--nlm-albedo-floor must be > 0" << std::endl; return 2; }
+            demod.floor = nlm_albedo_floor;
+        }
+    } else if (nlm_albedo_floor != 0.0) { std::cerr << "--nlm-albedo-floor needs --nlm-demodulate" << std::endl; return 2; }
     if (!features_prefix.empty() && (multi.num_devices > 0 || !sample_devices.empty())) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
     }
-    if (feature_spp > 0 && features_prefix.empty() && !guided) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
     if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
@@ -332,7 +355,11 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                if (guided) {
+                if (nlm_demodulate) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    rc = gdpt_progressive_denoise_demod(session, &nlm, guided ? &guide : nullptr, &demod, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
+                                                        filtered.data(), nullptr, nullptr, nullptr, &nlm_stats);
+                } else if (guided) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     rc = gdpt_progressive_denoise_guided(session, &nlm, &guide, feature_spp > 0 ? feature_spp : std::min(16, budget), 0, filtered.data(),
                                                          nullptr, nullptr, nullptr, &nlm_stats);
@@ -405,7 +432,8 @@ int main(int argc, char *argv[]) {
             if (!denoised_file.empty())
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
-                          << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string()) << ", written to " << denoised_file
+                          << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "") << ", written to "
+                          << denoised_file
                           << std::endl;
             if (recon_error)
                 std::cout << "[gdpt] reconstruction: error estimate " << spread.error_estimate << " from the spread of " << spread.members

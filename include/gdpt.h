@@ -764,6 +764,54 @@ int gdpt_progressive_denoise_guided(GdptProgressive *session, const GdptNlmParam
                                     double *var_out /* nullable */, double *features /* nullable */, double *features_var /* nullable */,
                                     GdptNlmStats *stats /* nullable */);
 
+/* ---- the non-local-means filter on the albedo-demodulated mean (not part of the reference) ----
+ * The guided filter keeps a texture only by lowering weights across albedo differences: exactly where a surface is textured fewer
+ * pixels are averaged and more noise stays. Here the illumination is filtered, not the colour: the mean is divided by the first-hit
+ * albedo, the quotient is filtered, and the albedo is multiplied back. The texture is carried by a nearly noise-free buffer and is
+ * restored exactly, and pixels on either side of a texel edge average each other freely. Inputs as gdpt_denoise_nlm_guided (img, var
+ * interleaved; feat, feat_var channel-planar, num_channels planes) and a block GdptNlmDemod: the albedo is planes albedo_channel ..
+ * albedo_channel + 2, the coverage plane coverage_channel (-1: none, cov = 1 everywhere). The EFFECTIVE ALBEDO of channel c = 0..2 is
+ *   a~_c(p) = max(floor, a_c(p) + (1 - cov(p)))
+ * (a feature render's albedo mean already averages zeros for misses: a background pixel gets a~ = 1, an edge pixel something in
+ * between). The albedo's own variance is NOT used: the variance planes of the albedo and of the coverage are read for validity only.
+ * A pixel is VALID if it is valid for the guided filter (for gdpt_denoise_nlm when there is no guide), its three albedo values are
+ * finite with variances finite and >= 0, and, with a coverage channel, its coverage is finite with variance finite and >= 0.
+ *   1. u'_c = u_c / a~_c,   v'_c = v_c / (a~_c a~_c)                          (in exactly these operations)
+ *   2. O, VO = the definition of gdpt_denoise_nlm (no guide) or gdpt_denoise_nlm_guided on (u', v'); features and groups untouched
+ *   3. out_c = O_c a~_c,    var_out_c = VO_c (a~_c a~_c)
+ * An invalid pixel keeps its input bits and is counted, as there. The film sums stay in the colour domain: sum_var_in and sum_sq_in
+ * are sums of the original v and u (gdpt_denoise_nlm's, bit for bit, when the valid sets agree), sum_var_out and sum_sq_out are sums
+ * of the remodulated outputs; error_out keeps its meaning and its weakness. r = 0 returns (u / a~) a~, which is not always the input
+ * bits. Exact: albedo 1 with coverage 1, or albedo 0 with coverage 0, give the undemodulated result bit for bit; multiplying img and
+ * the albedo planes by a per-pixel power of two m and var by m^2 (nothing at the floor, coverage 1) multiplies out by m and var_out
+ * by m^2, bit for bit. */
+typedef struct GdptNlmDemod { int32_t albedo_channel, coverage_channel; double floor; int32_t reserved[2]; } GdptNlmDemod;
+void gdpt_nlm_default_demod(GdptNlmDemod *d);   /* {0, 7, 1e-3, {0, 0}}: the layout of a feature render */
+/* Device pointers on the current device. guide == NULL here means NO feature term (in the guided entries NULL is the default guide):
+ * on the 15 % albedo checker of tests/nlm_guided_ref.py demodulating and also guiding by albedo measured 0.70 - 0.75 of the unfiltered
+ * RMSE at k = 0.45 against 0.59 - 0.66 for demodulating alone; the albedo is already divided out, so the guide only takes samples
+ * away. A non-NULL guide must have guide->num_channels == num_channels. demod == NULL: gdpt_nlm_default_demod. What
+ * gdpt_denoise_nlm_guided_device refuses is refused, and, naming the field: num_channels outside [0, 16]; albedo_channel outside
+ * [0, num_channels - 3]; coverage_channel outside [-1, num_channels) or inside the albedo triple; a non-finite floor or floor <= 0;
+ * non-zero reserved; NULL d_feat or d_feat_var. Enqueue-only with stats == NULL; scratch as gdpt_denoise_nlm_device. No CPU fallback. */
+int gdpt_denoise_nlm_demod_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                  int num_channels, const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: none */,
+                                  const GdptNlmDemod *demod /* NULL: defaults */, double *d_out, double *d_var_out /* nullable */, void *stream,
+                                  GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm_demod(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                           int num_channels, const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: none */,
+                           const GdptNlmDemod *demod /* NULL: defaults */, double *out, double *var_out /* nullable */,
+                           GdptNlmStats *stats /* nullable */);
+/* The demodulated filter on a session's buffer 0, built as gdpt_progressive_denoise_guided: the session renders its features on its
+ * stream (feature_spp samples of the window {budget_spp, 0}; 2 <= feature_spp <= budget_spp) and divides by their albedo; at least 2
+ * passes; Path, the primal of GradPath, a group's total. The planes are a feature render's: a guide must have num_channels ==
+ * GDPT_FEATURE_CHANNELS, and demod's channels lie within them. Blocking. */
+int gdpt_progressive_denoise_demod(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */,
+                                   const GdptNlmGuide *guide /* NULL: none */, const GdptNlmDemod *demod /* NULL: defaults */, int feature_spp,
+                                   int on_device, double *out, double *var_out /* nullable */, double *features /* nullable */,
+                                   double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
