@@ -102,6 +102,12 @@ def lib():
         L.gdpt_denoise_nlm_demod_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_demod.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, nls]
         L.gdpt_progressive_denoise_demod.argtypes = [vp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        vsp, vss = C.POINTER(defs.GdptVarSmoothParams), C.POINTER(defs.GdptVarSmoothStats)
+        L.gdpt_var_smooth_default_params.argtypes = [vsp]
+        L.gdpt_var_smooth_default_params.restype = None
+        L.gdpt_variance_smooth_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vp, vss]
+        L.gdpt_variance_smooth.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vss]
+        L.gdpt_progressive_denoise_smoothed.argtypes = [vp, C.c_int, vsp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, vp, nls, vss]
         L.gdpt_features_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp, vp,
                                                   C.POINTER(defs.GdptRenderStats)]
         L.gdpt_features_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp,
@@ -541,6 +547,37 @@ class Progressive:
                                                     C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
         return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
+    def denoise_smoothed(self, kind="plain", radius=None, feature_spp=0, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None,
+                         smoothed_var_ptr=None, features_ptrs=None, **params):
+        """One of the three filters above on the SMOOTHED variance of buffer 0 (gdpt_progressive_denoise_smoothed; from 2 passes on):
+        the session replaces its variance with the box mean over a (2 radius + 1)^2 window (variance_smooth; `radius` None = the
+        library's default, 2) and runs denoise (`kind` "plain"), denoise_guided ("guided") or denoise_demod ("demod") on it; for
+        "demod" the mean is taken in the albedo-normalised domain, with the filter's own `demod` block. `guide`, `demod`,
+        `feature_spp`, `params` as those three take them ("plain" takes none of the first three). Returns (HxWx3 filtered mean, HxWx3
+        variance of it, HxWx3 smoothed variance, GdptNlmStats, GdptVarSmoothStats), with `features=True` the two (8, H, W) feature
+        arrays before the stats; with `out_ptr` (and `var_out_ptr`, `smoothed_var_ptr`, `features_ptrs` = 2 device addresses)
+        everything stays in device memory and the two stats alone are returned. The variance and the stats of the filter are those
+        of the smoothed variance."""
+        kinds = {"plain": defs.DENOISE_PLAIN, "guided": defs.DENOISE_GUIDED, "demod": defs.DENOISE_DEMOD}
+        if kind not in kinds:
+            raise GdptError('denoise_smoothed: kind must be "plain", "guided" or "demod"')
+        sp, p, st, sst = var_smooth_params(radius), nlm_params(**params), defs.GdptNlmStats(), defs.GdptVarSmoothStats()
+        g = C.byref(guide) if guide is not None else None
+        d = C.byref(demod) if demod is not None else None
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        call = lambda *tail: _check(lib().gdpt_progressive_denoise_smoothed(self.handle, kinds[kind], C.byref(sp), C.byref(p), g, d,      # noqa: E731
+                                                                            int(feature_spp), *tail, C.byref(st), C.byref(sst)))
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            call(1, opt(out_ptr), opt(var_out_ptr), opt(smoothed_var_ptr), opt(fp[0]), opt(fp[1]))
+            return st, sst
+        out, var_out, sm = (np.empty(self.shape, dtype=np.float64) for _ in range(3))
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        call(0, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.c_void_p(sm.ctypes.data),
+             C.c_void_p(fm.ctypes.data) if features else None, C.c_void_p(fv.ctypes.data) if features else None)
+        return (out, var_out, sm, fm, fv, st, sst) if features else (out, var_out, sm, st, sst)
+
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
         <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
@@ -904,6 +941,59 @@ def denoise_nlm_demod_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var
     _check(lib().gdpt_denoise_nlm_demod_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
                                                C.byref(p), C.byref(guide) if guide is not None else None, C.byref(d), opt(out_ptr), opt(var_out_ptr),
                                                opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def var_smooth_params(radius=None):
+    """GdptVarSmoothParams (include/gdpt.h): the library's default (gdpt_var_smooth_default_params: radius 2) with the keyword given
+    in its place, taken literally."""
+    p = defs.GdptVarSmoothParams()
+    lib().gdpt_var_smooth_default_params(C.byref(p))
+    if radius is not None:
+        p.radius = int(radius)
+    return p
+
+
+def variance_smooth(img, var, feat=None, feat_var=None, demod=None, params=None, radius=None):
+    """The box mean of the variance of a mean over the valid pixels of a (2 radius + 1)^2 window on the GPU (gdpt_variance_smooth):
+    what the non-local-means filters are then run on in the place of `var`. `img`, `var`: HxWx3 float64. With the planar
+    (num_channels, H, W) arrays `feat`, `feat_var` the mean is taken of var / a~^2 and a~^2 multiplied back, a~ the effective albedo of
+    `demod` (a GdptNlmDemod, nlm_demod(...); None = the library's default block); without them `demod` must be None. `params`: a
+    GdptVarSmoothParams taken as it is (else var_smooth_params(radius)). Returns (HxWx3 smoothed variance, GdptVarSmoothStats)."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("variance_smooth: img and var must be HxWx3 arrays of one shape")
+    f = fv = None
+    if feat is not None or feat_var is not None:
+        if feat is None or feat_var is None:
+            raise GdptError("variance_smooth: feat and feat_var go together")
+        f = np.ascontiguousarray(feat, dtype=np.float64)
+        fv = np.ascontiguousarray(feat_var, dtype=np.float64)
+        if f.ndim != 3 or f.shape != fv.shape or f.shape[1:] != a.shape[:2]:
+            raise GdptError("variance_smooth: feat and feat_var must be (num_channels, H, W) arrays of one shape")
+        if demod is None:
+            demod = nlm_demod()
+    p = params if params is not None else var_smooth_params(radius)
+    out, st = np.empty(a.shape, dtype=np.float64), defs.GdptVarSmoothStats()
+    _check(lib().gdpt_variance_smooth(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                      C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                      int(f.shape[0]) if f is not None else 0, C.byref(p), C.byref(demod) if demod is not None else None,
+                                      C.c_void_p(out.ctypes.data), C.byref(st)))
+    return out, st
+
+
+def variance_smooth_device(width, height, img_ptr, var_ptr, var_out_ptr, feat_ptr=None, feat_var_ptr=None, num_channels=0, demod=None, stream=None,
+                           stats=True, params=None, radius=None):
+    """variance_smooth() on device addresses (gdpt_variance_smooth_device). `feat_ptr`, `feat_var_ptr` and `demod` go together and are
+    passed as they are: `demod` None is no block here. Returns GdptVarSmoothStats after waiting for `stream`; with `stats=False` the
+    call only enqueues and returns None."""
+    p = params if params is not None else var_smooth_params(radius)
+    st = defs.GdptVarSmoothStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_variance_smooth_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
+                                             C.byref(p), C.byref(demod) if demod is not None else None, opt(var_out_ptr), opt(stream),
+                                             C.byref(st) if stats else None))
     return st
 
 

@@ -155,6 +155,19 @@ class GdptNlmDemod(C.Structure):
     _fields_ = [("albedo_channel", C.c_int32), ("coverage_channel", C.c_int32), ("floor", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+VAR_SMOOTH_MAX_RADIUS = 4
+DENOISE_PLAIN, DENOISE_GUIDED, DENOISE_DEMOD = 0, 1, 2
+
+
+class GdptVarSmoothParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GdptVarSmoothStats(C.Structure):
+    _fields_ = [("pixels_left_out", C.c_uint64), ("sum_var_in", C.c_double), ("sum_var_out", C.c_double), ("smooth_ms", C.c_double),
+                ("radius", C.c_int32)]
+
+
 class GdptGroupReconParams(C.Structure):
     _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
                 ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]

@@ -27,6 +27,7 @@
 #include "poisson_kernels.h"
 #include "progressive_internal.h"
 #include "denoise_nlm.h"
+#include "variance_smooth.h"
 
 #include <algorithm>
 #include <cmath>
@@ -577,6 +578,77 @@ int gdpt_progressive_denoise_demod(GdptProgressive *session, const GdptNlmParams
                              [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
                                  gdpt::denoise_nlm_demod_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, guide, d, d_out, d_var_out, s.stream, st);
                              });
+    });
+}
+
+int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind, const GdptVarSmoothParams *smooth, const GdptNlmParams *nlm,
+                                      const GdptNlmGuide *guide, const GdptNlmDemod *demod, int feature_spp, int on_device, double *out,
+                                      double *var_out, double *smoothed_var, double *features, double *features_var, GdptNlmStats *stats,
+                                      GdptVarSmoothStats *smooth_stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_smoothed";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        if (kind != GDPT_DENOISE_PLAIN && kind != GDPT_DENOISE_GUIDED && kind != GDPT_DENOISE_DEMOD)
+            throw std::runtime_error(who + ": kind must be GDPT_DENOISE_PLAIN, GDPT_DENOISE_GUIDED or GDPT_DENOISE_DEMOD");
+        GdptVarSmoothParams sp;
+        if (smooth) sp = *smooth; else gdpt_var_smooth_default_params(&sp);
+        gdpt::var_smooth_check_params(who, sp);
+        GdptNlmParams p;
+        if (nlm) p = *nlm; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        if (kind == GDPT_DENOISE_PLAIN && guide) throw std::runtime_error(who + ": guide must be null for GDPT_DENOISE_PLAIN");
+        if (kind != GDPT_DENOISE_DEMOD && demod) throw std::runtime_error(who + ": demod must be null unless kind is GDPT_DENOISE_DEMOD");
+        if (kind == GDPT_DENOISE_PLAIN && (features || features_var))
+            throw std::runtime_error(who + ": features and features_var must be null for GDPT_DENOISE_PLAIN (it renders none)");
+        GdptNlmGuide g;                   // GUIDED: the guide in force
+        if (guide) g = *guide; else gdpt_nlm_default_guide(&g);
+        if (kind == GDPT_DENOISE_GUIDED || guide) {
+            gdpt::nlm_check_guide(who, g);
+            if (g.num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
+        }
+        GdptNlmDemod d;
+        if (demod) d = *demod; else gdpt_nlm_default_demod(&d);
+        if (kind == GDPT_DENOISE_DEMOD) gdpt::nlm_check_demod(who, d, GDPT_FEATURE_CHANNELS);
+        GdptVarSmoothStats sst{};         // (asked for always: the call is blocking)
+        // the variance of buffer 0 into s.smooth_buf, on the planes of `dm` (nullable) in s.feat_buf, and its copy out
+        auto smoothed = [&](GdptProgressive &s, const GdptNlmDemod *dm) {
+            if (!s.smooth_buf) s.smooth_buf.alloc(s.elems, "hipMalloc(progressive smoothed variance)");
+            gdpt::variance_smooth_launch(s.w, s.h, s.mean[0], s.var[0], dm ? s.feat_buf[0].data() : nullptr, dm ? s.feat_buf[1].data() : nullptr, sp, dm,
+                                         s.smooth_buf, s.stream, &sst);
+            copy_out(s, smoothed_var, s.smooth_buf, on_device);
+        };
+        if (kind == GDPT_DENOISE_PLAIN) {
+            GdptProgressive &s = *session;
+            if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+            ck(hipSetDevice(s.scene->device), "hipSetDevice");
+            compute_variances(s);
+            double *d_out = out, *d_var_out = var_out;
+            if (!on_device) {                 // through planes of the session's on the way to host memory
+                for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+                d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+            }
+            smoothed(s, nullptr);
+            GdptNlmStats st{};
+            if (gdpt_denoise_nlm_device(s.w, s.h, s.mean[0], s.smooth_buf, &p, d_out, d_var_out, s.stream, &st) != 0) throw std::runtime_error(gdpt_last_error());
+            if (!on_device) { copy_out(s, out, d_out, 0); copy_out(s, var_out, d_var_out, 0); }
+            ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+            if (stats) *stats = st;
+        } else {
+            filter_with_features(who, *session, feature_spp, on_device, out, var_out, features, features_var, stats,
+                                 [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
+                                     if (kind == GDPT_DENOISE_DEMOD) {
+                                         smoothed(s, &d);
+                                         gdpt::denoise_nlm_demod_launch(s.w, s.h, s.mean[0], s.smooth_buf, s.feat_buf[0], s.feat_buf[1], p, guide ? &g : nullptr, d,
+                                                                        d_out, d_var_out, s.stream, st);
+                                     } else {
+                                         smoothed(s, nullptr);
+                                         gdpt::denoise_nlm_guided_launch(s.w, s.h, s.mean[0], s.smooth_buf, s.feat_buf[0], s.feat_buf[1], p, g, d_out, d_var_out,
+                                                                         s.stream, st);
+                                     }
+                                 });
+        }
+        if (smooth_stats) *smooth_stats = sst;
     });
 }
 

@@ -29,6 +29,7 @@ struct GdptProgressive {
     gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
     gdpt::DeviceBuffer<double> nlm_buf[2];     // filtered mean and its variance on their way to host memory: allocated by the first denoise
     gdpt::DeviceBuffer<double> feat_buf[2];    // feature planes and their variances of the guided denoise (8 W H doubles each): allocated by the first one
+    gdpt::DeviceBuffer<double> smooth_buf;     // the smoothed variance of buffer 0 (gdpt_progressive_denoise_smoothed): allocated by the first one
     gdpt::DeviceBuffer<double> partials;
     gdpt::DeviceBuffer<film::Estimate> d_est;
     gdpt::PinnedBuffer<film::Estimate> h_est;

@@ -812,6 +812,70 @@ int gdpt_progressive_denoise_demod(GdptProgressive *session, const GdptNlmParams
                                    int on_device, double *out, double *var_out /* nullable */, double *features /* nullable */,
                                    double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
 
+/* ---- smoothing the variance that drives the non-local-means filters (not part of the reference) ----
+ * The three filters above take their weights from the per-pixel variance of a session's mean, which a session estimates from its K
+ * pass means: with K - 1 degrees of freedom the estimate has a relative error of sqrt(2 / (K - 1)), 141 % at K = 2, 82 % at K = 4.
+ * Every patch distance divides by v(p) + v(q) and subtracts alpha (v(p) + min(v(q), v(p))), so that noise goes straight into the
+ * weights: at 2 passes the filters at their defaults do nothing. The pre-pass here replaces the variance with its mean over a
+ * (2 radius + 1)^2 window; the filters are then run, unchanged, on what it writes (DESIGN.md 4.10 has the measurements, and the
+ * remedies that lost). Radiance is albedo x illumination, so on a textured surface the variance carries the albedo squared, and a mean
+ * in the colour domain smears it across texel edges: with a block GdptNlmDemod the mean is taken of v / a~^2 and a~^2 is multiplied back.
+ * Inputs: img, var W*H*3 doubles, interleaved; optionally feat, feat_var, num_channels channel-planar planes, and a block GdptNlmDemod
+ * over them (all three or none). 0 <= radius <= GDPT_VAR_SMOOTH_MAX_RADIUS.
+ * A pixel is VALID as for gdpt_denoise_nlm (its img and var triples finite, var >= 0); with a demod block it must also be valid as
+ * gdpt_denoise_nlm_demod asks without a guide (its albedo triple and, with a coverage channel, its coverage finite, with variances
+ * finite and >= 0). a~ is the EFFECTIVE ALBEDO of gdpt_denoise_nlm_demod, max(floor, a_c + (1 - cov)); without a demod block a~ = 1
+ * and nothing is multiplied or divided. For valid p, q ranging over the valid pixels of the film with |q - p|_inf <= radius:
+ *   n_c(q)       = v_c(q) / (a~_c(q) a~_c(q))
+ *   S_c(p)       = sum_q n_c(q): row sums of 2 radius + 1 taps in increasing x, starting from 0.0, then the sum of those row sums in
+ *                  increasing y, starting from 0.0; a tap outside the film or on an invalid pixel counts as 0.0
+ *   C(p)         = the number of those q   (>= 1: p itself)
+ *   var_out_c(p) = (S_c(p) / C(p)) (a~_c(p) a~_c(p))
+ * An invalid p keeps its input bits in var_out and is counted in pixels_left_out. sum_var_in and sum_var_out are the sums of var and
+ * of var_out over the valid pixels (per pixel (c0 + c1) + c2), reduced in a fixed order: the same call gives the same bits.
+ * Exact, bit for bit: radius 0 without a demod block returns var (a variance of -0.0 comes back as +0.0); a var that is one dyadic
+ * constant over the film comes back unchanged (the sums of at most 81 equal dyadic terms and their quotient are exact; without a demod
+ * block); var times a per-film power of two multiplies var_out by it (short of overflow and subnormals). */
+#define GDPT_VAR_SMOOTH_MAX_RADIUS 4
+typedef struct GdptVarSmoothParams { int32_t radius; int32_t reserved[3]; } GdptVarSmoothParams;
+typedef struct GdptVarSmoothStats  { uint64_t pixels_left_out; double sum_var_in, sum_var_out, smooth_ms; int32_t radius; } GdptVarSmoothStats;
+void gdpt_var_smooth_default_params(GdptVarSmoothParams *p);      /* radius 2; every field of a passed struct is taken literally */
+/* Device pointers on the current device. d_feat, d_feat_var and demod go together: all NULL (a~ = 1; num_channels is ignored) or all
+ * given (NULL demod does NOT mean the default block here). Refused, with a message that names the field, before any device call: NULL
+ * d_img, d_var or d_var_out; d_var_out aliasing an input; width or height < 1; radius outside [0, 4]; non-zero reserved; a demod block
+ * without d_feat or d_feat_var, or planes without a demod block; what gdpt_denoise_nlm_demod_device refuses in a demod block and
+ * num_channels. params == NULL: gdpt_var_smooth_default_params. Enqueued on `stream`; with stats it waits for the stream (the sums and
+ * smooth_ms, HIP events, come back), with stats == NULL it only enqueues. Scratch (the block partials of the sums) per (device,
+ * stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_variance_smooth_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat /* nullable */,
+                                const double *d_feat_var /* nullable */, int num_channels, const GdptVarSmoothParams *params /* NULL: defaults */,
+                                const GdptNlmDemod *demod /* NULL: none */, double *d_var_out, void *stream,
+                                GdptVarSmoothStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_variance_smooth(int width, int height, const double *img, const double *var, const double *feat /* nullable */,
+                         const double *feat_var /* nullable */, int num_channels, const GdptVarSmoothParams *params /* NULL: defaults */,
+                         const GdptNlmDemod *demod /* NULL: none */, double *var_out, GdptVarSmoothStats *stats /* nullable */);
+/* One of the three session filters on the smoothed variance of buffer 0. By definition the outputs are, bit for bit, those of this
+ * chain on the session's stream: gdpt_progressive_read (the mean and variance of buffer 0); for GUIDED and DEMOD
+ * gdpt_features_render_device as gdpt_progressive_denoise_guided renders it; gdpt_variance_smooth_device with `smooth` (for DEMOD on the
+ * rendered planes with the filter's own demod block, otherwise a~ = 1); then gdpt_denoise_nlm_device (PLAIN),
+ * gdpt_denoise_nlm_guided_device (GUIDED) or gdpt_denoise_nlm_demod_device (DEMOD) with the smoothed variance in the place of var.
+ * So var_out and stats (sum_var_in and error_in included) are those of the SMOOTHED variance, not of the session's own estimate.
+ * smooth, nlm: NULL = defaults. guide: PLAIN must be NULL; GUIDED NULL = the default guide; DEMOD NULL = no feature term. demod: DEMOD
+ * only, NULL = the default block. feature_spp, features, features_var: as gdpt_progressive_denoise_guided; PLAIN ignores feature_spp
+ * and refuses the two pointers. smoothed_var (nullable) receives the smoothed variance, W*H*3. Requirements and refusals otherwise as
+ * the three session calls: at least 2 passes; Path, the primal of GradPath, a group's total. All output pointers are host memory, or
+ * device memory with on_device != 0. Blocking. */
+#define GDPT_DENOISE_PLAIN 0
+#define GDPT_DENOISE_GUIDED 1
+#define GDPT_DENOISE_DEMOD 2
+int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind, const GdptVarSmoothParams *smooth /* NULL: defaults */,
+                                      const GdptNlmParams *nlm /* NULL: defaults */, const GdptNlmGuide *guide /* nullable */,
+                                      const GdptNlmDemod *demod /* nullable */, int feature_spp, int on_device, double *out,
+                                      double *var_out /* nullable */, double *smoothed_var /* nullable */, double *features /* nullable */,
+                                      double *features_var /* nullable */, GdptNlmStats *stats /* nullable */,
+                                      GdptVarSmoothStats *smooth_stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
