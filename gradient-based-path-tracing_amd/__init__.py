@@ -108,6 +108,14 @@ def lib():
         L.gdpt_variance_smooth_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vp, vss]
         L.gdpt_variance_smooth.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vss]
         L.gdpt_progressive_denoise_smoothed.argtypes = [vp, C.c_int, vsp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, vp, nls, vss]
+        pos, pys = C.POINTER(defs.GdptNlmPyramidOpStats), C.POINTER(defs.GdptNlmPyramidStats)
+        L.gdpt_nlm_pyramid_down_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, vp, vp, pos]
+        L.gdpt_nlm_pyramid_down.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, vp, pos]
+        L.gdpt_nlm_pyramid_up_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, vp, pos]
+        L.gdpt_nlm_pyramid_up.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, pos]
+        L.gdpt_denoise_nlm_multiscale_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, nlp, ngp, ndp, vp, vp, vp, pys]
+        L.gdpt_denoise_nlm_multiscale.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, nlp, ngp, ndp, vp, vp, pys]
+        L.gdpt_progressive_denoise_multiscale.argtypes = [vp, C.c_int, C.c_int, vsp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, pys]
         L.gdpt_features_render_device.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp, vp,
                                                   C.POINTER(defs.GdptRenderStats)]
         L.gdpt_features_render.argtypes = [vp, C.POINTER(defs.GdptRenderParams), C.POINTER(defs.GdptSampleWindow), vp, vp,
@@ -578,6 +586,34 @@ class Progressive:
              C.c_void_p(fm.ctypes.data) if features else None, C.c_void_p(fv.ctypes.data) if features else None)
         return (out, var_out, sm, fm, fv, st, sst) if features else (out, var_out, sm, st, sst)
 
+    def denoise_multiscale(self, kind="plain", levels=2, radius=None, feature_spp=0, guide=None, demod=None, features=False, out_ptr=None,
+                           var_out_ptr=None, features_ptrs=None, **params):
+        """The multi-scale (pyramid) form of one of the three filters above on buffer 0 (gdpt_progressive_denoise_multiscale; from 2
+        passes on): denoise_nlm_multiscale with `levels` (1 - 4) levels on the session's mean, its variance and, for "guided" and
+        "demod", the features it renders. `radius`: None = the variance as estimated, else it is first smoothed over that radius as
+        denoise_smoothed does. `guide`, `demod`, `feature_spp`, `params` as denoise_smoothed takes them. Returns (HxWx3 filtered mean,
+        HxWx3 variance of the finest level's filter, GdptNlmPyramidStats), with `features=True` the two (8, H, W) feature arrays before
+        the stats; with `out_ptr` (and `var_out_ptr`, `features_ptrs` = 2 device addresses) everything stays in device memory and the
+        stats alone are returned."""
+        k = _kind("denoise_multiscale", kind)
+        sp = C.byref(var_smooth_params(radius)) if radius is not None else None
+        p, st = nlm_params(**params), defs.GdptNlmPyramidStats()
+        g = C.byref(guide) if guide is not None else None
+        d = C.byref(demod) if demod is not None else None
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        call = lambda *tail: _check(lib().gdpt_progressive_denoise_multiscale(self.handle, k, int(levels), sp, C.byref(p), g, d,      # noqa: E731
+                                                                              int(feature_spp), *tail, C.byref(st)))
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            call(1, opt(out_ptr), opt(var_out_ptr), opt(fp[0]), opt(fp[1]))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        call(0, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
+             C.c_void_p(fv.ctypes.data) if features else None)
+        return (out, var_out, fm, fv, st) if features else (out, var_out, st)
+
     def run(self, target_error=0.0, pass_spp=16, max_passes=0):
         """Adds passes until the budget is spent, `max_passes` were added (0: no limit) or, from 2 passes on, the error estimate is
         <= target_error (0: no target). Returns status(); its stop_reason is "budget", "max_passes" or "target"."""
@@ -994,6 +1030,130 @@ def variance_smooth_device(width, height, img_ptr, var_ptr, var_out_ptr, feat_pt
     _check(lib().gdpt_variance_smooth_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
                                              C.byref(p), C.byref(demod) if demod is not None else None, opt(var_out_ptr), opt(stream),
                                              C.byref(st) if stats else None))
+    return st
+
+
+_KINDS = {"plain": defs.DENOISE_PLAIN, "guided": defs.DENOISE_GUIDED, "demod": defs.DENOISE_DEMOD}
+
+
+def _kind(who, kind):
+    """The GDPT_DENOISE_* value of "plain", "guided" or "demod"; an int is passed on as it is (the library refuses an unknown one)."""
+    if isinstance(kind, str):
+        if kind not in _KINDS:
+            raise GdptError(f'{who}: kind must be "plain", "guided" or "demod"')
+        return _KINDS[kind]
+    return int(kind)
+
+
+def _level_arrays(who, img, var, feat, feat_var):
+    """A level's host arrays as C-contiguous float64: HxWx3 twice, and (num_channels, H, W) twice or (None, None)."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError(f"{who}: img and var must be HxWx3 arrays of one shape")
+    if feat is None and feat_var is None:
+        return a, v, None, None
+    if feat is None or feat_var is None:
+        raise GdptError(f"{who}: feat and feat_var go together")
+    f = np.ascontiguousarray(feat, dtype=np.float64)
+    fv = np.ascontiguousarray(feat_var, dtype=np.float64)
+    if f.ndim != 3 or f.shape != fv.shape or f.shape[1:] != a.shape[:2]:
+        raise GdptError(f"{who}: feat and feat_var must be (num_channels, H, W) arrays of one shape")
+    return a, v, f, fv
+
+
+def _vp(a):
+    return C.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _ref(block):
+    return C.byref(block) if block is not None else None
+
+
+def nlm_pyramid_down(img, var, feat=None, feat_var=None, kind="plain", guide=None, demod=None):
+    """The next coarser level of a multi-scale non-local-means call on the GPU (gdpt_nlm_pyramid_down): every 2 x 2 cell's mean of
+    `img` and of the planes `feat`, and mean / n of `var` and `feat_var`, over the n pixels of the cell that are valid for the `kind`
+    ("plain", "guided", "demod") with its blocks `guide`, `demod` (None: as the library reads a NULL block for the kind); NaN where
+    n = 0. Returns (img', var', feat', feat_var', GdptNlmPyramidOpStats) of ((H + 1) // 2, (W + 1) // 2); the planes are None
+    without `feat`."""
+    a, v, f, fv = _level_arrays("nlm_pyramid_down", img, var, feat, feat_var)
+    h, w = a.shape[:2]
+    hc, wc = (h + 1) // 2, (w + 1) // 2
+    oi, ov = np.empty((hc, wc, 3), dtype=np.float64), np.empty((hc, wc, 3), dtype=np.float64)
+    of, ofv = (np.empty((f.shape[0], hc, wc), dtype=np.float64), np.empty((f.shape[0], hc, wc), dtype=np.float64)) if f is not None else (None, None)
+    st = defs.GdptNlmPyramidOpStats()
+    _check(lib().gdpt_nlm_pyramid_down(w, h, _vp(a), _vp(v), _vp(f), _vp(fv), int(f.shape[0]) if f is not None else 0, _kind("nlm_pyramid_down", kind),
+                                       _ref(guide), _ref(demod), _vp(oi), _vp(ov), _vp(of), _vp(ofv), C.byref(st)))
+    return oi, ov, of, ofv, st
+
+
+def nlm_pyramid_down_device(width, height, img_ptr, var_ptr, img_out_ptr, var_out_ptr, feat_ptr=None, feat_var_ptr=None, feat_out_ptr=None,
+                            feat_var_out_ptr=None, num_channels=0, kind="plain", guide=None, demod=None, stream=None, stats=True):
+    """nlm_pyramid_down() on device addresses (gdpt_nlm_pyramid_down_device). Returns GdptNlmPyramidOpStats after waiting for `stream`;
+    with `stats=False` the call only enqueues and returns None."""
+    st = defs.GdptNlmPyramidOpStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_nlm_pyramid_down_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
+                                              _kind("nlm_pyramid_down_device", kind), _ref(guide), _ref(demod), opt(img_out_ptr), opt(var_out_ptr),
+                                              opt(feat_out_ptr), opt(feat_var_out_ptr), opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def nlm_pyramid_up(img, var, filtered, coarse_out, feat=None, feat_var=None, kind="plain", guide=None, demod=None):
+    """A filtered coarser level put back into a filtered finer one on the GPU (gdpt_nlm_pyramid_up): `filtered` (HxWx3, the kind's
+    filter on this level) plus the bilinear interpolation of `coarse_out` - (the down mean of `filtered`), `coarse_out` the combined
+    output of the next coarser level. `img`, `var`, `feat`, `feat_var`: this level's inputs, read for validity; an invalid pixel
+    keeps the bits of `img`. Returns (HxWx3 combined output, GdptNlmPyramidOpStats)."""
+    a, v, f, fv = _level_arrays("nlm_pyramid_up", img, var, feat, feat_var)
+    h, w = a.shape[:2]
+    fl = np.ascontiguousarray(filtered, dtype=np.float64)
+    co = np.ascontiguousarray(coarse_out, dtype=np.float64)
+    if fl.shape != a.shape or co.shape != ((h + 1) // 2, (w + 1) // 2, 3):
+        raise GdptError("nlm_pyramid_up: filtered must have the shape of img, coarse_out that of the next coarser level")
+    out, st = np.empty(a.shape, dtype=np.float64), defs.GdptNlmPyramidOpStats()
+    _check(lib().gdpt_nlm_pyramid_up(w, h, _vp(a), _vp(v), _vp(f), _vp(fv), int(f.shape[0]) if f is not None else 0, _kind("nlm_pyramid_up", kind),
+                                     _ref(guide), _ref(demod), _vp(fl), _vp(co), _vp(out), C.byref(st)))
+    return out, st
+
+
+def nlm_pyramid_up_device(width, height, img_ptr, var_ptr, filtered_ptr, coarse_out_ptr, out_ptr, feat_ptr=None, feat_var_ptr=None, num_channels=0,
+                          kind="plain", guide=None, demod=None, stream=None, stats=True):
+    """nlm_pyramid_up() on device addresses (gdpt_nlm_pyramid_up_device); `stats` as nlm_pyramid_down_device."""
+    st = defs.GdptNlmPyramidOpStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_nlm_pyramid_up_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
+                                            _kind("nlm_pyramid_up_device", kind), _ref(guide), _ref(demod), opt(filtered_ptr), opt(coarse_out_ptr),
+                                            opt(out_ptr), opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def denoise_nlm_multiscale(img, var, feat=None, feat_var=None, kind="plain", levels=2, guide=None, demod=None, **params):
+    """A multi-scale (pyramid) form of denoise_nlm ("plain"), denoise_nlm_guided ("guided") or denoise_nlm_demod ("demod") on the GPU
+    (gdpt_denoise_nlm_multiscale): the kind's filter runs on `levels` (1 - 4) levels of a 2 x 2 mean pyramid and each level's low
+    frequencies are replaced by the filtered coarser level, which removes the noise a single window cannot reach. `guide`, `demod`:
+    None = as the library reads a NULL block for the kind (guided: the default guide; demod: the default block, no feature term);
+    `params`: the keywords of nlm_params. Returns (HxWx3 filtered image, HxWx3 variance of the finest level's filter, in which the
+    correction is ignored, GdptNlmPyramidStats). levels=1 is the kind's single-scale filter, bit for bit."""
+    a, v, f, fv = _level_arrays("denoise_nlm_multiscale", img, var, feat, feat_var)
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = nlm_params(**params), defs.GdptNlmPyramidStats()
+    _check(lib().gdpt_denoise_nlm_multiscale(int(a.shape[1]), int(a.shape[0]), _vp(a), _vp(v), _vp(f), _vp(fv), int(f.shape[0]) if f is not None else 0,
+                                             _kind("denoise_nlm_multiscale", kind), int(levels), C.byref(p), _ref(guide), _ref(demod), _vp(out),
+                                             _vp(var_out), C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_nlm_multiscale_device(width, height, img_ptr, var_ptr, out_ptr, var_out_ptr=None, feat_ptr=None, feat_var_ptr=None, num_channels=0,
+                                  kind="plain", levels=2, guide=None, demod=None, stream=None, stats=True, params=None, **kw):
+    """denoise_nlm_multiscale() on device addresses (gdpt_denoise_nlm_multiscale_device); `var_out_ptr` may be None. `params`: a
+    GdptNlmParams taken as it is (else the keywords of nlm_params). Returns GdptNlmPyramidStats after waiting for `stream`; with
+    `stats=False` the call only enqueues and returns None."""
+    p = params if params is not None else nlm_params(**kw)
+    st = defs.GdptNlmPyramidStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_multiscale_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr),
+                                                    int(num_channels), _kind("denoise_nlm_multiscale_device", kind), int(levels), C.byref(p), _ref(guide),
+                                                    _ref(demod), opt(out_ptr), opt(var_out_ptr), opt(stream), C.byref(st) if stats else None))
     return st
 
 

@@ -168,6 +168,19 @@ class GdptVarSmoothStats(C.Structure):
                 ("radius", C.c_int32)]
 
 
+NLM_MAX_LEVELS = 4
+
+
+class GdptNlmPyramidOpStats(C.Structure):
+    _fields_ = [("pixels_left_out", C.c_uint64), ("cells_empty", C.c_uint64), ("op_ms", C.c_double), ("coarse_width", C.c_int32),
+                ("coarse_height", C.c_int32)]
+
+
+class GdptNlmPyramidStats(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("reserved", C.c_int32), ("width", C.c_int32 * NLM_MAX_LEVELS), ("height", C.c_int32 * NLM_MAX_LEVELS),
+                ("level", GdptNlmStats * NLM_MAX_LEVELS), ("total_ms", C.c_double)]
+
+
 class GdptGroupReconParams(C.Structure):
     _fields_ = [("dataCost", C.c_double), ("weighted", C.c_int32), ("map_radius", C.c_int32),
                 ("recon", GdptReconParams), ("wrecon", GdptWeightedReconParams)]

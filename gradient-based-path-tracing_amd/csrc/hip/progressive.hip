@@ -28,6 +28,7 @@
 #include "progressive_internal.h"
 #include "denoise_nlm.h"
 #include "variance_smooth.h"
+#include "nlm_pyramid.h"
 
 #include <algorithm>
 #include <cmath>
@@ -649,6 +650,56 @@ int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind, const 
                                  });
         }
         if (smooth_stats) *smooth_stats = sst;
+    });
+}
+
+int gdpt_progressive_denoise_multiscale(GdptProgressive *session, int kind, int levels, const GdptVarSmoothParams *smooth, const GdptNlmParams *nlm,
+                                        const GdptNlmGuide *guide, const GdptNlmDemod *demod, int feature_spp, int on_device, double *out,
+                                        double *var_out, double *features, double *features_var, GdptNlmPyramidStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_multiscale";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        // (the session renders its own planes: a guide must be over GDPT_FEATURE_CHANNELS of them)
+        const gdpt::NlmKindBlocks kb = gdpt::nlm_pyramid_check_kind(who, kind, guide, demod, GDPT_FEATURE_CHANNELS, kind == GDPT_DENOISE_GUIDED || kind == GDPT_DENOISE_DEMOD);
+        gdpt::nlm_pyramid_check_levels(who, levels);
+        if (smooth) gdpt::var_smooth_check_params(who, *smooth);
+        GdptNlmParams p;
+        if (nlm) p = *nlm; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        if (kind == GDPT_DENOISE_PLAIN && (features || features_var))
+            throw std::runtime_error(who + ": features and features_var must be null for GDPT_DENOISE_PLAIN (it renders none)");
+        GdptNlmPyramidStats pst{};        // (asked for always: the call is blocking)
+        // the variance the levels start from: buffer 0's as estimated, or smoothed into s.smooth_buf as gdpt_progressive_denoise_smoothed does
+        auto variance = [&](GdptProgressive &s) -> const double * {
+            if (!smooth) return s.var[0];
+            if (!s.smooth_buf) s.smooth_buf.alloc(s.elems, "hipMalloc(progressive smoothed variance)");
+            const bool dm = kind == GDPT_DENOISE_DEMOD;
+            gdpt::variance_smooth_launch(s.w, s.h, s.mean[0], s.var[0], dm ? s.feat_buf[0].data() : nullptr, dm ? s.feat_buf[1].data() : nullptr, *smooth,
+                                         dm ? &kb.demod : nullptr, s.smooth_buf, s.stream, nullptr);
+            return s.smooth_buf;
+        };
+        if (kind == GDPT_DENOISE_PLAIN) {
+            GdptProgressive &s = *session;
+            if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+            ck(hipSetDevice(s.scene->device), "hipSetDevice");
+            compute_variances(s);
+            double *d_out = out, *d_var_out = var_out;
+            if (!on_device) {                 // through planes of the session's on the way to host memory
+                for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+                d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+            }
+            gdpt::denoise_nlm_multiscale_launch(s.w, s.h, s.mean[0], variance(s), nullptr, nullptr, kb, levels, p, d_out, d_var_out, s.stream, &pst);
+            if (!on_device) { copy_out(s, out, d_out, 0); copy_out(s, var_out, d_var_out, 0); }
+            ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+        } else {
+            filter_with_features(who, *session, feature_spp, on_device, out, var_out, features, features_var, nullptr,
+                                 [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *) {
+                                     gdpt::denoise_nlm_multiscale_launch(s.w, s.h, s.mean[0], variance(s), s.feat_buf[0], s.feat_buf[1], kb, levels, p, d_out,
+                                                                         d_var_out, s.stream, &pst);
+                                 });
+        }
+        if (stats) *stats = pst;
     });
 }
 

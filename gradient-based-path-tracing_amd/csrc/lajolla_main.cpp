@@ -51,6 +51,10 @@
 //                 (gdpt_progressive_denoise_smoothed): the variance of a few passes is mostly noise, and it sets the weights. With
 //                 --nlm-demodulate the average is taken of variance / albedo^2. It combines with --nlm-guide and --nlm-demodulate.
 //                 Without --nlm-var-smooth every output file is what it was
+//                 --nlm-levels L (1..4) runs the chosen filter on L levels of a 2 x 2 mean pyramid and replaces each level's low
+//                 frequencies by the filtered coarser level (gdpt_progressive_denoise_multiscale): the blotches a single window
+//                 cannot reach. It combines with --nlm-guide, --nlm-demodulate and --nlm-var-smooth. Without --nlm-levels every
+//                 output file is what it was
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -84,6 +88,7 @@ int main(int argc, char *argv[]) {
     bool nlm_option = false, nlm_k_set = false, nlm_guide_option = false, nlm_demodulate = false;
     double nlm_albedo_floor = 0.0;
     int nlm_var_smooth = -1;          // < 0: not given
+    int nlm_levels = 0;               // 0: not given
     std::string features_prefix = "", nlm_guide_names = "";
     int feature_spp = 0;
     double nlm_depth_tau = 0.0, nlm_kf = 0.0;
@@ -161,6 +166,10 @@ int main(int argc, char *argv[]) {
         else if (a == "--nlm-kf") { nlm_kf = std::stod(next()); nlm_guide_option = true; }
         else if (a == "--nlm-demodulate") nlm_demodulate = true;
         else if (a == "--nlm-albedo-floor") nlm_albedo_floor = std::stod(next());
+        else if (a == "--nlm-levels") {
+            nlm_levels = std::stoi(next());
+            if (nlm_levels < 1 || nlm_levels > GDPT_NLM_MAX_LEVELS) { std::cerr << "--nlm-levels takes a number of levels from 1 to 4" << std::endl; return 2; }
+        }
         else if (a == "--nlm-var-smooth") {
             nlm_var_smooth = std::stoi(next());
             if (nlm_var_smooth < 0 || nlm_var_smooth > GDPT_VAR_SMOOTH_MAX_RADIUS) { std::cerr << "--nlm-var-smooth takes a radius from 0 to 4" << std::endl; return 2; }
@@ -250,6 +259,7 @@ int main(int argc, char *argv[]) {
         }
     } else if (nlm_albedo_floor != 0.0) { std::cerr << "--nlm-albedo-floor needs --nlm-demodulate" << std::endl; return 2; }
     if (nlm_var_smooth >= 0 && denoised_file.empty()) { std::cerr << "--nlm-var-smooth needs --denoised" << std::endl; return 2; }
+    if (nlm_levels > 0 && denoised_file.empty()) { std::cerr << "--nlm-levels needs --denoised" << std::endl; return 2; }
     if (!features_prefix.empty() && (multi.num_devices > 0 || !sample_devices.empty())) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
@@ -315,6 +325,7 @@ int main(int argc, char *argv[]) {
         GdptReconSpreadStats spread{};
         GdptNlmStats nlm_stats{};
         GdptVarSmoothStats smooth_stats{};
+        GdptNlmPyramidStats pyramid_stats{};
         GdptGroupReconParams gp{};        // the reconstruction the estimate of --target-recon-error / --error-map goes through
         gp.dataCost = alpha; gp.weighted = weighted ? 1 : 0; gp.map_radius = error_radius;
         gp.recon = recon; gp.wrecon.recon = recon; gp.wrecon.conf_floor = conf_floor;
@@ -366,7 +377,18 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                if (nlm_var_smooth >= 0) {
+                if (nlm_levels > 0) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    GdptVarSmoothParams sp{};
+                    gdpt_var_smooth_default_params(&sp);
+                    sp.radius = nlm_var_smooth;
+                    rc = gdpt_progressive_denoise_multiscale(session, nlm_demodulate ? GDPT_DENOISE_DEMOD : guided ? GDPT_DENOISE_GUIDED : GDPT_DENOISE_PLAIN,
+                                                             nlm_levels, nlm_var_smooth >= 0 ? &sp : nullptr, &nlm, guided ? &guide : nullptr,
+                                                             nlm_demodulate ? &demod : nullptr, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
+                                                             filtered.data(), nullptr, nullptr, nullptr, &pyramid_stats);
+                    nlm_stats = pyramid_stats.level[0];
+                    smooth_stats.radius = nlm_var_smooth;
+                } else if (nlm_var_smooth >= 0) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     GdptVarSmoothParams sp{};
                     gdpt_var_smooth_default_params(&sp);
@@ -453,7 +475,9 @@ int main(int argc, char *argv[]) {
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
                           << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
-                          << (nlm_var_smooth >= 0 ? ", variance smoothed over radius " + std::to_string(smooth_stats.radius) : std::string()) << ", written to "
+                          << (nlm_var_smooth >= 0 ? ", variance smoothed over radius " + std::to_string(smooth_stats.radius) : std::string())
+                          << (nlm_levels > 0 ? ", " + std::to_string(pyramid_stats.levels) + " levels in " + std::to_string(pyramid_stats.total_ms) + " ms (the figures before are the finest level's)" : std::string())
+                          << ", written to "
                           << denoised_file
                           << std::endl;
             if (recon_error)

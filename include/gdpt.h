@@ -876,6 +876,99 @@ int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind, const 
                                       double *features_var /* nullable */, GdptNlmStats *stats /* nullable */,
                                       GdptVarSmoothStats *smooth_stats /* nullable */);
 
+/* ---- a multi-scale (pyramid) form of the non-local-means filters (not part of the reference) ----
+ * A window of radius 10 averages at most 441 pixels, so the error of a block mean over 8 x 8 pixels or more passes the three filters
+ * almost untouched: the blotches of a smooth wall. Here a pyramid is filtered, and each level's low frequencies are replaced by the
+ * filtered coarser level (Burt and Adelson's Laplacian pyramid; Boughida and Boubekeur, "Bayesian collaborative denoising for Monte
+ * Carlo rendering", EGSR 2017, section 5). DESIGN.md 4.11 has the measurements.
+ * A KIND is GDPT_DENOISE_PLAIN, GUIDED or DEMOD: gdpt_denoise_nlm, gdpt_denoise_nlm_guided or gdpt_denoise_nlm_demod with their blocks,
+ * by the conventions of gdpt_progressive_denoise_smoothed: PLAIN takes no block and no planes (guide, demod, feat, feat_var NULL);
+ * GUIDED takes a guide (NULL: the default guide) and no demod block; DEMOD takes a demod block (NULL: the default block) and a guide
+ * or none (NULL: no feature term). With planes, a guide must have guide->num_channels == num_channels. Level 0 is the call's input:
+ * img, var (interleaved) and, for GUIDED and DEMOD, feat, feat_var (num_channels planar planes). A pixel of a level is VALID exactly
+ * as the kind's filter defines validity on that level's arrays.
+ * DOWN (level l -> l+1): W' = (W + 1) / 2, H' = (H + 1) / 2 in integer division. Coarse pixel (X, Y) covers the fine pixels
+ *   (2X + dx, 2Y + dy), dx, dy in {0, 1}, that lie in the film; n of them are valid. Every coarse value (three img, three var, every
+ *   feature plane and its variance plane) is summed from 0.0 in the order (dx, dy) = (0,0), (1,0), (0,1), (1,1) over the valid pixels
+ *   only; a mean is divided by n, a variance by n n. With n = 0 every coarse value is NaN, so the coarse pixel is invalid for every
+ *   kind by the definitions above and no mask is carried.
+ * LEVELS: 1 <= levels <= GDPT_NLM_MAX_LEVELS. Level l+1 exists if l + 1 < levels and W_l H_l > 1; the stats report the levels made.
+ * FILTER: F_l, VF_l are out and var_out of the kind's filter on level l, with the call's GdptNlmParams, guide and demod unchanged.
+ * UP AND COMBINE, from the coarsest level L down: out_L = F_L. For a coarse pixel with n > 0, R(X, Y) = out_{l+1}(X, Y) - DF(X, Y),
+ *   DF the Down mean of F_l over the same valid pixels; with n = 0, R = 0.0. For a valid fine pixel (x, y): X = x >> 1,
+ *   X* = clamp(X + (x odd ? 1 : -1), 0, W' - 1), Y and Y* likewise, and per channel, in exactly this order and without contraction,
+ *     out_l = F_l + (((0.5625 R(X,Y) + 0.1875 R(X*,Y)) + 0.1875 R(X,Y*)) + 0.0625 R(X*,Y*))
+ *   An invalid fine pixel keeps its input bits.
+ * OUTPUTS: out = out_0. var_out = VF_0, the finest level's: THE CORRECTION IS IGNORED IN IT, it is the variance of the single-scale
+ * weighted average with fixed weights, not that of out. pixels_left_out is level 0's.
+ * Exact, bit for bit: levels = 1 gives the kind's existing entry point's out, var_out and stats; a film that is one dyadic constant
+ * with a dyadic constant variance comes back unchanged at every level count (every sum, quotient and the four dyadic weights are
+ * exact; with planes, where they are dyadic constants of variance 0, so that every weight is 1 and the albedo divides exactly); the
+ * same call gives the same bits. */
+#define GDPT_NLM_MAX_LEVELS 4
+typedef struct GdptNlmPyramidOpStats { uint64_t pixels_left_out, cells_empty; double op_ms; int32_t coarse_width, coarse_height; } GdptNlmPyramidOpStats;
+typedef struct GdptNlmPyramidStats { int32_t levels, reserved; int32_t width[GDPT_NLM_MAX_LEVELS], height[GDPT_NLM_MAX_LEVELS];
+                                     GdptNlmStats level[GDPT_NLM_MAX_LEVELS]; double total_ms; } GdptNlmPyramidStats;
+/* Down alone, device pointers on the current device: level (width, height) into d_*_out of ((width + 1) / 2, (height + 1) / 2).
+ * d_feat_out, d_feat_var_out go with d_feat, d_feat_var (all four or none; with none num_channels is ignored). Refused, with a message
+ * that names the field, before any device call: NULL d_img, d_var, d_img_out or d_var_out; an output aliasing an input or another
+ * output; width or height < 1; an unknown kind; blocks or planes that do not fit the kind (above); what the kind's filter refuses in
+ * a guide, a demod block and num_channels; missing planes where the kind reads some (GUIDED with groups, DEMOD). Enqueued on `stream`;
+ * with stats it waits for the stream (pixels_left_out: the invalid fine pixels; cells_empty: the coarse pixels with n = 0; op_ms, HIP
+ * events), with stats == NULL it only enqueues. Scratch per (device, stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_nlm_pyramid_down_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat /* nullable */,
+                                 const double *d_feat_var /* nullable */, int num_channels, int kind, const GdptNlmGuide *guide /* nullable */,
+                                 const GdptNlmDemod *demod /* nullable */, double *d_img_out, double *d_var_out, double *d_feat_out /* nullable */,
+                                 double *d_feat_var_out /* nullable */, void *stream, GdptNlmPyramidOpStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_nlm_pyramid_down(int width, int height, const double *img, const double *var, const double *feat /* nullable */,
+                          const double *feat_var /* nullable */, int num_channels, int kind, const GdptNlmGuide *guide /* nullable */,
+                          const GdptNlmDemod *demod /* nullable */, double *img_out, double *var_out, double *feat_out /* nullable */,
+                          double *feat_var_out /* nullable */, GdptNlmPyramidOpStats *stats /* nullable */);
+/* Up and combine alone: the fine level's inputs (read for validity, and img for the bits of an invalid pixel), d_filtered = F_l of
+ * (width, height), d_coarse_out = out_{l+1} of the coarse extent, into d_out of (width, height). Refusals as the down entry's, with
+ * NULL d_filtered, d_coarse_out or d_out and d_out aliasing an input. cells_empty comes back 0. */
+int gdpt_nlm_pyramid_up_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat /* nullable */,
+                               const double *d_feat_var /* nullable */, int num_channels, int kind, const GdptNlmGuide *guide /* nullable */,
+                               const GdptNlmDemod *demod /* nullable */, const double *d_filtered, const double *d_coarse_out, double *d_out,
+                               void *stream, GdptNlmPyramidOpStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_nlm_pyramid_up(int width, int height, const double *img, const double *var, const double *feat /* nullable */,
+                        const double *feat_var /* nullable */, int num_channels, int kind, const GdptNlmGuide *guide /* nullable */,
+                        const GdptNlmDemod *demod /* nullable */, const double *filtered, const double *coarse_out, double *out,
+                        GdptNlmPyramidOpStats *stats /* nullable */);
+/* The multi-scale filter. By definition the outputs are, bit for bit, those of the composition on `stream` of
+ * gdpt_nlm_pyramid_down_device, the kind's device filter (gdpt_denoise_nlm_device, gdpt_denoise_nlm_guided_device or
+ * gdpt_denoise_nlm_demod_device) on every level and gdpt_nlm_pyramid_up_device. Refused, with a message that names the field, before
+ * any device call: what the kind's filter refuses; levels outside [1, GDPT_NLM_MAX_LEVELS]; an unknown kind; blocks or planes that do
+ * not fit the kind; d_out or d_var_out aliasing an input or each other. params == NULL: gdpt_nlm_default_params. With stats it waits
+ * for the stream after every level's filter (a GdptNlmStats per level, the levels made, their extents; total_ms spans the call, HIP
+ * events); with stats == NULL it only enqueues. The pyramid and the levels' outputs are kept per (device, stream), dropped by
+ * gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_denoise_nlm_multiscale_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat /* nullable */,
+                                       const double *d_feat_var /* nullable */, int num_channels, int kind, int levels,
+                                       const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* nullable */,
+                                       const GdptNlmDemod *demod /* nullable */, double *d_out, double *d_var_out /* nullable */, void *stream,
+                                       GdptNlmPyramidStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm_multiscale(int width, int height, const double *img, const double *var, const double *feat /* nullable */,
+                                const double *feat_var /* nullable */, int num_channels, int kind, int levels,
+                                const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* nullable */,
+                                const GdptNlmDemod *demod /* nullable */, double *out, double *var_out /* nullable */,
+                                GdptNlmPyramidStats *stats /* nullable */);
+/* The multi-scale filter on a session's buffer 0. By definition the outputs are, bit for bit, those of this chain on the session's
+ * stream: gdpt_progressive_read (the mean and variance of buffer 0); for GUIDED and DEMOD gdpt_features_render_device as
+ * gdpt_progressive_denoise_guided renders it; with smooth != NULL gdpt_variance_smooth_device as gdpt_progressive_denoise_smoothed
+ * runs it on level 0 (smooth == NULL: the variance as estimated); then gdpt_denoise_nlm_multiscale_device. nlm, guide, demod,
+ * feature_spp, features, features_var: as gdpt_progressive_denoise_smoothed takes them for the kind. Requirements as the three session
+ * calls: at least 2 passes; Path, the primal of GradPath, a group's total. All output pointers are host memory, or device memory
+ * with on_device != 0. Blocking. */
+int gdpt_progressive_denoise_multiscale(GdptProgressive *session, int kind, int levels, const GdptVarSmoothParams *smooth /* NULL: none */,
+                                        const GdptNlmParams *nlm /* NULL: defaults */, const GdptNlmGuide *guide /* nullable */,
+                                        const GdptNlmDemod *demod /* nullable */, int feature_spp, int on_device, double *out,
+                                        double *var_out /* nullable */, double *features /* nullable */, double *features_var /* nullable */,
+                                        GdptNlmPyramidStats *stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
