@@ -96,6 +96,12 @@ def lib():
         L.gdpt_denoise_nlm_guided_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_guided.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, nls]
         L.gdpt_progressive_denoise_guided.argtypes = [vp, nlp, ngp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        nrp = C.POINTER(defs.GdptNlmRegress)
+        L.gdpt_nlm_default_regress.argtypes = [nrp]
+        L.gdpt_nlm_default_regress.restype = None
+        L.gdpt_denoise_nlm_regress_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm_regress.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, nls]
+        L.gdpt_progressive_denoise_regress.argtypes = [vp, nlp, ngp, nrp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
         ndp = C.POINTER(defs.GdptNlmDemod)
         L.gdpt_nlm_default_demod.argtypes = [ndp]
         L.gdpt_nlm_default_demod.restype = None
@@ -532,6 +538,29 @@ class Progressive:
                                                      C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
         return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
+    def denoise_regress(self, feature_spp, guide=None, regress=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
+        """The first-order feature regression on buffer 0 (gdpt_progressive_denoise_regress; from 2 passes on): the session renders
+        `feature_spp` samples of first-hit features as denoise_guided does, and fits the colour linearly on the regressor planes under
+        the guided filter's weights. `guide`: a GdptNlmGuide (nlm_guide(...)), `regress`: a GdptNlmRegress (nlm_regress(...)), None =
+        the library's defaults; `params`: the keywords of nlm_params. Returns and device-memory form as denoise_guided."""
+        p, st = nlm_params(**params), defs.GdptNlmStats()
+        g = guide if guide is not None else nlm_guide()
+        rg = regress if regress is not None else nlm_regress()
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            _check(lib().gdpt_progressive_denoise_regress(self.handle, C.byref(p), C.byref(g), C.byref(rg), int(feature_spp), 1, opt(out_ptr),
+                                                          opt(var_out_ptr), opt(fp[0]), opt(fp[1]), C.byref(st)))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        _check(lib().gdpt_progressive_denoise_regress(self.handle, C.byref(p), C.byref(g), C.byref(rg), int(feature_spp), 0,
+                                                      C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data),
+                                                      C.c_void_p(fm.ctypes.data) if features else None,
+                                                      C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
+        return (out, var_out, fm, fv, st) if features else (out, var_out, st)
+
     def denoise_demod(self, feature_spp, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
         """The albedo-demodulated non-local-means filter on buffer 0 (gdpt_progressive_denoise_demod; from 2 passes on): the session
         renders `feature_spp` samples of first-hit features along the camera rays of its own first samples, divides its mean by their
@@ -925,6 +954,67 @@ def denoise_nlm_guided_device(width, height, img_ptr, var_ptr, feat_ptr, feat_va
     opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
     _check(lib().gdpt_denoise_nlm_guided_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
                                                 C.byref(g), opt(out_ptr), opt(var_out_ptr), opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def nlm_regress(channels=None, scales=None, ridge=None):
+    """GdptNlmRegress (include/gdpt.h): the library's defaults (gdpt_nlm_default_regress: the planes 0 - 5 of a feature render, albedo
+    and shading normal, every scale 1, ridge 1e-2) with the keywords given in their places, taken literally. `channels`: the regressor
+    planes, at most 7; `scales`: one divisor per channel (None with `channels` given: 1.0 each)."""
+    r = defs.GdptNlmRegress()
+    lib().gdpt_nlm_default_regress(C.byref(r))
+    if channels is not None:
+        channels = [int(c) for c in channels]
+        if len(channels) > defs.NLM_MAX_REGRESSORS:
+            raise GdptError(f"nlm_regress: at most {defs.NLM_MAX_REGRESSORS} channels")
+        r.num_regressors = len(channels)
+        for j in range(defs.NLM_MAX_REGRESSORS):
+            r.channel[j] = channels[j] if j < len(channels) else 0
+            r.scale[j] = 1.0 if j < len(channels) else 0.0
+    if scales is not None:
+        scales = [float(x) for x in scales]
+        if len(scales) != r.num_regressors:
+            raise GdptError("nlm_regress: scales must have one entry per channel")
+        for j, x in enumerate(scales):
+            r.scale[j] = x
+    if ridge is not None:
+        r.ridge = float(ridge)
+    return r
+
+
+def denoise_nlm_regress(img, var, feat, feat_var, guide=None, regress=None, **params):
+    """denoise_nlm_guided() with a weighted linear fit of the colour on feature planes in the place of the weighted mean
+    (gdpt_denoise_nlm_regress): arguments as denoise_nlm_guided, with `regress` a GdptNlmRegress (nlm_regress(...)), None = the
+    library's default. Returns (HxWx3 fitted image, HxWx3 variance of it with the weights taken as fixed, GdptNlmStats). Pixels at
+    which a group's or a regressor's channel is not finite or has a negative variance are left out."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm_regress: img and var must be HxWx3 arrays of one shape")
+    g = guide if guide is not None else nlm_guide()
+    rg = regress if regress is not None else nlm_regress()
+    f, fv = _feature_planes(feat, feat_var, a.shape, g)
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = nlm_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_nlm_regress(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                          C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                          C.byref(p), C.byref(g), C.byref(rg), C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data),
+                                          C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_nlm_regress_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_ptr, out_ptr, var_out_ptr=None, guide=None, regress=None,
+                               stream=None, stats=True, params=None, **kw):
+    """denoise_nlm_regress() on device addresses (gdpt_denoise_nlm_regress_device); arguments as denoise_nlm_guided_device, with
+    `regress` (None = the library's default)."""
+    p = params if params is not None else nlm_params(**kw)
+    g = guide if guide is not None else nlm_guide()
+    rg = regress if regress is not None else nlm_regress()
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_regress_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
+                                                 C.byref(g), C.byref(rg), opt(out_ptr), opt(var_out_ptr), opt(stream),
+                                                 C.byref(st) if stats else None))
     return st
 
 

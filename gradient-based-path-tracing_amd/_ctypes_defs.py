@@ -151,6 +151,14 @@ class GdptNlmGuide(C.Structure):
                 ("k_f", C.c_double), ("alpha_f", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+NLM_MAX_REGRESSORS = 7
+
+
+class GdptNlmRegress(C.Structure):
+    _fields_ = [("num_regressors", C.c_int32), ("channel", C.c_int32 * NLM_MAX_REGRESSORS), ("scale", C.c_double * NLM_MAX_REGRESSORS),
+                ("ridge", C.c_double), ("reserved", C.c_int32 * 2)]
+
+
 class GdptNlmDemod(C.Structure):
     _fields_ = [("albedo_channel", C.c_int32), ("coverage_channel", C.c_int32), ("floor", C.c_double), ("reserved", C.c_int32 * 2)]
 

@@ -55,6 +55,13 @@
 //                 frequencies by the filtered coarser level (gdpt_progressive_denoise_multiscale): the blotches a single window
 //                 cannot reach. It combines with --nlm-guide, --nlm-demodulate and --nlm-var-smooth. Without --nlm-levels every
 //                 output file is what it was
+//                 --nlm-regress albedo,normal[,depth] replaces the weighted mean by a weighted linear fit of the colour on the named
+//                 first-hit features inside the window, read at the centre pixel (gdpt_progressive_denoise_regress): where the
+//                 colour is locally affine in them the weighted mean's bias vanishes, so the weights can be wide. depth needs
+//                 --nlm-depth-scale S > 0, a world-space distance (no default: the scale of depth belongs to the scene); --nlm-ridge L
+//                 sets the ridge (default 1e-2). With --nlm-regress and no --nlm-guide the guide is the albedo group alone, and with
+//                 no --nlm-k, k is 4.0: the configuration measured in DESIGN.md section 4.12. Not combined with --nlm-demodulate,
+//                 --nlm-var-smooth or --nlm-levels. Without --nlm-regress every output file is what it was
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -89,7 +96,9 @@ int main(int argc, char *argv[]) {
     double nlm_albedo_floor = 0.0;
     int nlm_var_smooth = -1;          // < 0: not given
     int nlm_levels = 0;               // 0: not given
-    std::string features_prefix = "", nlm_guide_names = "";
+    std::string features_prefix = "", nlm_guide_names = "", nlm_regress_names = "";
+    double nlm_ridge = 0.0, nlm_depth_scale = 0.0;
+    bool nlm_regress_option = false;
     int feature_spp = 0;
     double nlm_depth_tau = 0.0, nlm_kf = 0.0;
     double conf_floor = 0.0;
@@ -164,6 +173,9 @@ int main(int argc, char *argv[]) {
         else if (a == "--nlm-guide") nlm_guide_names = next();
         else if (a == "--nlm-depth-tau") { nlm_depth_tau = std::stod(next()); nlm_guide_option = true; }
         else if (a == "--nlm-kf") { nlm_kf = std::stod(next()); nlm_guide_option = true; }
+        else if (a == "--nlm-regress") nlm_regress_names = next();
+        else if (a == "--nlm-ridge") { nlm_ridge = std::stod(next()); nlm_regress_option = true; }
+        else if (a == "--nlm-depth-scale") { nlm_depth_scale = std::stod(next()); nlm_regress_option = true; }
         else if (a == "--nlm-demodulate") nlm_demodulate = true;
         else if (a == "--nlm-albedo-floor") nlm_albedo_floor = std::stod(next());
         else if (a == "--nlm-levels") {
@@ -258,13 +270,49 @@ int main(int argc, char *argv[]) {
             demod.floor = nlm_albedo_floor;
         }
     } else if (nlm_albedo_floor != 0.0) { std::cerr << "--nlm-albedo-floor needs --nlm-demodulate" << std::endl; return 2; }
+    GdptNlmRegress regress{};
+    gdpt_nlm_default_regress(&regress);
+    const bool regressed = !nlm_regress_names.empty();
+    if (regressed) {
+        if (denoised_file.empty()) { std::cerr << "--nlm-regress needs --denoised" << std::endl; return 2; }
+        if (nlm_demodulate || nlm_var_smooth >= 0 || nlm_levels > 0) {
+            std::cerr << "--nlm-regress is not combined with --nlm-demodulate, --nlm-var-smooth or --nlm-levels: the fit is defined on the session's own mean "
+                         "and variance at one scale" << std::endl;
+            return 2;
+        }
+        regress.num_regressors = 0;
+        bool seen[3] = {false, false, false};
+        size_t at = 0;
+        while (at <= nlm_regress_names.size()) {
+            const size_t comma = std::min(nlm_regress_names.find(',', at), nlm_regress_names.size());
+            const std::string name = nlm_regress_names.substr(at, comma - at);
+            const int which = name == "albedo" ? 0 : name == "normal" ? 1 : name == "depth" ? 2 : -1;
+            if (which < 0 || seen[which]) { std::cerr << "--nlm-regress takes albedo, normal and depth, each once, separated by commas" << std::endl; return 2; }
+            seen[which] = true;
+            if (which == 2 && !(nlm_depth_scale > 0.0)) {
+                std::cerr << "--nlm-regress depth needs --nlm-depth-scale S > 0, a world-space distance: the scale of depth belongs to the scene" << std::endl;
+                return 2;
+            }
+            for (int c = 0; c < (which == 2 ? 1 : 3); c++) {
+                regress.channel[regress.num_regressors] = which == 2 ? 6 : 3 * which + c;
+                regress.scale[regress.num_regressors++] = which == 2 ? nlm_depth_scale : 1.0;
+            }
+            at = comma + 1;
+        }
+        if (nlm_ridge != 0.0) {
+            if (!(nlm_ridge > 0.0)) { std::cerr << "--nlm-ridge must be > 0" << std::endl; return 2; }
+            regress.ridge = nlm_ridge;
+        }
+        if (!guided) { guide.num_groups = 1; guide.groups[0] = GdptNlmFeatureGroup{0, 3, 1e-3}; }
+        if (!nlm_k_set) nlm.k = 4.0;
+    } else if (nlm_regress_option) { std::cerr << "--nlm-ridge and --nlm-depth-scale need --nlm-regress" << std::endl; return 2; }
     if (nlm_var_smooth >= 0 && denoised_file.empty()) { std::cerr << "--nlm-var-smooth needs --denoised" << std::endl; return 2; }
     if (nlm_levels > 0 && denoised_file.empty()) { std::cerr << "--nlm-levels needs --denoised" << std::endl; return 2; }
     if (!features_prefix.empty() && (multi.num_devices > 0 || !sample_devices.empty())) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
     }
-    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
     if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
@@ -377,7 +425,11 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                if (nlm_levels > 0) {
+                if (regressed) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    rc = gdpt_progressive_denoise_regress(session, &nlm, &guide, &regress, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
+                                                          filtered.data(), nullptr, nullptr, nullptr, &nlm_stats);
+                } else if (nlm_levels > 0) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     GdptVarSmoothParams sp{};
                     gdpt_var_smooth_default_params(&sp);
@@ -474,7 +526,8 @@ int main(int argc, char *argv[]) {
             if (!denoised_file.empty())
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
-                          << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
+                          << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string())
+                          << (regressed ? ", first-order regression on " + nlm_regress_names + " (ridge " + std::to_string(regress.ridge) + ")" : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
                           << (nlm_var_smooth >= 0 ? ", variance smoothed over radius " + std::to_string(smooth_stats.radius) : std::string())
                           << (nlm_levels > 0 ? ", " + std::to_string(pyramid_stats.levels) + " levels in " + std::to_string(pyramid_stats.total_ms) + " ms (the figures before are the finest level's)" : std::string())
                           << ", written to "

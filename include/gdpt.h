@@ -764,6 +764,62 @@ int gdpt_progressive_denoise_guided(GdptProgressive *session, const GdptNlmParam
                                     double *var_out /* nullable */, double *features /* nullable */, double *features_var /* nullable */,
                                     GdptNlmStats *stats /* nullable */);
 
+/* ---- a first-order feature regression on the non-local-means weights (not part of the reference) ----
+ * Every filter above is a weighted mean, which is biased wherever the signal has a gradient inside the window; the guide's only
+ * answer is to lower weights. Here the weights stay and the weighted mean becomes a weighted linear fit of the colour on feature
+ * planes inside the window, read at the centre pixel (Bitterli, Rousselle, Moon, Iglesias-Guitian, Adler, Mitchell, Jarosz, Novak,
+ * "Nonlinearly weighted first-order regression for denoising Monte Carlo renderings", EGSR 2016, section 4; the successor of
+ * Rousselle, Manzi, Zwicker 2013): where the colour is locally affine in the regressors the bias vanishes.
+ * The definition extends gdpt_denoise_nlm_guided's; img, var, feat, feat_var, GdptNlmParams and GdptNlmGuide are its. The regressors
+ * are m = num_regressors planes c_j = channel[j-1], j = 1 .. m, each divided by scale[j-1] > 0; d = 1 + m unknowns per colour channel.
+ * A pixel is VALID if it is valid for the guided filter and every regressor plane is finite at it with variance >= 0 (the channels
+ * that count are those of the groups together with those of the regressors). On this validity, for valid p and p+o:
+ *   w_o(p)   = the guided filter's weight exp(-max(D_o(p), D^f_o(p))), 0 as there   (w_0(p) = 1)
+ *   z_0      = 1,   z_j(p,o) = (g_{c_j}(p+o) - g_{c_j}(p)) / scale[j-1]
+ *   A_ij     = sum_o (w_o z_i) z_j  (i >= j; A is symmetric),   b_c,i = sum_o (w_o z_i) u_c(p+o),   W = A_00 = sum_o w_o
+ *              every entry accumulated on its own over |o|_inf <= r in row-major order of o; then A_jj += ridge W for j >= 1
+ * A is symmetric positive definite: the tap o = 0 gives e_0 e_0^T with weight 1, every other diagonal entry gets ridge W >= ridge > 0.
+ * Four right-hand sides, A beta_c = b_c (c = 0, 1, 2) and A q = e_0, are solved by LDL^T without pivoting; no square root is taken.
+ * The order, every sum running over k in index order, subtracted term by term from its first operand:
+ *   for j = 0 .. d-1:   t_k = L_jk D_k (k < j);   D_j = A_jj - sum_{k<j} L_jk t_k;
+ *                       for i = j+1 .. d-1:   L_ij = (A_ij - sum_{k<j} L_ik t_k) / D_j
+ *   for i = 0 .. d-1:   y_i = rhs_i - sum_{k<i} L_ik y_k;       then y_i = y_i / D_i for every i;
+ *   for i = d-1 .. 0:   x_i = y_i - sum_{k>i} L_ki x_k
+ *   out_c(p)     = beta_c[0]
+ *   var_out_c(p) = sum_o (w_o(p) l_o(p))^2 v_c(p+o),   l_o = q_0 + sum_{j=1..m} q_j z_j(p,o) (terms added in index order)
+ * var_out is the variance of the linear estimator under fixed weights and carries the caveat of error_out above. An invalid p keeps
+ * its input triples bit for bit and is counted; the film sums and GdptNlmStats are gdpt_denoise_nlm's. r = 0 returns the input bits
+ * (W = 1, every z = 0). m = 0 is the guided filter, out = (sum w u) / W and var_out = sum (w / W)^2 v, equal to
+ * gdpt_denoise_nlm_guided's up to the rounding of where the division stands, not bit for bit.
+ * Defaults: the six planes 0 .. 5 (albedo and shading normal of a feature render), every scale 1, ridge 1e-2. Depth has no default
+ * scale as it has no default tau: its unit is the scene's. These rest on a synthetic film alone. */
+#define GDPT_NLM_MAX_REGRESSORS 7
+typedef struct GdptNlmRegress { int32_t num_regressors; int32_t channel[GDPT_NLM_MAX_REGRESSORS];
+                                double scale[GDPT_NLM_MAX_REGRESSORS]; double ridge; int32_t reserved[2]; } GdptNlmRegress;
+void gdpt_nlm_default_regress(GdptNlmRegress *r);   /* 6 regressors: planes 0..5 (albedo, normal), every scale 1.0, ridge 1e-2 */
+/* Device pointers on the current device. What gdpt_denoise_nlm_guided_device refuses is refused, and, naming the field:
+ * num_regressors outside [0, 7]; a channel outside [0, guide->num_channels); a channel listed twice; a scale that is non-finite or
+ * <= 0; a ridge that is non-finite or <= 0; non-zero reserved; NULL d_feat or d_feat_var when num_regressors > 0 or num_groups > 0.
+ * params, guide == NULL: gdpt_nlm_default_params, gdpt_nlm_default_guide (the library picks no other k or groups for the regression;
+ * the lajolla CLI does); regress == NULL: gdpt_nlm_default_regress. Enqueue-only with stats == NULL; scratch per (device, stream)
+ * as gdpt_denoise_nlm_device. When neither d_var_out nor stats is asked for, the second sweep over the window is not run. */
+int gdpt_denoise_nlm_regress_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                    const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                                    const GdptNlmRegress *regress /* NULL: defaults */, double *d_out, double *d_var_out /* nullable */,
+                                    void *stream, GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm_regress(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                             const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                             const GdptNlmRegress *regress /* NULL: defaults */, double *out, double *var_out /* nullable */,
+                             GdptNlmStats *stats /* nullable */);
+/* The regression on a session's buffer 0, built as gdpt_progressive_denoise_guided in every respect: the session renders its features
+ * on its stream, at least 2 passes, a group's total included, 2 <= feature_spp <= budget_spp; guide->num_channels must be
+ * GDPT_FEATURE_CHANNELS. Blocking. */
+int gdpt_progressive_denoise_regress(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */,
+                                     const GdptNlmGuide *guide /* NULL: defaults */, const GdptNlmRegress *regress /* NULL: defaults */,
+                                     int feature_spp, int on_device, double *out, double *var_out /* nullable */,
+                                     double *features /* nullable */, double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
+
 /* ---- the non-local-means filter on the albedo-demodulated mean (not part of the reference) ----
  * The guided filter keeps a texture only by lowering weights across albedo differences: exactly where a surface is textured fewer
  * pixels are averaged and more noise stays. Here the illumination is filtered, not the colour: the mean is divided by the first-hit
