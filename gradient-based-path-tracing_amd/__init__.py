@@ -108,6 +108,12 @@ def lib():
         L.gdpt_denoise_nlm_demod_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_demod.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, nlp, ngp, ndp, vp, vp, nls]
         L.gdpt_progressive_denoise_demod.argtypes = [vp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        atp = C.POINTER(defs.GdptAtrousParams)
+        L.gdpt_atrous_default_params.argtypes = [atp]
+        L.gdpt_atrous_default_params.restype = None
+        L.gdpt_denoise_atrous_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, atp, ngp, ndp, vp, vp, vp, nls]
+        L.gdpt_denoise_atrous.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, atp, ngp, ndp, vp, vp, nls]
+        L.gdpt_progressive_denoise_atrous.argtypes = [vp, atp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
         vsp, vss = C.POINTER(defs.GdptVarSmoothParams), C.POINTER(defs.GdptVarSmoothStats)
         L.gdpt_var_smooth_default_params.argtypes = [vsp]
         L.gdpt_var_smooth_default_params.restype = None
@@ -582,6 +588,29 @@ class Progressive:
         _check(lib().gdpt_progressive_denoise_demod(self.handle, C.byref(p), g, C.byref(d), int(feature_spp), 0, C.c_void_p(out.ctypes.data),
                                                     C.c_void_p(var_out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
                                                     C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
+        return (out, var_out, fm, fv, st) if features else (out, var_out, st)
+
+    def denoise_atrous(self, feature_spp=0, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
+        """The edge-avoiding a-trous wavelet filter on buffer 0 (gdpt_progressive_denoise_atrous; from 2 passes on), the cheap filter:
+        `guide`: a GdptNlmGuide (nlm_guide(...)) over the 8 planes, None = NO feature term; `demod`: a GdptNlmDemod (nlm_demod(...)),
+        None = NO demodulation; with either the session renders `feature_spp` samples of first-hit features as denoise_guided does,
+        with neither it renders none and `feature_spp` is ignored (`features` must be False then). `params`: the keywords of
+        atrous_params. Returns and device-memory form as denoise_guided."""
+        p, st = atrous_params(**params), defs.GdptNlmStats()
+        g = C.byref(guide) if guide is not None else None
+        d = C.byref(demod) if demod is not None else None
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            _check(lib().gdpt_progressive_denoise_atrous(self.handle, C.byref(p), g, d, int(feature_spp), 1, opt(out_ptr), opt(var_out_ptr),
+                                                         opt(fp[0]), opt(fp[1]), C.byref(st)))
+            return st
+        out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        _check(lib().gdpt_progressive_denoise_atrous(self.handle, C.byref(p), g, d, int(feature_spp), 0, C.c_void_p(out.ctypes.data),
+                                                     C.c_void_p(var_out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
+                                                     C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
         return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
     def denoise_smoothed(self, kind="plain", radius=None, feature_spp=0, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None,
@@ -1067,6 +1096,68 @@ def denoise_nlm_demod_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var
     _check(lib().gdpt_denoise_nlm_demod_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
                                                C.byref(p), C.byref(guide) if guide is not None else None, C.byref(d), opt(out_ptr), opt(var_out_ptr),
                                                opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def atrous_params(levels=None, first_level=None, k=None, alpha=None, epsilon=None):
+    """GdptAtrousParams (include/gdpt.h): the library's defaults (gdpt_atrous_default_params: 5 levels from level 0, k 2.0, alpha 1,
+    epsilon 1e-10) with the keywords given in their places, taken literally."""
+    p = defs.GdptAtrousParams()
+    lib().gdpt_atrous_default_params(C.byref(p))
+    if levels is not None:
+        p.levels = int(levels)
+    if first_level is not None:
+        p.first_level = int(first_level)
+    if k is not None:
+        p.k = float(k)
+    if alpha is not None:
+        p.alpha = float(alpha)
+    if epsilon is not None:
+        p.epsilon = float(epsilon)
+    return p
+
+
+def denoise_atrous(img, var, feat=None, feat_var=None, guide=None, demod=None, **params):
+    """The edge-avoiding a-trous wavelet filter on the GPU (gdpt_denoise_atrous), the cheap filter: `levels` passes of a 5x5 B3-spline
+    kernel whose taps are spread by 1, 2, 4, ... pixels, every tap weighted by the variance-cancelling pixel distance of denoise_nlm,
+    capped by the feature distance of `guide` (a GdptNlmGuide, nlm_guide(...); None = NO feature term), on img / a~ when `demod` (a
+    GdptNlmDemod, nlm_demod(...); None = NO demodulation) is given. `img`, `var`: HxWx3 float64; `feat`, `feat_var`: planar
+    (num_channels, H, W) float64 arrays, needed with a group or a demod block; `params`: the keywords of atrous_params. Returns
+    (HxWx3 filtered image, HxWx3 variance of it with the weights taken as fixed, GdptNlmStats); stats.window_radius is the reach of
+    the last level."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_atrous: img and var must be HxWx3 arrays of one shape")
+    f = fv = None
+    channels = guide.num_channels if guide is not None else 0
+    if feat is not None and feat_var is not None:
+        f = np.ascontiguousarray(feat, dtype=np.float64)
+        fv = np.ascontiguousarray(feat_var, dtype=np.float64)
+        if f.ndim != 3 or f.shape != fv.shape or f.shape[1:] != a.shape[:2]:
+            raise GdptError("denoise_atrous: feat and feat_var must be (num_channels, H, W) arrays of one shape")
+        channels = int(f.shape[0])
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    p, st = atrous_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_atrous(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                     C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                     channels, C.byref(p), C.byref(guide) if guide is not None else None,
+                                     C.byref(demod) if demod is not None else None, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data),
+                                     C.byref(st)))
+    return out, var_out, st
+
+
+def denoise_atrous_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_ptr, num_channels, out_ptr, var_out_ptr=None, guide=None,
+                          demod=None, stream=None, stats=True, params=None, **kw):
+    """denoise_atrous() on device addresses (gdpt_denoise_atrous_device); arguments as denoise_nlm_demod_device, with `guide` and
+    `demod` None = none of either, and `params` a GdptAtrousParams taken as it is (else the keywords of atrous_params)."""
+    p = params if params is not None else atrous_params(**kw)
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_atrous_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
+                                            C.byref(p), C.byref(guide) if guide is not None else None,
+                                            C.byref(demod) if demod is not None else None, opt(out_ptr), opt(var_out_ptr), opt(stream),
+                                            C.byref(st) if stats else None))
     return st
 
 

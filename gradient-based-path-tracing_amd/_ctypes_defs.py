@@ -163,6 +163,14 @@ class GdptNlmDemod(C.Structure):
     _fields_ = [("albedo_channel", C.c_int32), ("coverage_channel", C.c_int32), ("floor", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+ATROUS_MAX_LEVELS = 6
+
+
+class GdptAtrousParams(C.Structure):
+    _fields_ = [("levels", C.c_int32), ("first_level", C.c_int32), ("k", C.c_double), ("alpha", C.c_double), ("epsilon", C.c_double),
+                ("reserved", C.c_int32 * 2)]
+
+
 VAR_SMOOTH_MAX_RADIUS = 4
 DENOISE_PLAIN, DENOISE_GUIDED, DENOISE_DEMOD = 0, 1, 2
 

@@ -28,6 +28,7 @@
 #include "progressive_internal.h"
 #include "denoise_nlm.h"
 #include "nlm_regress.h"
+#include "denoise_atrous.h"
 #include "variance_smooth.h"
 #include "nlm_pyramid.h"
 
@@ -608,7 +609,51 @@ int gdpt_progressive_denoise_demod(GdptProgressive *session, const GdptNlmParams
     });
 }
 
-int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind, const GdptVarSmoothParams *smooth, const GdptNlmParams *nlm,
+int gdpt_progressive_denoise_atrous(GdptProgressive *session, const GdptAtrousParams *params, const GdptNlmGuide *guide, const GdptNlmDemod *demod,
+                                    int feature_spp, int on_device, double *out, double *var_out, double *features, double *features_var,
+                                    GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_atrous";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        GdptAtrousParams p;
+        if (params) p = *params; else gdpt_atrous_default_params(&p);
+        gdpt::atrous_check_params(who, p);
+        if (guide) {                      // (NULL: no feature term)
+            gdpt::nlm_check_guide(who, *guide);
+            if (guide->num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
+        }
+        if (demod) gdpt::nlm_check_demod(who, *demod, GDPT_FEATURE_CHANNELS);
+        if ((guide && guide->num_groups > 0) || demod) {
+            filter_with_features(who, *session, feature_spp, on_device, out, var_out, features, features_var, stats,
+                                 [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
+                                     gdpt::denoise_atrous_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, guide, demod, d_out, d_var_out, s.stream, st);
+                                 });
+            return;
+        }
+        // neither a group nor a demod block: no features are rendered (as gdpt_progressive_denoise)
+        if (features || features_var) throw std::runtime_error(who + ": features need a group or a demod block (none are rendered without)");
+        GdptProgressive &s = *session;
+        if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        compute_variances(s);
+        double *d_out = out, *d_var_out = var_out;
+        if (!on_device) {                 // through planes of the session's on the way to host memory
+            for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
+            d_out = s.nlm_buf[0]; d_var_out = var_out ? s.nlm_buf[1].data() : nullptr;
+        }
+        GdptNlmStats st{};                // (asked for always: the call is blocking)
+        gdpt::denoise_atrous_launch(s.w, s.h, s.mean[0], s.var[0], nullptr, nullptr, p, nullptr, nullptr, d_out, d_var_out, s.stream, &st);
+        if (!on_device) {
+            copy_out(s, out, d_out, 0);
+            copy_out(s, var_out, d_var_out, 0);
+            ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise)");
+        }
+        if (stats) *stats = st;
+    });
+}
+
+int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind,const GdptVarSmoothParams *smooth, const GdptNlmParams *nlm,
                                       const GdptNlmGuide *guide, const GdptNlmDemod *demod, int feature_spp, int on_device, double *out,
                                       double *var_out, double *smoothed_var, double *features, double *features_var, GdptNlmStats *stats,
                                       GdptVarSmoothStats *smooth_stats) {

@@ -62,6 +62,14 @@
 //                 sets the ridge (default 1e-2). With --nlm-regress and no --nlm-guide the guide is the albedo group alone, and with
 //                 no --nlm-k, k is 4.0: the configuration measured in DESIGN.md section 4.12. Not combined with --nlm-demodulate,
 //                 --nlm-var-smooth or --nlm-levels. Without --nlm-regress every output file is what it was
+//                 --atrous-levels L (1..6) writes the edge-avoiding a-trous wavelet filter's result in the place of the non-local
+//                 means' (gdpt_progressive_denoise_atrous), the cheap filter for previews: L passes of a 5 x 5 B3-spline kernel whose
+//                 taps are spread by 1, 2, 4, .. pixels, every tap weighted by the variance-cancelling pixel distance and capped by
+//                 the feature distance. --atrous-k K sets its k (default 2.0). The guide is --nlm-guide's (with --nlm-depth-tau,
+//                 --nlm-kf), albedo,normal when the flag is absent; --nlm-demodulate, --nlm-albedo-floor and --feature-spp act as
+//                 they do above, and under --nlm-demodulate the default guide is the normal alone. Not combined with --nlm-window,
+//                 --nlm-patch, --nlm-k, --nlm-var-smooth, --nlm-levels or --nlm-regress. Without --atrous-levels every output file
+//                 is what it was
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -99,6 +107,9 @@ int main(int argc, char *argv[]) {
     std::string features_prefix = "", nlm_guide_names = "", nlm_regress_names = "";
     double nlm_ridge = 0.0, nlm_depth_scale = 0.0;
     bool nlm_regress_option = false;
+    int atrous_levels = 0;            // 0: not given
+    double atrous_k = 0.0;
+    bool atrous_k_set = false;
     int feature_spp = 0;
     double nlm_depth_tau = 0.0, nlm_kf = 0.0;
     double conf_floor = 0.0;
@@ -176,6 +187,11 @@ int main(int argc, char *argv[]) {
         else if (a == "--nlm-regress") nlm_regress_names = next();
         else if (a == "--nlm-ridge") { nlm_ridge = std::stod(next()); nlm_regress_option = true; }
         else if (a == "--nlm-depth-scale") { nlm_depth_scale = std::stod(next()); nlm_regress_option = true; }
+        else if (a == "--atrous-levels") {
+            atrous_levels = std::stoi(next());
+            if (atrous_levels < 1 || atrous_levels > GDPT_ATROUS_MAX_LEVELS) { std::cerr << "--atrous-levels takes a number of levels from 1 to 6" << std::endl; return 2; }
+        }
+        else if (a == "--atrous-k") { atrous_k = std::stod(next()); atrous_k_set = true; }
         else if (a == "--nlm-demodulate") nlm_demodulate = true;
         else if (a == "--nlm-albedo-floor") nlm_albedo_floor = std::stod(next());
         else if (a == "--nlm-levels") {
@@ -306,13 +322,31 @@ int main(int argc, char *argv[]) {
         if (!guided) { guide.num_groups = 1; guide.groups[0] = GdptNlmFeatureGroup{0, 3, 1e-3}; }
         if (!nlm_k_set) nlm.k = 4.0;
     } else if (nlm_regress_option) { std::cerr << "--nlm-ridge and --nlm-depth-scale need --nlm-regress" << std::endl; return 2; }
+    GdptAtrousParams atrous{};
+    gdpt_atrous_default_params(&atrous);
+    const bool atrous_on = atrous_levels > 0;
+    if (atrous_on) {
+        if (denoised_file.empty()) { std::cerr << "--atrous-levels needs --denoised" << std::endl; return 2; }
+        if (nlm_option || nlm_var_smooth >= 0 || nlm_levels > 0 || regressed) {
+            std::cerr << "--atrous-levels is not combined with --nlm-window, --nlm-patch, --nlm-k, --nlm-var-smooth, --nlm-levels or --nlm-regress: the a-trous "
+                         "filter has no window, no patch and a k of its own (--atrous-k), and is not composed with the other filters" << std::endl;
+            return 2;
+        }
+        atrous.levels = atrous_levels;
+        if (atrous_k_set) {
+            if (!(atrous_k > 0.0)) { std::cerr << "--atrous-k must be > 0" << std::endl; return 2; }
+            atrous.k = atrous_k;
+        }
+        // without --nlm-guide: albedo and normal (the default guide), the normal alone over a demodulated mean
+        if (!guided && nlm_demodulate) { guide.num_groups = 1; guide.groups[0] = GdptNlmFeatureGroup{3, 3, 1e-3}; }
+    } else if (atrous_k_set) { std::cerr << "--atrous-k needs --atrous-levels" << std::endl; return 2; }
     if (nlm_var_smooth >= 0 && denoised_file.empty()) { std::cerr << "--nlm-var-smooth needs --denoised" << std::endl; return 2; }
     if (nlm_levels > 0 && denoised_file.empty()) { std::cerr << "--nlm-levels needs --denoised" << std::endl; return 2; }
     if (!features_prefix.empty() && (multi.num_devices > 0 || !sample_devices.empty())) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
     }
-    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed && !atrous_on) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
     if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
@@ -425,7 +459,12 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                if (regressed) {
+                if (atrous_on) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    rc = gdpt_progressive_denoise_atrous(session, &atrous, &guide, nlm_demodulate ? &demod : nullptr,
+                                                         feature_spp > 0 ? feature_spp : std::min(16, budget), 0, filtered.data(), nullptr, nullptr, nullptr,
+                                                         &nlm_stats);
+                } else if (regressed) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     rc = gdpt_progressive_denoise_regress(session, &nlm, &guide, &regress, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
                                                           filtered.data(), nullptr, nullptr, nullptr, &nlm_stats);
@@ -527,6 +566,7 @@ int main(int argc, char *argv[]) {
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
                           << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string())
+                          << (atrous_on ? ", a-trous wavelet filter over " + std::to_string(atrous.levels) + " levels (window: the reach of the last)" : std::string())
                           << (regressed ? ", first-order regression on " + nlm_regress_names + " (ridge " + std::to_string(regress.ridge) + ")" : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
                           << (nlm_var_smooth >= 0 ? ", variance smoothed over radius " + std::to_string(smooth_stats.radius) : std::string())
                           << (nlm_levels > 0 ? ", " + std::to_string(pyramid_stats.levels) + " levels in " + std::to_string(pyramid_stats.total_ms) + " ms (the figures before are the finest level's)" : std::string())

@@ -820,6 +820,66 @@ int gdpt_progressive_denoise_regress(GdptProgressive *session, const GdptNlmPara
                                      int feature_spp, int on_device, double *out, double *var_out /* nullable */,
                                      double *features /* nullable */, double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
 
+/* ---- an edge-avoiding a-trous wavelet filter with variance-guided weights: the cheap filter (not part of the reference) ----
+ * Every filter above weighs a (2r+1)^2 window by patch distances, 441 offsets of 49 patch taps at the defaults. This one runs L
+ * passes of a 5x5 B3-spline kernel whose taps are spread by 1, 2, 4, ... pixels, 25 L taps per pixel, and reaches +-62 pixels in five
+ * passes (Dammertz, Sewtz, Hanika, Lensch, "Edge-avoiding A-Trous wavelet transform for fast global illumination filtering", HPG
+ * 2010; Schied et al., "Spatiotemporal variance-guided filtering", HPG 2017). The edge-stopping weight is the distance the filters
+ * above already use: e_o(p) of gdpt_denoise_nlm at patch radius 0, capped by the feature distance of gdpt_denoise_nlm_guided; the
+ * filter can sit between the two steps of gdpt_denoise_nlm_demod (GdptNlmDemod, below).
+ * Inputs: those of gdpt_denoise_nlm_guided (img, var W*H*3 doubles, interleaved; feat, feat_var num_channels channel-planar planes; a
+ * GdptNlmGuide, NULL or no group: no feature term) and an optional GdptNlmDemod. Parameters: 1 <= levels, 0 <= first_level,
+ * first_level + levels <= GDPT_ATROUS_MAX_LEVELS; level i = 0 .. levels-1 uses the step s_i = 2^(first_level + i); k, alpha, epsilon
+ * as gdpt_denoise_nlm's.
+ * A pixel is VALID if it is valid for the guided filter on (img, var, the groups' channels) and, with a demod block, its albedo and
+ * coverage values are valid as gdpt_denoise_nlm_demod defines them. The valid set is fixed by the inputs: it is the same at every
+ * level. An invalid pixel keeps its input bits in out and var_out, is counted once in pixels_left_out and is never a tap.
+ *   1. u_0 = u, v_0 = v; with a demod block the quotients u / a~, v / a~^2 of step 1 of gdpt_denoise_nlm_demod, in those operations.
+ *   2. for each level i and valid p, over the taps (a, b) in {-2..2}^2, a the row, b the column, in row-major order, o = (b s_i, a s_i),
+ *      a tap counting only if p+o lies in the film and is valid:
+ *        e   = e_o(p) of gdpt_denoise_nlm on u_i, v_i: the channel terms summed as (t0 + t1) + t2 and divided by 3;   D = max(0, e)
+ *        D^f = the guided filter's feature distance of the pair (p, p+o) on feat, feat_var (the same at every level; no group: 0)
+ *        w   = (h_a h_b) exp(-max(D, D^f)),   h = (1/16, 1/4, 3/8, 1/4, 1/16)
+ *        Wsum += w,   num_c += w u_i,c(p+o),   vnum_c += (w w) v_i,c(p+o)
+ *      u_{i+1},c(p) = num_c / Wsum,   v_{i+1},c(p) = vnum_c / (Wsum Wsum).   The centre tap has D = 0 and weight 9/64, so Wsum > 0.
+ *      Every level reads the previous level's planes only, never its own output.
+ *   3. out = u_L, var_out = v_L; with a demod block multiplied back as in step 3 of gdpt_denoise_nlm_demod.
+ * GdptNlmStats: sum_var_in, sum_sq_in over the original var and img of the valid pixels, sum_var_out, sum_sq_out over the final
+ * outputs; window_radius reports the reach 2 s of the last level, patch_radius 0; filter_ms covers all levels. var_out takes the
+ * weights as fixed AND ignores the correlation that earlier levels introduce between pixels: from the second level on the taps are
+ * no longer independent, so var_out (and error_out with it) underestimates, more than error_out of the filters above already does.
+ * Exact, bit for bit: one call with levels = n equals n successive calls with levels = 1 and first_level = f, f + 1, ..., each fed
+ * the previous call's out and var_out, when there is no demod block; no group, or features that are constant over the film with
+ * variance 0, give the unguided result; a demod block with albedo 1 and coverage 1 gives the undemodulated result. */
+#define GDPT_ATROUS_MAX_LEVELS 6
+typedef struct GdptAtrousParams { int32_t levels, first_level; double k, alpha, epsilon; int32_t reserved[2]; } GdptAtrousParams;
+void gdpt_atrous_default_params(GdptAtrousParams *p);   /* 5, 0, 2.0, 1.0, 1e-10 */
+struct GdptNlmDemod;   /* defined with gdpt_denoise_nlm_demod, below */
+/* Device pointers on the current device; one kernel per level, enqueued on `stream`. Refused before any device call, naming the field:
+ * NULL d_img, d_var or d_out; an output aliasing an input or the other output; width or height < 1; levels or first_level outside
+ * their ranges; k, alpha, epsilon non-finite or outside gdpt_denoise_nlm's ranges; non-zero reserved; num_channels outside [0,
+ * GDPT_NLM_MAX_CHANNELS]; what gdpt_denoise_nlm_demod_device refuses for the guide and the demod block; NULL d_feat or d_feat_var when
+ * a group or a demod block needs them. Enqueue-only with stats == NULL; scratch (the sums and the planes between the levels) per
+ * (device, stream) as gdpt_denoise_nlm_device, dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_denoise_atrous_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                               int num_channels, const GdptAtrousParams *params /* NULL: defaults */,
+                               const GdptNlmGuide *guide /* NULL: no feature term, as in the demod entries */,
+                               const struct GdptNlmDemod *demod /* NULL: no demodulation */, double *d_out, double *d_var_out /* nullable */,
+                               void *stream, GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_atrous(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                        int num_channels, const GdptAtrousParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: none */,
+                        const struct GdptNlmDemod *demod /* NULL: none */, double *out, double *var_out /* nullable */,
+                        GdptNlmStats *stats /* nullable */);
+/* The filter on a session's buffer 0, built as gdpt_progressive_denoise_demod: the session renders its features on its stream, at
+ * least 2 passes, Path sessions, the primal of GradPath sessions and a group's total, 2 <= feature_spp <= budget_spp; a guide's
+ * num_channels must be GDPT_FEATURE_CHANNELS. With neither a group nor a demod block no features are rendered, feature_spp is ignored
+ * and features, features_var must be NULL. Blocking. */
+int gdpt_progressive_denoise_atrous(GdptProgressive *session, const GdptAtrousParams *params /* NULL: defaults */,
+                                    const GdptNlmGuide *guide /* NULL: none */, const struct GdptNlmDemod *demod /* NULL: none */,
+                                    int feature_spp, int on_device, double *out, double *var_out /* nullable */,
+                                    double *features /* nullable */, double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
+
 /* ---- the non-local-means filter on the albedo-demodulated mean (not part of the reference) ----
  * The guided filter keeps a texture only by lowering weights across albedo differences: exactly where a surface is textured fewer
  * pixels are averaged and more noise stays. Here the illumination is filtered, not the colour: the mean is divided by the first-hit

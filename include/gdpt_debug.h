@@ -41,7 +41,10 @@
  *                               tests in a row) instead of two records per trip with the cursor in the leaf reference; same route name
  *   nlm_direct (0/1)            gdpt_denoise_nlm*: the direct form of the filter (one thread per pixel, every patch distance summed
  *                               from global memory: the literal definition) instead of the tiled form (a block's tile and halo
- *                               staged in LDS, separable patch sums)
+ *                               staged in LDS, separable patch sums). gdpt_denoise_atrous* picks a form per level: 0 the staged
+ *                               form up to step 4 and the direct form beyond (the measured routes), 1 the direct form at every
+ *                               step, 2 the staged form at every step that has one (1 - 8), for measurements; the other filters
+ *                               read 2 as 1
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
  *
