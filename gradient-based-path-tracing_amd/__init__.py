@@ -175,6 +175,7 @@ def lib():
         L.gdpt_debug_get_stamps.argtypes = [C.POINTER(C.c_double)]
         L.gdpt_debug_get_stamps.restype = None
         L.gdpt_debug_last_route.restype = C.c_char_p
+        L.gdpt_debug_last_dct_shape.restype = C.c_char_p
         L.gdpt_debug_overlapped_launches.argtypes = [vp]
         L.gdpt_debug_overlapped_launches.restype = C.c_longlong
         L.gdpt_debug_leaf_histogram.argtypes = [vp, C.POINTER(C.c_int32)]
@@ -1598,6 +1599,11 @@ class debug_knobs:
         return lib().gdpt_debug_last_route().decode()
 
     @staticmethod
+    def last_dct_shape():
+        """Shape of the folded GEMMs of this thread's last GDPT_SOLVER_DCT_MFMA solve (include/gdpt_debug.h: gdpt_debug_last_dct_shape)."""
+        return lib().gdpt_debug_last_dct_shape().decode()
+
+    @staticmethod
     def route_names():
         """Every route name the library can report (include/gdpt_debug.h: gdpt_debug_route_names)."""
         n = lib().gdpt_debug_route_names(None, 0)
@@ -1675,7 +1681,7 @@ class debug_knobs:
         """GDPT_FORCE_EAGER=1 -> force_eager=1 ... for the manual sweep scripts (tests/sweep_*.py, tune_render.py)."""
         environ = os.environ if environ is None else environ
         names = ("force_eager", "log2k", "keep_frac", "search_frac", "blocks_per_cu", "no_lds_scene", "lds_wide",
-                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct")
+                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct", "lds_fixed_layout")
         lib().gdpt_debug_knobs_reset()
         for n in names:
             v = environ.get("GDPT_" + n.upper())

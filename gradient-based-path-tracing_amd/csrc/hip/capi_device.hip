@@ -244,7 +244,7 @@ GdptLaunchScratch &claim_scratch(GdptScene *sc, bool overlap, bool capturing, si
     }
     if (!overlap) {
         if (!capturing) {
-            sc->join();                    // the launch, and a host read of the counters behind it, have the handle to themselves
+            sc->join();                    // the launch, and a host read of the counters behind it, have the handle to themselves (and the hint is cleared)
             if (ss.used) ck(hipStreamWaitEvent(stream, ss.released, 0), "hipStreamWaitEvent(launch scratch)");   // (another caller's stream)
         }
     } else {
@@ -322,7 +322,11 @@ void run_launch(GdptScene *sc, const gdpt::RenderLaunch &rl, const ScratchClaim 
     if (stamped) ck(hipMemsetAsync(&rl.counters->stamps[12], 0xFF, 2 * sizeof(unsigned long long), ks), "hipMemsetAsync(stamps)");   // min slots
     if (stats) ck(hipEventRecord(sc->ev0, stream), "hipEventRecord");
     gdpt::launch_render(sc->view, rl, stream);
-    if (rl.kernel_stream) sc->overlapped++;               // (a launch that threw leaves the set parity where it was)
+    if (rl.kernel_stream) {
+        sc->overlapped++;                                 // (a launch that threw leaves the set parity where it was)
+        // a solve enqueued from here on may find this kernel's blocks resident: tell it what they leave (render_kernels.h)
+        gdpt::set_render_beside_hint(sc->device, sc, gdpt::render_free_lds_per_cu(sc->view, rl));
+    }
     // the set is free again behind this point of the caller's stream (a launch recorded into a graph leaves no event of ours in it)
     if (claim.record_release) { ck(hipEventRecord(claim.set->released, stream), "hipEventRecord(launch scratch)"); claim.set->used = true; }
     if (!stats) return;
@@ -360,6 +364,8 @@ void render_device_impl(GdptScene *sc, const GdptRenderParams *params, int scene
     RenderLaunch rl = begin_launch(sc, b, false, sc->traits.plan_take_pct, stream, stats, &claim);
     rl.img = img; rl.cx0 = cx0; rl.cy0 = cy0; rl.cx1 = cx1; rl.cy1 = cy1;
     rl.wide_stack_need = GDPT_HBM_BVH8 ? std::min(sc->traits.wide8_stack_need, GDPT_BVH_MAX_DEPTH) : sc->traits.wide_stack_need;   // LDS slots; the BVH8 may go on in private memory
+    rl.lds_stack_need = walks_bvh2(rl.route) ? sc->traits.bvh_depth : sc->traits.wide_stack_need;      // (the tree the LDS copy holds)
+    rl.lds_fixed_layout = debug_knob_int("lds_fixed_layout", 0) != 0;
     rl.replay_per_step = debug_knob_int("replay_per_step", 0);
     const long long items = band_slots(sc->view.cam.width, b.row_end - b.row_begin) * rl.plan.n;
     if (needs_bounce_log(rl.route)) {
@@ -485,6 +491,7 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
 
 // include/gdpt_debug.h: which kernel the calling thread's last render launched (render_kernels.hip: launch_render)
 const char *gdpt_debug_last_route(void) { return gdpt::last_route(); }
+const char *gdpt_debug_last_dct_shape(void) { return gdpt::last_dct_shape(); }
 long long gdpt_debug_overlapped_launches(const GdptScene *scene) { return scene ? (long long)scene->overlapped : -1; }
 int gdpt_debug_leaf_histogram(const GdptScene *scene, int32_t hist[4]) {
     return gdpt::guarded([&]() {

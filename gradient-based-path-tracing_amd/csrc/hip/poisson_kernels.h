@@ -24,6 +24,9 @@ PoissonResult assemble_solve_device(int w, int h, const double *img, const doubl
                                     double *d_c, double *d_cx, double *d_cy, double alpha, double *d_out, int solver, double tol, int max_iters,
                                     hipStream_t stream, bool timed);
 
+// Shape of the folded GEMMs of the calling thread's last GDPT_SOLVER_DCT_MFMA solve (include/gdpt_debug.h: gdpt_debug_last_dct_shape).
+const char *last_dct_shape();
+
 // Launch geometry of the element-wise kernels (the CG's cg_*, the DCT solvers' right-hand side, scaling and final pass) over the
 // n3 = 3 W H doubles of a film: film::stride_grid(n3, film::kMaxBlocks) (image_kernels.h). A pair's scratch goes, before its stream
 // is destroyed, with forget_stream (device_mem.h).

@@ -20,7 +20,9 @@
 #include "poisson_kernels.h"
 #include "device_mem.h"
 #include "image_kernels.h"
+#include "render_kernels.h"
 #include "../capi_common.h"
+#include "../lds_layout.h"
 #include "../../../include/gdpt.h"
 
 #include <rocblas/rocblas.h>
@@ -287,11 +289,27 @@ __global__ __launch_bounds__(kBlock) void dct_finalize_kernel(Geo g, const doubl
 // row stride gives (2 (BK+1) r mod 32 = 2 r) and the even stride of the first version did not (SQ_LDS_BANK_CONFLICT as many
 // cycles as SQ_ACTIVE_INST_LDS: every A read a two-way conflict, profiles/r03_poisson_pmc.txt). A wave owns 16 x 32 = two MFMA tiles; result
 // register r of lane l is C[(l>>4) + 4r][l&15] (the f64 map, not the f32 one).
+// A third shape exists for one situation: BK = 16 with BM = 32 is the SMALL-FOOTPRINT shape, a 32 x 32 block tile worked by 4 waves
+// (256 threads, one 16 x 16 MFMA tile each), B tile k-major [16][34], ONE LDS buffer (staged, barrier, computed from, barrier; the next
+// step's global loads are in flight meanwhile): 8.5 KB of LDS and one wave per SIMD, which is what fits beside two resident blocks
+// of the lane machine on an LDS-resident scene (render_kernels.h: render_beside_hint; cbox leaves 17.5 KB per CU). Its speed matters
+// little: it exists so that a frame's solve completes inside the next frame's render kernel instead of waiting for that kernel's
+// LDS. Every output element is accumulated by the same 16x16x4 MFMA sequence with k ascending in every shape (a step of BK is BK / 4
+// consecutive MFMAs, steps ascend), from operands that are the same doubles whichever thread staged them, so the result does not
+// depend on the shape, bit for bit (tests/test_gpu_dct_small_shape.py).
 // Epilogues (EPI, column pass only): 0 plain; 1 the spectral division  F^ = H^ / (alpha - (float)(lapY[y] + lapX[x]))  with
 // the DC override F^[0,0] = sum(w u) (src/render.cpp:229-239: the block holding element (0,0) reduces the per-block partials
 // of dct_rhs_kernel itself); 2 the final  out[(y*W+x)*3+ch] = f / (4 (W-1)(H-1))  (:245-247), planar -> interleaved.
 // (History, whole 512x512x3 solve on MI355X: unfolded 64x64 tiles with 4 waves 132 us, rocBLAS dgemm_strided_batched 103 us.)
 constexpr int kGemmBN = 64, kGemmLdB = 80, kGemmThreads = 512;
+constexpr int kGemmSmallBN = 32, kGemmSmallLdB = 34, kGemmSmallThreads = 256;
+constexpr bool gemm_small(int bk, int bm) { return bk == 16 && bm == 32; }
+constexpr int gemm_bn(int bk, int bm) { return gemm_small(bk, bm) ? kGemmSmallBN : kGemmBN; }
+constexpr int gemm_ldb(int bk, int bm) { return gemm_small(bk, bm) ? kGemmSmallLdB : kGemmLdB; }
+constexpr int gemm_threads(int bk, int bm) { return gemm_small(bk, bm) ? kGemmSmallThreads : kGemmThreads; }
+constexpr int gemm_buffers(int bk, int bm) { return gemm_small(bk, bm) ? 1 : 2; }
+// static LDS of a shape: the A and B tiles (double-buffered but for the small shape) + red[]
+constexpr int gemm_lds_bytes(int bk, int bm) { return gemm_buffers(bk, bm) * (bm * (bk + 1) + bk * gemm_ldb(bk, bm)) * (int)sizeof(double) + (kBlock / 64) * (int)sizeof(double); }
 struct GemmEpi {
     double alpha; const double *lap_x, *lap_y;      // EPI 1
     const double *dc_partials; int dc_nb;            // EPI 1: [3][dc_nb] block partials of sum(w u)
@@ -308,16 +326,20 @@ struct GemmEpi {
 // that XCD's L2 once and the other seven members hit there; the parity tables (1 MB at 512) end up in every L2.
 // Grid = 8 x ceil(groups / 8) x members blocks, 1-D; ids whose group does not exist return at once.
 template <int FORM, int EPI, int BK, int BM>
-__global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_f64(int M, int N, int K, int tiles_m, int tiles_n, const double *X, int ldx, long long strideX,
+__global__ __launch_bounds__(gemm_threads(BK, BM), BK == 32 ? 2 : 4) void dct_fold_gemm_f64(int M, int N, int K, int tiles_m, int tiles_n, const double *X, int ldx, long long strideX,
                                                                      const double *E0, const double *E1, int ldE,
                                                                      double *C, int ldc, long long strideC, GemmEpi e) {
     typedef double d4 __attribute__((ext_vector_type(4)));
     typedef double d2 __attribute__((ext_vector_type(2)));
     static_assert((BM == 64 || BM == 32) && (BK == 16 || BK == 32), "tile shapes");
     // HB / HA staging passes per step and thread for the B / A tile; odd A row stride, see above; NT MFMA tiles per wave
-    constexpr int kGemmBM = BM, kGemmBK = BK, kGemmLdA = BK + 1, HB = BK / 16, HA = BM * BK / 1024, NT = BM / 32;
-    __shared__ __attribute__((aligned(16))) double sA[2][kGemmBM * kGemmLdA];
-    __shared__ __attribute__((aligned(16))) double sB[2][kGemmBK * kGemmLdB];
+    // (the names of the namespace's 64-column constants stand for this shape's own from here on)
+    constexpr bool SMALL = gemm_small(BK, BM);
+    constexpr int kGemmBN = gemm_bn(BK, BM), kGemmLdB = gemm_ldb(BK, BM), kGemmThreads = gemm_threads(BK, BM);
+    constexpr int kGemmBM = BM, kGemmBK = BK, kGemmLdA = BK + 1, HB = BK / 16, HA = BM * BK / (2 * kGemmThreads), NT = SMALL ? 1 : BM / 32;
+    static_assert(HA >= 1 && HB * kGemmThreads * 2 == BK * kGemmBN, "every thread stages one pair per pass");
+    __shared__ __attribute__((aligned(16))) double sA[gemm_buffers(BK, BM)][kGemmBM * kGemmLdA];
+    __shared__ __attribute__((aligned(16))) double sB[gemm_buffers(BK, BM)][kGemmBK * kGemmLdB];
     __shared__ double red[kBlock / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int ch, p, tile_m, tile_n;
@@ -342,13 +364,14 @@ __global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_
     const int Mt = FORM == 0 ? M : Qn, Nt = FORM == 0 ? Qn : N;     // extent of this block's (parity-compact) output index space
     const int m0 = tile_m * kGemmBM, n0 = tile_n * kGemmBN;
     if (m0 >= Mt || n0 >= Nt) return;                    // (block-uniform: the odd parity has one output less)
-    // a wave owns 16 rows x (16 NT) columns: 4 x 2 waves on a 64-row tile, 2 x 4 on a 32-row tile
-    const int wm = (BM == 64 ? (wave >> 1) : (wave >> 2)) * 16, wn = (BM == 64 ? (wave & 1) * 32 : (wave & 3) * 16);
-    // staging roles: A tile BM x BK -> thread (row tid / (BK/2) + (1024/BK) pass, 2 consecutive k at 2 (tid % (BK/2)));
-    // B tile BK x 64 -> thread (k = (tid >> 5) + 16 pass, 2 consecutive n)
+    // a wave owns 16 rows x (16 NT) columns: 4 x 2 waves on a 64-row tile, 2 x 4 on a 32-row tile, 2 x 2 on the 32 x 32 tile
+    const int wm = (BM == 64 || SMALL ? (wave >> 1) : (wave >> 2)) * 16, wn = (BM == 64 ? (wave & 1) * 32 : SMALL ? (wave & 1) * 16 : (wave & 3) * 16);
+    // staging roles: A tile BM x BK -> thread (row tid / (BK/2) + (2 threads / BK) pass, 2 consecutive k at 2 (tid % (BK/2)));
+    // B tile BK x BN -> thread (k = tid / (BN/2) + 16 pass, 2 consecutive n)
     const int am = tid / (BK / 2), ak = (tid % (BK / 2)) * 2;
-    const int bk = tid >> 5, bn = (tid & 31) * 2;
-    constexpr int kRowsPerPass = 1024 / BK;
+    const int bk = tid / (kGemmBN / 2), bn = (tid % (kGemmBN / 2)) * 2;
+    constexpr int kRowsPerPass = 2 * kGemmThreads / BK;
+    static_assert(kGemmThreads / (kGemmBN / 2) == 16, "a B staging pass covers 16 k");
     const double sgn = p ? -1.0 : 1.0;
     // vector loads when every 16-byte pair is aligned and the tile lies inside the matrices (block-uniform)
     const bool fast = ((ldx | ldE | K) & 1) == 0 && m0 + kGemmBM <= Mt && n0 + kGemmBN <= Nt &&
@@ -440,6 +463,15 @@ __global__ __launch_bounds__(kGemmThreads, BK == 32 ? 2 : 4) void dct_fold_gemm_
             if (s + 2 < steps) { stage(0, g0); if (s + 4 < steps) fetch((s + 4) * kGemmBK, g0); }
             __syncthreads();
         }
+    } else if (SMALL) {
+        fetch(0, g0);
+        for (int s = 0; s < steps; s++) {
+            stage(0, g0);
+            __syncthreads();
+            if (s + 1 < steps) fetch((s + 1) * kGemmBK, g0);          // in flight during the MFMAs below
+            compute(0);
+            __syncthreads();                                          // (the buffer is free for the next step's stage)
+        }
     } else {
         fetch(0, g0);
         stage(0, g0);
@@ -515,6 +547,7 @@ struct Workspace {
 
 // ---- direct DCT-I solver (GEMM) ---------------------------------------------------------------------
 namespace {
+thread_local const char *g_dct_shape = "";      // include/gdpt_debug.h: gdpt_debug_last_dct_shape
 
 struct DctPlan {
     int n = 0;
@@ -674,19 +707,30 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
         e.alpha = alpha; e.lap_x = lap_x; e.lap_y = lap_y; e.dc_partials = ws.partials; e.dc_nb = nb;
         e.denom = 4.0 * (double)(w - 1) * (double)(h - 1); e.out = d_out; e.out_w = w;
         const int qw = (w + 1) / 2, qh = (h + 1) / 2;           // outputs of the even parity along the folded dimension
-        const dim3 block(gp::kGemmThreads);
         const long long pl = (long long)plane;
         // The shape follows the grid (dct_fold_gemm_f64): with 64-row tiles, at most one block per CU -> 32-row tiles (twice the
         // blocks, two of them resident per CU) with deep prefetch; at most two per CU -> 64 rows, deep prefetch; more -> 64 rows, the
         // small-footprint shape. Test knobs dct_bk / dct_bm force a shape.
         const long long blocks64 = (long long)((h + 63) / 64) * ((qw + gp::kGemmBN - 1) / gp::kGemmBN) * 6;
         int bm = blocks64 <= num_cus ? 32 : 64, bk = blocks64 <= 2LL * num_cus ? 32 : 16;
-        { const int f = gdpt::debug_knob_int("dct_bk", 0); if (f == 16 || f == 32) bk = f; }
-        { const int f = gdpt::debug_knob_int("dct_bm", 0); if (f == 32 || f == 64) bm = f; }
-        if (bm == 32) bk = 32;                                   // (the 32-row tile exists in the deep-prefetch shape only)
+        const int f_bk = gdpt::debug_knob_int("dct_bk", 0), f_bm = gdpt::debug_knob_int("dct_bm", 0);
+        if (f_bk == 16 || f_bk == 32) bk = f_bk;
+        if (f_bm == 32 || f_bm == 64) bm = f_bm;
+        // The small-footprint shape (32-row tile, BK 16): forced by both knobs together, or, with no knob set, taken while a render
+        // kernel may be resident on the CUs (the render launcher's hint: the LDS its blocks leave per CU) when the shape chosen above
+        // does not fit into what is left and the small one does. The hint follows the call sequence, so the choice does too.
+        bool small = f_bk == 16 && f_bm == 32;
+        if (f_bk == 0 && f_bm == 0) {
+            const int left = gdpt::render_beside_hint(dev);
+            small = left > 0 && gd::lds_allocated(gp::gemm_lds_bytes(bk, bm)) > left && gd::lds_allocated(gp::gemm_lds_bytes(16, 32)) <= left;
+        }
+        if (small) { bm = 32; bk = 16; }
+        else if (bm == 32) bk = 32;                              // (otherwise the 32-row tile exists in the deep-prefetch shape only)
+        const int bn = gp::gemm_bn(bk, bm);
+        const dim3 block(gp::gemm_threads(bk, bm));
         // tile counts of the parity-compact index spaces (even parity: the larger one), 1-D XCD-aware grids
-        const int tm_rows = (h + bm - 1) / bm, tn_rows = (qw + gp::kGemmBN - 1) / gp::kGemmBN;     // row pass: M = h, N' = ceil(w/2)
-        const int tm_cols = (qh + bm - 1) / bm, tn_cols = (w + gp::kGemmBN - 1) / gp::kGemmBN;     // column pass: M' = ceil(h/2), N = w
+        const int tm_rows = (h + bm - 1) / bm, tn_rows = (qw + bn - 1) / bn;     // row pass: M = h, N' = ceil(w/2)
+        const int tm_cols = (qh + bm - 1) / bm, tn_cols = (w + bn - 1) / bn;     // column pass: M' = ceil(h/2), N = w
         const dim3 grid_rows((unsigned)(8 * ((tm_rows * 3 + 7) / 8) * (tn_rows * 2)));
         const dim3 grid_cols((unsigned)(8 * ((tn_cols * 3 + 7) / 8) * (tm_cols * 2)));
 #define GDPT_DCT_CHAIN(BK_, BM_)                                                                                                                              \
@@ -694,9 +738,10 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
         hipLaunchKernelGGL((gp::dct_fold_gemm_f64<1, 1, BK_, BM_>), grid_cols, block, 0, stream, h, w, h, tm_cols, tn_cols, (const double *)B, w, pl, EhT[0], EhT[1], ld_eht, A, w, pl, e);   /* A = Ch^T * B, / (alpha - lambda), DC */ \
         hipLaunchKernelGGL((gp::dct_fold_gemm_f64<0, 0, BK_, BM_>), grid_rows, block, 0, stream, h, w, w, tm_rows, tn_rows, (const double *)A, w, pl, Ew[0], Ew[1], ld_ew, B, w, pl, e);      /* B = A * Cw */ \
         hipLaunchKernelGGL((gp::dct_fold_gemm_f64<1, 2, BK_, BM_>), grid_cols, block, 0, stream, h, w, h, tm_cols, tn_cols, (const double *)B, w, pl, EhT[0], EhT[1], ld_eht, A, w, pl, e);   /* out = Ch^T * B / denom */
-        if (bm == 32) { GDPT_DCT_CHAIN(32, 32) }
-        else if (bk == 32) { GDPT_DCT_CHAIN(32, 64) }
-        else { GDPT_DCT_CHAIN(16, 64) }
+        if (small) { GDPT_DCT_CHAIN(16, 32) g_dct_shape = "32x32x16"; }
+        else if (bm == 32) { GDPT_DCT_CHAIN(32, 32) g_dct_shape = "32x64x32"; }
+        else if (bk == 32) { GDPT_DCT_CHAIN(32, 64) g_dct_shape = "64x64x32"; }
+        else { GDPT_DCT_CHAIN(16, 64) g_dct_shape = "64x64x16"; }
 #undef GDPT_DCT_CHAIN
     }
     ck(hipGetLastError(), "dct kernel launch");
@@ -712,6 +757,8 @@ PoissonResult poisson_dct(int dev, DctWorkspace &ws, int w, int h, const double 
 }
 
 } // namespace
+
+const char *last_dct_shape() { return g_dct_shape; }
 
 void launch_assemble(int w, int h, int row_begin, int row_end, const double *img, const double *cx0, const double *cy0, const double *cx1,
                      const double *cy1, double *c, double *cx, double *cy, hipStream_t stream) {

@@ -35,12 +35,12 @@
 #include "device_trace.h"
 #include "../leaf_cursor.h"
 #include "../item_slice.h"
+#include "../lds_layout.h"
 
 namespace gd {
 
 constexpr int kBlock = 256;
-constexpr int kLdsSceneBytes = 20 * 1024;     // nodes + prims + shading table + materials of a "small" scene
-constexpr int kLdsSceneLevels = 12;           // stack slots per lane when the scene is LDS-resident
+static_assert(kBlock == kLdsBlockLanes, "lds_layout.h sizes the stack columns for this block");      // (kLdsSceneBytes, kLdsSceneLevels: there)
 
 struct LaneCounters { unsigned rays, bounces, nonfinite; };
 
@@ -79,7 +79,9 @@ struct KernelArgs {
     int stream_spp, first_sample;      // the spp samples are streams [first_sample, first_sample + spp) of the pixel's block of stream_spp
                                        // PCG streams (include/gdpt.h: GdptSampleWindow); a plain render has stream_spp = spp, first_sample = 0.
                                        // The kernels that pull work items find first_sample in chunk_begin and do not read the field
-    int stack_levels;                  // scenes walked from HBM: traversal-stack slots per lane in dynamic LDS (= the tree's bound)
+    int stack_levels;                  // traversal-stack slots per lane in dynamic LDS (= the tree's bound; lds_fixed_layout: the cap)
+    int lds_scene_bytes;               // one-sided lane machine on an LDS-resident scene: bytes of dynamic LDS behind the stack, which
+                                       // hold the scene copy (lds_layout.h); 0 for every other kernel
     int replay_per_step;               // two-sided lane machine: replay iterations of an offset per wave step (>= 1)
     int num_chunks;                    // work items per pixel: chunk c covers streams [chunk_begin[c], chunk_begin[c+1]) of the pixel's block
                                        // (= first_sample + the plan's sample range)
@@ -935,6 +937,8 @@ GD void reduce_and_store(const KernelArgs &a, Accum &acc, int K, bool writer, in
 
 // dynamic LDS of the kernels that walk the scene from HBM: the traversal stack, sized from the tree's own bound
 inline size_t hbm_dynamic_lds(const KernelArgs &a) { return (size_t)a.stack_levels * kBlock * sizeof(int); }
+// dynamic LDS of gdpt_render_phases: the same stack, and behind it the scene copy where the scene is LDS-resident (launch_render: lds_scene_layout)
+inline size_t phases_dynamic_lds(const KernelArgs &a) { return hbm_dynamic_lds(a) + (size_t)a.lds_scene_bytes; }
 
 // Copies nodes (BVH2 or wide form), primitive records, the shading table and the materials into LDS (small scenes)
 // and returns the trace context of this lane.
@@ -1096,19 +1100,23 @@ GD CamConst &camera_here() {
 // (The kernel's traversal configuration and the leaf trips of its LDS forms under names of their own: the test instrument,
 // debug_kat_trace.hip, walks with the same ones.)
 constexpr int kPhasesLdsLeafK = GDPT_SPEC_LEAF ? 0 : GDPT_LDS_LEAF_K;
+// the kernel's static LDS (s_acc, s_priv, s_chunks; the stamped builds add s_stamps): what render_free_lds_per_cu counts per block
+constexpr int kPhasesStaticLds = (15 + kPrivDoubles) * kBlock * (int)sizeof(double) + 66 * (int)sizeof(int);
+constexpr int kPhasesStampLds = (kBlock / 64) * (SEG_COUNT + 1) * (int)sizeof(unsigned long long);
 template <bool LDS_SCENE, bool WIDE, bool WW, int PLAIN, int LEAF_K>
 using PhasesTraceCfg = TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE, LEAF_K>;
 template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE ? kPhasesLdsLeafK : 0)>
 __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv, KernelArgs a) {
-    // LDS-resident scenes: fixed 12-slot stack + the scene copy. Scenes walked from HBM: dynamic LDS = a.stack_levels stack
-    // slots per lane (the tree's own bound, not the builder's maximum of 32).
-    __shared__ int s_stack_fixed[LDS_SCENE ? kLdsSceneLevels * kBlock : 1];
-    __shared__ __attribute__((aligned(16))) unsigned char s_scene[LDS_SCENE ? kLdsSceneBytes : 16];
+    // Dynamic LDS = a.stack_levels stack slots per lane (the tree's own bound, not the builder's maximum of 32) and, for LDS-resident
+    // scenes, behind them the scene copy, which takes the bytes its tables need (lds_layout.h; launch_render sizes both). The stack
+    // sits at the base of the segment for every kernel; the copy's offset is wave-uniform and joins the table offsets, which follow
+    // from the scene's counts and were never constants.
     __shared__ double s_acc[15 * kBlock];
     __shared__ double s_priv[kPrivDoubles * kBlock];
     __shared__ int s_chunks[66];
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
-    int *s_stack = LDS_SCENE ? s_stack_fixed : (int *)s_dyn;
+    int *s_stack = (int *)s_dyn;
+    unsigned char *s_scene = s_dyn + (LDS_SCENE ? a.stack_levels * (kBlock * (int)sizeof(int)) : 0);
     const int tid = threadIdx.x;
     if (tid <= a.num_chunks && tid < 66) s_chunks[tid] = a.chunk_begin[tid];       // LDS copy of the chunk table (item_to_pixel)
     TraceCtx tx = setup_trace<LDS_SCENE, WIDE>(sv, s_scene, s_stack, tid, kBlock, a.count != 0);

@@ -44,6 +44,12 @@ inline bool is_stamped(Route r) { return r >= Route::LAMBERT_STAMPED_LDS_PLAIN &
 // the one-sided lane machine (gdpt_render_phases) in its product builds: its launch touches nothing but the scene, its partials,
 // queue head and counters, so it may run beside the previous frame's tail (capi_device.hip: begin_launch)
 inline bool can_overlap(Route r) { return r <= Route::GENERAL_HBM && !is_stamped(r); }
+// gdpt_render_phases on an LDS-resident scene (the stamped builds included): the launch sizes its scene copy and stack from the scene
+// (../lds_layout.h)
+inline bool phases_lds_scene(Route r) {
+    return r == Route::LAMBERT_PLAIN_LDS_CONST || r == Route::LAMBERT_PLAIN_LDS_TEX || r == Route::LAMBERT_LDS_WIDE || r == Route::LAMBERT_LDS_BVH2 ||
+           r == Route::LAMBERT_STAMPED_LDS_PLAIN || r == Route::LAMBERT_STAMPED_LDS || r == Route::GENERAL_LDS_WIDE || r == Route::GENERAL_LDS_BVH2;
+}
 // the only kernels that walk the LDS copy in its BVH2 form; every other route walks a BVH4 (or the HBM tree)
 inline bool walks_bvh2(Route r) { return r == Route::LAMBERT_LDS_BVH2 || r == Route::GENERAL_LDS_BVH2; }
 
@@ -82,6 +88,8 @@ struct RenderLaunch {
     int thresh_a, thresh_c;        // trace-phase exit fractions /256 (unfinished rays; lanes still searching a leaf), -1 = default
     int force_log2k;               // lanes per pixel = 2^force_log2k (-1 = automatic)
     int wide_stack_need;           // traversal-stack bound of the tree the HBM kernels walk (host-verified)
+    int lds_stack_need;            // phases_lds_scene routes: the same bound of the tree the LDS copy holds (BVH4: wide_stack_need, BVH2: its depth)
+    bool lds_fixed_layout;         // knob lds_fixed_layout: the caps (kLdsSceneLevels, kLdsSceneBytes) instead of what the scene needs
     void *bounce_log;              // two-sided routes: per-lane log (device), sized by twosided_log_bytes(blocks)
     size_t bounce_log_bytes;
     int num_cus;                   // compute units of the device (persistent grid size)
@@ -128,6 +136,16 @@ int wf_slot_count(long long num_items);
 size_t wf_aux_bytes(int slots);
 // Enqueues the render of rl.route on `stream` and records the route (last_route). Throws std::runtime_error on a launch failure.
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream);
+
+// LDS a CU has left beside the resident blocks of this launch, allocation granule counted; 0 for every route but phases_lds_scene.
+int render_free_lds_per_cu(const DevSceneView &sv, const RenderLaunch &rl);
+// Per-device hint for the solver (poisson_kernels.hip), owned by the render launcher: > 0 while a lane machine on an LDS-resident scene
+// may be resident on the device's CUs on a render stream — the value is render_free_lds_per_cu of the last such launch. `owner` is the
+// handle that set it; only its owner clears it (an in-stream launch, GdptScene::join, destruction of the handle). It follows the call
+// sequence, not the clock: nothing asks the device.
+void set_render_beside_hint(int device, const void *owner, int free_lds_per_cu);
+void clear_render_beside_hint(int device, const void *owner);
+int render_beside_hint(int device);
 
 // Route of the calling thread's last render launch (include/gdpt_debug.h: gdpt_debug_last_route): launch_render sets it,
 // reset_route clears it ("") at the start of a render.

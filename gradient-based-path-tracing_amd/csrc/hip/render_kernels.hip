@@ -3,6 +3,8 @@
 #include "render_wavefront.h"
 
 #include "../capi_common.h"
+#include <map>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 
@@ -201,6 +203,42 @@ static void run_wavefront(const DevSceneView &sv, const gd::KernelArgs &a, const
     }
 }
 
+// The dynamic LDS of a lane machine on an LDS-resident scene: the one place that lays it out (launch_render's kernel arguments and
+// render_free_lds_per_cu both come from here).
+static gd::LdsLayout phases_lds_layout(const DevSceneView &sv, const RenderLaunch &rl) {
+    const bool wide = !walks_bvh2(rl.route);
+    const gd::LdsSceneCounts c{wide ? sv.num_nodes4 : sv.num_nodes, sv.num_prims, sv.num_tris, sv.num_materials, sv.num_lights};
+    const gd::LdsLayout l = gd::lds_scene_layout(wide, c, rl.lds_stack_need, rl.lds_fixed_layout);
+    if (!l.ok) throw std::runtime_error("launch_render: the scene does not fit the block's LDS copy");
+    return l;
+}
+int render_free_lds_per_cu(const DevSceneView &sv, const RenderLaunch &rl) {
+    if (!phases_lds_scene(rl.route)) return 0;
+    const int per_block = gd::lds_allocated(gd::kPhasesStaticLds + (is_stamped(rl.route) ? gd::kPhasesStampLds : 0) + phases_lds_layout(sv, rl).total);
+    const int left = gd::kLdsPerCu - (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * per_block;
+    return left > 0 ? left : 0;
+}
+namespace {
+struct BesideHint { const void *owner = nullptr; int free_lds = 0; };
+std::mutex g_hint_mu;
+std::map<int, BesideHint> &g_hints = *new std::map<int, BesideHint>();     // (leaked on purpose, like the solver's registries)
+}
+void set_render_beside_hint(int device, const void *owner, int free_lds_per_cu) {
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    BesideHint &h = g_hints[device];
+    h.owner = owner; h.free_lds = free_lds_per_cu;
+}
+void clear_render_beside_hint(int device, const void *owner) {
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    auto it = g_hints.find(device);
+    if (it != g_hints.end() && it->second.owner == owner) it->second = BesideHint();
+}
+int render_beside_hint(int device) {
+    std::lock_guard<std::mutex> lk(g_hint_mu);
+    auto it = g_hints.find(device);
+    return it == g_hints.end() ? 0 : it->second.free_lds;
+}
+
 void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t stream) {
     const Route r = rl.route;
     // an overlapped launch (rl.kernel_stream): queue reset and render kernel on that stream; what writes the images stays on `stream`
@@ -225,6 +263,10 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
         a.stack_levels = rl.wide_stack_need > 0 ? rl.wide_stack_need : GDPT_BVH_MAX_DEPTH;
         a.replay_per_step = rl.replay_per_step >= 1 ? rl.replay_per_step : 4;       // render_twosided.h: kReplayPerStep
         if (a.stack_levels > GDPT_BVH_MAX_DEPTH) throw std::runtime_error("launch_render: traversal stack bound exceeds the builder's maximum");
+        if (phases_lds_scene(r)) {          // the stack and the scene copy behind it, both sized from the scene (lds_layout.h)
+            const gd::LdsLayout l = phases_lds_layout(sv, rl);
+            a.stack_levels = l.stack_levels; a.lds_scene_bytes = l.total - l.scene_off;
+        }
         grid = start_queue(a, rl, W, ks);
     }
     if (needs_bounce_log(r) && (!rl.bounce_log || rl.bounce_log_bytes < twosided_log_bytes(grid.x))) throw std::runtime_error("launch_render: bounce log missing");

@@ -3,10 +3,10 @@
 #include "render_device.h"
 namespace gdpt {
 void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, bool whole_leaf, hipStream_t stream) {
-    if (lds && plain && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, gd::kPlainBoth, 0>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds && plain) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, gd::kPlainBoth>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, 0, 0>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, true>), grid, dim3(gd::kBlock), gd::hbm_dynamic_lds(a), stream, sv, a);
+    if (lds && plain && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, gd::kPlainBoth, 0>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds && plain) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, gd::kPlainBoth>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true, 0, 0>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, true>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, true>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
 }
 } // namespace gdpt

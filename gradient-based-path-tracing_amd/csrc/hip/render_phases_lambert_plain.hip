@@ -5,11 +5,11 @@
 #include "render_device.h"
 namespace gdpt {
 void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, bool whole_leaf, hipStream_t stream) {
-    if (lds && const_tex && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainBoth, 0>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds && const_tex) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainBoth>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainNoSpheres, 0>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (lds) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainNoSpheres>), grid, dim3(gd::kBlock), 0, stream, sv, a);
-    else if (const_tex) hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, false, gd::kPlainBoth>), grid, dim3(gd::kBlock), gd::hbm_dynamic_lds(a), stream, sv, a);
-    else hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, false, gd::kPlainNoSpheres>), grid, dim3(gd::kBlock), gd::hbm_dynamic_lds(a), stream, sv, a);
+    if (lds && const_tex && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainBoth, 0>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds && const_tex) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainBoth>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds && whole_leaf) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainNoSpheres, 0>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (lds) hipLaunchKernelGGL((gd::gdpt_render_phases<true, true, true, true, false, gd::kPlainNoSpheres>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else if (const_tex) hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, false, gd::kPlainBoth>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
+    else hipLaunchKernelGGL((gd::gdpt_render_phases<true, false, true, true, false, gd::kPlainNoSpheres>), grid, dim3(gd::kBlock), gd::phases_dynamic_lds(a), stream, sv, a);
 }
 } // namespace gdpt

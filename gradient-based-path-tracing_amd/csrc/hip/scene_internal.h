@@ -61,13 +61,16 @@ struct GdptScene {
         for (auto &b : d_buf) b.grow(elems, "hipMalloc(image buffers)");
     }
     // Waits on the host for everything the render streams hold. (What a caller's stream still holds is that caller's, as before.)
+    // No render of this handle is resident behind it: the solver's hint (render_kernels.h) goes with the wait.
     void join() {
+        gdpt::clear_render_beside_hint(device, this);
         if (!in_flight) return;
         for (auto &st : render_stream) if (st) gdpt::ck(hipStreamSynchronize(st), "hipStreamSynchronize(render stream)");
         in_flight = false;
     }
     ~GdptScene() {                              // the members free themselves on the device: streams join and go before the buffers
         hipSetDevice(device);
+        gdpt::clear_render_beside_hint(device, this);
         for (auto &st : render_stream) st.reset();
         for (auto &ss : scratch) if (ss.used) (void)hipEventSynchronize(ss.released);      // a caller's stream may still reduce from the set
     }

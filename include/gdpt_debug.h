@@ -32,7 +32,11 @@
  *   wf_sort              (0/1/2) wavefront pipeline: ray queue in slot order / sorted by (octant, origin cell) / by (origin cell, octant)
  *   multi_fail_band / multi_fail_stage (int)  gdpt_multi_*: band `multi_fail_band` throws in stage 1 (render), 2 (halo +
  *                               assembly), 3 (all-gather) or 4 (solve): the other bands must stand down, not hang
- *   dct_bk (16 / 32), dct_bm (32 / 64)   GDPT_SOLVER_DCT_MFMA: force a shape of the folded GEMM (default: by grid size)
+ *   dct_bk (16 / 32), dct_bm (32 / 64)   GDPT_SOLVER_DCT_MFMA: force a shape of the folded GEMM (default: by grid size, and the
+ *                               small-footprint shape beside a resident render kernel). dct_bm = 32 alone is the deep-prefetch 32-row shape;
+ *                               dct_bm = 32 with dct_bk = 16 is the small-footprint shape (32 x 32 tile, 256 threads)
+ *   lds_fixed_layout (0/1)      one-sided lane machine on an LDS-resident scene: the block takes the caps (12 stack levels, 20 KB of scene
+ *                               copy) instead of the LDS its scene needs; same kernel, same route name
  *   replay_per_step (n >= 1)    two-sided lane machine: replay iterations of an offset per wave step (default 4; 1 = one per step)
  *   no_plain_kernel (0/1)       one-sided lane machine: the kernel with sphere and texture code even for a triangles-only, constant-texture scene
  *   no_render_overlap (0/1)     one-sided lane machine: every launch wholly on the caller's stream, none on the handle's render streams
@@ -89,6 +93,10 @@ int gdpt_debug_chunk_plan(int spp, int force_log2k, long long film_pixels, long 
 /* Route of the last gdpt_render / gdpt_path_render (and their _device forms) made by the CALLING thread: one of the
  * names above, "" before the first one (or after a render that failed before its launch). The string is static. */
 const char *gdpt_debug_last_route(void);
+/* Shape of the folded GEMMs of the last GDPT_SOLVER_DCT_MFMA solve enqueued by the CALLING thread: "64x64x32", "32x64x32", "64x64x16"
+ * (block tile rows x columns x K step) or "32x32x16", the small-footprint shape a solve takes while a render kernel may be resident
+ * beside it; "" before the first such solve. The string is static. */
+const char *gdpt_debug_last_dct_shape(void);
 /* Renders of this handle so far whose kernel went on one of the handle's own render streams (include/gdpt.h: gdpt_render_device);
  * -1 for a null handle. Lets a test see that the overlapped path was taken. */
 struct GdptScene;
