@@ -77,6 +77,7 @@ def lib():
         L.gdpt_progressive_group_run.argtypes = [vp, C.c_double, C.c_int, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
         L.gdpt_progressive_group_total.argtypes = [vp]
         L.gdpt_progressive_group_total.restype = vp
+        L.gdpt_progressive_group_halves.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
         L.gdpt_progressive_group_member_status.argtypes = [vp, C.c_int, C.POINTER(defs.GdptProgressiveStatus)]
         sst, grp = C.POINTER(defs.GdptReconSpreadStats), C.POINTER(defs.GdptGroupReconParams)
         L.gdpt_recon_spread_device.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(vp), dp, vp, C.c_int, vp, vp, vp, sst]
@@ -120,6 +121,12 @@ def lib():
         L.gdpt_variance_smooth_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vp, vss]
         L.gdpt_variance_smooth.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vsp, ndp, vp, vss]
         L.gdpt_progressive_denoise_smoothed.argtypes = [vp, C.c_int, vsp, nlp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, vp, nls, vss]
+        slp, sls, vpp = C.POINTER(defs.GdptSelectParams), C.POINTER(defs.GdptSelectStats), C.POINTER(vp)
+        L.gdpt_select_default_params.argtypes = [slp]
+        L.gdpt_select_default_params.restype = None
+        L.gdpt_filter_select_device.argtypes = [C.c_int, C.c_int, C.c_int, vpp, vpp, vpp, vp, vp, vp, vp, slp, vp, vp, vp, vp, vp, sls]
+        L.gdpt_progressive_group_denoise_select.argtypes = [vp, C.POINTER(defs.GdptSelectCandidate), C.c_int, slp, C.c_int, C.c_int, vp, vp, vp, vp, vp, sls, nls]
+        L.gdpt_filter_select.argtypes = [C.c_int, C.c_int, C.c_int, vpp, vpp, vpp, vp, vp, vp, vp, slp, vp, vp, vp, vp, sls]
         pos, pys = C.POINTER(defs.GdptNlmPyramidOpStats), C.POINTER(defs.GdptNlmPyramidStats)
         L.gdpt_nlm_pyramid_down_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, vp, vp, pos]
         L.gdpt_nlm_pyramid_down.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, ngp, ndp, vp, vp, vp, vp, pos]
@@ -753,6 +760,64 @@ class ProgressiveGroup:
                                                               C.c_void_p(var.ctypes.data) if variance else None, C.byref(sp), C.byref(rs)))
         return (img, emap, var, sp, rs) if variance else (img, emap, sp, rs)
 
+    def halves(self):
+        """(A, B): Progressive views of two independent halves of the group's samples (gdpt_progressive_group_halves): the members
+        that hold samples, in member order, merged alternately into A and B; rebuilt if a round has run since the last call. They
+        read and denoise as `total` does and, like it, take no passes or merges of their own."""
+        a, b = C.c_void_p(), C.c_void_p()
+        _check(lib().gdpt_progressive_group_halves(self.handle, C.byref(a), C.byref(b)))
+        return tuple(Progressive._view(self, h.value, self.total.shape, self.total.path) for h in (a, b))
+
+    _SELECT_FILTERS = {"mean": defs.SELECT_MEAN, "nlm": defs.SELECT_NLM, "guided": defs.SELECT_NLM_GUIDED, "demod": defs.SELECT_NLM_DEMOD,
+                       "regress": defs.SELECT_NLM_REGRESS, "atrous": defs.SELECT_ATROUS}
+
+    def denoise_select(self, candidates, radius=None, feature_spp=4, maps=False, features=False, out_ptrs=None):
+        """The filters in `candidates` run on the two halves and on the total, and per pixel the one whose error the halves estimate
+        smallest (gdpt_progressive_group_denoise_select). A candidate is a dict: `filter` one of "mean", "nlm", "guided", "demod",
+        "regress", "atrous" (or a GDPT_SELECT_* value); `var_smooth`: a radius, for "nlm", "guided" and "demod" only; `nlm`: a
+        GdptNlmParams or a dict of nlm_params keywords; `atrous`: a GdptAtrousParams or a dict of atrous_params keywords; `guide`,
+        `demod`, `regress`: the blocks, None as in the matching Progressive.denoise_* call. Returns (out HxWx3, GdptSelectStats, list
+        of the candidates' GdptNlmStats on the total); with `maps=True` (out, sel HxW int32, mse HxW, stats, list); with
+        `features=True` the two (8, H, W) feature arrays follow `out` (or `mse`). `out_ptrs` = (out, sel or None, mse or None) device
+        addresses on devices[0]: everything stays there and (stats, list) are returned."""
+        n = len(candidates)
+        arr, keep = (defs.GdptSelectCandidate * max(1, n))(), []
+        for j, c in enumerate(candidates):
+            c = dict(c)
+            f = c.pop("filter")
+            if isinstance(f, str):
+                if f not in self._SELECT_FILTERS:
+                    raise GdptError(f"ProgressiveGroup.denoise_select: candidates[{j}]: filter must be one of {', '.join(self._SELECT_FILTERS)}")
+                f = self._SELECT_FILTERS[f]
+            vs = c.pop("var_smooth", None)
+            arr[j].filter, arr[j].var_smooth_radius = int(f), -1 if vs is None else int(vs)
+            nlm, atrous = c.pop("nlm", None), c.pop("atrous", None)
+            blocks = dict(nlm=nlm_params(**nlm) if isinstance(nlm, dict) else nlm, atrous=atrous_params(**atrous) if isinstance(atrous, dict) else atrous,
+                          guide=c.pop("guide", None), demod=c.pop("demod", None), regress=c.pop("regress", None))
+            if c:
+                raise GdptError(f"ProgressiveGroup.denoise_select: candidates[{j}]: unknown key {sorted(c)[0]}")
+            for name, b in blocks.items():
+                if b is not None:
+                    keep.append(b)
+                    setattr(arr[j], name, C.pointer(b))
+        p = select_params(radius)
+        st, cst = defs.GdptSelectStats(), (defs.GdptNlmStats * max(1, n))()
+        if out_ptrs is not None:
+            ptrs = [C.c_void_p(int(x)) if x else None for x in (list(out_ptrs) + [None, None])[:3]]
+            _check(lib().gdpt_progressive_group_denoise_select(self.handle, arr, n, C.byref(p), int(feature_spp), 1, *ptrs, None, None, C.byref(st), cst))
+            return st, list(cst[:n])
+        shape = self.total.shape
+        out = np.empty(shape, dtype=np.float64)
+        sel = np.empty(shape[:2], dtype=np.int32) if maps else None
+        mse = np.empty(shape[:2], dtype=np.float64) if maps else None
+        fm = np.empty((defs.FEATURE_CHANNELS,) + shape[:2], dtype=np.float64) if features else None
+        fv = np.empty((defs.FEATURE_CHANNELS,) + shape[:2], dtype=np.float64) if features else None
+        host = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None      # noqa: E731
+        _check(lib().gdpt_progressive_group_denoise_select(self.handle, arr, n, C.byref(p), int(feature_spp), 0, host(out), host(sel), host(mse), host(fm),
+                                                           host(fv), C.byref(st), cst))
+        res = (out,) + ((sel, mse) if maps else ()) + ((fm, fv) if features else ())
+        return res + (st, list(cst[:n]))
+
     def member_status(self, i):
         st = defs.GdptProgressiveStatus()
         _check(lib().gdpt_progressive_group_member_status(self.handle, int(i), C.byref(st)))
@@ -1212,6 +1277,66 @@ def variance_smooth_device(width, height, img_ptr, var_ptr, var_out_ptr, feat_pt
     _check(lib().gdpt_variance_smooth_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), int(num_channels),
                                              C.byref(p), C.byref(demod) if demod is not None else None, opt(var_out_ptr), opt(stream),
                                              C.byref(st) if stats else None))
+    return st
+
+
+def select_params(radius=None):
+    """GdptSelectParams (include/gdpt.h): the library's default (gdpt_select_default_params: radius 4) with the keyword given in its
+    place, taken literally."""
+    p = defs.GdptSelectParams()
+    lib().gdpt_select_default_params(C.byref(p))
+    if radius is not None:
+        p.radius = int(radius)
+    return p
+
+
+def _pointer_array(ptrs):
+    """A C array of void pointers from addresses; 0 or None gives NULL."""
+    return (C.c_void_p * max(1, len(ptrs)))(*[C.c_void_p(int(x)) if x else None for x in ptrs])
+
+
+def filter_select(FA, FB, T, uA, vA, uB, vB, params=None, radius=None, maps=True, E=False):
+    """The per-pixel choice among candidate filters by the two-half error estimate on the GPU (gdpt_filter_select). `FA`, `FB`, `T`:
+    sequences of n HxWx3 float64 arrays, candidate j run on half A, on half B and on all samples; `uA`, `vA`, `uB`, `vB`: the halves'
+    means and the variances of those means. `params`: a GdptSelectParams taken as it is (else select_params(radius)). Returns
+    (out HxWx3, sel HxW int32, mse HxW, GdptSelectStats), with `E=True` also the (n, H, W) window means E_j before the stats; with
+    `maps=False` only (out, stats)."""
+    arr = lambda a: np.ascontiguousarray(a, dtype=np.float64)      # noqa: E731
+    FA, FB, T = [arr(a) for a in FA], [arr(a) for a in FB], [arr(a) for a in T]
+    halves = [arr(a) for a in (uA, vA, uB, vB)]
+    if len(FA) != len(T) or len(FB) != len(T):
+        raise GdptError("filter_select: FA, FB and T must hold one image per candidate each")
+    shape = halves[0].shape
+    if len(shape) != 3 or shape[2] != 3 or any(a.shape != shape for a in FA + FB + T + halves):
+        raise GdptError("filter_select: every image must be an HxWx3 array of one shape")
+    n, (h, w) = len(T), shape[:2]
+    p = params if params is not None else select_params(radius)
+    out, st = np.empty(shape, dtype=np.float64), defs.GdptSelectStats()
+    sel = np.empty((h, w), dtype=np.int32) if maps else None
+    mse = np.empty((h, w), dtype=np.float64) if maps else None
+    Ej = np.empty((n, h, w), dtype=np.float64) if E else None
+    host = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None      # noqa: E731
+    _check(lib().gdpt_filter_select(int(w), int(h), n, _pointer_array([a.ctypes.data for a in FA]), _pointer_array([a.ctypes.data for a in FB]),
+                                    _pointer_array([a.ctypes.data for a in T]), *[host(a) for a in halves], C.byref(p), host(out), host(sel),
+                                    host(mse), host(Ej), C.byref(st)))
+    if not maps:
+        return out, st
+    return (out, sel, mse, Ej, st) if E else (out, sel, mse, st)
+
+
+def filter_select_device(width, height, FA_ptrs, FB_ptrs, T_ptrs, uA_ptr, vA_ptr, uB_ptr, vB_ptr, out_ptr, sel_ptr=None, mse_ptr=None, E_ptr=None,
+                         stream=None, stats=True, params=None, radius=None):
+    """filter_select() on device addresses (gdpt_filter_select_device); `FA_ptrs`, `FB_ptrs`, `T_ptrs` are sequences of n addresses.
+    `sel_ptr` (int32, W*H), `mse_ptr` (W*H) and `E_ptr` (n*W*H) may be None. Returns GdptSelectStats after waiting for `stream`; with
+    `stats=False` the call only enqueues and returns None."""
+    if len(FA_ptrs) != len(T_ptrs) or len(FB_ptrs) != len(T_ptrs):
+        raise GdptError("filter_select_device: FA_ptrs, FB_ptrs and T_ptrs must hold one address per candidate each")
+    p = params if params is not None else select_params(radius)
+    st = defs.GdptSelectStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_filter_select_device(int(width), int(height), len(T_ptrs), _pointer_array(FA_ptrs), _pointer_array(FB_ptrs),
+                                           _pointer_array(T_ptrs), opt(uA_ptr), opt(vA_ptr), opt(uB_ptr), opt(vB_ptr), C.byref(p), opt(out_ptr),
+                                           opt(sel_ptr), opt(mse_ptr), opt(E_ptr), opt(stream), C.byref(st) if stats else None))
     return st
 
 

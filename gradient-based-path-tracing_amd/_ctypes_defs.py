@@ -184,6 +184,26 @@ class GdptVarSmoothStats(C.Structure):
                 ("radius", C.c_int32)]
 
 
+SELECT_MAX_CANDIDATES, SELECT_MAX_RADIUS = 8, 8
+
+
+class GdptSelectParams(C.Structure):
+    _fields_ = [("radius", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GdptSelectStats(C.Structure):
+    _fields_ = [("pixels_left_out", C.c_uint64), ("chosen", C.c_uint64 * SELECT_MAX_CANDIDATES), ("sum_e", C.c_double * SELECT_MAX_CANDIDATES),
+                ("sum_mse", C.c_double), ("sum_sq_out", C.c_double), ("select_ms", C.c_double), ("radius", C.c_int32), ("num_candidates", C.c_int32)]
+
+
+SELECT_MEAN, SELECT_NLM, SELECT_NLM_GUIDED, SELECT_NLM_DEMOD, SELECT_NLM_REGRESS, SELECT_ATROUS = range(6)
+
+
+class GdptSelectCandidate(C.Structure):
+    _fields_ = [("filter", C.c_int32), ("var_smooth_radius", C.c_int32), ("nlm", C.POINTER(GdptNlmParams)), ("atrous", C.POINTER(GdptAtrousParams)),
+                ("guide", C.POINTER(GdptNlmGuide)), ("demod", C.POINTER(GdptNlmDemod)), ("regress", C.POINTER(GdptNlmRegress))]
+
+
 NLM_MAX_LEVELS = 4
 
 

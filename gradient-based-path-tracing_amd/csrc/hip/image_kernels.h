@@ -83,5 +83,8 @@ __device__ __forceinline__ TilePixel tile_pixel(const TileGrid &g, int t) {
 // of nb partials into *est.
 struct Estimate { double sum_var, sum_mean2, left_out; };
 void launch_finish(int nb, const double *partials, Estimate *est, hipStream_t stream);
+// The same for a kernel that leaves `runs` runs of nb partials: finish_runs_kernel, one block on `stream`, reduces run k into sums[k],
+// each in the order above.
+void launch_finish_runs(int nb, int runs, const double *partials, double *sums, hipStream_t stream);
 
 } // namespace film

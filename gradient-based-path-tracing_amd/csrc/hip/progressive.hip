@@ -405,7 +405,7 @@ static void filter_with_features(const std::string &who, GdptProgressive &s, int
     GdptRenderParams rp{};
     rp.spp = feature_spp; rp.rng_scheme = GDPT_RNG_SAMPLE;
     const GdptSampleWindow win{s.block, 0};
-    gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
+    if (!s.feat_current) gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
     double *d_out = out, *d_var_out = var_out;
     if (!on_device) {                 // through planes of the session's on the way to host memory
         for (int k = 0; k < (var_out ? 2 : 1); k++) if (!s.nlm_buf[k]) s.nlm_buf[k].alloc(s.elems, "hipMalloc(progressive denoise)");
@@ -435,6 +435,7 @@ int gdpt_progressive_create_slice(GdptScene *scene, const GdptProgressiveConfig 
 int gdpt_progressive_merge(GdptProgressive *dst, const GdptProgressive *src) {
     return gdpt::guarded([&]() {
         if (!dst || !src) throw std::runtime_error("gdpt_progressive_merge: null argument");
+        if (dst->group_half) throw std::runtime_error("gdpt_progressive_merge: dst is a half of a group (its group rebuilds it)");
         if (dst->group_total) throw std::runtime_error("gdpt_progressive_merge: dst is the total of a group (its group rebuilds it)");
         prg::merge(*dst, *src);
     });
@@ -450,6 +451,7 @@ void gdpt_progressive_free(GdptProgressive *session) {
 int gdpt_progressive_add_pass(GdptProgressive *session, int spp, GdptRenderStats *stats) {
     return gdpt::guarded([&]() {
         if (!session) throw std::runtime_error("gdpt_progressive_add_pass: null session");
+        if (session->group_half) throw std::runtime_error("gdpt_progressive_add_pass: the session is a half of a group (it draws no samples of its own)");
         if (session->group_total) throw std::runtime_error("gdpt_progressive_add_pass: the session is the total of a group (it draws no samples of its own)");
         prg::add_pass(*session, spp, stats);
     });
@@ -780,6 +782,7 @@ int gdpt_progressive_run(GdptProgressive *session, double target_error, int pass
         if (pass_spp <= 0) throw std::runtime_error("gdpt_progressive_run: pass_spp must be > 0");
         if (std::isnan(target_error)) throw std::runtime_error("gdpt_progressive_run: target_error is NaN");
         GdptProgressive &s = *session;
+        if (s.group_half) throw std::runtime_error("gdpt_progressive_run: the session is a half of a group (run the group)");
         if (s.group_total) throw std::runtime_error("gdpt_progressive_run: the session is the total of a group (run the group)");
         auto reached = [&]() { return target_error > 0 && s.passes >= 2 && error_estimate(s) <= target_error; };
         int added = 0;

@@ -20,6 +20,7 @@
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "progressive_internal.h"
+#include "filter_select.h"
 #include "recon_spread.h"
 
 #include <algorithm>
@@ -46,15 +47,22 @@ struct GdptProgressiveGroup {
     hipStream_t total_stream = nullptr;
     GdptProgressive *total = nullptr;
     bool total_current = true;       // the total holds what the members hold
+    GdptProgressive *half[2] = {nullptr, nullptr};     // accumulators beside the total, on its device and stream: the members that hold samples,
+    bool halves_current = false;                       // in member order, merged alternately into [0] and [1] (gdpt_progressive_group_halves)
     std::vector<gdpt::DeviceBuffer<double>> recon_stage;     // on devices[0]: reconstructions of members on other devices, allocated on first use
+    std::vector<gdpt::DeviceBuffer<double>> select_films;    // on devices[0]: gdpt_progressive_group_denoise_select's 3n filtered films, the halves' four planes,
+    gdpt::DeviceBuffer<double> select_out, select_mse, select_feat[2];      // its outputs on their way to host memory; allocated on first use
+    gdpt::DeviceBuffer<int32_t> select_sel;
     gdpt::DeviceBuffer<double> spread_var, spread_map;       // on devices[0]: the statistic's planes on their way to host memory, allocated on first use
 
     ~GdptProgressiveGroup() {
+        for (GdptProgressive *h : half) if (h) gdpt_progressive_free(h);
         if (total) gdpt_progressive_free(total);
         for (Member &m : members) if (m.session) gdpt_progressive_free(m.session);
         if (!members.empty()) {
             hipSetDevice(members[0].device);
             recon_stage.clear(); spread_var.reset(); spread_map.reset();
+            select_films.clear(); select_out.reset(); select_mse.reset(); select_sel.reset(); select_feat[0].reset(); select_feat[1].reset();
         }
         if (total_stream && !members.empty()) {
             gdpt::forget_stream(members[0].device, total_stream);     // the solvers' and reconstructions' per-stream scratch goes with the stream
@@ -97,7 +105,7 @@ bool round(GdptProgressiveGroup &g, int pass_spp) {
     for (size_t k = 1; k < todo.size(); k++) th.emplace_back(one, todo[k]);
     one(todo[0]);
     for (std::thread &t : th) t.join();
-    g.total_current = false;
+    g.total_current = g.halves_current = false;
     for (int i : todo) {
         const Member &m = g.members[(size_t)i];
         if (!m.error.empty()) throw std::runtime_error("device " + std::to_string(m.device) + " (member " + std::to_string(i) + "): " + m.error);
@@ -245,6 +253,11 @@ int gdpt_progressive_group_create(const GdptSceneDesc *desc, const int32_t *devi
         if (gdpt_progressive_create_slice(g->members[0].scene.get(), &cfg, 0, 0, g->total_stream, &g->total) != 0)
             throw std::runtime_error(gdpt_last_error());
         g->total->group_total = true;
+        for (GdptProgressive *&h : g->half) {
+            if (gdpt_progressive_create_slice(g->members[0].scene.get(), &cfg, 0, 0, g->total_stream, &h) != 0)
+                throw std::runtime_error(gdpt_last_error());
+            h->group_total = h->group_half = true;
+        }
         *out = g.release();
     });
 }
@@ -340,6 +353,183 @@ int gdpt_progressive_group_run_recon(GdptProgressiveGroup *group, double target_
 }
 
 GdptProgressive *gdpt_progressive_group_total(GdptProgressiveGroup *group) { return group ? group->total : nullptr; }
+
+int gdpt_progressive_group_halves(GdptProgressiveGroup *group, GdptProgressive **half_a, GdptProgressive **half_b) {
+    return gdpt::guarded([&]() {
+        const char *fn = "gdpt_progressive_group_halves";
+        if (!group || !half_a || !half_b) throw std::runtime_error(std::string(fn) + ": null argument");
+        GdptProgressiveGroup &g = *group;
+        const std::vector<int> used = members_with_samples(g);
+        if (used.size() < 2)
+            throw std::runtime_error(std::string(fn) + ": two halves need at least two members that hold samples (" + std::to_string(used.size()) + " do)");
+        if (!g.halves_current) {
+            for (GdptProgressive *h : g.half) prg::reset(*h);
+            for (size_t k = 0; k < used.size(); k++) prg::merge(*g.half[k & 1], *g.members[(size_t)used[k]].session);
+            g.halves_current = true;
+        }
+        *half_a = g.half[0]; *half_b = g.half[1];
+    });
+}
+
+// whether the candidate's session entry renders feature planes
+static bool renders_features(const GdptSelectCandidate &c) {
+    return c.filter == GDPT_SELECT_NLM_GUIDED || c.filter == GDPT_SELECT_NLM_DEMOD || c.filter == GDPT_SELECT_NLM_REGRESS ||
+           (c.filter == GDPT_SELECT_ATROUS && ((c.guide && c.guide->num_groups > 0) || c.demod));
+}
+
+int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const GdptSelectCandidate *candidates, int n, const GdptSelectParams *select_params,
+                                          int feature_spp, int on_device, double *out, int32_t *sel, double *mse, double *features, double *features_var,
+                                          GdptSelectStats *stats, GdptNlmStats *cand_stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_group_denoise_select";
+        if (!group) throw std::runtime_error(who + ": null group");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        if (n < 1 || n > GDPT_SELECT_MAX_CANDIDATES) throw std::runtime_error(who + ": n must be in [1, " + std::to_string(GDPT_SELECT_MAX_CANDIDATES) + "]");
+        if (!candidates) throw std::runtime_error(who + ": candidates is null");
+        GdptSelectParams sp;
+        if (select_params) sp = *select_params; else gdpt_select_default_params(&sp);
+        gdpt::select_check_params(who, sp);
+        bool any_features = false;
+        for (int j = 0; j < n; j++) {
+            const GdptSelectCandidate &c = candidates[j];
+            const std::string cj = who + ": candidates[" + std::to_string(j) + "]: ";
+            if (c.filter < GDPT_SELECT_MEAN || c.filter > GDPT_SELECT_ATROUS) throw std::runtime_error(cj + "filter must be one of GDPT_SELECT_MEAN .. GDPT_SELECT_ATROUS");
+            const bool smoothable = c.filter == GDPT_SELECT_NLM || c.filter == GDPT_SELECT_NLM_GUIDED || c.filter == GDPT_SELECT_NLM_DEMOD;
+            if (c.var_smooth_radius < -1 || c.var_smooth_radius > GDPT_VAR_SMOOTH_MAX_RADIUS)
+                throw std::runtime_error(cj + "var_smooth_radius must be -1 (none) or in [0, " + std::to_string(GDPT_VAR_SMOOTH_MAX_RADIUS) + "]");
+            if (c.var_smooth_radius >= 0 && !smoothable) throw std::runtime_error(cj + "var_smooth_radius must be -1 unless filter is GDPT_SELECT_NLM, _NLM_GUIDED or _NLM_DEMOD");
+            if (c.filter == GDPT_SELECT_MEAN && (c.nlm || c.atrous || c.guide || c.demod || c.regress)) throw std::runtime_error(cj + "GDPT_SELECT_MEAN takes no parameter block");
+            if (c.filter != GDPT_SELECT_ATROUS && c.atrous) throw std::runtime_error(cj + "atrous must be null unless filter is GDPT_SELECT_ATROUS");
+            if (c.filter == GDPT_SELECT_ATROUS && c.nlm) throw std::runtime_error(cj + "nlm must be null for GDPT_SELECT_ATROUS");
+            if (c.filter != GDPT_SELECT_NLM_REGRESS && c.regress) throw std::runtime_error(cj + "regress must be null unless filter is GDPT_SELECT_NLM_REGRESS");
+            if (c.filter != GDPT_SELECT_NLM_DEMOD && c.filter != GDPT_SELECT_ATROUS && c.demod) throw std::runtime_error(cj + "demod must be null unless filter is GDPT_SELECT_NLM_DEMOD or GDPT_SELECT_ATROUS");
+            if (c.filter == GDPT_SELECT_NLM && c.guide) throw std::runtime_error(cj + "guide must be null for GDPT_SELECT_NLM");
+            any_features = any_features || renders_features(c);
+        }
+        if ((features || features_var) && !any_features) throw std::runtime_error(who + ": features need a candidate that renders some (none does)");
+        GdptProgressiveGroup &g = *group;
+        // 1. the halves and the total are current
+        GdptProgressive *half[2] = {nullptr, nullptr};
+        if (gdpt_progressive_group_halves(group, &half[0], &half[1]) != 0) throw std::runtime_error(who + ": " + gdpt_last_error());
+        if (!g.total_current) rebuild_total(g);
+        {
+            const std::vector<int> used = members_with_samples(g);
+            for (int k = 0; k < 2; k++) {
+                if (half[k]->passes >= 2) continue;
+                std::string list;
+                for (size_t i = (size_t)k; i < used.size(); i += 2) list += (list.empty() ? "" : ", ") + std::to_string(used[i]);
+                throw std::runtime_error(who + ": half " + (k == 0 ? "A" : "B") + " (members " + list + ") holds " + std::to_string(half[k]->passes) +
+                                         " pass: every half needs at least 2 for its variance");
+            }
+        }
+        GdptProgressive &t = *g.total;
+        ck(hipSetDevice(t.device), "hipSetDevice");
+        const size_t px = (size_t)t.w * t.h;
+        if (g.select_films.size() < (size_t)(3 * n + 4)) g.select_films.resize((size_t)(3 * n + 4));
+        for (int i = 0; i < 3 * n + 4; i++) if (!g.select_films[(size_t)i]) g.select_films[(size_t)i].alloc(t.elems, "hipMalloc(group select films)");
+        GdptProgressive *const part[3] = {half[0], half[1], g.total};
+        const size_t fbytes = (size_t)GDPT_FEATURE_CHANNELS * px * sizeof(double);
+        bool features_taken = false;
+        // 2. one feature render, by the first run on the total that needs the planes; the halves get copies (they share the total's scene,
+        // budget and stream, so their own renders would give the same bits) and no session renders again during this call
+        struct KeepFeatures {
+            GdptProgressive *const *part;
+            ~KeepFeatures() { for (int k = 0; k < 3; k++) part[k]->feat_current = false; }
+        } keep{part};
+        // 3. every candidate on A, B and the total, into the group's films (device memory)
+        const double *FA[GDPT_SELECT_MAX_CANDIDATES], *FB[GDPT_SELECT_MAX_CANDIDATES], *T[GDPT_SELECT_MAX_CANDIDATES];
+        for (int j = 0; j < n; j++) {
+            const GdptSelectCandidate &c = candidates[j];
+            for (int k : {2, 0, 1}) {         // (the total first: it renders the planes)
+                double *film = g.select_films[(size_t)(3 * j + k)];
+                (k == 0 ? FA : k == 1 ? FB : T)[j] = film;
+                GdptNlmStats st{};
+                // the planes of the first feature-rendering run on the total go out with it
+                double *fm = nullptr, *fv = nullptr;
+                if (k == 2 && renders_features(c) && !features_taken && (features || features_var)) {
+                    if (on_device) { fm = features; fv = features_var; }
+                    else {
+                        for (auto &b : g.select_feat) if (!b) b.alloc((size_t)GDPT_FEATURE_CHANNELS * px, "hipMalloc(group select features)");
+                        fm = g.select_feat[0]; fv = g.select_feat[1];
+                    }
+                    features_taken = true;
+                }
+                GdptVarSmoothParams vs{};
+                gdpt_var_smooth_default_params(&vs);
+                vs.radius = c.var_smooth_radius;
+                int rc = 0;
+                switch (c.filter) {
+                case GDPT_SELECT_MEAN: {
+                    double *const means[5] = {film, nullptr, nullptr, nullptr, nullptr};
+                    rc = gdpt_progressive_read(part[k], 1, means, nullptr, nullptr);
+                    break;
+                }
+                case GDPT_SELECT_NLM:
+                    rc = c.var_smooth_radius >= 0
+                             ? gdpt_progressive_denoise_smoothed(part[k], GDPT_DENOISE_PLAIN, &vs, c.nlm, nullptr, nullptr, feature_spp, 1, film, nullptr, nullptr, nullptr, nullptr, &st, nullptr)
+                             : gdpt_progressive_denoise(part[k], c.nlm, 1, film, nullptr, &st);
+                    break;
+                case GDPT_SELECT_NLM_GUIDED:
+                    rc = c.var_smooth_radius >= 0
+                             ? gdpt_progressive_denoise_smoothed(part[k], GDPT_DENOISE_GUIDED, &vs, c.nlm, c.guide, nullptr, feature_spp, 1, film, nullptr, nullptr, fm, fv, &st, nullptr)
+                             : gdpt_progressive_denoise_guided(part[k], c.nlm, c.guide, feature_spp, 1, film, nullptr, fm, fv, &st);
+                    break;
+                case GDPT_SELECT_NLM_DEMOD:
+                    rc = c.var_smooth_radius >= 0
+                             ? gdpt_progressive_denoise_smoothed(part[k], GDPT_DENOISE_DEMOD, &vs, c.nlm, c.guide, c.demod, feature_spp, 1, film, nullptr, nullptr, fm, fv, &st, nullptr)
+                             : gdpt_progressive_denoise_demod(part[k], c.nlm, c.guide, c.demod, feature_spp, 1, film, nullptr, fm, fv, &st);
+                    break;
+                case GDPT_SELECT_NLM_REGRESS:
+                    rc = gdpt_progressive_denoise_regress(part[k], c.nlm, c.guide, c.regress, feature_spp, 1, film, nullptr, fm, fv, &st);
+                    break;
+                default:
+                    rc = gdpt_progressive_denoise_atrous(part[k], c.atrous, c.guide, c.demod, feature_spp, 1, film, nullptr, fm, fv, &st);
+                    break;
+                }
+                if (rc != 0) throw std::runtime_error(who + ": candidates[" + std::to_string(j) + "] on " + (k == 0 ? "half A" : k == 1 ? "half B" : "the total") + ": " + gdpt_last_error());
+                if (k == 2 && cand_stats) cand_stats[j] = st;
+                if (k == 2 && renders_features(c) && !t.feat_current) {
+                    ck(hipSetDevice(t.device), "hipSetDevice");
+                    for (int m = 0; m < 2; m++)
+                        for (int b = 0; b < 2; b++) {
+                            if (!half[m]->feat_buf[b]) half[m]->feat_buf[b].alloc((size_t)GDPT_FEATURE_CHANNELS * px, "hipMalloc(progressive features)");
+                            ck(hipMemcpyAsync(half[m]->feat_buf[b], t.feat_buf[b], fbytes, hipMemcpyDeviceToDevice, g.total_stream), "hipMemcpyAsync(group select features)");
+                        }
+                    for (int m = 0; m < 3; m++) part[m]->feat_current = true;
+                }
+            }
+        }
+        ck(hipSetDevice(t.device), "hipSetDevice");
+        double *uv[4];
+        for (int i = 0; i < 4; i++) uv[i] = g.select_films[(size_t)(3 * n + i)];
+        for (int k = 0; k < 2; k++) {
+            double *const means[5] = {uv[2 * k], nullptr, nullptr, nullptr, nullptr};
+            double *const vars[5] = {uv[2 * k + 1], nullptr, nullptr, nullptr, nullptr};
+            if (gdpt_progressive_read(half[k], 1, means, vars, nullptr) != 0) throw std::runtime_error(who + ": " + gdpt_last_error());
+        }
+        // 4. the selection, on the total's stream
+        double *d_out = out, *d_mse = mse;
+        int32_t *d_sel = sel;
+        if (!on_device) {
+            if (!g.select_out) g.select_out.alloc(t.elems, "hipMalloc(group select outputs)");
+            d_out = g.select_out;
+            if (sel) { if (!g.select_sel) g.select_sel.alloc(px, "hipMalloc(group select outputs)"); d_sel = g.select_sel; }
+            if (mse) { if (!g.select_mse) g.select_mse.alloc(px, "hipMalloc(group select outputs)"); d_mse = g.select_mse; }
+        }
+        GdptSelectStats st{};
+        if (gdpt_filter_select_device(t.w, t.h, n, FA, FB, T, uv[0], uv[1], uv[2], uv[3], &sp, d_out, d_sel, d_mse, nullptr, g.total_stream, &st) != 0)
+            throw std::runtime_error(who + ": " + gdpt_last_error());
+        if (!on_device) {
+            ck(hipMemcpyAsync(out, d_out, t.elems * sizeof(double), hipMemcpyDeviceToHost, g.total_stream), "hipMemcpyAsync(D2H)");
+            if (sel) ck(hipMemcpyAsync(sel, d_sel, px * sizeof(int32_t), hipMemcpyDeviceToHost, g.total_stream), "hipMemcpyAsync(D2H)");
+            if (mse) ck(hipMemcpyAsync(mse, d_mse, px * sizeof(double), hipMemcpyDeviceToHost, g.total_stream), "hipMemcpyAsync(D2H)");
+            if (features_taken && features) ck(hipMemcpyAsync(features, g.select_feat[0], fbytes, hipMemcpyDeviceToHost, g.total_stream), "hipMemcpyAsync(D2H)");
+            if (features_taken && features_var) ck(hipMemcpyAsync(features_var, g.select_feat[1], fbytes, hipMemcpyDeviceToHost, g.total_stream), "hipMemcpyAsync(D2H)");
+        }
+        ck(hipStreamSynchronize(g.total_stream), "hipStreamSynchronize(group select)");
+        if (stats) *stats = st;
+    });
+}
 
 int gdpt_progressive_group_member_status(const GdptProgressiveGroup *group, int member, GdptProgressiveStatus *status) {
     return gdpt::guarded([&]() {

@@ -21,6 +21,7 @@ struct GdptProgressive {
     int done = 0, passes = 0;        // W and K of the statistics held: own passes and merged sessions
     int stop_reason = GDPT_STOP_NONE;
     bool group_total = false;        // the borrowed total of a GdptProgressiveGroup: the public add_pass / run / merge refuse it
+    bool group_half = false;         // ... one of its two halves (group_total is set too): the refusals say so
     std::vector<std::pair<int, int>> merged_intervals;    // [begin, end) of the block, as taken in by merges
     size_t elems = 0;
     gdpt::DeviceBuffer<double> pass[5], mean[5], m2[5];
@@ -29,6 +30,8 @@ struct GdptProgressive {
     gdpt::DeviceBuffer<double> asm_buf[4];     // c, cx, cy, reconstruction: allocated by the first reconstruct
     gdpt::DeviceBuffer<double> nlm_buf[2];     // filtered mean and its variance on their way to host memory: allocated by the first denoise
     gdpt::DeviceBuffer<double> feat_buf[2];    // feature planes and their variances of the guided denoise (8 W H doubles each): allocated by the first one
+    bool feat_current = false;                 // feat_buf holds the planes the next guided denoise would render: it renders none (set and cleared by
+                                               // gdpt_progressive_group_denoise_select alone, which renders once for its three sessions)
     gdpt::DeviceBuffer<double> smooth_buf;     // the smoothed variance of buffer 0 (gdpt_progressive_denoise_smoothed): allocated by the first one
     gdpt::DeviceBuffer<double> partials;
     gdpt::DeviceBuffer<film::Estimate> d_est;

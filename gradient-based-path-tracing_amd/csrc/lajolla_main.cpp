@@ -70,6 +70,19 @@
 //                 they do above, and under --nlm-demodulate the default guide is the normal alone. Not combined with --nlm-window,
 //                 --nlm-patch, --nlm-k, --nlm-var-smooth, --nlm-levels or --nlm-regress. Without --atrous-levels every output file
 //                 is what it was
+//                 --select LIST writes, per pixel, the candidate whose error two independent halves of the samples estimate smallest
+//                 (gdpt_progressive_group_denoise_select). LIST names 1..8 of mean,nlm,guided,demod,regress,atrous,atrous-demod, each
+//                 once, separated by commas; each is what its own flag gives without further flags: mean the unfiltered mean; nlm
+//                 the plain filter (k 0.45); guided --nlm-guide albedo,normal (k 1.0); demod --nlm-demodulate (no guide); regress
+//                 --nlm-regress albedo,normal (the albedo group as guide, k 4.0); atrous --atrous-levels 5 (guide albedo,normal);
+//                 atrous-demod --atrous-levels 5 --nlm-demodulate (guide normal). --nlm-var-smooth S acts on nlm, guided and demod;
+//                 --nlm-kf on every guide; --nlm-depth-tau T adds the depth group to the guides of guided, atrous and atrous-demod;
+//                 --nlm-albedo-floor on demod and atrous-demod; --feature-spp as above. --select-radius S (0..8, default 4) is the
+//                 window of the estimate; --select-map FILE writes the index of the winning candidate in LIST (-1: pixel left out)
+//                 and --select-mse FILE the winning estimate, in all three channels. It needs --sample-devices with two or more
+//                 entries (0,0 is two slices on one GPU); not combined with --nlm-window, --nlm-patch, --nlm-k, --nlm-guide,
+//                 --nlm-demodulate, --nlm-levels, --nlm-regress, --nlm-ridge, --nlm-depth-scale, --atrous-levels or --atrous-k.
+//                 Without --select every output file is what it was
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -78,6 +91,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -111,6 +125,9 @@ int main(int argc, char *argv[]) {
     double atrous_k = 0.0;
     bool atrous_k_set = false;
     int feature_spp = 0;
+    std::string select_list = "", select_map_file = "", select_mse_file = "";
+    int select_radius = 4;
+    bool select_radius_set = false;
     double nlm_depth_tau = 0.0, nlm_kf = 0.0;
     double conf_floor = 0.0;
     GdptMultiConfig multi{};          // num_devices == 0: single-device entry points
@@ -202,6 +219,13 @@ int main(int argc, char *argv[]) {
             nlm_var_smooth = std::stoi(next());
             if (nlm_var_smooth < 0 || nlm_var_smooth > GDPT_VAR_SMOOTH_MAX_RADIUS) { std::cerr << "--nlm-var-smooth takes a radius from 0 to 4" << std::endl; return 2; }
         }
+        else if (a == "--select") select_list = next();
+        else if (a == "--select-radius") {
+            select_radius = std::stoi(next()); select_radius_set = true;
+            if (select_radius < 0 || select_radius > GDPT_SELECT_MAX_RADIUS) { std::cerr << "--select-radius takes a radius from 0 to 8" << std::endl; return 2; }
+        }
+        else if (a == "--select-map") select_map_file = next();
+        else if (a == "--select-mse") select_mse_file = next();
         else if (a == "--features") features_prefix = next();
         else if (a == "--feature-spp") { feature_spp = std::stoi(next()); if (feature_spp <= 0) { std::cerr << "--feature-spp must be > 0" << std::endl; return 2; } }
         else if (a == "--rng") { std::string v = next(); rng = (v == "tile") ? GDPT_RNG_TILE : GDPT_RNG_SAMPLE; }
@@ -243,6 +267,48 @@ int main(int argc, char *argv[]) {
     if (pass_spp <= 0 && (target_error != 0.0 || !variance_file.empty())) { std::cerr << "--target-error and --variance need --pass-spp" << std::endl; return 2; }
     if (!denoised_file.empty() && pass_spp <= 0) {
         std::cerr << "--denoised needs --pass-spp: the filter is driven by the variance of the mean, and no variance exists without passes" << std::endl;
+        return 2;
+    }
+    // --select: the names of LIST in order; what the single-filter flags would refuse beside each other is refused here at once
+    enum { SelMean, SelNlm, SelGuided, SelDemod, SelRegress, SelAtrous, SelAtrousDemod };
+    std::vector<int> select_names;
+    const bool select_on = !select_list.empty();
+    double select_kf = 0.0, select_depth_tau = 0.0, select_floor = 0.0;
+    if (select_on) {
+        static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod"};
+        if (denoised_file.empty()) { std::cerr << "--select needs --denoised" << std::endl; return 2; }
+        if (sample_devices.size() < 2) {
+            std::cerr << "--select needs --sample-devices with two or more entries: the estimate comes from two independent halves of the samples "
+                         "(0,0 is two slices on one GPU)" << std::endl;
+            return 2;
+        }
+        if (nlm_option || !nlm_guide_names.empty() || nlm_demodulate || nlm_levels > 0 || !nlm_regress_names.empty() || nlm_regress_option || atrous_levels > 0 ||
+            atrous_k_set) {
+            std::cerr << "--select is not combined with --nlm-window, --nlm-patch, --nlm-k, --nlm-guide, --nlm-demodulate, --nlm-levels, --nlm-regress, --nlm-ridge, "
+                         "--nlm-depth-scale, --atrous-levels or --atrous-k: every name in its list carries its own configuration" << std::endl;
+            return 2;
+        }
+        size_t at = 0;
+        while (at <= select_list.size()) {
+            const size_t comma = std::min(select_list.find(',', at), select_list.size());
+            const std::string name = select_list.substr(at, comma - at);
+            int which = -1;
+            for (int k = 0; k < 7; k++) if (name == names[k]) which = k;
+            if (which < 0 || std::find(select_names.begin(), select_names.end(), which) != select_names.end()) {
+                std::cerr << "--select takes mean, nlm, guided, demod, regress, atrous and atrous-demod, each once, separated by commas" << std::endl;
+                return 2;
+            }
+            select_names.push_back(which);
+            at = comma + 1;
+        }
+        if (nlm_kf != 0.0 && !(nlm_kf > 0.0)) { std::cerr << "--nlm-kf must be > 0" << std::endl; return 2; }
+        if (nlm_depth_tau != 0.0 && !(nlm_depth_tau > 0.0)) { std::cerr << "--nlm-depth-tau must be > 0" << std::endl; return 2; }
+        if (nlm_albedo_floor != 0.0 && !(nlm_albedo_floor > 0.0)) { std::cerr << "--nlm-albedo-floor must be > 0" << std::endl; return 2; }
+        // taken over here: below they belong to --nlm-guide and --nlm-demodulate
+        select_kf = nlm_kf; select_depth_tau = nlm_depth_tau; select_floor = nlm_albedo_floor;
+        nlm_kf = nlm_depth_tau = nlm_albedo_floor = 0.0; nlm_guide_option = false;
+    } else if (select_radius_set || !select_map_file.empty() || !select_mse_file.empty()) {
+        std::cerr << "--select-radius, --select-map and --select-mse need --select" << std::endl;
         return 2;
     }
     if (nlm_option && denoised_file.empty()) { std::cerr << "--nlm-window, --nlm-patch and --nlm-k need --denoised" << std::endl; return 2; }
@@ -346,7 +412,7 @@ int main(int argc, char *argv[]) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
     }
-    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed && !atrous_on) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed && !atrous_on && !select_on) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
     if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
@@ -408,6 +474,7 @@ int main(int argc, char *argv[]) {
         GdptNlmStats nlm_stats{};
         GdptVarSmoothStats smooth_stats{};
         GdptNlmPyramidStats pyramid_stats{};
+        GdptSelectStats select_stats{};
         GdptGroupReconParams gp{};        // the reconstruction the estimate of --target-recon-error / --error-map goes through
         gp.dataCost = alpha; gp.weighted = weighted ? 1 : 0; gp.map_radius = error_radius;
         gp.recon = recon; gp.wrecon.recon = recon; gp.wrecon.conf_floor = conf_floor;
@@ -459,7 +526,62 @@ int main(int argc, char *argv[]) {
             }
             if (rc == 0 && !denoised_file.empty()) {
                 std::vector<double> filtered((size_t)w * h * 3);
-                if (atrous_on) {
+                if (select_on) {
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    const int n = (int)select_names.size();
+                    // one set of blocks per kind, as the kind's own flag would set them
+                    GdptNlmParams p_plain = nlm, p_guided = nlm, p_regress = nlm;
+                    p_guided.k = 1.0; p_regress.k = 4.0;
+                    auto with_depth = [&](GdptNlmGuide g) {
+                        if (select_kf > 0.0) g.k_f = select_kf;
+                        if (select_depth_tau > 0.0) g.groups[g.num_groups++] = GdptNlmFeatureGroup{6, 1, select_depth_tau};
+                        return g;
+                    };
+                    GdptNlmGuide g_default{}, g_normal{}, g_albedo{};
+                    gdpt_nlm_default_guide(&g_default);
+                    g_normal = g_default; g_normal.num_groups = 1; g_normal.groups[0] = GdptNlmFeatureGroup{3, 3, 1e-3};
+                    g_albedo = g_default; g_albedo.num_groups = 1; g_albedo.groups[0] = GdptNlmFeatureGroup{0, 3, 1e-3};
+                    if (select_kf > 0.0) g_albedo.k_f = select_kf;
+                    g_default = with_depth(g_default); g_normal = with_depth(g_normal);
+                    GdptNlmDemod dm{};
+                    gdpt_nlm_default_demod(&dm);
+                    if (select_floor > 0.0) dm.floor = select_floor;
+                    GdptNlmRegress rg{};
+                    gdpt_nlm_default_regress(&rg);
+                    GdptAtrousParams at{};
+                    gdpt_atrous_default_params(&at);
+                    std::vector<GdptSelectCandidate> cands((size_t)n);
+                    for (int j = 0; j < n; j++) {
+                        GdptSelectCandidate &c = cands[(size_t)j];
+                        c = GdptSelectCandidate{};
+                        c.var_smooth_radius = -1;
+                        switch (select_names[(size_t)j]) {
+                        case SelMean: c.filter = GDPT_SELECT_MEAN; break;
+                        case SelNlm: c.filter = GDPT_SELECT_NLM; c.nlm = &p_plain; c.var_smooth_radius = nlm_var_smooth; break;
+                        case SelGuided: c.filter = GDPT_SELECT_NLM_GUIDED; c.nlm = &p_guided; c.guide = &g_default; c.var_smooth_radius = nlm_var_smooth; break;
+                        case SelDemod: c.filter = GDPT_SELECT_NLM_DEMOD; c.nlm = &p_plain; c.demod = &dm; c.var_smooth_radius = nlm_var_smooth; break;
+                        case SelRegress: c.filter = GDPT_SELECT_NLM_REGRESS; c.nlm = &p_regress; c.guide = &g_albedo; c.regress = &rg; break;
+                        case SelAtrous: c.filter = GDPT_SELECT_ATROUS; c.atrous = &at; c.guide = &g_default; break;
+                        default: c.filter = GDPT_SELECT_ATROUS; c.atrous = &at; c.guide = &g_normal; c.demod = &dm; break;
+                        }
+                    }
+                    GdptSelectParams sp{};
+                    gdpt_select_default_params(&sp);
+                    sp.radius = select_radius;
+                    std::vector<int32_t> sel((size_t)w * h);
+                    std::vector<double> mse((size_t)w * h);
+                    rc = gdpt_progressive_group_denoise_select(group, cands.data(), n, &sp, feature_spp > 0 ? feature_spp : std::min(16, budget), 0, filtered.data(),
+                                                               sel.data(), mse.data(), nullptr, nullptr, &select_stats, nullptr);
+                    std::vector<double> rgb((size_t)w * h * 3);
+                    if (rc == 0 && !select_map_file.empty()) {
+                        for (size_t i = 0; i < (size_t)w * h; i++) for (int k = 0; k < 3; k++) rgb[3 * i + k] = (double)sel[i];
+                        rc = gdpt_imwrite(select_map_file.c_str(), w, h, rgb.data());
+                    }
+                    if (rc == 0 && !select_mse_file.empty()) {
+                        for (size_t i = 0; i < (size_t)w * h; i++) for (int k = 0; k < 3; k++) rgb[3 * i + k] = mse[i];
+                        rc = gdpt_imwrite(select_mse_file.c_str(), w, h, rgb.data());
+                    }
+                } else if (atrous_on) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     rc = gdpt_progressive_denoise_atrous(session, &atrous, &guide, nlm_demodulate ? &demod : nullptr,
                                                          feature_spp > 0 ? feature_spp : std::min(16, budget), 0, filtered.data(), nullptr, nullptr, nullptr,
@@ -562,7 +684,15 @@ int main(int argc, char *argv[]) {
             std::cout << "[gdpt] progressive: " << prog.passes << " passes, " << prog.spp_done << " of " << budget
                       << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
                       << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
-            if (!denoised_file.empty())
+            if (select_on) {
+                static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod"};
+                const double valid = (double)((size_t)w * h - select_stats.pixels_left_out);
+                std::cout << "[gdpt] selected: radius " << select_stats.radius << ", " << select_stats.pixels_left_out << " pixels left out;";
+                for (int j = 0; j < select_stats.num_candidates; j++)
+                    std::cout << " " << names[select_names[(size_t)j]] << " " << (valid > 0 ? 100.0 * (double)select_stats.chosen[j] / valid : 0.0) << " % (error "
+                              << (select_stats.sum_sq_out > 0 ? std::sqrt(std::max(0.0, select_stats.sum_e[j]) / select_stats.sum_sq_out) : 0.0) << ");";
+                std::cout << " select_ms " << select_stats.select_ms << ", written to " << denoised_file << std::endl;
+            } else if (!denoised_file.empty())
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
                           << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string())

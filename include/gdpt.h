@@ -461,6 +461,13 @@ void gdpt_progressive_group_free(GdptProgressiveGroup *group);
 int gdpt_progressive_group_run(GdptProgressiveGroup *group, double target_error, int pass_spp, int max_rounds,
                                GdptProgressiveStatus *status);
 GdptProgressive *gdpt_progressive_group_total(GdptProgressiveGroup *group);   /* borrowed; valid until gdpt_progressive_group_free */
+/* Two independent halves of the group's samples, for estimates that need them (gdpt_filter_select): two more accumulators beside the
+ * total, on devices[0] and the total's stream, built and emptied like it. The members that hold samples, in member order, are merged
+ * alternately into A and B; a round marks the halves stale together with the total, and this call rebuilds them if they are. Both
+ * are borrowed, valid until gdpt_progressive_group_free, and are what the total is to gdpt_progressive_read and
+ * gdpt_progressive_denoise_*; add_pass, run and merge refuse them as they refuse the total. Refused: fewer than two members with
+ * samples. Blocking. */
+int gdpt_progressive_group_halves(GdptProgressiveGroup *group, GdptProgressive **half_a, GdptProgressive **half_b);
 int gdpt_progressive_group_member_status(const GdptProgressiveGroup *group, int member, GdptProgressiveStatus *status);
 
 /* ---- variance-weighted reconstruction: generalised least squares on per-row confidences (not part of the reference) ----
@@ -1084,6 +1091,89 @@ int gdpt_progressive_denoise_multiscale(GdptProgressive *session, int kind, int 
                                         const GdptNlmDemod *demod /* nullable */, int feature_spp, int on_device, double *out,
                                         double *var_out /* nullable */, double *features /* nullable */, double *features_var /* nullable */,
                                         GdptNlmPyramidStats *stats /* nullable */);
+
+/* ---- choosing among candidate filters per pixel, by the error two half sessions estimate of each (not part of the reference) ----
+ * Which denoiser is best changes from region to region and with the sample count (DESIGN.md 4.14 has the measurements). Two
+ * independent half sessions A and B of one film give an honest estimate: filter A with a candidate F; u_B is independent of F(A) and
+ * has variance v_B, so (F(A) - u_B)^2 - v_B is an unbiased estimate of the squared error of F(A), bias included, and likewise with
+ * the halves exchanged (the two-buffer estimate of Rousselle, Manzi and Zwicker, "Robust denoising using feature and color
+ * information", 2013, section 5, and of Bitterli et al., "Nonlinearly weighted first-order regression for denoising Monte Carlo
+ * renderings", 2016, section 5). Averaged over a small window, the candidate with the smallest estimate is taken per pixel.
+ * Inputs: n candidates, 1 <= n <= GDPT_SELECT_MAX_CANDIDATES; every plane W*H*3 doubles, interleaved. uA, vA, uB, vB: the two halves'
+ * means and the variances of those means. FA[j], FB[j]: candidate j run on each half. T[j]: the image to deliver for candidate j
+ * (the candidate on all samples). 0 <= radius s <= GDPT_SELECT_MAX_RADIUS.
+ * A pixel is VALID if its triples of uA, vA, uB, vB and of every FA[j], FB[j], T[j] are finite and its vA and vB are >= 0.
+ * For a valid pixel q and channel c, every operation rounded on its own (no contraction):
+ *   t_c(q) = 0.5 * (((FA_j,c - uB_c) (FA_j,c - uB_c) - vB_c) + ((FB_j,c - uA_c) (FB_j,c - uA_c) - vA_c))
+ *   e_j(q) = ((t_0 + t_1) + t_2) / 3.0
+ *   S_j(p) = the sum of e_j(q), C(p) = the number, of the valid q with |q - p|_inf <= s: row sums of 2s + 1 taps in increasing x,
+ *            starting from 0.0, then the sum of those row sums in increasing y, starting from 0.0; a tap outside the film or on an
+ *            invalid pixel counts as 0.0 (the order of gdpt_variance_smooth)
+ *   E_j(p) = S_j(p) / C(p)
+ *   sel(p) = the smallest j whose E_j(p) is minimal: j is scanned upward and replaces the best on strict <
+ *   out(p) = T[sel(p)](p), bit for bit;  mse(p) = E_sel(p)(p), which may be negative
+ * An invalid p has out(p) = T[0](p) bit for bit, sel(p) = -1, mse(p) = NaN (and E_j(p) = NaN) and is counted in pixels_left_out.
+ * Stats: chosen[j], the valid pixels with sel = j; sum_e[j], the film sum of the unsmoothed e_j over the valid pixels; sum_mse, the film
+ * sum of E_sel; sum_sq_out, that of out squared per pixel; all reduced in a fixed order: the same call gives the same bits.
+ * WHAT THE NUMBERS ARE. e_j estimates the error of candidate j run on HALF the samples; the delivered T[j] is the candidate on all of
+ * them, and that it is no worse is expected, not measured. mse and sum_mse are minima over noisy estimates and are biased low; by how
+ * much, and with what sign the film figure comes out, is not established (DESIGN.md 4.14 has what was measured). sum_e[j], taken before any selection, is the unbiased figure. No stopping rule
+ * is built on any of them.
+ * Exact, bit for bit: n = 1 returns T[0]; a candidate listed twice never loses to its copy; permuting the candidates permutes sel and
+ * leaves out alone where no two E_j are equal; s = 0 gives E = e; every image times 2^m and every variance times 4^m leaves sel alone
+ * and multiplies mse by 4^m (short of overflow and subnormals). */
+#define GDPT_SELECT_MAX_CANDIDATES 8
+#define GDPT_SELECT_MAX_RADIUS 8
+typedef struct GdptSelectParams { int32_t radius; int32_t reserved[3]; } GdptSelectParams;
+typedef struct GdptSelectStats  { uint64_t pixels_left_out; uint64_t chosen[GDPT_SELECT_MAX_CANDIDATES]; double sum_e[GDPT_SELECT_MAX_CANDIDATES];
+                                  double sum_mse, sum_sq_out, select_ms; int32_t radius, num_candidates; } GdptSelectStats;
+void gdpt_select_default_params(GdptSelectParams *p);      /* radius 4; every field of a passed struct is taken literally */
+/* Device pointers on the current device; d_FA, d_FB, d_T are host arrays of n device pointers. d_sel (int32, W*H), d_mse (W*H) and
+ * d_E (n*W*H: plane j holds E_j) are nullable. Refused, with a message that names the field, before any device call: n out of range;
+ * a NULL image or d_out; an output that overlaps an input or another output anywhere in its extent; width or height < 1; radius outside [0, 8]; non-zero
+ * reserved. params == NULL: gdpt_select_default_params. Enqueued on `stream`: one launch, which writes no plane it reads; with stats
+ * it waits for the stream (the sums and select_ms, HIP events, come back), with stats == NULL it only enqueues. Scratch (the block
+ * partials of the sums) per (device, stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_filter_select_device(int width, int height, int n, const double *const *d_FA, const double *const *d_FB, const double *const *d_T,
+                              const double *d_uA, const double *d_vA, const double *d_uB, const double *d_vB,
+                              const GdptSelectParams *params /* NULL: defaults */, double *d_out, int32_t *d_sel /* nullable */,
+                              double *d_mse /* nullable */, double *d_E /* nullable */, void *stream, GdptSelectStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_filter_select(int width, int height, int n, const double *const *FA, const double *const *FB, const double *const *T, const double *uA,
+                       const double *vA, const double *uB, const double *vB, const GdptSelectParams *params /* NULL: defaults */, double *out,
+                       int32_t *sel /* nullable */, double *mse /* nullable */, double *E /* nullable */, GdptSelectStats *stats /* nullable */);
+
+/* The selection among filters of a progressive group, behind one call. A candidate names one of the session filters and its blocks:
+ * filter GDPT_SELECT_MEAN (the unfiltered mean; no block), _NLM (gdpt_progressive_denoise), _NLM_GUIDED (_denoise_guided), _NLM_DEMOD
+ * (_denoise_demod), _NLM_REGRESS (_denoise_regress), _ATROUS (_denoise_atrous; `atrous` in the place of `nlm`). var_smooth_radius: -1
+ * for none; >= 0 runs the candidate through gdpt_progressive_denoise_smoothed at that radius and is allowed for _NLM, _NLM_GUIDED and
+ * _NLM_DEMOD only. NULL pointers mean what they mean in the matching gdpt_progressive_denoise_* entry; a block the filter does not take
+ * must be NULL.
+ * By definition the outputs are, bit for bit, those of this chain on the total's stream: the halves (gdpt_progressive_group_halves) and
+ * the total are made current; for each candidate and each of A, B and the total, the candidate's session entry into a film the group
+ * owns (GDPT_SELECT_MEAN: gdpt_progressive_read of buffer 0); gdpt_progressive_read of the halves' means and variances;
+ * gdpt_filter_select_device with T[j] the candidate on the total. If any candidate needs feature planes they are rendered once, as
+ * gdpt_progressive_denoise_guided renders them, by the first such run on the total, and shared by all 3n runs (the three sessions
+ * share one scene, budget and stream). features, features_var (nullable) receive them from that run on the
+ * total. Each half needs at least 2 passes: the message names the half and its members. Path groups and the primal of GradPath groups
+ * are served. sel (int32, W*H) and mse (W*H) are nullable; cand_stats (nullable, n entries) receives the GdptNlmStats of every
+ * candidate's run on the total (zeros for GDPT_SELECT_MEAN). The 3n filtered films and the halves' planes are owned by the group and
+ * freed with it. All output pointers are host memory, or device memory on devices[0] with on_device != 0. Refused before any device
+ * work, with the field named: n out of range, NULL candidates or out, an unknown filter, a var_smooth_radius outside [-1, 4] or on a
+ * filter that does not take one, a block the filter does not take, radius outside [0, 8], non-zero reserved. Blocking. */
+#define GDPT_SELECT_MEAN 0
+#define GDPT_SELECT_NLM 1
+#define GDPT_SELECT_NLM_GUIDED 2
+#define GDPT_SELECT_NLM_DEMOD 3
+#define GDPT_SELECT_NLM_REGRESS 4
+#define GDPT_SELECT_ATROUS 5
+typedef struct GdptSelectCandidate { int32_t filter; int32_t var_smooth_radius; const GdptNlmParams *nlm; const GdptAtrousParams *atrous;
+                                     const GdptNlmGuide *guide; const GdptNlmDemod *demod; const GdptNlmRegress *regress; } GdptSelectCandidate;
+int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const GdptSelectCandidate *candidates, int n,
+                                          const GdptSelectParams *select_params /* NULL: defaults */, int feature_spp, int on_device, double *out,
+                                          int32_t *sel /* nullable */, double *mse /* nullable */, double *features /* nullable */,
+                                          double *features_var /* nullable */, GdptSelectStats *stats /* nullable */,
+                                          GdptNlmStats *cand_stats /* nullable */);
 
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
