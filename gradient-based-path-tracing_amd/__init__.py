@@ -97,6 +97,12 @@ def lib():
         L.gdpt_denoise_nlm_guided_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_guided.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, vp, vp, nls]
         L.gdpt_progressive_denoise_guided.argtypes = [vp, nlp, ngp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        njs, vpp_ = C.POINTER(defs.GdptNlmJointStats), C.POINTER(vp)
+        L.gdpt_denoise_nlm_joint_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vpp_, vpp_, nlp, ngp, vp, vp, vpp_, vpp_, vp, njs]
+        L.gdpt_denoise_nlm_joint.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, vpp_, vpp_, nlp, ngp, vp, vp, vpp_, vpp_, njs]
+        L.gdpt_progressive_denoise_reconstruct.argtypes = [vp, nlp, ngp, C.c_int, C.POINTER(defs.GdptVarSmoothParams), C.c_double,
+                                                           C.POINTER(defs.GdptWeightedReconParams), C.c_int, vp, vpp_, vpp_, njs,
+                                                           C.POINTER(defs.GdptWeightedReconStats)]
         nrp = C.POINTER(defs.GdptNlmRegress)
         L.gdpt_nlm_default_regress.argtypes = [nrp]
         L.gdpt_nlm_default_regress.restype = None
@@ -528,6 +534,33 @@ class Progressive:
         out, var_out = np.empty(self.shape, dtype=np.float64), np.empty(self.shape, dtype=np.float64)
         _check(lib().gdpt_progressive_denoise(self.handle, C.byref(p), 0, C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data), C.byref(st)))
         return out, var_out, st
+
+    def denoise_reconstruct(self, alpha=0.04, guide=None, feature_spp=0, var_smooth_radius=None, weighted=None, conf_floor=0.0, recon=None,
+                            filtered=False, out_ptr=None, filtered_ptrs=None, filtered_var_ptrs=None, **params):
+        """The joint filter and the reconstruction of what it wrote (gdpt_progressive_denoise_reconstruct; GradPath, from 2 passes on):
+        the non-local-means weights of the assembled primal c (with `guide`, a GdptNlmGuide, capped by `feature_spp` samples of the
+        session's first-hit features; None = unguided) filter c, cx, cy and their variances alike, and the filtered triple is
+        reconstructed. `var_smooth_radius`: None = the primal's variance as estimated, else it is smoothed over that radius first (the
+        weights' variance only). `weighted`: None = the L2 reconstruction; RECON_L2 / RECON_L1 = reconstruct_weighted's two forms on
+        the FILTERED variances, with `conf_floor` and `recon` (a dict of the keywords of recon_params). `params`: the keywords of
+        nlm_params. Returns (HxWx3 image, GdptNlmJointStats, GdptWeightedReconStats), with `filtered=True` (image, [c, cx, cy]
+        filtered, [their variances], the two stats); with `out_ptr` (and `filtered_ptrs`, `filtered_var_ptrs`: 3 device addresses
+        each) everything stays in device memory and the two stats alone are returned."""
+        p, st, rst = nlm_params(**params), defs.GdptNlmJointStats(), defs.GdptWeightedReconStats()
+        g = C.byref(guide) if guide is not None else None
+        sp = C.byref(var_smooth_params(var_smooth_radius)) if var_smooth_radius is not None else None
+        wp = C.byref(weighted_recon_params(weighted, conf_floor, **(recon or {}))) if weighted is not None else None
+        call = lambda *tail: _check(lib().gdpt_progressive_denoise_reconstruct(self.handle, C.byref(p), g, int(feature_spp), sp, float(alpha), wp,      # noqa: E731
+                                                                               *tail, C.byref(st), C.byref(rst)))
+        if out_ptr is not None:
+            call(1, C.c_void_p(int(out_ptr)), _ptr_table(filtered_ptrs), _ptr_table(filtered_var_ptrs))
+            return st, rst
+        out = np.empty(self.shape, dtype=np.float64)
+        fl = [np.empty(self.shape, dtype=np.float64) for _ in range(3)] if filtered else None
+        fv = [np.empty(self.shape, dtype=np.float64) for _ in range(3)] if filtered else None
+        call(0, C.c_void_p(out.ctypes.data), _ptr_table([a.ctypes.data for a in fl] if filtered else None),
+             _ptr_table([a.ctypes.data for a in fv] if filtered else None))
+        return (out, fl, fv, st, rst) if filtered else (out, st, rst)
 
     def denoise_guided(self, feature_spp, guide=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
         """The feature-guided non-local-means filter on buffer 0 (gdpt_progressive_denoise_guided; from 2 passes on): the session
@@ -1049,6 +1082,62 @@ def denoise_nlm_guided_device(width, height, img_ptr, var_ptr, feat_ptr, feat_va
     opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
     _check(lib().gdpt_denoise_nlm_guided_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
                                                 C.byref(g), opt(out_ptr), opt(var_out_ptr), opt(stream), C.byref(st) if stats else None))
+    return st
+
+
+def _joint_table(ptrs, n):
+    """n addresses as the `double *const *` of the C ABI (None entries stay NULL); None: a NULL table."""
+    if ptrs is None:
+        return None
+    arr = (C.c_void_p * max(1, n))()
+    for i in range(n):
+        arr[i] = int(ptrs[i]) if i < len(ptrs) and ptrs[i] else None
+    return arr
+
+
+def denoise_nlm_joint(img, var, companions, companion_vars, feat=None, feat_var=None, guide=None, **params):
+    """denoise_nlm_guided() whose weights also filter companion films (gdpt_denoise_nlm_joint): `img`, `var` the guide film,
+    `companions`, `companion_vars` lists of at most 4 HxWx3 films and their variances, filtered with the guide film's weights.
+    `guide`: a GdptNlmGuide (nlm_guide(...)), None = the library's default when `feat` is given and NO feature term when it is not.
+    Returns (HxWx3 filtered guide film, its variance, list of filtered companions, list of their variances, GdptNlmJointStats). A
+    pixel that is not finite, or has a negative variance, in any of the films is left out of all of them."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm_joint: img and var must be HxWx3 arrays of one shape")
+    cs = [np.ascontiguousarray(x, dtype=np.float64) for x in companions]
+    cv = [np.ascontiguousarray(x, dtype=np.float64) for x in companion_vars]
+    if len(cs) != len(cv) or any(x.shape != a.shape for x in cs + cv):
+        raise GdptError("denoise_nlm_joint: companions and companion_vars must be lists of one length of arrays shaped like img")
+    g = guide if guide is not None else (nlm_guide() if feat is not None else nlm_guide(groups=[]))
+    f, fv = _feature_planes(feat, feat_var, a.shape, g)
+    n = len(cs)
+    out, var_out = np.empty(a.shape, dtype=np.float64), np.empty(a.shape, dtype=np.float64)
+    co, cvo = [np.empty(a.shape, dtype=np.float64) for _ in range(n)], [np.empty(a.shape, dtype=np.float64) for _ in range(n)]
+    p, st = nlm_params(**params), defs.GdptNlmJointStats()
+    tab = lambda arrs: _joint_table([x.ctypes.data for x in arrs], n)      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_joint(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                        C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                        n, tab(cs), tab(cv), C.byref(p), C.byref(g), C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data),
+                                        tab(co), tab(cvo), C.byref(st)))
+    return out, var_out, co, cvo, st
+
+
+def denoise_nlm_joint_device(width, height, img_ptr, var_ptr, comp_ptrs, comp_var_ptrs, out_ptr, comp_out_ptrs, var_out_ptr=None,
+                             comp_var_out_ptrs=None, feat_ptr=None, feat_var_ptr=None, guide=None, stream=None, stats=True, params=None, **kw):
+    """denoise_nlm_joint() on device addresses (gdpt_denoise_nlm_joint_device): `comp_ptrs`, `comp_var_ptrs`, `comp_out_ptrs` and
+    `comp_var_out_ptrs` (None, or None entries: not wanted) are lists of one length, at most 4. `guide`: None = the library's default
+    when `feat_ptr` is given and NO feature term when it is not. Returns GdptNlmJointStats after waiting for `stream`; with
+    `stats=False` the call only enqueues and returns None."""
+    p = params if params is not None else nlm_params(**kw)
+    g = guide if guide is not None else (nlm_guide() if feat_ptr else nlm_guide(groups=[]))
+    st = defs.GdptNlmJointStats() if stats else None
+    n = len(comp_ptrs)
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_joint_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), n,
+                                               _joint_table(comp_ptrs, n), _joint_table(comp_var_ptrs, n), C.byref(p), C.byref(g), opt(out_ptr),
+                                               opt(var_out_ptr), _joint_table(comp_out_ptrs, n), _joint_table(comp_var_out_ptrs, n), opt(stream),
+                                               C.byref(st) if stats else None))
     return st
 
 

@@ -151,6 +151,13 @@ class GdptNlmGuide(C.Structure):
                 ("k_f", C.c_double), ("alpha_f", C.c_double), ("reserved", C.c_int32 * 2)]
 
 
+NLM_JOINT_MAX = 4
+
+
+class GdptNlmJointStats(C.Structure):
+    _fields_ = [("guide", GdptNlmStats), ("sum_var_in", C.c_double * NLM_JOINT_MAX), ("sum_var_out", C.c_double * NLM_JOINT_MAX)]
+
+
 NLM_MAX_REGRESSORS = 7
 
 

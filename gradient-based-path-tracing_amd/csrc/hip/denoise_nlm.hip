@@ -28,7 +28,7 @@
 // finish_pixel multiplies a~ back. A thread recomputes its own a~ from the planar planes there, and reloads its own original triples
 // for the colour-domain sums: (u / a~) a~ is not always u.
 // The device helpers of all of them (the guide's and the divisor's blocks, load_pixel, pair_distance, OwnFeatures, the LDS sizing, the
-// sums) are in nlm_device.h, which nlm_regress.hip shares.
+// sums, and a pixel's weighted sums: Accum, finish_pixel) are in nlm_device.h, which nlm_regress.hip and nlm_joint.hip share.
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "image_kernels.h"
@@ -68,58 +68,6 @@ struct GuidedDemodArgs : GuidedArgs {
 template <bool GUIDED, bool DEMOD>
 using ArgsOf = typename std::conditional<GUIDED, typename std::conditional<DEMOD, GuidedDemodArgs, GuidedArgs>::type,
                                          typename std::conditional<DEMOD, DemodArgs, Args>::type>::type;
-
-struct Accum {
-    double num[3] = {0.0, 0.0, 0.0}, vnum[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
-    // Df (guided kernels): the pair's feature distance, >= 0
-    template <bool GUIDED = false>
-    __device__ __forceinline__ void add(double S, int C, const double u[3], const double v[3], double Df = 0.0) {
-        double D = S / (double)C;
-        D = D > 0.0 ? D : 0.0;
-        if (GUIDED) D = fmax(D, Df);
-        const double wgt = exp(-D);
-        wsum += wgt;
-#pragma unroll
-        for (int c = 0; c < 3; c++) { num[c] += wgt * u[c]; vnum[c] += (wgt * wgt) * v[c]; }
-    }
-};
-
-// the pixel's outputs and its terms of the film sums; u, v: its valid input triples (what load_pixel gave). A demodulated kernel
-// multiplies the pixel's own a~ back and takes the sums' input terms from the original triples in global memory.
-template <class A>
-__device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
-    double o[3], vo[3];
-    const double w2 = acc.wsum * acc.wsum;
-    if constexpr (A::kDemod) {
-        double al[3], uo[3], vi[3];
-        effective_albedo(a.dm, i / 3, al);
-#pragma unroll
-        for (int c = 0; c < 3; c++) {
-            const double oc = acc.num[c] / acc.wsum, voc = acc.vnum[c] / w2, al2 = al[c] * al[c];
-            o[c] = oc * al[c];
-            vo[c] = voc * al2;
-            a.out[i + c] = o[c];
-            if (a.var_out) a.var_out[i + c] = vo[c];
-            uo[c] = a.img[i + c]; vi[c] = a.var[i + c];
-        }
-        s.var_in += (vi[0] + vi[1]) + vi[2];
-        s.sq_in += (uo[0] * uo[0] + uo[1] * uo[1]) + uo[2] * uo[2];
-        s.var_out += (vo[0] + vo[1]) + vo[2];
-        s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
-        return;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        o[c] = acc.num[c] / acc.wsum;
-        vo[c] = acc.vnum[c] / w2;
-        a.out[i + c] = o[c];
-        if (a.var_out) a.var_out[i + c] = vo[c];
-    }
-    s.var_in += (v[0] + v[1]) + v[2];
-    s.sq_in += (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
-    s.var_out += (vo[0] + vo[1]) + vo[2];
-    s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
-}
 
 template <bool GUIDED, bool DEMOD>
 __global__ __launch_bounds__(kBlock) void direct_kernel(ArgsOf<GUIDED, DEMOD> a) {

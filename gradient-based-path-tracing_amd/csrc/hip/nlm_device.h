@@ -1,7 +1,7 @@
 // nlm_device.h — the device helpers the non-local-means kernels share (denoise_nlm.hip, nlm_regress.hip): the tile constants, the
 // guide's and the divisor's blocks, the tiled form's LDS sizing, a pixel's validity and loading, the pair distance, the thread's own
-// features and the film sums. `A` is a kernel's argument block: the fields of nlm::Args (denoise_nlm.hip), kGuided / kDemod, and with
-// them `gd` / `dm`.
+// features, a pixel's weighted sums (Accum, finish_pixel: nlm_joint.hip shares them with denoise_nlm.hip) and the film sums. `A` is a
+// kernel's argument block: the fields of nlm::Args (denoise_nlm.hip), kGuided / kDemod, and with them `gd` / `dm`.
 #pragma once
 #include "../../../include/gdpt.h"
 #include "image_kernels.h"
@@ -174,5 +174,64 @@ struct OwnFeatures {
         return Df;
     }
 };
+
+// one term of a pixel's weighted sums: the triples u, v of p+o under the weight wgt. The one copy of these two expressions: the filtered
+// film's sums and the companions' (nlm_joint.hip) both come from it, so equal inputs give equal bits.
+__device__ __forceinline__ void add_term(double num[3], double vnum[3], double wgt, const double u[3], const double v[3]) {
+#pragma unroll
+    for (int c = 0; c < 3; c++) { num[c] += wgt * u[c]; vnum[c] += (wgt * wgt) * v[c]; }
+}
+
+struct Accum {
+    double num[3] = {0.0, 0.0, 0.0}, vnum[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
+    // Df (guided kernels): the pair's feature distance, >= 0. Returns the weight w_o(p).
+    template <bool GUIDED = false>
+    __device__ __forceinline__ double add(double S, int C, const double u[3], const double v[3], double Df = 0.0) {
+        double D = S / (double)C;
+        D = D > 0.0 ? D : 0.0;
+        if (GUIDED) D = fmax(D, Df);
+        const double wgt = exp(-D);
+        wsum += wgt;
+        add_term(num, vnum, wgt, u, v);
+        return wgt;
+    }
+};
+
+// the pixel's outputs and its terms of the film sums; u, v: its valid input triples (what load_pixel gave). A demodulated kernel
+// multiplies the pixel's own a~ back and takes the sums' input terms from the original triples in global memory.
+template <class A>
+__device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double u[3], const double v[3], const Accum &acc, Sums &s) {
+    double o[3], vo[3];
+    const double w2 = acc.wsum * acc.wsum;
+    if constexpr (A::kDemod) {
+        double al[3], uo[3], vi[3];
+        effective_albedo(a.dm, i / 3, al);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const double oc = acc.num[c] / acc.wsum, voc = acc.vnum[c] / w2, al2 = al[c] * al[c];
+            o[c] = oc * al[c];
+            vo[c] = voc * al2;
+            a.out[i + c] = o[c];
+            if (a.var_out) a.var_out[i + c] = vo[c];
+            uo[c] = a.img[i + c]; vi[c] = a.var[i + c];
+        }
+        s.var_in += (vi[0] + vi[1]) + vi[2];
+        s.sq_in += (uo[0] * uo[0] + uo[1] * uo[1]) + uo[2] * uo[2];
+        s.var_out += (vo[0] + vo[1]) + vo[2];
+        s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+        return;
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        o[c] = acc.num[c] / acc.wsum;
+        vo[c] = acc.vnum[c] / w2;
+        a.out[i + c] = o[c];
+        if (a.var_out) a.var_out[i + c] = vo[c];
+    }
+    s.var_in += (v[0] + v[1]) + v[2];
+    s.sq_in += (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+    s.var_out += (vo[0] + vo[1]) + vo[2];
+    s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+}
 
 } // namespace nlm

@@ -726,6 +726,67 @@ int gdpt_progressive_denoise_smoothed(GdptProgressive *session, int kind,const G
     });
 }
 
+int gdpt_progressive_denoise_reconstruct(GdptProgressive *session, const GdptNlmParams *nlm, const GdptNlmGuide *guide, int feature_spp,
+                                         const GdptVarSmoothParams *var_smooth, double dataCost, const GdptWeightedReconParams *weighted_recon,
+                                         int on_device, double *out, double *const filtered[3], double *const filtered_var[3],
+                                         GdptNlmJointStats *stats, GdptWeightedReconStats *recon_stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_reconstruct";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        GdptNlmParams p;
+        if (nlm) p = *nlm; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        GdptNlmGuide g;                   // guide == NULL: no group, so no feature term and no planes
+        if (guide) g = *guide; else { gdpt_nlm_default_guide(&g); g.num_groups = 0; }
+        gdpt::nlm_check_guide(who, g);
+        if (guide && g.num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
+        if (var_smooth) gdpt::var_smooth_check_params(who, *var_smooth);
+        GdptProgressive &s = *session;
+        if (s.nbuf != 5) throw std::runtime_error(who + ": an Integrator::Path session has no gradients (filter its mean with gdpt_progressive_denoise*)");
+        if (s.passes < 2) throw std::runtime_error(who + ": variances need at least 2 passes");
+        if (guide && (feature_spp < 2 || feature_spp > s.block)) throw std::runtime_error(who + ": feature_spp must be in [2, budget_spp]");
+        ck(hipSetDevice(s.scene->device), "hipSetDevice");
+        assemble_means(s);
+        compute_variances(s);
+        const double *d_var_c = s.var[0];
+        if (var_smooth) {                 // the guide film's variance only: the companions' and the reconstruction's stay the session's
+            if (!s.smooth_buf) s.smooth_buf.alloc(s.elems, "hipMalloc(progressive smoothed variance)");
+            gdpt::variance_smooth_launch(s.w, s.h, s.asm_buf[0], s.var[0], nullptr, nullptr, *var_smooth, nullptr, s.smooth_buf, s.stream, nullptr);
+            d_var_c = s.smooth_buf;
+        }
+        if (guide) {                      // the feature render of gdpt_progressive_denoise_guided (filter_with_features)
+            const size_t felems = (size_t)s.w * s.h * GDPT_FEATURE_CHANNELS;
+            for (auto &b : s.feat_buf) if (!b) b.alloc(felems, "hipMalloc(progressive features)");
+            GdptRenderParams rp{};
+            rp.spp = feature_spp; rp.rng_scheme = GDPT_RNG_SAMPLE;
+            const GdptSampleWindow win{s.block, 0};
+            if (!s.feat_current) gdpt::features_launch(s.scene, &rp, &win, s.feat_buf[0], s.feat_buf[1], s.stream, nullptr);
+        }
+        for (auto &b : s.joint_buf) if (!b) b.alloc(s.elems, "hipMalloc(progressive joint filter)");
+        const double *comp[2] = {s.asm_buf[1], s.asm_buf[2]}, *comp_var[2] = {s.var[5], s.var[6]};
+        double *comp_out[2] = {s.joint_buf[1], s.joint_buf[2]}, *comp_var_out[2] = {s.joint_buf[4], s.joint_buf[5]};
+        GdptNlmJointStats st{};           // (asked for always: the call is blocking)
+        gdpt::denoise_nlm_joint_launch(s.w, s.h, s.asm_buf[0], d_var_c, guide ? s.feat_buf[0].data() : nullptr, guide ? s.feat_buf[1].data() : nullptr, 2,
+                                       comp, comp_var, p, g, s.joint_buf[0], s.joint_buf[3], comp_out, comp_var_out, s.stream, &st);
+        GdptWeightedReconStats rs{};
+        if (weighted_recon) {
+            if (gdpt_reconstruct_weighted_device(s.w, s.h, s.joint_buf[0], s.joint_buf[1], s.joint_buf[2], s.joint_buf[3], s.joint_buf[4], s.joint_buf[5],
+                                                 dataCost, weighted_recon, s.asm_buf[3], nullptr, s.stream, &rs) != 0)
+                throw std::runtime_error(gdpt_last_error());
+        } else if (gdpt_reconstruct_device(s.w, s.h, s.joint_buf[0], s.joint_buf[1], s.joint_buf[2], dataCost, nullptr, s.asm_buf[3], s.stream, &rs.recon) != 0)
+            throw std::runtime_error(gdpt_last_error());
+        copy_out(s, out, s.asm_buf[3], on_device);
+        for (int k = 0; k < 3; k++) {
+            if (filtered) copy_out(s, filtered[k], s.joint_buf[k], on_device);
+            if (filtered_var) copy_out(s, filtered_var[k], s.joint_buf[3 + k], on_device);
+        }
+        ck(hipStreamSynchronize(s.stream), "hipStreamSynchronize(progressive denoise reconstruct)");
+        if (stats) *stats = st;
+        if (recon_stats) *recon_stats = rs;
+    });
+}
+
 int gdpt_progressive_denoise_multiscale(GdptProgressive *session, int kind, int levels, const GdptVarSmoothParams *smooth, const GdptNlmParams *nlm,
                                         const GdptNlmGuide *guide, const GdptNlmDemod *demod, int feature_spp, int on_device, double *out,
                                         double *var_out, double *features, double *features_var, GdptNlmPyramidStats *stats) {

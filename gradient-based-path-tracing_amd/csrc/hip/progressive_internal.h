@@ -33,6 +33,7 @@ struct GdptProgressive {
     bool feat_current = false;                 // feat_buf holds the planes the next guided denoise would render: it renders none (set and cleared by
                                                // gdpt_progressive_group_denoise_select alone, which renders once for its three sessions)
     gdpt::DeviceBuffer<double> smooth_buf;     // the smoothed variance of buffer 0 (gdpt_progressive_denoise_smoothed): allocated by the first one
+    gdpt::DeviceBuffer<double> joint_buf[6];   // the jointly filtered c, cx, cy and their variances (gdpt_progressive_denoise_reconstruct): allocated by the first one
     gdpt::DeviceBuffer<double> partials;
     gdpt::DeviceBuffer<film::Estimate> d_est;
     gdpt::PinnedBuffer<film::Estimate> h_est;

@@ -83,6 +83,12 @@
 //                 entries (0,0 is two slices on one GPU); not combined with --nlm-window, --nlm-patch, --nlm-k, --nlm-guide,
 //                 --nlm-demodulate, --nlm-levels, --nlm-regress, --nlm-ridge, --nlm-depth-scale, --atrous-levels or --atrous-k.
 //                 Without --select every output file is what it was
+//                 --nlm-joint (GradPath scenes) writes to FILE the reconstruction of the JOINTLY FILTERED c, cx, cy instead
+//                 (gdpt_progressive_denoise_reconstruct): the filter's weights, from the primal and its variance, average the gradients and
+//                 all three variances too; -o stays the plain reconstruction. It honours --nlm-window / -patch / -k, --nlm-guide (with
+//                 --nlm-kf, --nlm-depth-tau, --feature-spp), --nlm-var-smooth (the weights' variance only), --reconstruct l2 | wl2 | wl1
+//                 (the weighted ones on the filtered variances) and --conf-floor; not --reconstruct l1, --nlm-demodulate, --nlm-regress,
+//                 --nlm-levels, --atrous-levels, --select or --gpus
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
@@ -117,6 +123,7 @@ int main(int argc, char *argv[]) {
     bool nlm_option = false, nlm_k_set = false, nlm_guide_option = false, nlm_demodulate = false;
     double nlm_albedo_floor = 0.0;
     int nlm_var_smooth = -1;          // < 0: not given
+    bool nlm_joint = false;
     int nlm_levels = 0;               // 0: not given
     std::string features_prefix = "", nlm_guide_names = "", nlm_regress_names = "";
     double nlm_ridge = 0.0, nlm_depth_scale = 0.0;
@@ -210,6 +217,7 @@ int main(int argc, char *argv[]) {
         }
         else if (a == "--atrous-k") { atrous_k = std::stod(next()); atrous_k_set = true; }
         else if (a == "--nlm-demodulate") nlm_demodulate = true;
+        else if (a == "--nlm-joint") nlm_joint = true;
         else if (a == "--nlm-albedo-floor") nlm_albedo_floor = std::stod(next());
         else if (a == "--nlm-levels") {
             nlm_levels = std::stoi(next());
@@ -258,6 +266,20 @@ int main(int argc, char *argv[]) {
             }
         }
         else filenames.push_back(a);
+    }
+    if (nlm_joint) {
+        if (denoised_file.empty()) { std::cerr << "--nlm-joint needs --denoised" << std::endl; return 2; }
+        if (multi.num_devices > 0) { std::cerr << "--nlm-joint is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
+        if (nlm_demodulate || !nlm_regress_names.empty() || nlm_levels > 0 || atrous_levels > 0 || !select_list.empty()) {
+            std::cerr << "--nlm-joint is not combined with --nlm-demodulate, --nlm-regress, --nlm-levels, --atrous-levels or --select: the joint filter is the "
+                         "plain or guided non-local-means filter on the primal and the gradients" << std::endl;
+            return 2;
+        }
+        if (recon.norm == GDPT_RECON_L1 && !weighted) {
+            std::cerr << "--nlm-joint is not combined with --reconstruct l1: the unweighted IRLS solve has no variant that takes the filtered variances "
+                         "(use l2, wl2 or wl1)" << std::endl;
+            return 2;
+        }
     }
     if (recon.norm == GDPT_RECON_L1 && multi.num_devices > 0) { std::cerr << "--reconstruct l1 is a single-device option (not with --gpus / --devices)" << std::endl; return 2; }
     if (!sample_devices.empty() && pass_spp <= 0) { std::cerr << "--sample-devices needs --pass-spp (it splits a progressive session)" << std::endl; return 2; }
@@ -448,6 +470,10 @@ int main(int argc, char *argv[]) {
         GdptMulti *mscene = nullptr;
         GdptProgressiveGroup *group = nullptr;
         const bool path = desc->integrator == GDPT_INTEGRATOR_PATH;
+        if (nlm_joint && path) {
+            std::cerr << "--nlm-joint needs a GradPath scene: an Integrator::Path scene has no gradients to filter beside the image" << std::endl;
+            return 2;
+        }
         GdptProgressiveConfig cfg{};      // of the session or group that --pass-spp asks for
         cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = shift; cfg.budget_spp = spp;
         if ((grouped   ? gdpt_progressive_group_create(desc, sample_devices.data(), (int)sample_devices.size(), &cfg, &group)
@@ -472,6 +498,7 @@ int main(int argc, char *argv[]) {
         GdptProgressiveStatus prog{};
         GdptReconSpreadStats spread{};
         GdptNlmStats nlm_stats{};
+        GdptNlmJointStats joint_stats{};
         GdptVarSmoothStats smooth_stats{};
         GdptNlmPyramidStats pyramid_stats{};
         GdptSelectStats select_stats{};
@@ -581,6 +608,18 @@ int main(int argc, char *argv[]) {
                         for (size_t i = 0; i < (size_t)w * h; i++) for (int k = 0; k < 3; k++) rgb[3 * i + k] = mse[i];
                         rc = gdpt_imwrite(select_mse_file.c_str(), w, h, rgb.data());
                     }
+                } else if (nlm_joint) {      // the reconstruction of the jointly filtered c, cx, cy
+                    const int budget = spp > 0 ? spp : desc->samples_per_pixel;
+                    GdptVarSmoothParams sp{};
+                    gdpt_var_smooth_default_params(&sp);
+                    sp.radius = nlm_var_smooth;
+                    GdptWeightedReconParams wp{};
+                    wp.recon = recon; wp.conf_floor = conf_floor;
+                    rc = gdpt_progressive_denoise_reconstruct(session, &nlm, guided ? &guide : nullptr, feature_spp > 0 ? feature_spp : std::min(16, budget),
+                                                              nlm_var_smooth >= 0 ? &sp : nullptr, alpha, weighted ? &wp : nullptr, 0, filtered.data(), nullptr,
+                                                              nullptr, &joint_stats, nullptr);
+                    nlm_stats = joint_stats.guide;
+                    smooth_stats.radius = nlm_var_smooth;
                 } else if (atrous_on) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     rc = gdpt_progressive_denoise_atrous(session, &atrous, &guide, nlm_demodulate ? &demod : nullptr,
@@ -692,6 +731,12 @@ int main(int argc, char *argv[]) {
                     std::cout << " " << names[select_names[(size_t)j]] << " " << (valid > 0 ? 100.0 * (double)select_stats.chosen[j] / valid : 0.0) << " % (error "
                               << (select_stats.sum_sq_out > 0 ? std::sqrt(std::max(0.0, select_stats.sum_e[j]) / select_stats.sum_sq_out) : 0.0) << ");";
                 std::cout << " select_ms " << select_stats.select_ms << ", written to " << denoised_file << std::endl;
+            } else if (nlm_joint) {
+                auto ratio = [](double out, double in) { return in > 0.0 ? out / in : 0.0; };
+                std::cout << "[gdpt] joint: " << joint_stats.guide.pixels_left_out << " pixels left out; variance c \u00d7"
+                          << ratio(joint_stats.guide.sum_var_out, joint_stats.guide.sum_var_in) << ", cx \u00d7"
+                          << ratio(joint_stats.sum_var_out[0], joint_stats.sum_var_in[0]) << ", cy \u00d7"
+                          << ratio(joint_stats.sum_var_out[1], joint_stats.sum_var_in[1]) << std::endl;
             } else if (!denoised_file.empty())
                 std::cout << "[gdpt] denoised: error_in " << nlm_stats.error_in << ", error_out " << nlm_stats.error_out << " (weights taken as fixed, bias left out; "
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius

@@ -1175,6 +1175,64 @@ int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const Gdp
                                           double *features_var /* nullable */, GdptSelectStats *stats /* nullable */,
                                           GdptNlmStats *cand_stats /* nullable */);
 
+/* ---- joint filtering: the non-local-means weights of one film applied to companion films (not part of the reference) ----
+ * Every filter above writes one film. A GradPath session holds three that belong together, the assembled c, cx, cy: here the weights
+ * are computed once, from a GUIDE FILM and its variance (optionally capped by the feature guide), and applied to n COMPANION FILMS and
+ * their variances as well (the joint filtering step of Manzi, Vicini, Zwicker, "Regularizing image reconstruction for gradient-domain
+ * rendering with feature patches", Eurographics 2016, and of Rousselle, Jarosz, Novak, "Image-space control variates for rendering",
+ * SIGGRAPH Asia 2016, without their regularisers). The filtered variances are what gdpt_reconstruct_weighted takes.
+ * The definition extends gdpt_denoise_nlm_guided's; img, var (the guide film), feat, feat_var, GdptNlmParams and GdptNlmGuide are its.
+ * comp[j], comp_var[j], 0 <= j < n, 0 <= n <= GDPT_NLM_JOINT_MAX: W*H*3 doubles each, interleaved like every film.
+ * A pixel is VALID if it is valid for gdpt_denoise_nlm_guided, every companion triple at it is finite, and every companion variance at
+ * it is finite and >= 0. w_o(p) is gdpt_denoise_nlm_guided's weight over THIS validity; out, var_out of the guide film are defined as
+ * there, and for every companion, over the same offsets in the same row-major order,
+ *   comp_out_j,c(p)     = sum_o w_o(p) a_j,c(p+o) / sum_o w_o(p)
+ *   comp_var_out_j,c(p) = sum_o w_o(p)^2 s_j,c(p+o) / (sum_o w_o(p))^2        (a_j = comp[j], s_j = comp_var[j])
+ * An invalid p keeps every input triple, the guide film's and the companions', bit for bit, and is counted once in
+ * guide.pixels_left_out. GdptNlmJointStats.guide is the GdptNlmStats of the guide film; sum_var_in[j], sum_var_out[j] are the sums of
+ * comp_var[j] and comp_var_out[j] over the valid pixels (per pixel (c0 + c1) + c2), reduced in the same fixed order; entries j >= n
+ * are 0. Exact, bit for bit:
+ *   - with every companion valid everywhere, out, var_out and stats.guide (but filter_ms) are gdpt_denoise_nlm_guided's; so with n = 0,
+ *     and with num_groups = 0 they are gdpt_denoise_nlm's;
+ *   - a companion that is the guide film itself (comp[j] = img, comp_var[j] = var) comes back as out, var_out;
+ *   - r = 0 returns every input. */
+#define GDPT_NLM_JOINT_MAX 4
+typedef struct GdptNlmJointStats { GdptNlmStats guide; double sum_var_in[GDPT_NLM_JOINT_MAX], sum_var_out[GDPT_NLM_JOINT_MAX]; } GdptNlmJointStats;
+/* Device pointers on the current device; d_comp, d_comp_var, d_comp_out, d_comp_var_out are host arrays of n device pointers. What
+ * gdpt_denoise_nlm_guided_device refuses is refused, and, naming the field, before any device call: n outside [0, 4]; with n > 0 a NULL
+ * d_comp, d_comp_var or d_comp_out, or a NULL entry of one of them (d_comp_var_out, and any entry of it, is nullable); any output whose
+ * byte range overlaps an input's or another output's. guide == NULL: gdpt_nlm_default_guide; guide->num_groups == 0 takes NULL d_feat,
+ * d_feat_var. Enqueued on `stream`; with stats it waits for the stream, with stats == NULL it only enqueues. Scratch per (device,
+ * stream), dropped by gdpt_poisson_forget_stream. No CPU fallback. */
+int gdpt_denoise_nlm_joint_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                  int n, const double *const *d_comp, const double *const *d_comp_var,
+                                  const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                                  double *d_out, double *d_var_out /* nullable */, double *const *d_comp_out,
+                                  double *const *d_comp_var_out /* nullable */, void *stream, GdptNlmJointStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_denoise_nlm_joint(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                           int n, const double *const *comp, const double *const *comp_var,
+                           const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                           double *out, double *var_out /* nullable */, double *const *comp_out, double *const *comp_var_out /* nullable */,
+                           GdptNlmJointStats *stats /* nullable */);
+/* The joint filter on a GradPath session, then the reconstruction of what it wrote. By definition the outputs are, bit for bit, those
+ * of this chain on the session's stream: the running means assembled into c, cx, cy (gdpt_assemble_device) and the assembled_vars of
+ * gdpt_progressive_read; with var_smooth != NULL gdpt_variance_smooth_device (a~ = 1) on (c, var c), its output taking var c's place
+ * as the guide film's variance only; with guide != NULL gdpt_features_render_device as gdpt_progressive_denoise_guided renders it
+ * (guide == NULL: no feature term and no render; feature_spp is ignored); gdpt_denoise_nlm_joint_device with the guide film (c, var c)
+ * and the companions (cx, var cx), (cy, var cy); then, with weighted_recon == NULL, gdpt_reconstruct_device (L2) on the filtered c, cx,
+ * cy, otherwise gdpt_reconstruct_weighted_device on them with the FILTERED variances (its recon.norm selects weighted L2 or L1).
+ * filtered, filtered_var (nullable; any entry nullable): receive the filtered c, cx, cy and their variances. recon_stats (nullable):
+ * with weighted_recon its fields are filled, otherwise recon_stats->recon alone. Needs a GradPath session with at least 2 passes, a
+ * group's total and its halves included; an Integrator::Path session is refused by name. All output pointers are host memory, or
+ * device memory with on_device != 0. Blocking. */
+int gdpt_progressive_denoise_reconstruct(GdptProgressive *session, const GdptNlmParams *nlm /* NULL: defaults */,
+                                         const GdptNlmGuide *guide /* NULL: unguided */, int feature_spp,
+                                         const GdptVarSmoothParams *var_smooth /* NULL: none */, double dataCost,
+                                         const GdptWeightedReconParams *weighted_recon /* NULL: L2 */, int on_device, double *out,
+                                         double *const filtered[3] /* nullable */, double *const filtered_var[3] /* nullable */,
+                                         GdptNlmJointStats *stats /* nullable */, GdptWeightedReconStats *recon_stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
