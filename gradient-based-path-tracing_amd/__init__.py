@@ -109,6 +109,9 @@ def lib():
         L.gdpt_denoise_nlm_regress_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, vp, nls]
         L.gdpt_denoise_nlm_regress.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, nls]
         L.gdpt_progressive_denoise_regress.argtypes = [vp, nlp, ngp, nrp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm_collab_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, vp, nls]
+        L.gdpt_denoise_nlm_collab.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, nlp, ngp, nrp, vp, vp, nls]
+        L.gdpt_progressive_denoise_collab.argtypes = [vp, nlp, ngp, nrp, C.c_int, C.c_int, vp, vp, vp, nls]
         ndp = C.POINTER(defs.GdptNlmDemod)
         L.gdpt_nlm_default_demod.argtypes = [ndp]
         L.gdpt_nlm_default_demod.restype = None
@@ -608,6 +611,28 @@ class Progressive:
                                                       C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
         return (out, var_out, fm, fv, st) if features else (out, var_out, st)
 
+    def denoise_collab(self, feature_spp, guide=None, regress=None, features=False, out_ptr=None, features_ptrs=None, **params):
+        """The collaborative form of denoise_regress on buffer 0 (gdpt_progressive_denoise_collab; from 2 passes on): every pixel takes
+        the weighted average of all fits whose windows cover it. Arguments as denoise_regress, without a variance of the result:
+        returns (HxWx3 image, GdptNlmStats), with `features=True` the two (8, H, W) feature arrays before the stats; with `out_ptr`
+        (and `features_ptrs`) everything stays in device memory and the stats alone are returned."""
+        p, st = nlm_params(**params), defs.GdptNlmStats()
+        g = guide if guide is not None else nlm_guide()
+        rg = regress if regress is not None else nlm_regress()
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        if out_ptr is not None:
+            fp = list(features_ptrs) if features_ptrs is not None else [None, None]
+            _check(lib().gdpt_progressive_denoise_collab(self.handle, C.byref(p), C.byref(g), C.byref(rg), int(feature_spp), 1, opt(out_ptr),
+                                                         opt(fp[0]), opt(fp[1]), C.byref(st)))
+            return st
+        out = np.empty(self.shape, dtype=np.float64)
+        fshape = (defs.FEATURE_CHANNELS,) + tuple(self.shape[:2])
+        fm, fv = (np.empty(fshape, dtype=np.float64), np.empty(fshape, dtype=np.float64)) if features else (None, None)
+        _check(lib().gdpt_progressive_denoise_collab(self.handle, C.byref(p), C.byref(g), C.byref(rg), int(feature_spp), 0,
+                                                     C.c_void_p(out.ctypes.data), C.c_void_p(fm.ctypes.data) if features else None,
+                                                     C.c_void_p(fv.ctypes.data) if features else None, C.byref(st)))
+        return (out, fm, fv, st) if features else (out, st)
+
     def denoise_demod(self, feature_spp, guide=None, demod=None, features=False, out_ptr=None, var_out_ptr=None, features_ptrs=None, **params):
         """The albedo-demodulated non-local-means filter on buffer 0 (gdpt_progressive_denoise_demod; from 2 passes on): the session
         renders `feature_spp` samples of first-hit features along the camera rays of its own first samples, divides its mean by their
@@ -802,12 +827,12 @@ class ProgressiveGroup:
         return tuple(Progressive._view(self, h.value, self.total.shape, self.total.path) for h in (a, b))
 
     _SELECT_FILTERS = {"mean": defs.SELECT_MEAN, "nlm": defs.SELECT_NLM, "guided": defs.SELECT_NLM_GUIDED, "demod": defs.SELECT_NLM_DEMOD,
-                       "regress": defs.SELECT_NLM_REGRESS, "atrous": defs.SELECT_ATROUS}
+                       "regress": defs.SELECT_NLM_REGRESS, "atrous": defs.SELECT_ATROUS, "collab": defs.SELECT_NLM_COLLAB}
 
     def denoise_select(self, candidates, radius=None, feature_spp=4, maps=False, features=False, out_ptrs=None):
         """The filters in `candidates` run on the two halves and on the total, and per pixel the one whose error the halves estimate
         smallest (gdpt_progressive_group_denoise_select). A candidate is a dict: `filter` one of "mean", "nlm", "guided", "demod",
-        "regress", "atrous" (or a GDPT_SELECT_* value); `var_smooth`: a radius, for "nlm", "guided" and "demod" only; `nlm`: a
+        "regress", "atrous", "collab" (or a GDPT_SELECT_* value); `var_smooth`: a radius, for "nlm", "guided" and "demod" only; `nlm`: a
         GdptNlmParams or a dict of nlm_params keywords; `atrous`: a GdptAtrousParams or a dict of atrous_params keywords; `guide`,
         `demod`, `regress`: the blocks, None as in the matching Progressive.denoise_* call. Returns (out HxWx3, GdptSelectStats, list
         of the candidates' GdptNlmStats on the total); with `maps=True` (out, sel HxW int32, mse HxW, stats, list); with
@@ -1199,6 +1224,44 @@ def denoise_nlm_regress_device(width, height, img_ptr, var_ptr, feat_ptr, feat_v
     _check(lib().gdpt_denoise_nlm_regress_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
                                                  C.byref(g), C.byref(rg), opt(out_ptr), opt(var_out_ptr), opt(stream),
                                                  C.byref(st) if stats else None))
+    return st
+
+
+def denoise_nlm_collab(img, var, feat, feat_var, guide=None, regress=None, coef=False, **params):
+    """The collaborative form of denoise_nlm_regress() (gdpt_denoise_nlm_collab): every pixel takes the weighted average of all fits
+    whose windows cover it. Arguments as denoise_nlm_regress. Returns (HxWx3 image, GdptNlmStats), with `coef=True` (image, the
+    (3 (1 + m), H, W) coefficient film, stats): plane c (1 + m) + j holds beta_c,j. There is no variance of the result: the stats'
+    sum_var_out and error_out are NaN."""
+    a = np.ascontiguousarray(img, dtype=np.float64)
+    v = np.ascontiguousarray(var, dtype=np.float64)
+    if a.ndim != 3 or a.shape[2] != 3 or v.shape != a.shape:
+        raise GdptError("denoise_nlm_collab: img and var must be HxWx3 arrays of one shape")
+    g = guide if guide is not None else nlm_guide()
+    rg = regress if regress is not None else nlm_regress()
+    f, fv = _feature_planes(feat, feat_var, a.shape, g)
+    out = np.empty(a.shape, dtype=np.float64)
+    planes = np.empty((3 * (1 + max(0, int(rg.num_regressors))),) + a.shape[:2], dtype=np.float64) if coef else None
+    p, st = nlm_params(**params), defs.GdptNlmStats()
+    _check(lib().gdpt_denoise_nlm_collab(int(a.shape[1]), int(a.shape[0]), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                         C.c_void_p(f.ctypes.data) if f is not None else None, C.c_void_p(fv.ctypes.data) if fv is not None else None,
+                                         C.byref(p), C.byref(g), C.byref(rg), C.c_void_p(out.ctypes.data),
+                                         C.c_void_p(planes.ctypes.data) if coef else None, C.byref(st)))
+    return (out, planes, st) if coef else (out, st)
+
+
+def denoise_nlm_collab_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_ptr, out_ptr, coef_ptr=None, guide=None, regress=None,
+                              stream=None, stats=True, params=None, **kw):
+    """denoise_nlm_collab() on device addresses (gdpt_denoise_nlm_collab_device); arguments as denoise_nlm_regress_device, with
+    `coef_ptr` (3 (1 + m) planes of width * height doubles; None = the library keeps the coefficient film) in the place of
+    `var_out_ptr`."""
+    p = params if params is not None else nlm_params(**kw)
+    g = guide if guide is not None else nlm_guide()
+    rg = regress if regress is not None else nlm_regress()
+    st = defs.GdptNlmStats() if stats else None
+    opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+    _check(lib().gdpt_denoise_nlm_collab_device(int(width), int(height), opt(img_ptr), opt(var_ptr), opt(feat_ptr), opt(feat_var_ptr), C.byref(p),
+                                                C.byref(g), C.byref(rg), opt(out_ptr), opt(coef_ptr), opt(stream),
+                                                C.byref(st) if stats else None))
     return st
 
 
@@ -1895,7 +1958,7 @@ class debug_knobs:
         """GDPT_FORCE_EAGER=1 -> force_eager=1 ... for the manual sweep scripts (tests/sweep_*.py, tune_render.py)."""
         environ = os.environ if environ is None else environ
         names = ("force_eager", "log2k", "keep_frac", "search_frac", "blocks_per_cu", "no_lds_scene", "lds_wide",
-                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct", "lds_fixed_layout")
+                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct", "lds_fixed_layout", "nlm_collab_pass")
         lib().gdpt_debug_knobs_reset()
         for n in names:
             v = environ.get("GDPT_" + n.upper())

@@ -203,7 +203,7 @@ class GdptSelectStats(C.Structure):
                 ("sum_mse", C.c_double), ("sum_sq_out", C.c_double), ("select_ms", C.c_double), ("radius", C.c_int32), ("num_candidates", C.c_int32)]
 
 
-SELECT_MEAN, SELECT_NLM, SELECT_NLM_GUIDED, SELECT_NLM_DEMOD, SELECT_NLM_REGRESS, SELECT_ATROUS = range(6)
+SELECT_MEAN, SELECT_NLM, SELECT_NLM_GUIDED, SELECT_NLM_DEMOD, SELECT_NLM_REGRESS, SELECT_ATROUS, SELECT_NLM_COLLAB = range(7)
 
 
 class GdptSelectCandidate(C.Structure):

@@ -28,6 +28,7 @@
 #include "progressive_internal.h"
 #include "denoise_nlm.h"
 #include "nlm_regress.h"
+#include "nlm_collab.h"
 #include "denoise_atrous.h"
 #include "variance_smooth.h"
 #include "nlm_pyramid.h"
@@ -583,6 +584,30 @@ int gdpt_progressive_denoise_regress(GdptProgressive *session, const GdptNlmPara
                              [&](GdptProgressive &s, double *d_out, double *d_var_out, GdptNlmStats *st) {
                                  gdpt::denoise_nlm_regress_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, g, rg, d_out, d_var_out,
                                                                   s.stream, st);
+                             });
+    });
+}
+
+int gdpt_progressive_denoise_collab(GdptProgressive *session, const GdptNlmParams *params, const GdptNlmGuide *guide, const GdptNlmRegress *regress,
+                                    int feature_spp, int on_device, double *out, double *features, double *features_var, GdptNlmStats *stats) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_progressive_denoise_collab";
+        if (!session) throw std::runtime_error(who + ": null session");
+        if (!out) throw std::runtime_error(who + ": out is null");
+        GdptNlmParams p;
+        if (params) p = *params; else gdpt_nlm_default_params(&p);
+        gdpt::nlm_check_params(who, p);
+        GdptNlmGuide g;
+        if (guide) g = *guide; else gdpt_nlm_default_guide(&g);
+        gdpt::nlm_check_guide(who, g);
+        if (g.num_channels != GDPT_FEATURE_CHANNELS) throw std::runtime_error(who + ": num_channels must be GDPT_FEATURE_CHANNELS (the session renders its own features)");
+        GdptNlmRegress rg;
+        if (regress) rg = *regress; else gdpt_nlm_default_regress(&rg);
+        gdpt::nlm_check_regress(who, rg, g.num_channels);
+        filter_with_features(who, *session, feature_spp, on_device, out, nullptr, features, features_var, stats,
+                             [&](GdptProgressive &s, double *d_out, double *, GdptNlmStats *st) {
+                                 gdpt::denoise_nlm_collab_launch(s.w, s.h, s.mean[0], s.var[0], s.feat_buf[0], s.feat_buf[1], p, g, rg, d_out, nullptr,
+                                                                 s.stream, st);
                              });
     });
 }

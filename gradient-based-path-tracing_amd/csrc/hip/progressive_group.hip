@@ -374,6 +374,7 @@ int gdpt_progressive_group_halves(GdptProgressiveGroup *group, GdptProgressive *
 // whether the candidate's session entry renders feature planes
 static bool renders_features(const GdptSelectCandidate &c) {
     return c.filter == GDPT_SELECT_NLM_GUIDED || c.filter == GDPT_SELECT_NLM_DEMOD || c.filter == GDPT_SELECT_NLM_REGRESS ||
+           c.filter == GDPT_SELECT_NLM_COLLAB ||
            (c.filter == GDPT_SELECT_ATROUS && ((c.guide && c.guide->num_groups > 0) || c.demod));
 }
 
@@ -393,7 +394,7 @@ int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const Gdp
         for (int j = 0; j < n; j++) {
             const GdptSelectCandidate &c = candidates[j];
             const std::string cj = who + ": candidates[" + std::to_string(j) + "]: ";
-            if (c.filter < GDPT_SELECT_MEAN || c.filter > GDPT_SELECT_ATROUS) throw std::runtime_error(cj + "filter must be one of GDPT_SELECT_MEAN .. GDPT_SELECT_ATROUS");
+            if (c.filter < GDPT_SELECT_MEAN || c.filter > GDPT_SELECT_NLM_COLLAB) throw std::runtime_error(cj + "filter must be one of GDPT_SELECT_MEAN .. GDPT_SELECT_NLM_COLLAB");
             const bool smoothable = c.filter == GDPT_SELECT_NLM || c.filter == GDPT_SELECT_NLM_GUIDED || c.filter == GDPT_SELECT_NLM_DEMOD;
             if (c.var_smooth_radius < -1 || c.var_smooth_radius > GDPT_VAR_SMOOTH_MAX_RADIUS)
                 throw std::runtime_error(cj + "var_smooth_radius must be -1 (none) or in [0, " + std::to_string(GDPT_VAR_SMOOTH_MAX_RADIUS) + "]");
@@ -401,7 +402,8 @@ int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const Gdp
             if (c.filter == GDPT_SELECT_MEAN && (c.nlm || c.atrous || c.guide || c.demod || c.regress)) throw std::runtime_error(cj + "GDPT_SELECT_MEAN takes no parameter block");
             if (c.filter != GDPT_SELECT_ATROUS && c.atrous) throw std::runtime_error(cj + "atrous must be null unless filter is GDPT_SELECT_ATROUS");
             if (c.filter == GDPT_SELECT_ATROUS && c.nlm) throw std::runtime_error(cj + "nlm must be null for GDPT_SELECT_ATROUS");
-            if (c.filter != GDPT_SELECT_NLM_REGRESS && c.regress) throw std::runtime_error(cj + "regress must be null unless filter is GDPT_SELECT_NLM_REGRESS");
+            if (c.filter != GDPT_SELECT_NLM_REGRESS && c.filter != GDPT_SELECT_NLM_COLLAB && c.regress)
+                throw std::runtime_error(cj + "regress must be null unless filter is GDPT_SELECT_NLM_REGRESS or GDPT_SELECT_NLM_COLLAB");
             if (c.filter != GDPT_SELECT_NLM_DEMOD && c.filter != GDPT_SELECT_ATROUS && c.demod) throw std::runtime_error(cj + "demod must be null unless filter is GDPT_SELECT_NLM_DEMOD or GDPT_SELECT_ATROUS");
             if (c.filter == GDPT_SELECT_NLM && c.guide) throw std::runtime_error(cj + "guide must be null for GDPT_SELECT_NLM");
             any_features = any_features || renders_features(c);
@@ -481,6 +483,9 @@ int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const Gdp
                     break;
                 case GDPT_SELECT_NLM_REGRESS:
                     rc = gdpt_progressive_denoise_regress(part[k], c.nlm, c.guide, c.regress, feature_spp, 1, film, nullptr, fm, fv, &st);
+                    break;
+                case GDPT_SELECT_NLM_COLLAB:
+                    rc = gdpt_progressive_denoise_collab(part[k], c.nlm, c.guide, c.regress, feature_spp, 1, film, fm, fv, &st);
                     break;
                 default:
                     rc = gdpt_progressive_denoise_atrous(part[k], c.atrous, c.guide, c.demod, feature_spp, 1, film, nullptr, fm, fv, &st);

@@ -62,6 +62,9 @@
 //                 sets the ridge (default 1e-2). With --nlm-regress and no --nlm-guide the guide is the albedo group alone, and with
 //                 no --nlm-k, k is 4.0: the configuration measured in DESIGN.md section 4.12. Not combined with --nlm-demodulate,
 //                 --nlm-var-smooth or --nlm-levels. Without --nlm-regress every output file is what it was
+//                 --nlm-collaborative (with --nlm-regress) gives every pixel the weighted average of all fits whose windows cover
+//                 it in the place of its own fit's centre value (gdpt_progressive_denoise_collab). The
+//                 result carries no variance estimate: error_out prints as nan. Without the flag every output file is what it was
 //                 --atrous-levels L (1..6) writes the edge-avoiding a-trous wavelet filter's result in the place of the non-local
 //                 means' (gdpt_progressive_denoise_atrous), the cheap filter for previews: L passes of a 5 x 5 B3-spline kernel whose
 //                 taps are spread by 1, 2, 4, .. pixels, every tap weighted by the variance-cancelling pixel distance and capped by
@@ -71,10 +74,10 @@
 //                 --nlm-patch, --nlm-k, --nlm-var-smooth, --nlm-levels or --nlm-regress. Without --atrous-levels every output file
 //                 is what it was
 //                 --select LIST writes, per pixel, the candidate whose error two independent halves of the samples estimate smallest
-//                 (gdpt_progressive_group_denoise_select). LIST names 1..8 of mean,nlm,guided,demod,regress,atrous,atrous-demod, each
+//                 (gdpt_progressive_group_denoise_select). LIST names 1..8 of mean,nlm,guided,demod,regress,atrous,atrous-demod,collab, each
 //                 once, separated by commas; each is what its own flag gives without further flags: mean the unfiltered mean; nlm
 //                 the plain filter (k 0.45); guided --nlm-guide albedo,normal (k 1.0); demod --nlm-demodulate (no guide); regress
-//                 --nlm-regress albedo,normal (the albedo group as guide, k 4.0); atrous --atrous-levels 5 (guide albedo,normal);
+//                 --nlm-regress albedo,normal (the albedo group as guide, k 4.0); collab the same with --nlm-collaborative; atrous --atrous-levels 5 (guide albedo,normal);
 //                 atrous-demod --atrous-levels 5 --nlm-demodulate (guide normal). --nlm-var-smooth S acts on nlm, guided and demod;
 //                 --nlm-kf on every guide; --nlm-depth-tau T adds the depth group to the guides of guided, atrous and atrous-demod;
 //                 --nlm-albedo-floor on demod and atrous-demod; --feature-spp as above. --select-radius S (0..8, default 4) is the
@@ -127,7 +130,7 @@ int main(int argc, char *argv[]) {
     int nlm_levels = 0;               // 0: not given
     std::string features_prefix = "", nlm_guide_names = "", nlm_regress_names = "";
     double nlm_ridge = 0.0, nlm_depth_scale = 0.0;
-    bool nlm_regress_option = false;
+    bool nlm_regress_option = false, nlm_collaborative = false;
     int atrous_levels = 0;            // 0: not given
     double atrous_k = 0.0;
     bool atrous_k_set = false;
@@ -209,6 +212,7 @@ int main(int argc, char *argv[]) {
         else if (a == "--nlm-depth-tau") { nlm_depth_tau = std::stod(next()); nlm_guide_option = true; }
         else if (a == "--nlm-kf") { nlm_kf = std::stod(next()); nlm_guide_option = true; }
         else if (a == "--nlm-regress") nlm_regress_names = next();
+        else if (a == "--nlm-collaborative") nlm_collaborative = true;
         else if (a == "--nlm-ridge") { nlm_ridge = std::stod(next()); nlm_regress_option = true; }
         else if (a == "--nlm-depth-scale") { nlm_depth_scale = std::stod(next()); nlm_regress_option = true; }
         else if (a == "--atrous-levels") {
@@ -292,12 +296,12 @@ int main(int argc, char *argv[]) {
         return 2;
     }
     // --select: the names of LIST in order; what the single-filter flags would refuse beside each other is refused here at once
-    enum { SelMean, SelNlm, SelGuided, SelDemod, SelRegress, SelAtrous, SelAtrousDemod };
+    enum { SelMean, SelNlm, SelGuided, SelDemod, SelRegress, SelAtrous, SelAtrousDemod, SelCollab };
     std::vector<int> select_names;
     const bool select_on = !select_list.empty();
     double select_kf = 0.0, select_depth_tau = 0.0, select_floor = 0.0;
     if (select_on) {
-        static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod"};
+        static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod", "collab"};
         if (denoised_file.empty()) { std::cerr << "--select needs --denoised" << std::endl; return 2; }
         if (sample_devices.size() < 2) {
             std::cerr << "--select needs --sample-devices with two or more entries: the estimate comes from two independent halves of the samples "
@@ -315,9 +319,10 @@ int main(int argc, char *argv[]) {
             const size_t comma = std::min(select_list.find(',', at), select_list.size());
             const std::string name = select_list.substr(at, comma - at);
             int which = -1;
-            for (int k = 0; k < 7; k++) if (name == names[k]) which = k;
+            for (int k = 0; k < 8; k++) if (name == names[k]) which = k;
             if (which < 0 || std::find(select_names.begin(), select_names.end(), which) != select_names.end()) {
-                std::cerr << "--select takes mean, nlm, guided, demod, regress, atrous and atrous-demod, each once, separated by commas" << std::endl;
+                std::cerr << "--select takes mean, nlm, guided, demod, regress, atrous and atrous-demod, each once, separated by commas; and collab, the collaborative "
+                             "form of regress, likewise" << std::endl;
                 return 2;
             }
             select_names.push_back(which);
@@ -377,6 +382,10 @@ int main(int argc, char *argv[]) {
     GdptNlmRegress regress{};
     gdpt_nlm_default_regress(&regress);
     const bool regressed = !nlm_regress_names.empty();
+    if (nlm_collaborative && !regressed) {
+        std::cerr << "--nlm-collaborative needs --nlm-regress: it averages the fits of the first-order regression" << std::endl;
+        return 2;
+    }
     if (regressed) {
         if (denoised_file.empty()) { std::cerr << "--nlm-regress needs --denoised" << std::endl; return 2; }
         if (nlm_demodulate || nlm_var_smooth >= 0 || nlm_levels > 0) {
@@ -589,6 +598,7 @@ int main(int argc, char *argv[]) {
                         case SelDemod: c.filter = GDPT_SELECT_NLM_DEMOD; c.nlm = &p_plain; c.demod = &dm; c.var_smooth_radius = nlm_var_smooth; break;
                         case SelRegress: c.filter = GDPT_SELECT_NLM_REGRESS; c.nlm = &p_regress; c.guide = &g_albedo; c.regress = &rg; break;
                         case SelAtrous: c.filter = GDPT_SELECT_ATROUS; c.atrous = &at; c.guide = &g_default; break;
+                        case SelCollab: c.filter = GDPT_SELECT_NLM_COLLAB; c.nlm = &p_regress; c.guide = &g_albedo; c.regress = &rg; break;
                         default: c.filter = GDPT_SELECT_ATROUS; c.atrous = &at; c.guide = &g_normal; c.demod = &dm; break;
                         }
                     }
@@ -627,8 +637,12 @@ int main(int argc, char *argv[]) {
                                                          &nlm_stats);
                 } else if (regressed) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
-                    rc = gdpt_progressive_denoise_regress(session, &nlm, &guide, &regress, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
-                                                          filtered.data(), nullptr, nullptr, nullptr, &nlm_stats);
+                    if (nlm_collaborative)
+                        rc = gdpt_progressive_denoise_collab(session, &nlm, &guide, &regress, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
+                                                             filtered.data(), nullptr, nullptr, &nlm_stats);
+                    else
+                        rc = gdpt_progressive_denoise_regress(session, &nlm, &guide, &regress, feature_spp > 0 ? feature_spp : std::min(16, budget), 0,
+                                                              filtered.data(), nullptr, nullptr, nullptr, &nlm_stats);
                 } else if (nlm_levels > 0) {
                     const int budget = spp > 0 ? spp : desc->samples_per_pixel;
                     GdptVarSmoothParams sp{};
@@ -724,7 +738,7 @@ int main(int argc, char *argv[]) {
                       << " samples per pixel, error estimate " << prog.error_estimate << " (" << prog.pixels_left_out
                       << " pixels left out), stopped by " << why[prog.stop_reason] << std::endl;
             if (select_on) {
-                static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod"};
+                static const char *const names[] = {"mean", "nlm", "guided", "demod", "regress", "atrous", "atrous-demod", "collab"};
                 const double valid = (double)((size_t)w * h - select_stats.pixels_left_out);
                 std::cout << "[gdpt] selected: radius " << select_stats.radius << ", " << select_stats.pixels_left_out << " pixels left out;";
                 for (int j = 0; j < select_stats.num_candidates; j++)
@@ -742,7 +756,8 @@ int main(int argc, char *argv[]) {
                           << nlm_stats.pixels_left_out << " pixels left out), window " << nlm_stats.window_radius << ", patch " << nlm_stats.patch_radius
                           << ", filter_ms " << nlm_stats.filter_ms << (guided ? ", guided by " + nlm_guide_names : std::string())
                           << (atrous_on ? ", a-trous wavelet filter over " + std::to_string(atrous.levels) + " levels (window: the reach of the last)" : std::string())
-                          << (regressed ? ", first-order regression on " + nlm_regress_names + " (ridge " + std::to_string(regress.ridge) + ")" : std::string()) << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
+                          << (regressed ? ", first-order regression on " + nlm_regress_names + " (ridge " + std::to_string(regress.ridge) + ")" : std::string())
+                          << (nlm_collaborative ? ", collaborative (no variance estimate)" : "") << (nlm_demodulate ? ", demodulated by the first-hit albedo" : "")
                           << (nlm_var_smooth >= 0 ? ", variance smoothed over radius " + std::to_string(smooth_stats.radius) : std::string())
                           << (nlm_levels > 0 ? ", " + std::to_string(pyramid_stats.levels) + " levels in " + std::to_string(pyramid_stats.total_ms) + " ms (the figures before are the finest level's)" : std::string())
                           << ", written to "

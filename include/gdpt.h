@@ -827,6 +827,50 @@ int gdpt_progressive_denoise_regress(GdptProgressive *session, const GdptNlmPara
                                      int feature_spp, int on_device, double *out, double *var_out /* nullable */,
                                      double *features /* nullable */, double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
 
+/* ---- the collaborative form of the first-order regression (not part of the reference) ----
+ * gdpt_denoise_nlm_regress keeps of every window's fit its value at the centre alone. The fit is a model for every pixel of its
+ * window, so a pixel can take the weighted average of all fits whose windows cover it, about (2r+1)^2 estimates in the place of one
+ * (Bitterli et al. 2016, "collaborative filtering"). Where the point estimate's error is variance, not bias, this lowers it.
+ * The inputs, the validity rule, w_o(p), z(p,o), A, b_c, the ridge and the LDL^T order are exactly gdpt_denoise_nlm_regress's, d = 1 + m.
+ *   1. Fit. For every valid p the whole solution beta_c(p) in R^d, c = 0, 1, 2, is kept in a coefficient film of 3 d channel-planar
+ *      planes of width * height doubles: plane c d + j holds beta_c,j. An invalid p stores beta_c,0 = u_c(p) (its input bits) and 0.0
+ *      elsewhere; nothing reads it.
+ *   2. Gather. For every valid q, over the offsets t with |t|_inf <= r in row-major order of t, with p = q + t inside the film and valid:
+ *        omega_t(q) = w_{-t}(p), the weight the fit centred at p gave its partner q. Neither the pair distance nor the feature
+ *                     distance is symmetric in its variances: the patch distance is sum_n e(p+n; q+n) with the centre's triple
+ *                     first, summed and counted over the same patch taps n in the same order as the fit's S_o, C_o, and the feature
+ *                     distance takes p in the centre's place and q in the partner's.
+ *        y_c        = beta_c,0(p) + sum_{j=1..m} beta_c,j(p) z_j,   z_j = (g_{c_j}(q) - g_{c_j}(p)) / scale[j-1]
+ *                     (terms added in index order; the division is skipped at scale 1)
+ *        N_c += omega y_c,   Omega += omega;   out_c(q) = N_c / Omega.   The tap t = 0 has omega = 1, so Omega >= 1.
+ *   3. An invalid q keeps its input triple bit for bit and is counted once in pixels_left_out; an invalid p contributes to nobody.
+ *   4. There is NO var_out. The variance of this estimator under fixed weights is a double sum over the window, O(r^4) per pixel, and a
+ *      cheap surrogate would be a number with no meaning. GdptNlmStats.sum_var_out and .error_out are NaN: "not estimated". To learn
+ *      where the collaborative image beats another filter's, use the two-half estimate of gdpt_progressive_group_denoise_select's
+ *      kind (gdpt_filter_select), which needs no candidate variance. sum_var_in, sum_sq_in, sum_sq_out, error_in, pixels_left_out,
+ *      the radii and filter_ms (both passes) are as everywhere.
+ * Exact by construction: r = 0 returns the input bits; no pass writes a plane it reads; the same call gives the same bits (a gather,
+ * no atomics); the coefficient plane c d + 0 equals gdpt_denoise_nlm_regress's out channel c bit for bit.
+ * Refused: what gdpt_denoise_nlm_regress_device refuses, the field named, and a d_coef whose 3 d planes overlap an input or d_out.
+ * d_coef == NULL: the film is kept in the library's scratch per (device, stream), 24 width height doubles at d = 8, grown on demand
+ * and dropped by gdpt_poisson_forget_stream. Enqueue-only with stats == NULL. Quality rests on a synthetic film alone (DESIGN.md
+ * section 4.16). */
+int gdpt_denoise_nlm_collab_device(int width, int height, const double *d_img, const double *d_var, const double *d_feat, const double *d_feat_var,
+                                   const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                                   const GdptNlmRegress *regress /* NULL: defaults */, double *d_out,
+                                   double *d_coef /* nullable: 3 (1 + m) planes */, void *stream, GdptNlmStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. coef (nullable) receives the coefficient film. */
+int gdpt_denoise_nlm_collab(int width, int height, const double *img, const double *var, const double *feat, const double *feat_var,
+                            const GdptNlmParams *params /* NULL: defaults */, const GdptNlmGuide *guide /* NULL: defaults */,
+                            const GdptNlmRegress *regress /* NULL: defaults */, double *out, double *coef /* nullable */,
+                            GdptNlmStats *stats /* nullable */);
+/* The collaborative regression on a session's buffer 0, built as gdpt_progressive_denoise_regress in every respect (Path sessions,
+ * GradPath primals, a group's total; at least 2 passes; the coefficient film is the library's). Blocking. */
+int gdpt_progressive_denoise_collab(GdptProgressive *session, const GdptNlmParams *params /* NULL: defaults */,
+                                    const GdptNlmGuide *guide /* NULL: defaults */, const GdptNlmRegress *regress /* NULL: defaults */,
+                                    int feature_spp, int on_device, double *out, double *features /* nullable */,
+                                    double *features_var /* nullable */, GdptNlmStats *stats /* nullable */);
+
 /* ---- an edge-avoiding a-trous wavelet filter with variance-guided weights: the cheap filter (not part of the reference) ----
  * Every filter above weighs a (2r+1)^2 window by patch distances, 441 offsets of 49 patch taps at the defaults. This one runs L
  * passes of a 5x5 B3-spline kernel whose taps are spread by 1, 2, 4, ... pixels, 25 L taps per pixel, and reaches +-62 pixels in five
@@ -1145,7 +1189,9 @@ int gdpt_filter_select(int width, int height, int n, const double *const *FA, co
 
 /* The selection among filters of a progressive group, behind one call. A candidate names one of the session filters and its blocks:
  * filter GDPT_SELECT_MEAN (the unfiltered mean; no block), _NLM (gdpt_progressive_denoise), _NLM_GUIDED (_denoise_guided), _NLM_DEMOD
- * (_denoise_demod), _NLM_REGRESS (_denoise_regress), _ATROUS (_denoise_atrous; `atrous` in the place of `nlm`). var_smooth_radius: -1
+ * (_denoise_demod), _NLM_REGRESS (_denoise_regress), _ATROUS (_denoise_atrous; `atrous` in the place of `nlm`), _NLM_COLLAB
+ * (_denoise_collab; the blocks of _NLM_REGRESS; its cand_stats entry carries sum_var_out = error_out = NaN, as that entry's stats do:
+ * the selection needs no candidate variance, and is the tool that tells per pixel whether it beats _NLM_REGRESS). var_smooth_radius: -1
  * for none; >= 0 runs the candidate through gdpt_progressive_denoise_smoothed at that radius and is allowed for _NLM, _NLM_GUIDED and
  * _NLM_DEMOD only. NULL pointers mean what they mean in the matching gdpt_progressive_denoise_* entry; a block the filter does not take
  * must be NULL.
@@ -1167,6 +1213,7 @@ int gdpt_filter_select(int width, int height, int n, const double *const *FA, co
 #define GDPT_SELECT_NLM_DEMOD 3
 #define GDPT_SELECT_NLM_REGRESS 4
 #define GDPT_SELECT_ATROUS 5
+#define GDPT_SELECT_NLM_COLLAB 6
 typedef struct GdptSelectCandidate { int32_t filter; int32_t var_smooth_radius; const GdptNlmParams *nlm; const GdptAtrousParams *atrous;
                                      const GdptNlmGuide *guide; const GdptNlmDemod *demod; const GdptNlmRegress *regress; } GdptSelectCandidate;
 int gdpt_progressive_group_denoise_select(GdptProgressiveGroup *group, const GdptSelectCandidate *candidates, int n,

@@ -49,6 +49,9 @@
  *                               form up to step 4 and the direct form beyond (the measured routes), 1 the direct form at every
  *                               step, 2 the staged form at every step that has one (1 - 8), for measurements; the other filters
  *                               read 2 as 1
+ *   nlm_collab_pass (0/1/2)     gdpt_denoise_nlm_collab*, for measurements: 1 launches the fit alone (the coefficient film is written,
+ *                               out is not), 2 the gather alone (on the coefficient film an earlier call left in the caller's d_coef);
+ *                               0, the default, both
  *   stamps               (0/1)  Lambertian lane machine: the diagnostic build with in-kernel cycle stamps; a render with
  *                               stats then leaves its per-segment wave cycles for gdpt_debug_get_stamps
  *
