@@ -1871,6 +1871,14 @@ class debug_knobs:
         return d
 
     @staticmethod
+    def setup_passes():
+        """Full-width passes of the sample set-up in the last render made under debug_knobs(stamps=1), over all waves (slot 11 of
+        gdpt_debug_get_stamps; stamps()["wave_steps"] is the count to set it against)."""
+        v = (C.c_double * 16)()
+        lib().gdpt_debug_get_stamps(v)
+        return v[11]
+
+    @staticmethod
     def last_route():
         """Kernel route of this thread's last render (include/gdpt_debug.h: gdpt_debug_last_route)."""
         return lib().gdpt_debug_last_route().decode()
@@ -1958,7 +1966,7 @@ class debug_knobs:
         """GDPT_FORCE_EAGER=1 -> force_eager=1 ... for the manual sweep scripts (tests/sweep_*.py, tune_render.py)."""
         environ = os.environ if environ is None else environ
         names = ("force_eager", "log2k", "keep_frac", "search_frac", "blocks_per_cu", "no_lds_scene", "lds_wide",
-                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "nlm_direct", "lds_fixed_layout", "nlm_collab_pass")
+                 "no_twosided_machine", "presplit", "presplit_floor", "bvh_leaf_max", "bvh_leaf_factor", "sbvh", "sbvh_alpha", "plan_rounds", "plan_shrink", "plan_digits", "bvh_collapse_dp", "stamps", "wavefront", "wf_slots", "wf_sort", "multi_fail_band", "multi_fail_stage", "dct_bk", "dct_bm", "full_material_switch", "no_plain_kernel", "replay_per_step", "no_render_overlap", "whole_leaf_trips", "no_setup_batch", "nlm_direct", "lds_fixed_layout", "nlm_collab_pass")
         lib().gdpt_debug_knobs_reset()
         for n in names:
             v = environ.get("GDPT_" + n.upper())

@@ -285,9 +285,10 @@ gdpt::RenderLaunch begin_launch(GdptScene *sc, const Band &b, bool path, int tak
     in.no_twosided_machine = knob("no_twosided_machine", 0) != 0; in.wavefront = knob("wavefront", kWavefrontDefault) != 0;
     in.stamps = knob("stamps", 0) != 0; in.no_plain_kernel = knob("no_plain_kernel", 0) != 0;
     in.full_material_switch = knob("full_material_switch", 0) != 0; in.whole_leaf_trips = knob("whole_leaf_trips", 0) != 0;
+    in.no_setup_batch = knob("no_setup_batch", 0) != 0;
     gdpt::RenderLaunch rl{};
     rl.route = gdpt::choose_route(in);
-    rl.whole_leaf_trips = in.whole_leaf_trips;
+    rl.whole_leaf_trips = in.whole_leaf_trips; rl.no_setup_batch = in.no_setup_batch;
     rl.spp = b.spp; rl.stream_spp = b.stream_spp; rl.first_sample = b.first_sample; rl.row_begin = b.row_begin; rl.row_end = b.row_end; rl.max_depth = b.max_depth;
     rl.count_traversal = stats && stats->nodes_visited == ~0ull;   // request flag: caller presets nodes_visited = UINT64_MAX
     rl.force_log2k = knob("log2k", -1);

@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../pcg_jump.h"
 
 #define GD __device__ __forceinline__
 
@@ -70,6 +71,11 @@ GD Pcg pcg_init(uint64_t stream) {
 GD double pcg_real(Pcg &r) { // next_pcg32_real<double>: 32 random mantissa bits
     uint64_t u = ((uint64_t)pcg_next(r) << 20) | 0x3ff0000000000000ULL;
     return __longlong_as_double((long long)u) - 1.0;
+}
+// pcg_init(stream) followed by two draws whose results the caller has from elsewhere (../pcg_jump.h)
+GD Pcg pcg_init_behind_two(uint64_t stream) {
+    Pcg s; s.inc = pcg_stream_inc(stream); s.state = pcg_jump2(s.inc);
+    return s;
 }
 
 } // namespace gd

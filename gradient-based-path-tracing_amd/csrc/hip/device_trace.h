@@ -273,6 +273,17 @@ struct FilterCache { double dx, dy, ox, oy; };
 // CAM: DevCamera (a view's by-value copy: the compiler keeps what it reads of it in SGPRs for the whole kernel) or CamConst (the camera
 // where the kernel's arguments lie, read with scalar loads where it is used — the lane machine, render_device.h: camera_here).
 typedef const __attribute__((address_space(4))) DevCamera CamConst;
+// the ray through the film position (rx, ry) in [0, 1]^2
+template <class CAM>
+GD Ray camera_ray(CAM &cam, double rx, double ry) {
+    D3 pt = xform_point(&cam.sample_to_cam[0], mk(rx, ry, 0.0));
+    D3 dir = normalize(pt);
+    Ray r;
+    r.org = mk(cam.org[0], cam.org[1], cam.org[2]);
+    r.dir = normalize(xform_vector(&cam.cam_to_world[0], dir));
+    r.tnear = 0; r.tfar = __builtin_huge_val();
+    return r;
+}
 template <bool PIXEL_SPACE = false, class CAM = const DevCamera>
 GD Ray sample_primary(CAM &cam, double sx, double sy, FilterCache *cache = nullptr, bool store = false) {
     const bool exact = PIXEL_SPACE && cam.pow2_film != 0;        // wave-uniform
@@ -288,13 +299,27 @@ GD Ray sample_primary(CAM &cam, double sx, double sy, FilterCache *cache = nullp
     double rx, ry;
     if (exact) { rx = (fx + 0.5 + off.x) * cam.inv_width; ry = (fy + 0.5 + off.y) * cam.inv_height; }
     else { rx = (fx + 0.5 + off.x) / cam.width; ry = (fy + 0.5 + off.y) / cam.height; }
-    D3 pt = xform_point(&cam.sample_to_cam[0], mk(rx, ry, 0.0));
-    D3 dir = normalize(pt);
-    Ray r;
-    r.org = mk(cam.org[0], cam.org[1], cam.org[2]);
-    r.dir = normalize(xform_vector(&cam.cam_to_world[0], dir));
-    r.tnear = 0; r.tfar = __builtin_huge_val();
-    return r;
+    return camera_ray(cam, rx, ry);
+}
+
+// sample_primary<true>'s exact path (cam.pow2_film != 0) cut in two, for a caller that makes the first half ahead of use and for more
+// lanes than need it now (render_device.h: lane_camera_batched). Every value is formed by the expressions above.
+//   sample_setup: what depends on (pixel, stream index) alone: the stream `base + s`, its first two numbers, the filter offset they give;
+//   primary_from_setup: the ray through pixel (px, py), itself or an offset neighbour (px >= -1), with that offset.
+// Why the second half needs neither the two numbers nor a comparison with cached ones: the caller above passes sx = px + r with r = m * 2^-32,
+// 0 <= m < 2^32, and px an integer in [-1, 2^15]. |px + r| < 2^16 needs at most 16 + 32 bits: the sum is exact, floor(sx) = px (r < 1) and
+// sx - floor(sx) = r bit for bit, for the base ray and for each offset ray alike. So filter_sample sees the same (r_x, r_y) for all five
+// rays of a sample: its result is the sample's, and fx = (double)px. (tests/setup_batch_check.cpp runs this argument on the host.)
+template <class CAM>
+GD D2 sample_setup(CAM &cam, unsigned long long base, int s) {
+    Pcg r = pcg_init(base + (unsigned long long)s);
+    const double rx = pcg_real(r), ry = pcg_real(r);
+    return filter_sample(cam.filter_type, cam.filter_param, rx, ry);
+}
+template <class CAM>
+GD Ray primary_from_setup(CAM &cam, int px, int py, D2 off) {
+    const double fx = (double)px, fy = (double)py;
+    return camera_ray(cam, (fx + 0.5 + off.x) * cam.inv_width, (fy + 0.5 + off.y) * cam.inv_height);
 }
 
 } // namespace gd

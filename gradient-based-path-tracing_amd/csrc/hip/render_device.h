@@ -48,7 +48,7 @@ struct LaneCounters { unsigned rays, bounces, nonfinite; };
 // wave's cycles go, segment by segment. s_memtime is read by the wave (scalar), so a segment's share includes what the
 // lanes that sit it out wait for — the point of the exercise. The product kernels are built with ON = false: every call
 // below compiles to nothing. Stamp values only ever reach RenderCounters::stamps, never an output image.
-enum { SEG_QUEUE = 0, SEG_TRACE = 1, SEG_VERTEX = 2, SEG_CONSUME = 3, SEG_BSDF = 4, SEG_FINISH = 5, SEG_CAMERA = 6, SEG_STEPS = 7, SEG_PUBLISH = 8, SEG_TAKE = 9, SEG_ITEM = 10, SEG_COUNT = 12, SEG_T_START = 12, SEG_T_DRY = 13, SEG_T_END = 14, SEG_SLOTS = 16 };
+enum { SEG_QUEUE = 0, SEG_TRACE = 1, SEG_VERTEX = 2, SEG_CONSUME = 3, SEG_BSDF = 4, SEG_FINISH = 5, SEG_CAMERA = 6, SEG_STEPS = 7, SEG_PUBLISH = 8, SEG_TAKE = 9, SEG_ITEM = 10, SEG_SETUPS = 11 /* a count like SEG_STEPS: full-width passes of sample_setup */, SEG_COUNT = 12, SEG_T_START = 12, SEG_T_DRY = 13, SEG_T_END = 14, SEG_SLOTS = 16 };
 // The accumulators belong to the WAVE, not to a lane: they live in LDS (`slot` = the wave's row of 13 words) and every mark
 // is booked by the first ACTIVE lane. (Per-lane accumulators, as first built, book a step that a lane sits out onto that
 // lane's next mark: read from lane 0 they showed 13 % of the wave's time in "publish", which really takes 5 %.)
@@ -645,7 +645,8 @@ enum { C_NO_LOOP = 0,        // the bounce loop never ran (max_depth < 2): jacob
 
 // Cold per-lane fields live in a private LDS slot (a "manual spill" that costs an LDS access instead of a scratch
 // round trip): radiance (touched on emitter hits and when a sample is finished), p2_1 and the filter cache
-// (offset phase only).  Layout: slot[c * stride], c = 0..2 radiance, 3 p2_1, 4..7 filter cache (dx, dy, ox, oy).
+// (offset phase only).  Layout: slot[c * stride], c = 0..2 radiance, 3 p2_1, 4..7 filter cache (dx, dy, ox, oy); under lane_camera_batched
+// 4, 5 the filter offset of the lane's next sample and 6, 7 the current sample's.
 struct LanePriv {
     double *slot; int stride;
     GD D3 radiance() const { return mk(slot[0], slot[stride], slot[2 * stride]); }
@@ -654,14 +655,22 @@ struct LanePriv {
     GD void set_p2_1(double v) { slot[3 * stride] = v; }
     GD FilterCache fc() const { FilterCache f; f.dx = slot[4 * stride]; f.dy = slot[5 * stride]; f.ox = slot[6 * stride]; f.oy = slot[7 * stride]; return f; }
     GD void set_fc(const FilterCache &f) { slot[4 * stride] = f.dx; slot[5 * stride] = f.dy; slot[6 * stride] = f.ox; slot[7 * stride] = f.oy; }
+    // lane_camera_batched stores no (dx, dy): slots 6, 7 hold the filter offset of the lane's current sample as before, slots 4, 5 the one of
+    // its next sample of the same item while Lane::kc says so (kKcSetupNext)
+    GD D2 setup_cur() const { D2 o; o.x = slot[6 * stride]; o.y = slot[7 * stride]; return o; }
+    GD void set_setup_cur(D2 o) { slot[6 * stride] = o.x; slot[7 * stride] = o.y; }
+    GD D2 setup_next() const { D2 o; o.x = slot[4 * stride]; o.y = slot[5 * stride]; return o; }
+    GD void set_setup_next(D2 o) { slot[4 * stride] = o.x; slot[5 * stride] = o.y; }
 };
 constexpr int kPrivDoubles = 8;
 
 constexpr int kKcNonfinite = 1 << 30;
+constexpr int kKcSetupNext = 1 << 29;         // lane_camera_batched: the set-up of sample s + 1 is made (LanePriv::setup_next); 0 in every other machine
+constexpr int kKcFlags = kKcNonfinite | kKcSetupNext;
 struct Lane {
     int st, s, s_end, num_vertices;
     int mats;                 // mat0 | mat1 << 12 (material ids of the base primary hit / the bounce-1 hit), 0xFFF = none
-    int kc;                   // offset index k | cmode << 2 | kKcNonfinite (an offset of this sample was non-finite)
+    int kc;                   // offset index k | cmode << 2 | kKcNonfinite (an offset of this sample was non-finite) | kKcSetupNext
     unsigned long long rng_state, rng_inc;
     D3 org, dir;              // the pending ray
     D3 f; double pdf;         // S_BOUNCE: f*|cos| and solid-angle pdf of `dir` at the vertex the ray leaves
@@ -672,7 +681,7 @@ struct Lane {
     GD int mat0() const { return mats & 0xFFF; }
     GD int mat1() const { return (mats >> 12) & 0xFFF; }
     GD int k() const { return kc & 3; }
-    GD int cmode() const { return (kc & ~kKcNonfinite) >> 2; }
+    GD int cmode() const { return (kc & ~kKcFlags) >> 2; }
 };
 
 // SERIAL_RNG: one PCG stream runs through consecutive samples (TILE scheme); otherwise each sample owns stream
@@ -712,7 +721,7 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             if (nv.light_id >= 0) { D3 Le = emission(tx.lights, nv, -ray.dir); rad0 = Le; L.contrib = Le; }   // :490-493
             lp.set_radiance(rad0); lp.set_p2_1(1.0);
             L.num_vertices = 3;
-            if (!loop_allows(max_depth, 3)) { L.kc = C_NO_LOOP << 2; act = ACT_OFFSETS; } else act = ACT_BOUNCE;
+            if (!loop_allows(max_depth, 3)) { L.kc = (L.kc & kKcSetupNext) | (C_NO_LOOP << 2); act = ACT_OFFSETS; } else act = ACT_BOUNCE;
         }
     } else if (st0 == S_BOUNCE) {
         const bool first = (L.num_vertices == 3);
@@ -745,7 +754,7 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             }
         }
         if (!stop) act = ACT_BOUNCE;
-        else if (first) { L.kc = C_AFTER_BOUNCE1 << 2; act = ACT_OFFSETS; }
+        else if (first) { L.kc = (L.kc & kKcSetupNext) | (C_AFTER_BOUNCE1 << 2); act = ACT_OFFSETS; }
         else { acc_no_offsets(acc, lp.radiance(), L.contrib, L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
         // (one-sided lobes: offsets alive after bounce 1 are retired by bounce 2's re-sampling, see file header)
     }
@@ -804,8 +813,8 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
         else {
             // bs.eta == 0 for every one-sided lobe, so eta_scale (:553-558) stays 1 on this path
             if (pdf <= 0) {                                                         // :760-763: break before any update; the ray's
-                if (L.num_vertices == 3) { L.kc = C_BROKE_BOUNCE1 << 2; act = ACT_OFFSETS; }           // hit is unobservable
-                else if (L.num_vertices == 4 && L.mat0() == L.mat1()) { L.kc = C_BROKE_BOUNCE2 << 2; act = ACT_OFFSETS; }   // :607-612 passed
+                if (L.num_vertices == 3) { L.kc = (L.kc & kKcSetupNext) | (C_BROKE_BOUNCE1 << 2); act = ACT_OFFSETS; }           // hit is unobservable
+                else if (L.num_vertices == 4 && L.mat0() == L.mat1()) { L.kc = (L.kc & kKcSetupNext) | (C_BROKE_BOUNCE2 << 2); act = ACT_OFFSETS; }   // :607-612 passed
                 else { acc_no_offsets(acc, lp.radiance(), L.contrib, L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
             } else arm = true;
         }
@@ -857,6 +866,49 @@ GD void lane_camera(const DevSceneView &sv, CAM &cam, int act, int x, int y, uns
         if (act == ACT_OFFSET_RAY) fc = lp.fc();
         Ray r = sample_primary<true>(cam, (x + ox) + rx, (y + oy) + ry, &fc, act == ACT_PRIMARY_RAY);
         if (act == ACT_PRIMARY_RAY) lp.set_fc(fc);
+        L.org = r.org; L.dir = r.dir;                                               // a fresh pending ray: the caller arms the walk (lane_arm)
+    }
+    stamps.mark(SEG_CAMERA);
+}
+
+// lane_camera for the persistent one-sided machine on a power-of-two film (SAMPLE streams; the caller checks cam.pow2_film, wave-uniform):
+// the camera block with the sample's set-up (device_trace.h: sample_setup — stream seeding, two draws, the pixel filter: about half of
+// lane_camera's instructions, many of them quarter-rate fp64) taken out of the step and made at full wave width. Only a sample's base ray
+// needs a new set-up, under a tenth of the lanes of a step, yet some lane does in almost every step, so lane_camera pays for it every time.
+// Here a lane finds its set-up made:
+//   * `fresh`: the caller has just put it into the lane's current slot (a new item: the wave's table, gdpt_render_phases);
+//   * kKcSetupNext: an earlier pass made it ahead; it moves from the next slot to the current one;
+//   * neither: the pass runs now, and EVERY lane of the wave takes part: a lane in need makes the set-up of sample s, every other lane
+//     that holds an item with a sample s + 1 and has not got that one's yet makes it ahead. After a pass no lane needs another before
+//     its next sample but one.
+// (pixel, stream index) decide a set-up, so when and where it is made shows in no result. The five rays of a sample share the offset in
+// the current slot (device_trace.h: why no (dx, dy) are kept or compared), and the base ray's RNG continues behind the two draws by jump.
+template <class STAMPS, class CAM>
+GD void lane_camera_batched(CAM &cam, int act, bool fresh, int x, int y, unsigned long long base, Lane &L, LanePriv &lp, STAMPS &stamps) {
+    const bool prim = act == ACT_PRIMARY_RAY;
+    if (prim && !fresh && (L.kc & kKcSetupNext)) { lp.set_setup_cur(lp.setup_next()); L.kc &= ~kKcSetupNext; fresh = true; }
+    const bool need = prim && !fresh;
+    if (__any(need)) {
+        // (a lane between items, S_DONE and no ray to make, keeps the s / s_end of an item that is over or of an empty slot)
+        const bool ahead = !need && (prim || L.st != S_DONE) && L.s + 1 < L.s_end && !(L.kc & kKcSetupNext);
+        if (need || ahead) {
+            const D2 o = sample_setup(cam, base, L.s + (need ? 0 : 1));
+            if (need) lp.set_setup_cur(o); else { lp.set_setup_next(o); L.kc |= kKcSetupNext; }
+        }
+        stamps.tick(SEG_SETUPS);
+    }
+    if (prim || act == ACT_OFFSET_RAY) {
+        int ox = 0, oy = 0;
+        if (prim) {
+            const Pcg r = pcg_init_behind_two(base + (unsigned long long)L.s);
+            L.rng_state = r.state; L.rng_inc = r.inc;
+            L.st = S_PRIMARY;
+        } else {
+            const int k = L.k();
+            ox = (k == 0) ? -1 : (k == 1 ? 1 : 0); oy = (k == 2) ? 1 : (k == 3 ? -1 : 0);   // x0,x1,y0,y1 (:385-403)
+            L.st = S_OFFSET;
+        }
+        const Ray r = primary_from_setup(cam, x + ox, y + oy, lp.setup_cur());
         L.org = r.org; L.dir = r.dir;                                               // a fresh pending ray: the caller arms the walk (lane_arm)
     }
     stamps.mark(SEG_CAMERA);
@@ -1046,9 +1098,11 @@ struct SliceQueue {
     unsigned next = 0, end = 0, start = 0;       // items [next, end) of the slice that began at `start` are not handed out yet
     ItemSlice slice = {0, 0, 0, 0};              // `start` taken apart
     bool exhausted = false;
+    bool refilled = false;                       // the last take() fetched the slice [start, end) (gdpt_render_phases fills its set-up table then)
     // `item`: kNoItem, or the lane's new item with its parts in `parts`.
     GD unsigned take(const KernelArgs &a, bool idle, int tid, ItemParts &parts) {
         unsigned item = kNoItem;
+        refilled = false;
         const unsigned long long m_idle = __ballot(idle);
         if (m_idle) {
             const unsigned num_items = (unsigned)a.num_items, num_slots = (unsigned)a.num_slots, tiles_x = (unsigned)a.tiles_x;
@@ -1067,6 +1121,7 @@ struct SliceQueue {
                     next = start = got_lo;
                     end = (want < num_items - got_lo) ? got_lo + want : num_items;
                     slice = item_slice_begin(start, num_slots, tiles_x);
+                    refilled = true;
                 }
             }
             const unsigned avail = end - next;
@@ -1100,12 +1155,17 @@ GD CamConst &camera_here() {
 // (The kernel's traversal configuration and the leaf trips of its LDS forms under names of their own: the test instrument,
 // debug_kat_trace.hip, walks with the same ones.)
 constexpr int kPhasesLdsLeafK = GDPT_SPEC_LEAF ? 0 : GDPT_LDS_LEAF_K;
-// the kernel's static LDS (s_acc, s_priv, s_chunks; the stamped builds add s_stamps): what render_free_lds_per_cu counts per block
+// the kernel's static LDS (s_acc, s_priv, s_chunks; the stamped builds add s_stamps, the SETUP builds s_setup): what render_free_lds_per_cu counts per block
 constexpr int kPhasesStaticLds = (15 + kPrivDoubles) * kBlock * (int)sizeof(double) + 66 * (int)sizeof(int);
+constexpr int kPhasesSetupLds = kBlock * 2 * (int)sizeof(double);      // SETUP builds: s_setup, one (ox, oy) per lane
 constexpr int kPhasesStampLds = (kBlock / 64) * (SEG_COUNT + 1) * (int)sizeof(unsigned long long);
 template <bool LDS_SCENE, bool WIDE, bool WW, int PLAIN, int LEAF_K>
 using PhasesTraceCfg = TraceCfg<WW, WIDE, !LDS_SCENE, !(PLAIN & kPlainNoSpheres), !LDS_SCENE, LEAF_K>;
-template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE ? kPhasesLdsLeafK : 0)>
+// SETUP: on power-of-two films the camera block is lane_camera_batched, fed by a per-wave table of the set-ups of a slice's item-firsts.
+// The plain Lambertian kernels for an LDS-resident scene with constant textures are built with it, product and stamped, in both leaf forms
+// (render_kernels.h: has_setup_batch; knob no_setup_batch: their twins without). Films of any other size, and every other instantiation,
+// run lane_camera.
+template <bool LAMBERT, bool LDS_SCENE, bool WIDE, bool WW, bool STAMPED = false, int PLAIN = 0, int LEAF_K = (LDS_SCENE ? kPhasesLdsLeafK : 0), bool SETUP = false>
 __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv, KernelArgs a) {
     // Dynamic LDS = a.stack_levels stack slots per lane (the tree's own bound, not the builder's maximum of 32) and, for LDS-resident
     // scenes, behind them the scene copy, which takes the bytes its tables need (lds_layout.h; launch_render sizes both). The stack
@@ -1114,6 +1174,9 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
     __shared__ double s_acc[15 * kBlock];
     __shared__ double s_priv[kPrivDoubles * kBlock];
     __shared__ int s_chunks[66];
+    // SETUP: per wave, the set-ups (ox, oy) of the first samples of the items of its current slice, entry = item - slice start
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    __shared__ d2 s_setup[SETUP ? kBlock : 1];
     extern __shared__ __attribute__((aligned(16))) unsigned char s_dyn[];
     int *s_stack = (int *)s_dyn;
     unsigned char *s_scene = s_dyn + (LDS_SCENE ? a.stack_levels * (kBlock * (int)sizeof(int)) : 0);
@@ -1148,12 +1211,14 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
     // +2.4 %). The kernels with the full material switch keep the queue at the head of the loop: there the same move cost
     // 3-5 % (one more block of live state across the BSDF switch; measured on disney_metal / disney_diffuse, same box).
     constexpr bool QUEUE_MID = LAMBERT;
-    auto hand_out = [&](int &act) __attribute__((always_inline)) {
+    static_assert(!SETUP || QUEUE_MID, "the set-up table is read where an item is handed out, in the step that makes its first camera ray");
+    const bool batched = SETUP && sv.cam.pow2_film != 0;            // wave-uniform: sample_primary's exact path
+    d2 *const setups = s_setup + (SETUP ? (tid & ~63) : 0);
+    auto hand_out = [&](int &act, bool &fresh) __attribute__((always_inline)) {
         const bool idle = (L.st == S_DONE);
         if (idle && my_item != kNoItem) {               // item finished: publish its 15 sums, clear the slot
             Accum r = acc.result();
             // one 128-byte record per item (15 sums + pad), written as eight 16-byte stores: a single HBM line
-            typedef double d2 __attribute__((ext_vector_type(2)));
             d2 *dst = (d2 *)(a.partials + (size_t)my_item * 16);
             dst[0] = d2{r.r.x, r.r.y}; dst[1] = d2{r.r.z, r.dx0.x}; dst[2] = d2{r.dx0.y, r.dx0.z}; dst[3] = d2{r.dy0.x, r.dy0.y};
             dst[4] = d2{r.dy0.z, r.dx1.x}; dst[5] = d2{r.dx1.y, r.dx1.z}; dst[6] = d2{r.dy1.x, r.dy1.y}; dst[7] = d2{r.dy1.z, 0.0};
@@ -1165,6 +1230,27 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
         const unsigned got_item = wq.take(a, idle, tid, parts);
         stamps.mark(SEG_TAKE);
         if (STAMPED && wq.exhausted && t_dry == ~0ull) t_dry = __builtin_amdgcn_s_memrealtime();
+        if (batched && wq.refilled) {
+            // A new slice: lane i makes the set-up of the first sample of item start + i, pixel and stream formed as below for the lane that
+            // will get the item. One pass at full width per refill (the short slices of the queue's tail: as many lanes as items). Entries
+            // of empty slots are not written and never read. The lanes that read an entry below belong to this wave: the writes are
+            // complete (lgkmcnt) and ordered before the reads for the compiler (fences, wave barrier).
+            const unsigned i = (unsigned)(tid & 63);
+            if (i < wq.end - wq.start) {
+                const ItemParts p = item_slice_at(wq.slice, i, (unsigned)a.num_slots, (unsigned)a.tiles_x);
+                const int px = (int)(p.tx * 16u + (p.pin & 15u)), py = a.row_begin + (int)(p.ty * 16u + (p.pin >> 4));
+                const int s0 = s_chunks[p.c], s1 = s_chunks[p.c + 1];
+                if (px < W && py < a.row_end && s0 < s1) {
+                    const D2 o = sample_setup(camera_here(), ((unsigned long long)py * W + px) * (unsigned long long)a.stream_spp, s0);
+                    setups[i] = d2{o.x, o.y};
+                }
+            }
+            stamps.tick(SEG_SETUPS);
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            __builtin_amdgcn_s_waitcnt(0xC07F);         // lgkmcnt(0)
+            __builtin_amdgcn_wave_barrier();
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        }
         if (got_item != kNoItem) {
             my_item = got_item;
             // item_to_pixel with the parts the queue carried from the slice's first item (no division here)
@@ -1173,14 +1259,18 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             const bool inside = x < W && y < a.row_end;
             base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;     // (s0, s1 carry the window's first_sample)
             L.s = s0; L.s_end = s1;
-            if (inside && s0 < s1) act = ACT_PRIMARY_RAY;       // (an empty slot of a ragged edge tile stays S_DONE and is published as zeros)
+            if (inside && s0 < s1) {                            // (an empty slot of a ragged edge tile stays S_DONE and is published as zeros)
+                act = ACT_PRIMARY_RAY;
+                if (batched) { const d2 o = setups[got_item - wq.start]; D2 oo; oo.x = o.x; oo.y = o.y; lp.set_setup_cur(oo); fresh = true; }
+            }
         }
         stamps.mark(SEG_ITEM);
     };
     for (;;) {
         int act = ACT_NONE;
+        bool fresh = false;                                     // the lane's current set-up slot was filled at the hand-out of this step
         if (!QUEUE_MID) {
-            hand_out(act);
+            hand_out(act, fresh);
             if (act == ACT_PRIMARY_RAY) L.st = S_START;         // lane_consume turns it into the first camera ray
             if (!__any(L.st != S_DONE)) { if (wq.exhausted) break; else continue; }
             stamps.mark(SEG_QUEUE);
@@ -1194,9 +1284,10 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
             if (tx.count) { tc.lane_steps++; if (wave_leader()) tc.wave_steps++; }
             act = lane_consume<LAMBERT, false, AccLds, Stamps<STAMPED>, PLAIN>(sv, tx, a.max_depth, spp, base, L, tv, lp, acc, lc, tc, &stamps);
         }
-        if (QUEUE_MID) hand_out(act);
+        if (QUEUE_MID) hand_out(act, fresh);
         // ---- (S, second half) camera rays: next sample, next offset, first sample of a new item
-        lane_camera<false, Stamps<STAMPED>>(sv, camera_here(), act, x, y, base, L, tv, lp, &stamps);
+        if (batched) lane_camera_batched(camera_here(), act, fresh, x, y, base, L, lp, stamps);
+        else lane_camera<false, Stamps<STAMPED>>(sv, camera_here(), act, x, y, base, L, tv, lp, &stamps);
         lane_arm(sv, act, tv);
         if (QUEUE_MID) {
             if (!__any(L.st != S_DONE) && wq.exhausted) break;
@@ -1451,8 +1542,8 @@ namespace gdpt {
 // (render_kernels.hip: launch_render calls one per route)
 // whole_leaf (knob whole_leaf_trips): the LDS kernels in their LEAF_K = 0 form; the kernels that walk the tree from HBM have no other
 void launch_phases_lambert(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, bool whole_leaf, hipStream_t stream);
-void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, bool whole_leaf, hipStream_t stream);   // triangles only (and constant textures)
-void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, bool whole_leaf, hipStream_t stream);   // diagnostic build
+void launch_phases_lambert_plain(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool const_tex, bool whole_leaf, bool setup, hipStream_t stream);   // triangles only (and constant textures)
+void launch_phases_lambert_stamped(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool plain, bool whole_leaf, bool setup, hipStream_t stream);   // diagnostic build
 void launch_reduce_partials(const DevSceneView &sv, const gd::KernelArgs &a, hipStream_t stream);
 void launch_phases_general(const DevSceneView &sv, const gd::KernelArgs &a, dim3 grid, bool lds, bool lds_wide, bool whole_leaf, hipStream_t stream);
 // kernels built for {Lambertian, `lobe`} (render_phases_general_sets_*.hip): GDPT_MAT_DISNEY_DIFFUSE / _METAL (a), _CLEARCOAT / _SHEEN (b)

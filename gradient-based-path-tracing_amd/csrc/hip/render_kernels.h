@@ -50,6 +50,10 @@ inline bool phases_lds_scene(Route r) {
     return r == Route::LAMBERT_PLAIN_LDS_CONST || r == Route::LAMBERT_PLAIN_LDS_TEX || r == Route::LAMBERT_LDS_WIDE || r == Route::LAMBERT_LDS_BVH2 ||
            r == Route::LAMBERT_STAMPED_LDS_PLAIN || r == Route::LAMBERT_STAMPED_LDS || r == Route::GENERAL_LDS_WIDE || r == Route::GENERAL_LDS_BVH2;
 }
+// the gdpt_render_phases builds with the batched sample set-up and its per-wave table in static LDS (render_device.h: SETUP): the plain
+// Lambertian kernel for an LDS-resident scene with constant textures and its stamped twin; RenderLaunch::no_setup_batch selects their
+// twins without
+inline bool has_setup_batch(Route r) { return r == Route::LAMBERT_PLAIN_LDS_CONST || r == Route::LAMBERT_STAMPED_LDS_PLAIN; }
 // the only kernels that walk the LDS copy in its BVH2 form; every other route walks a BVH4 (or the HBM tree)
 inline bool walks_bvh2(Route r) { return r == Route::LAMBERT_LDS_BVH2 || r == Route::GENERAL_LDS_BVH2; }
 
@@ -71,6 +75,9 @@ struct RouteInputs {
     // knob whole_leaf_trips: picks no other route — the LDS-resident one-sided lane machines run their LEAF_K = 0 instantiation (a leaf
     // trip tests the whole leaf) under the route name they always have; launch_render takes it from RenderLaunch::whole_leaf_trips
     bool whole_leaf_trips;
+    // knob no_setup_batch: picks no other route either — the has_setup_batch routes run their instantiation with lane_camera in the step
+    // (RenderLaunch::no_setup_batch)
+    bool no_setup_batch;
 };
 // Pure: no HIP call, no knob read. Throws std::runtime_error for an rng_scheme / shift_mode pair no kernel serves.
 Route choose_route(const RouteInputs &in);
@@ -106,6 +113,7 @@ struct RenderLaunch {
     int wf_slots;
     int replay_per_step;           // two-sided lane machine (render_twosided.h), 0 = default
     bool whole_leaf_trips;         // RouteInputs::whole_leaf_trips
+    bool no_setup_batch;           // RouteInputs::no_setup_batch
     double *partials;              // device, >= 16 doubles per work item (partial sums)
     unsigned long long *queue_head;// device, work-queue head
     // overlapped launch (can_overlap routes only; nullptr = everything on the caller's stream): the queue reset and the render kernel

@@ -214,7 +214,8 @@ static gd::LdsLayout phases_lds_layout(const DevSceneView &sv, const RenderLaunc
 }
 int render_free_lds_per_cu(const DevSceneView &sv, const RenderLaunch &rl) {
     if (!phases_lds_scene(rl.route)) return 0;
-    const int per_block = gd::lds_allocated(gd::kPhasesStaticLds + (is_stamped(rl.route) ? gd::kPhasesStampLds : 0) + phases_lds_layout(sv, rl).total);
+    const int setup = (has_setup_batch(rl.route) && !rl.no_setup_batch) ? gd::kPhasesSetupLds : 0;      // s_setup of the SETUP builds
+    const int per_block = gd::lds_allocated(gd::kPhasesStaticLds + setup + (is_stamped(rl.route) ? gd::kPhasesStampLds : 0) + phases_lds_layout(sv, rl).total);
     const int left = gd::kLdsPerCu - (rl.blocks_per_cu > 0 ? rl.blocks_per_cu : 2) * per_block;
     return left > 0 ? left : 0;
 }
@@ -274,17 +275,18 @@ void launch_render(const DevSceneView &sv, const RenderLaunch &rl, hipStream_t s
         throw std::runtime_error("launch_render: wavefront buffers missing");
     set_route(r);
     const bool wl = rl.whole_leaf_trips;       // (knob; read by the LDS-resident one-sided lane machines only)
+    const bool sb = !rl.no_setup_batch;        // (knob; read by the has_setup_batch routes only)
     switch (r) {
-    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, wl, ks); break;
-    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, wl, ks); break;
-    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, wl, ks); break;
-    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, wl, ks); break;
+    case Route::LAMBERT_PLAIN_LDS_CONST: launch_phases_lambert_plain(sv, a, grid, true, true, wl, sb, ks); break;
+    case Route::LAMBERT_PLAIN_LDS_TEX: launch_phases_lambert_plain(sv, a, grid, true, false, wl, false, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_CONST: launch_phases_lambert_plain(sv, a, grid, false, true, wl, false, ks); break;
+    case Route::LAMBERT_PLAIN_HBM_TEX: launch_phases_lambert_plain(sv, a, grid, false, false, wl, false, ks); break;
     case Route::LAMBERT_LDS_WIDE: launch_phases_lambert(sv, a, grid, true, true, wl, ks); break;
     case Route::LAMBERT_LDS_BVH2: launch_phases_lambert(sv, a, grid, true, false, wl, ks); break;
     case Route::LAMBERT_HBM: launch_phases_lambert(sv, a, grid, false, false, wl, ks); break;
-    case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, wl, stream); break;
-    case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, wl, stream); break;
-    case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, wl, stream); break;
+    case Route::LAMBERT_STAMPED_LDS_PLAIN: launch_phases_lambert_stamped(sv, a, grid, true, true, wl, sb, stream); break;
+    case Route::LAMBERT_STAMPED_LDS: launch_phases_lambert_stamped(sv, a, grid, true, false, wl, false, stream); break;
+    case Route::LAMBERT_STAMPED_HBM: launch_phases_lambert_stamped(sv, a, grid, false, false, wl, false, stream); break;
     case Route::GENERAL_SET_A_DISNEY_DIFFUSE: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_DIFFUSE, ks); break;
     case Route::GENERAL_SET_A_DISNEY_METAL: launch_phases_general_set_a(sv, a, grid, GDPT_MAT_DISNEY_METAL, ks); break;
     case Route::GENERAL_SET_B_DISNEY_CLEARCOAT: launch_phases_general_set_b(sv, a, grid, GDPT_MAT_DISNEY_CLEARCOAT, ks); break;

@@ -43,6 +43,9 @@
  *   full_material_switch (0/1)  lane machines: the kernel with the full material switch even when the scene fits a small set
  *   whole_leaf_trips (0/1)      one-sided lane machine on an LDS-resident scene: the kernel whose leaf trips test the whole leaf (four
  *                               tests in a row) instead of two records per trip with the cursor in the leaf reference; same route name
+ *   no_setup_batch (0/1)        route lambert_plain/lds_const (and its stamped build, lambert_stamped/lds_plain): the kernel whose camera block
+ *                               makes each sample's set-up (stream seeding, two draws, pixel filter) in the step that needs it, instead
+ *                               of ahead and at full wave width; same route name
  *   nlm_direct (0/1)            gdpt_denoise_nlm*: the direct form of the filter (one thread per pixel, every patch distance summed
  *                               from global memory: the literal definition) instead of the tiled form (a block's tile and halo
  *                               staged in LDS, separable patch sums). gdpt_denoise_atrous* picks a form per level: 0 the staged
@@ -86,7 +89,8 @@ extern "C" {
 int gdpt_debug_knob_set(const char *name, double value);
 /* Wave cycles per segment of the last stamped render (summed over waves): [0] loop head remainder, [1] traversal,
  * [2] hit-vertex rebuild, [3] state arms, [4] BSDF block, [5] offset / finish arm, [6] camera-ray block, [7] wave steps
- * (a count), [8] publishing finished items, [9] work-queue take, [10] item -> pixel mapping, [11] unused; wall clock
+ * (a count), [8] publishing finished items, [9] work-queue take, [10] item -> pixel mapping, [11] full-width passes of the sample
+ * set-up (a count like [7]: per-wave table fills and on-demand passes; 0 under no_setup_batch and on other films than powers of two); wall clock
  * (s_memrealtime, 100 MHz ticks): [12] first wave started, [13] first wave found the queue empty, [14] last wave ended. */
 void gdpt_debug_get_stamps(double out[16]);
 /* The work-item plan of the persistent render kernels (make_chunk_plan, csrc/hip/render_kernels.hip): chunk c of a pixel

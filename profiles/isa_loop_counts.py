@@ -31,7 +31,7 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "gradient-based-path-tracing_amd", "csrc")
-DEFAULT_KERNEL = "gdpt_render_phasesILb1ELb1ELb1ELb1ELb0ELi3ELi2EE"      # Lambertian, LDS scene, wide, no spheres, constant textures
+DEFAULT_KERNEL = "gdpt_render_phasesILb1ELb1ELb1ELb1ELb0ELi3ELi2ELb1EE"  # Lambertian, LDS scene, wide, no spheres, constant textures, batched set-up
 
 
 def makefile_hipflags(csrc):
