@@ -29,6 +29,7 @@
 #include "denoise_nlm.h"
 #include "denoise_atrous.h"
 #include "nlm_device.h"
+#include "nlm_host.h"
 
 #include <cmath>
 #include <mutex>
@@ -236,14 +237,10 @@ namespace gdpt {
 
 namespace {
 
-struct AtrousWorkspace {
-    std::mutex mu;                    // held while a call runs on this (device, stream) pair
-    DeviceBuffer<double> partials;
-    DeviceBuffer<film::Estimate> d_est;     // [0] sum var in, sum u^2 in, left out; [1] sum var out, sum u^2 out, left out
-    PinnedBuffer<film::Estimate> h_est;
+// the sums', and what the levels keep between them
+struct AtrousWorkspace : SumsWorkspace {
     DeviceBuffer<double> plane[4];    // the two (u, v) film pairs between the levels
     DeviceBuffer<unsigned char> mask; // the valid set
-    Event ev[2];
 };
 
 // leaked on purpose, as the filter's registry (denoise_nlm.hip); a pair's entry goes with forget_stream (device_mem.h)
@@ -290,10 +287,7 @@ void denoise_atrous_launch(int w, int h, const double *d_img, const double *d_va
     ck(hipGetDevice(&dev), "hipGetDevice");
     AtrousWorkspace &ws = g_workspaces.get(dev, stream);
     std::lock_guard<std::mutex> lk(ws.mu);
-    if (!ws.partials) ws.partials.alloc(6 * film::kMaxBlocks, "hipMalloc(atrous partials)");
-    if (!ws.d_est) ws.d_est.alloc(2, "hipMalloc(atrous sums)");
-    if (!ws.h_est) ws.h_est.alloc(2, "hipHostMalloc(atrous sums)");
-    for (auto &e : ws.ev) if (!e) e.create();
+    ws.prepare("atrous");
     const size_t pixels = (size_t)w * h;
     if (p.levels > 1) {               // (a call of one level reads and writes the caller's planes alone)
         for (int k = 0; k < (p.levels > 2 ? 4 : 2); k++) ws.plane[k].grow(3 * pixels, stream, "hipMalloc(atrous planes)");
@@ -306,16 +300,7 @@ void denoise_atrous_launch(int w, int h, const double *d_img, const double *d_va
     a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
     a.img = d_img; a.var = d_var; a.partials = ws.partials;
     a.mask = p.levels > 1 ? ws.mask.data() : nullptr;
-    if (guide) {
-        nlm::Guide &gd = a.gd;
-        gd.feat = d_feat; gd.fvar = d_feat_var; gd.plane = pixels;
-        gd.groups = guide->num_groups; gd.kf2 = guide->k_f * guide->k_f; gd.alpha_f = guide->alpha_f;
-        for (int j = 0; j < guide->num_groups; j++) {
-            const GdptNlmFeatureGroup &grp = guide->groups[j];
-            gd.first[j] = grp.first_channel; gd.count[j] = grp.num_channels; gd.tau[j] = grp.tau;
-            for (int c = grp.first_channel; c < grp.first_channel + grp.num_channels; c++) gd.used |= 1u << c;
-        }
-    }
+    if (guide) fill_guide(a.gd, *guide, d_feat, d_feat_var, pixels);
     nlm::Demod dm{};
     if (demod) dm = nlm::Demod{d_feat, d_feat_var, pixels, demod->albedo_channel, demod->coverage_channel, demod->floor};
     const int nb = a.g.blocks;
@@ -346,20 +331,7 @@ void denoise_atrous_launch(int w, int h, const double *d_img, const double *d_va
         ck(hipGetLastError(), "atrous launch");
     }
     if (!stats) return;
-    film::launch_finish(nb, ws.partials, ws.d_est, stream);
-    film::launch_finish(nb, ws.partials.data() + 3 * nb, ws.d_est.data() + 1, stream);
-    ck(hipGetLastError(), "atrous reduction launch");
-    ck(hipEventRecord(ws.ev[1], stream), "hipEventRecord");
-    ck(hipMemcpyAsync(ws.h_est, ws.d_est, 2 * sizeof(film::Estimate), hipMemcpyDeviceToHost, stream), "hipMemcpyAsync(atrous sums)");
-    ck(hipStreamSynchronize(stream), "hipStreamSynchronize(atrous)");
-    *stats = GdptNlmStats{};
-    const film::Estimate &in = ws.h_est.data()[0], &out = ws.h_est.data()[1];
-    stats->pixels_left_out = (uint64_t)in.left_out;
-    stats->sum_var_in = in.sum_var; stats->sum_sq_in = in.sum_mean2;
-    stats->sum_var_out = out.sum_var; stats->sum_sq_out = out.sum_mean2;
-    stats->error_in = std::sqrt(in.sum_var / in.sum_mean2);
-    stats->error_out = std::sqrt(out.sum_var / out.sum_mean2);
-    { float ms = 0; ck(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]), "hipEventElapsedTime"); stats->filter_ms = ms; }
+    ws.read_stats(nb, stream, "atrous", stats);
     stats->window_radius = 2 << (p.first_level + p.levels - 1); stats->patch_radius = 0;
 }
 
@@ -368,18 +340,13 @@ void denoise_atrous_launch(int w, int h, const double *d_img, const double *d_va
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
 
 // What both entry points refuse; `who` names the caller. Returns the parameters in force.
 GdptAtrousParams check_arguments(const std::string &who, int width, int height, const double *img, const double *var, const double *feat,
                                  const double *feat_var, int num_channels, const GdptAtrousParams *params, const GdptNlmGuide *guide,
                                  const GdptNlmDemod *demod, const double *out, const double *var_out) {
-    if (!img) throw std::runtime_error(who + ": img is null");
-    if (!var) throw std::runtime_error(who + ": var is null");
-    if (!out) throw std::runtime_error(who + ": out is null");
-    if (out == img || out == var) throw std::runtime_error(who + ": out must not alias an input");
-    if (var_out && (var_out == img || var_out == var || var_out == out)) throw std::runtime_error(who + ": var_out must not alias an input or out");
-    if (width < 1 || height < 1) throw std::runtime_error(who + ": width and height must be >= 1");
-    if ((long long)width * height > (1LL << 29)) throw std::runtime_error(who + ": width * height: film too large");
+    gdpt::check_film(who, width, height, img, var, out, var_out);
     GdptAtrousParams p;
     if (params) p = *params;
     else gdpt_atrous_default_params(&p);
@@ -398,12 +365,6 @@ GdptAtrousParams check_arguments(const std::string &who, int width, int height, 
     if (feat && (out == feat || out == feat_var)) throw std::runtime_error(who + ": out must not alias an input");
     if (var_out && feat && (var_out == feat || var_out == feat_var)) throw std::runtime_error(who + ": var_out must not alias an input or out");
     return p;
-}
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
 }
 
 } // namespace
@@ -435,22 +396,10 @@ int gdpt_denoise_atrous(int width, int height, const double *img, const double *
         const std::string who = "gdpt_denoise_atrous";
         const GdptAtrousParams p = check_arguments(who, width, height, img, var, feat, feat_var, num_channels, params, guide, demod, out, var_out);
         need_a_device(who);
-        const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
         const bool planes = (guide && guide->num_groups > 0) || demod;
-        const size_t felems = planes ? (size_t)width * height * num_channels : 0, fbytes = felems * sizeof(double);
-        gdpt::DeviceBuffer<double> d_img, d_var, d_out, d_var_out, d_feat, d_feat_var;
-        d_img.alloc(elems, "hipMalloc(atrous io)"); d_var.alloc(elems, "hipMalloc(atrous io)"); d_out.alloc(elems, "hipMalloc(atrous io)");
-        if (var_out) d_var_out.alloc(elems, "hipMalloc(atrous io)");
-        d_feat.alloc(felems, "hipMalloc(atrous features)"); d_feat_var.alloc(felems, "hipMalloc(atrous features)");
-        ck(hipMemcpy(d_img, img, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-        ck(hipMemcpy(d_var, var, bytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-        if (felems) {
-            ck(hipMemcpy(d_feat, feat, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-            ck(hipMemcpy(d_feat_var, feat_var, fbytes, hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-        }
-        gdpt::denoise_atrous_launch(width, height, d_img, d_var, d_feat, d_feat_var, p, guide, demod, d_out, d_var_out, nullptr, stats);
-        ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
-        if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        gdpt::FilmMirrors m(width, height, img, var, feat, feat_var, planes ? (size_t)width * height * num_channels : 0, out, var_out);
+        gdpt::denoise_atrous_launch(width, height, m.img.d, m.var.d, m.feat.d, m.fvar.d, p, guide, demod, m.out.d, m.var_out.d, nullptr, stats);
+        m.down(out, var_out);
     });
 }
 

@@ -22,6 +22,13 @@ inline void ck(hipError_t e, const char *what) {
     if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// what an entry point that launches kernels refuses on a machine without a device; `who` names the caller
+inline void need_a_device(const std::string &who) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
+    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
+}
+
 struct DeviceSpace {
     static void *alloc(size_t bytes, const char *what) { void *p = nullptr; ck(hipMalloc(&p, bytes), what); return p; }
     static void free(void *p) { (void)hipFree(p); }

@@ -108,6 +108,7 @@ __global__ __launch_bounds__(gd::kBlock, 2) void features_kernel(DevSceneView sv
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
 
 struct FeatureWorkspace {
     std::mutex mu;                    // held while a call runs on this (device, stream) pair
@@ -141,12 +142,6 @@ void check_fields(const std::string &who, const GdptScene *scene, const GdptRend
         if (p && p->spp > 0 && (long long)win->first_sample + p->spp > (long long)win->stream_spp)
             throw std::runtime_error(who + ": window [first_sample, first_sample + spp) must lie inside [0, stream_spp)");
     }
-}
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
 }
 
 // ... and what needs the handle: the samples per pixel, the band against the film, the stream block against 63 bits

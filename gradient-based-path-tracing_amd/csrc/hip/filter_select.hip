@@ -271,6 +271,7 @@ void filter_select_launch(int w, int h, int n, const double *const *d_FA, const 
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
 
 // what both entry points refuse; `who` names the caller. Returns the parameters in force.
 GdptSelectParams check_arguments(const std::string &who, int width, int height, int n, const double *const *FA, const double *const *FB,
@@ -317,12 +318,6 @@ GdptSelectParams check_arguments(const std::string &who, int width, int height, 
     else gdpt_select_default_params(&p);
     gdpt::select_check_params(who, p);
     return p;
-}
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
 }
 
 } // namespace

@@ -1,11 +1,14 @@
-// nlm_device.h — the device helpers the non-local-means kernels share (denoise_nlm.hip, nlm_regress.hip): the tile constants, the
-// guide's and the divisor's blocks, the tiled form's LDS sizing, a pixel's validity and loading, the pair distance, the thread's own
-// features, a pixel's weighted sums (Accum, finish_pixel: nlm_joint.hip shares them with denoise_nlm.hip) and the film sums. `A` is a
-// kernel's argument block: the fields of nlm::Args (denoise_nlm.hip), kGuided / kDemod, and with them `gd` / `dm`.
+// nlm_device.h — the device code the non-local-means family shares (denoise_nlm.hip, nlm_joint.hip, nlm_regress.hip, nlm_collab.hip;
+// denoise_atrous.hip takes the pixel helpers): the tile constants, the argument blocks, the guide's and the divisor's blocks, a pixel's
+// validity and loading, the pair distance and the pair weight, the direct form's tap loop (patch_distance), the tiled form's LDS stage
+// with its loop over the window offsets (Stage), the thread's own features, a pixel's weighted sums (Accum, finish_pixel) and the film
+// sums. `A` is a kernel's argument block: the fields of nlm::Args, kGuided / kDemod, and with them `gd` / `dm`.
 #pragma once
 #include "../../../include/gdpt.h"
 #include "image_kernels.h"
 #include "denoise_nlm.h"
+
+#include <type_traits>
 
 namespace nlm {
 
@@ -33,6 +36,32 @@ struct Demod {
     int albedo, coverage;
     double floor;
 };
+
+// the argument block of a kernel; the guided and demodulated ones add their blocks
+struct Args {
+    static constexpr bool kGuided = false, kDemod = false;
+    TileGrid g;                  // 16 x 16 tiles
+    int r, f;
+    double k2, alpha, eps;
+    const double *img, *var;
+    double *out, *var_out;       // var_out nullable
+    double *partials;            // [0] sum var in, [1] sum u^2 in, [2] pixels left out, [3] sum var out, [4] sum u^2 out, [5] = [2]; gridDim.x doubles each
+};
+struct GuidedArgs : Args {
+    static constexpr bool kGuided = true;
+    Guide gd;
+};
+struct DemodArgs : Args {
+    static constexpr bool kDemod = true;
+    Demod dm;
+};
+struct GuidedDemodArgs : GuidedArgs {
+    static constexpr bool kDemod = true;
+    Demod dm;
+};
+template <bool GUIDED, bool DEMOD>
+using ArgsOf = typename std::conditional<GUIDED, typename std::conditional<DEMOD, GuidedDemodArgs, GuidedArgs>::type,
+                                         typename std::conditional<DEMOD, DemodArgs, Args>::type>::type;
 
 // pitch of the e plane for patches of ew = 16 + 2f points a row
 __host__ __device__ inline int e_pitch(int f) { return f == 0 ? kTile : 48; }
@@ -68,6 +97,13 @@ __device__ __forceinline__ double pair_distance(const double ua[3], const double
 struct Sums {
     double var_in = 0.0, sq_in = 0.0, var_out = 0.0, sq_out = 0.0, left_out = 0.0;
 };
+// a finished pixel's terms of the film sums: its input triples u, v and its outputs o, vo
+__device__ __forceinline__ void add_sums(Sums &s, const double u[3], const double v[3], const double o[3], const double vo[3]) {
+    s.var_in += (v[0] + v[1]) + v[2];
+    s.sq_in += (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
+    s.var_out += (vo[0] + vo[1]) + vo[2];
+    s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+}
 
 // the effective albedo a~ of pixel p (film index y w + x); returns whether its albedo and coverage values are valid
 __device__ __forceinline__ bool effective_albedo(const Demod &dm, size_t p, double al[3]) {
@@ -144,6 +180,130 @@ __device__ __forceinline__ bool load_pixel(const A &a, int x, int y, double u[3]
     return ok;
 }
 
+// direct form: S_o, C_o of the valid pair (x, y), (x + ox, y + oy), tap by tap from global memory; load(x, y, u, v) is the kernel's
+// pixel loader
+template <class A, class Load>
+__device__ __forceinline__ void patch_distance(const A &a, Load load, int x, int y, int ox, int oy, double &S, int &C) {
+    const int f = a.f;
+    S = 0.0; C = 0;
+    for (int ny = -f; ny <= f; ny++)
+        for (int nx = -f; nx <= f; nx++) {
+            const int ax = x + nx, ay = y + ny, bx = ax + ox, by = ay + oy;
+            if (ax < 0 || ay < 0 || ax >= a.g.w || ay >= a.g.h || bx < 0 || by < 0 || bx >= a.g.w || by >= a.g.h) continue;
+            double ua[3], va[3], ub[3], vb[3];
+            const bool oka = load(ax, ay, ua, va), okb = load(bx, by, ub, vb);
+            if (!oka || !okb) continue;
+            S += pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
+            C++;
+        }
+}
+
+// The tiled form's stage: the tile with a halo of r + f pixels in LDS, plane by plane (three u, three v, a validity flag; out-of-film
+// and invalid entries are u = v = 0, flag 0), sized by the call's r and f: (16 + 2(r+f))^2 entries of 52 bytes, 42 x 42 = 91.7 KB at
+// r = 10, f = 3 (108 624 bytes with the planes below). Per window offset: e_o and its count on the (16 + 2f)^2 points the tile's
+// patches touch, into LDS; row sums of 2f + 1 taps; column sums of the row sums (the separable box of box_kernel, recon_spread.hip).
+// (16 + 2f)^2 pair distances per offset and tile instead of 256 (2f+1)^2: 484 against 12544 at f = 3.
+// LDS banking: every plane is a plane of doubles or of ints, so consecutive lanes read consecutive elements. In the row pass a
+// half-wave covers two rows of 16 outputs; the e plane's pitch is 16 (f = 0) or 48 doubles, = 16 mod 32, which puts the second row's
+// 16 doubles on the other half of the 64 banks. In the column pass a half-wave reads 32 consecutive doubles of the row sums (pitch 16).
+struct Stage {
+    int r, f, sw, sn, ew, ep, taps, tid, pc;
+    double *su, *sv, *pe, *ph;
+    int *sflag, *ce, *ch;
+    int ia[2], ie[2], jrow[2];
+
+    // the stage of a call's r and f in the block's dynamic LDS (lds_doubles, lds_ints)
+    __device__ __forceinline__ void lay_out(int r_, int f_, double *lds) {
+        r = r_; f = f_;
+        const int halo = r + f;
+        sw = kTile + 2 * halo; sn = sw * sw;           // the stage: the tile and its halo
+        ew = kTile + 2 * f;                            // the points the tile's patches touch, a row
+        const int en = ew * ew;
+        ep = e_pitch(f); taps = 2 * f + 1;
+        su = lds; sv = lds + 3 * sn;                   // plane c at su + c sn, sv + c sn
+        pe = lds + 6 * sn;                             // e_o of the current offset, pitch ep
+        ph = pe + ep * ew;                             // its row sums, pitch 16
+        sflag = (int *)(ph + kTile * ew);
+        ce = sflag + sn; ch = ce + ep * ew;
+        tid = threadIdx.x;
+        const int lx = tid & (kTile - 1), ly = tid / kTile;
+        // the (at most two) pair distances and row sums of an offset that fall to this thread
+        for (int k = 0; k < 2; k++) {
+            const int q = tid + k * kBlock;
+            const int qy = q / ew, qx = q - qy * ew;
+            ia[k] = q < en ? (qy + r) * sw + qx + r : -1;
+            ie[k] = qy * ep + qx;
+            jrow[k] = q < kTile * ew ? (q / kTile) * ep + (q & (kTile - 1)) : -1;
+        }
+        pc = (ly + halo) * sw + lx + halo;             // the thread's own pixel in the stage
+    }
+
+    // the tile at (x0, y0) with its halo into the stage, through the kernel's pixel loader load(x, y, u, v); the caller's barriers
+    // stand before (the previous tile's stage has been read) and after
+    template <class Load>
+    __device__ __forceinline__ void fill(const TileGrid &g, int x0, int y0, Load load) const {
+        const int halo = r + f;
+        for (int k = tid; k < sn; k += kBlock) {
+            const int ry = k / sw, rx = k - ry * sw;
+            const int gx = x0 - halo + rx, gy = y0 - halo + ry;
+            double u[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
+            bool ok = false;
+            if (gx >= 0 && gy >= 0 && gx < g.w && gy < g.h) ok = load(gx, gy, u, v);
+#pragma unroll
+            for (int c = 0; c < 3; c++) { su[c * sn + k] = ok ? u[c] : 0.0; sv[c * sn + k] = ok ? v[c] : 0.0; }
+            sflag[k] = ok ? 1 : 0;
+        }
+    }
+
+    // the staged triples of entry i
+    __device__ __forceinline__ void mean(int i, double u[3]) const { u[0] = su[i]; u[1] = su[sn + i]; u[2] = su[2 * sn + i]; }
+    __device__ __forceinline__ void variance(int i, double v[3]) const { v[0] = sv[i]; v[1] = sv[sn + i]; v[2] = sv[2 * sn + i]; }
+
+    // The loop over the window offsets: tap(iq, S, C, oy, ox) is called for the thread's own pixel p (`ok`: whether it is valid) and
+    // every valid partner q = p + o, with the partner's index iq in the stage and S_o, C_o of the pair. FROM_PARTNER swaps the roles
+    // of an offset's two pixels: S and C are those of the fit centred at q for its offset -o, that is the pair distances
+    // e(q + n, p + n) with q's triple first, over the same patch taps n and summed in the same separable order.
+    template <bool FROM_PARTNER = false, class Tap>
+    __device__ __forceinline__ void sweep(double k2, double alpha, double eps, bool ok, Tap tap) const {
+        for (int oy = -r; oy <= r; oy++)
+            for (int ox = -r; ox <= r; ox++) {
+                const int shift = oy * sw + ox;
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    if (ia[k] < 0) continue;
+                    const int i0 = ia[k], i1 = i0 + shift;
+                    const int both = sflag[i0] & sflag[i1];
+                    double e = 0.0;
+                    if (both) {
+                        const int ja = FROM_PARTNER ? i1 : i0, jb = FROM_PARTNER ? i0 : i1;
+                        double ua[3], va[3], ub[3], vb[3];
+#pragma unroll
+                        for (int c = 0; c < 3; c++) { ua[c] = su[c * sn + ja]; va[c] = sv[c * sn + ja]; ub[c] = su[c * sn + jb]; vb[c] = sv[c * sn + jb]; }
+                        e = pair_distance(ua, va, ub, vb, k2, alpha, eps);
+                    }
+                    pe[ie[k]] = e; ce[ie[k]] = both;
+                }
+                __syncthreads();
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    if (jrow[k] < 0) continue;
+                    double S = 0.0;
+                    int C = 0;
+                    for (int n = 0; n < taps; n++) { S += pe[jrow[k] + n]; C += ce[jrow[k] + n]; }
+                    ph[tid + k * kBlock] = S; ch[tid + k * kBlock] = C;
+                }
+                __syncthreads();
+                const int iq = pc + shift;
+                if (ok && sflag[iq] != 0) {            // (a set flag: p + o is inside the film)
+                    double S = 0.0;
+                    int C = 0;
+                    for (int n = 0; n < taps; n++) { S += ph[tid + n * kTile]; C += ch[tid + n * kTile]; }
+                    tap(iq, S, C, oy, ox);
+                }
+            }
+    }
+};
+
 // A thread's own pixel in registers: the feature values and variances of the channels in use (0 elsewhere). Every loop over groups and
 // channels below runs to the caps with static indices, under wave-uniform conditions.
 struct OwnFeatures {
@@ -182,15 +342,21 @@ __device__ __forceinline__ void add_term(double num[3], double vnum[3], double w
     for (int c = 0; c < 3; c++) { num[c] += wgt * u[c]; vnum[c] += (wgt * wgt) * v[c]; }
 }
 
+// w_o(p) of a valid pair with C >= 1; Df (guided kernels): the pair's feature distance, >= 0
+template <bool GUIDED = true>
+__device__ __forceinline__ double pair_weight(double S, int C, double Df) {
+    double D = S / (double)C;
+    D = D > 0.0 ? D : 0.0;
+    if (GUIDED) D = fmax(D, Df);
+    return exp(-D);
+}
+
 struct Accum {
     double num[3] = {0.0, 0.0, 0.0}, vnum[3] = {0.0, 0.0, 0.0}, wsum = 0.0;
-    // Df (guided kernels): the pair's feature distance, >= 0. Returns the weight w_o(p).
+    // Returns the weight w_o(p).
     template <bool GUIDED = false>
     __device__ __forceinline__ double add(double S, int C, const double u[3], const double v[3], double Df = 0.0) {
-        double D = S / (double)C;
-        D = D > 0.0 ? D : 0.0;
-        if (GUIDED) D = fmax(D, Df);
-        const double wgt = exp(-D);
+        const double wgt = pair_weight<GUIDED>(S, C, Df);
         wsum += wgt;
         add_term(num, vnum, wgt, u, v);
         return wgt;
@@ -215,10 +381,7 @@ __device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double 
             if (a.var_out) a.var_out[i + c] = vo[c];
             uo[c] = a.img[i + c]; vi[c] = a.var[i + c];
         }
-        s.var_in += (vi[0] + vi[1]) + vi[2];
-        s.sq_in += (uo[0] * uo[0] + uo[1] * uo[1]) + uo[2] * uo[2];
-        s.var_out += (vo[0] + vo[1]) + vo[2];
-        s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+        add_sums(s, uo, vi, o, vo);
         return;
     }
 #pragma unroll
@@ -228,10 +391,7 @@ __device__ __forceinline__ void finish_pixel(const A &a, size_t i, const double 
         a.out[i + c] = o[c];
         if (a.var_out) a.var_out[i + c] = vo[c];
     }
-    s.var_in += (v[0] + v[1]) + v[2];
-    s.sq_in += (u[0] * u[0] + u[1] * u[1]) + u[2] * u[2];
-    s.var_out += (vo[0] + vo[1]) + vo[2];
-    s.sq_out += (o[0] * o[0] + o[1] * o[1]) + o[2] * o[2];
+    add_sums(s, u, v, o, vo);
 }
 
 } // namespace nlm

@@ -4,31 +4,28 @@
 // NC companion films (a_j, s_j), which play no part in the weights beyond a pixel's validity.
 //
 // Kernels: joint_direct_kernel<GUIDED, NC> and joint_tiled_kernel<GUIDED, NC>, the two forms of denoise_nlm.hip (chosen by the same
-// test knob nlm_direct) on the device helpers of nlm_device.h, which all three files share: load_pixel, pair_distance, OwnFeatures, the
-// LDS sizing, Accum, finish_pixel, the film sums. 16 x 16 tiles, at most 1024 blocks striding over them (film::tile_grid), a thread on a
-// pixel of the tile, block partials through leave_block_sum for finish_runs_kernel (image_kernels.h): a fixed order, the same bits
-// every time. No launch writes a plane it reads.
-//   The guide film's sums go through nlm::Accum::add, term by term in the order of nlm::tiled_kernel / direct_kernel, and end in
-//   nlm::finish_pixel: with every companion valid its out, var_out and sums are the guided filter's bit for bit. Accum::add returns the
-//   weight; the companions' terms go through nlm::add_term, the very function Accum::add uses for the guide film (one copy of the two
-//   expressions, so one contraction into fma), and are divided as finish_pixel divides: a companion that is the guide film itself comes
-//   back as out, var_out bit for bit.
-//   The tiled form's stage is the one of nlm::tiled_kernel, sized by the same functions (108 624 bytes at r = 10, f = 3), and holds the
-//   guide film alone: the companions do not go into LDS. A thread reads a_j(p+o) and s_j(p+o) from global memory at the point where it
-//   has w_o(p), as the guided kernel reads its feature planes there: a tile row of a film is 16 x 24 contiguous bytes, a wave's read
-//   four such rows, served from L1 / L2. Per thread 6 NC accumulators more. NC is a compile-time count (1 .. 4; a call without
-//   companions is the guided filter itself), so every accumulator index is static: no scratch, no spilled VGPR
+// test knob nlm_direct) on the same device code (nlm_device.h): the tap loop and the stage are run through load_joint_pixel, the guide
+// film's argument block is nlm::Args itself. Block partials go through leave_block_sum for finish_runs_kernel (image_kernels.h): a
+// fixed order, the same bits every time. No launch writes a plane it reads.
+//   The guide film's sums go through nlm::Accum::add and end in nlm::finish_pixel: with every companion valid its out, var_out and
+//   sums are the guided filter's bit for bit. Accum::add returns the weight; the companions' terms go through nlm::add_term, the very
+//   function Accum::add uses for the guide film (one copy of the two expressions, so one contraction into fma), and are divided as
+//   finish_pixel divides: a companion that is the guide film itself comes back as out, var_out bit for bit.
+//   The stage holds the guide film alone: the companions do not go into LDS. A thread reads a_j(p+o) and s_j(p+o) from global memory
+//   at the point where it has w_o(p), as the guided kernel reads its feature planes there: a tile row of a film is 16 x 24 contiguous
+//   bytes, a wave's read four such rows, served from L1 / L2. Per thread 6 NC accumulators more. NC is a compile-time count (1 .. 4; a
+//   call without companions is the guided filter itself), so every accumulator index is static: no scratch, no spilled VGPR
 //   (profiles/nlm_kernel_resources.txt).
 #include "../../../include/gdpt.h"
 #include "../capi_common.h"
 #include "image_kernels.h"
 #include "denoise_nlm.h"
 #include "nlm_device.h"
+#include "nlm_host.h"
 
 #include <cmath>
 #include <cstdint>
 #include <mutex>
-#include <type_traits>
 #include <vector>
 
 namespace nlmj {
@@ -39,22 +36,9 @@ constexpr int kMaxN = GDPT_NLM_JOINT_MAX;
 constexpr int kGuideRuns = 6;                      // what nlm::leave_partials leaves: runs 0 .. 5
 constexpr int kMaxRuns = kGuideRuns + 2 * kMaxN;   // then sum_var_in[j], sum_var_out[j] of companion j as runs 6 + 2 j, 7 + 2 j
 
-// the fields of nlm::Args, under the names the shared helpers read
-struct Base {
-    static constexpr bool kGuided = false, kDemod = false;
-    TileGrid g;                  // 16 x 16 tiles
-    int r, f;
-    double k2, alpha, eps;
-    const double *img, *var;     // the guide film
-    double *out, *var_out;       // var_out nullable
-    double *partials;            // kGuideRuns + 2 NC runs of gridDim.x doubles
-};
-struct GuidedBase : Base {
-    static constexpr bool kGuided = true;
-    Guide gd;
-};
+// the guide film's block (partials: kGuideRuns + 2 NC runs of gridDim.x doubles), and the companions
 template <bool GUIDED, int NC>
-struct Args : std::conditional<GUIDED, GuidedBase, Base>::type {
+struct Args : ArgsOf<GUIDED, false> {
     const double *comp[NC], *comp_var[NC];
     double *comp_out[NC], *comp_var_out[NC];      // comp_var_out[j] nullable
 };
@@ -159,7 +143,8 @@ template <bool GUIDED, int NC>
 __global__ __launch_bounds__(kBlock) void joint_direct_kernel(Args<GUIDED, NC> a) {
     using A = Args<GUIDED, NC>;
     __shared__ double red[kBlock / 64];
-    const int r = a.r, f = a.f;
+    const int r = a.r;
+    const auto load = [&](int x, int y, double u[3], double v[3]) { return load_joint_pixel<A, NC>(a, x, y, u, v); };
     Sums s;
     CompanionSums<NC> cs;
     cs.clear();
@@ -169,7 +154,7 @@ __global__ __launch_bounds__(kBlock) void joint_direct_kernel(Args<GUIDED, NC> a
         if (x >= a.g.w || y >= a.g.h) continue;
         const size_t i = ((size_t)y * a.g.w + x) * 3;
         double u[3], v[3];
-        if (!load_joint_pixel<A, NC>(a, x, y, u, v)) { keep_pixel(a, i, u, v, s); keep_companions<A, NC>(a, i); continue; }
+        if (!load(x, y, u, v)) { keep_pixel(a, i, u, v, s); keep_companions<A, NC>(a, i); continue; }
         OwnFeatures own;
         if constexpr (GUIDED) own.load(a.gd, (size_t)y * a.g.w + x);
         Accum acc;
@@ -180,23 +165,14 @@ __global__ __launch_bounds__(kBlock) void joint_direct_kernel(Args<GUIDED, NC> a
                 const int qx = x + ox, qy = y + oy;
                 if (qx < 0 || qy < 0 || qx >= a.g.w || qy >= a.g.h) continue;
                 double uq[3], vq[3];
-                if (!load_joint_pixel<A, NC>(a, qx, qy, uq, vq)) continue;
-                double S = 0.0;
-                int C = 0;
-                for (int ny = -f; ny <= f; ny++)
-                    for (int nx = -f; nx <= f; nx++) {
-                        const int ax = x + nx, ay = y + ny, bx = ax + ox, by = ay + oy;
-                        if (ax < 0 || ay < 0 || ax >= a.g.w || ay >= a.g.h || bx < 0 || by < 0 || bx >= a.g.w || by >= a.g.h) continue;
-                        double ua[3], va[3], ub[3], vb[3];
-                        const bool oka = load_joint_pixel<A, NC>(a, ax, ay, ua, va), okb = load_joint_pixel<A, NC>(a, bx, by, ub, vb);
-                        if (!oka || !okb) continue;
-                        S += pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
-                        C++;
-                    }
+                if (!load(qx, qy, uq, vq)) continue;
+                double S;
+                int C;
+                patch_distance(a, load, x, y, ox, oy, S, C);      // (C >= 1: the tap n = 0 counts)
                 const size_t q = (size_t)qy * a.g.w + qx;
                 double wgt;
                 if constexpr (GUIDED) wgt = acc.template add<true>(S, C, uq, vq, own.distance(a.gd, q));
-                else wgt = acc.add(S, C, uq, vq);      // (C >= 1: the tap n = 0 counts)
+                else wgt = acc.add(S, C, uq, vq);
                 cp.add(a, q * 3, wgt);
             }
         finish_pixel(a, i, u, v, acc, s);
@@ -205,107 +181,50 @@ __global__ __launch_bounds__(kBlock) void joint_direct_kernel(Args<GUIDED, NC> a
     leave_joint_partials<A, NC>(a, s, cs, red);
 }
 
-// nlm::tiled_kernel with the companions: the guide film's tile and halo staged in LDS under the joint validity, e_o of an offset on
-// the points the tile's patches touch, its separable box, then the weight; the companions' terms of p+o from global memory
+// nlm::tiled_kernel with the companions: the guide film's tile and halo staged under the joint validity; the companions' terms of
+// p+o from global memory
 template <bool GUIDED, int NC>
 __global__ __launch_bounds__(kBlock) void joint_tiled_kernel(Args<GUIDED, NC> a) {
     using A = Args<GUIDED, NC>;
     extern __shared__ double lds[];
     __shared__ double red[kBlock / 64];
-    const int r = a.r, f = a.f, halo = r + f;
-    const int sw = kTile + 2 * halo, sn = sw * sw;      // the stage: the tile and its halo
-    const int ew = kTile + 2 * f, en = ew * ew;         // the points the tile's patches touch
-    const int ep = e_pitch(f), taps = 2 * f + 1;
-    double *const su = lds, *const sv = lds + 3 * sn;   // plane c at su + c sn, sv + c sn
-    double *const pe = lds + 6 * sn;                    // e_o of the current offset, pitch ep
-    double *const ph = pe + ep * ew;                    // its row sums, pitch 16
-    int *const sflag = (int *)(ph + kTile * ew);
-    int *const ce = sflag + sn, *const ch = ce + ep * ew;
-    const int tid = threadIdx.x, lx = tid & (kTile - 1), ly = tid / kTile;
-    // the (at most two) pair distances and row sums of an offset that fall to this thread
-    int ia[2], ie[2], jrow[2];
-    for (int k = 0; k < 2; k++) {
-        const int q = tid + k * kBlock;
-        const int qy = q / ew, qx = q - qy * ew;
-        ia[k] = q < en ? (qy + r) * sw + qx + r : -1;
-        ie[k] = qy * ep + qx;
-        jrow[k] = q < kTile * ew ? (q / kTile) * ep + (q & (kTile - 1)) : -1;
-    }
-    const int pc = (ly + halo) * sw + lx + halo;        // the thread's own pixel in the stage
+    Stage st;
+    st.lay_out(a.r, a.f, lds);
+    const int pc = st.pc;
+    const auto load = [&](int x, int y, double u[3], double v[3]) { return load_joint_pixel<A, NC>(a, x, y, u, v); };
     Sums s;
     CompanionSums<NC> cs;
     cs.clear();
     for (int t = blockIdx.x; t < a.g.tiles; t += gridDim.x) {
         const TilePixel tp = tile_pixel<kTile, kTile>(a.g, t);
-        const int x0 = tp.x0, y0 = tp.y0;
         __syncthreads();                                // the previous tile's stage has been read
-        for (int k = tid; k < sn; k += kBlock) {
-            const int ry = k / sw, rx = k - ry * sw;
-            const int gx = x0 - halo + rx, gy = y0 - halo + ry;
-            double u[3] = {0.0, 0.0, 0.0}, v[3] = {0.0, 0.0, 0.0};
-            bool ok = false;
-            if (gx >= 0 && gy >= 0 && gx < a.g.w && gy < a.g.h) ok = load_joint_pixel<A, NC>(a, gx, gy, u, v);
-#pragma unroll
-            for (int c = 0; c < 3; c++) { su[c * sn + k] = ok ? u[c] : 0.0; sv[c * sn + k] = ok ? v[c] : 0.0; }
-            sflag[k] = ok ? 1 : 0;
-        }
+        st.fill(a.g, tp.x0, tp.y0, load);
         __syncthreads();
         const int x = tp.x, y = tp.y;
         const bool inside = x < a.g.w && y < a.g.h;
-        const bool okp = inside && sflag[pc] != 0;
+        const bool okp = inside && st.sflag[pc] != 0;
         OwnFeatures own;
         if constexpr (GUIDED) { if (okp) own.load(a.gd, (size_t)y * a.g.w + x); }
         Accum acc;
         Companions<NC> cp;
         cp.clear();
-        for (int oy = -r; oy <= r; oy++)
-            for (int ox = -r; ox <= r; ox++) {
-                const int shift = oy * sw + ox;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (ia[k] < 0) continue;
-                    const int i0 = ia[k], i1 = i0 + shift;
-                    const int both = sflag[i0] & sflag[i1];
-                    double e = 0.0;
-                    if (both) {
-                        double ua[3], va[3], ub[3], vb[3];
-#pragma unroll
-                        for (int c = 0; c < 3; c++) { ua[c] = su[c * sn + i0]; va[c] = sv[c * sn + i0]; ub[c] = su[c * sn + i1]; vb[c] = sv[c * sn + i1]; }
-                        e = pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
-                    }
-                    pe[ie[k]] = e; ce[ie[k]] = both;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (jrow[k] < 0) continue;
-                    double S = 0.0;
-                    int C = 0;
-                    for (int n = 0; n < taps; n++) { S += pe[jrow[k] + n]; C += ce[jrow[k] + n]; }
-                    ph[tid + k * kBlock] = S; ch[tid + k * kBlock] = C;
-                }
-                __syncthreads();
-                const int iq = pc + shift;
-                if (okp && sflag[iq] != 0) {            // (a set flag: p+o is inside the film)
-                    double S = 0.0;
-                    int C = 0;
-                    for (int n = 0; n < taps; n++) { S += ph[tid + n * kTile]; C += ch[tid + n * kTile]; }
-                    const double uq[3] = {su[iq], su[sn + iq], su[2 * sn + iq]}, vq[3] = {sv[iq], sv[sn + iq], sv[2 * sn + iq]};
-                    const size_t q = (size_t)(y + oy) * a.g.w + (x + ox);
-                    double wgt;
-                    if constexpr (GUIDED) wgt = acc.template add<true>(S, C, uq, vq, own.distance(a.gd, q));
-                    else wgt = acc.add(S, C, uq, vq);
-                    cp.add(a, q * 3, wgt);
-                }
-            }
+        st.sweep(a.k2, a.alpha, a.eps, okp, [&](int iq, double S, int C, int oy, int ox) {
+            double uq[3], vq[3];
+            st.mean(iq, uq); st.variance(iq, vq);
+            const size_t q = (size_t)(y + oy) * a.g.w + (x + ox);
+            double wgt;
+            if constexpr (GUIDED) wgt = acc.template add<true>(S, C, uq, vq, own.distance(a.gd, q));
+            else wgt = acc.add(S, C, uq, vq);
+            cp.add(a, q * 3, wgt);
+        });
         if (!inside) continue;
         const size_t i = ((size_t)y * a.g.w + x) * 3;
+        double u[3], v[3];
         if (okp) {
-            const double u[3] = {su[pc], su[sn + pc], su[2 * sn + pc]}, v[3] = {sv[pc], sv[sn + pc], sv[2 * sn + pc]};
+            st.mean(pc, u); st.variance(pc, v);
             finish_pixel(a, i, u, v, acc, s);
             finish_companions<A, NC>(a, i, acc, cp, cs);
         } else {
-            double u[3], v[3];
             load_pixel(a, x, y, u, v);                  // (the stage holds zeros in its place)
             keep_pixel(a, i, u, v, s);
             keep_companions<A, NC>(a, i);
@@ -343,32 +262,14 @@ struct JointCall {
 template <bool GUIDED, int NC>
 void launch_form(const JointCall &c, const GdptNlmParams &p, const GdptNlmGuide &g, double *partials, bool direct, hipStream_t stream) {
     nlmj::Args<GUIDED, NC> a{};
-    a.g = film::tile_grid(c.w, c.h, kNlmTile, kNlmTile); a.r = p.window_radius; a.f = p.patch_radius;
-    a.k2 = p.k * p.k; a.alpha = p.alpha; a.eps = p.epsilon;
-    a.img = c.img; a.var = c.var; a.out = c.out; a.var_out = c.var_out; a.partials = partials;
-    if constexpr (GUIDED) {
-        nlm::Guide &gd = a.gd;
-        gd.feat = c.feat; gd.fvar = c.fvar; gd.plane = (size_t)c.w * c.h;
-        gd.groups = g.num_groups; gd.kf2 = g.k_f * g.k_f; gd.alpha_f = g.alpha_f;
-        for (int j = 0; j < g.num_groups; j++) {
-            const GdptNlmFeatureGroup &grp = g.groups[j];
-            gd.first[j] = grp.first_channel; gd.count[j] = grp.num_channels; gd.tau[j] = grp.tau;
-            for (int ch = grp.first_channel; ch < grp.first_channel + grp.num_channels; ch++) gd.used |= 1u << ch;
-        }
-    }
+    fill_base(a, c.w, c.h, p, c.img, c.var, c.out, c.var_out, partials);
+    if constexpr (GUIDED) fill_guide(a.gd, g, c.feat, c.fvar, (size_t)c.w * c.h);
     for (int j = 0; j < NC; j++) {
         a.comp[j] = c.comp[j]; a.comp_var[j] = c.comp_var[j];
         a.comp_out[j] = c.comp_out[j]; a.comp_var_out[j] = c.comp_var_out ? c.comp_var_out[j] : nullptr;
     }
-    const int nb = a.g.blocks;
-    if (direct) {
-        hipLaunchKernelGGL((nlmj::joint_direct_kernel<GUIDED, NC>), dim3(nb), dim3(film::kBlock), 0, stream, a);
-        return;
-    }
-    const size_t lds = (size_t)nlm::lds_doubles(a.r, a.f) * sizeof(double) + (size_t)nlm::lds_ints(a.r, a.f) * sizeof(int);
-    ck(hipFuncSetAttribute(reinterpret_cast<const void *>(nlmj::joint_tiled_kernel<GUIDED, NC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds),
-       "hipFuncSetAttribute(nlm joint stage)");
-    hipLaunchKernelGGL((nlmj::joint_tiled_kernel<GUIDED, NC>), dim3(nb), dim3(film::kBlock), lds, stream, a);
+    if (direct) hipLaunchKernelGGL((nlmj::joint_direct_kernel<GUIDED, NC>), dim3(a.g.blocks), dim3(film::kBlock), 0, stream, a);
+    else launch_staged(nlmj::joint_tiled_kernel<GUIDED, NC>, a.g.blocks, a.r, a.f, stream, a, "hipFuncSetAttribute(nlm joint stage)");
 }
 
 template <int NC>
@@ -494,12 +395,7 @@ void nlm_joint_check_arguments(const std::string &who, int width, int height, co
 namespace {
 
 using gdpt::ck;
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
-}
+using gdpt::need_a_device;
 
 } // namespace
 
@@ -531,33 +427,21 @@ int gdpt_denoise_nlm_joint(int width, int height, const double *img, const doubl
         gdpt::nlm_joint_check_arguments(who, width, height, img, var, feat, feat_var, n, comp, comp_var, params, guide, out, var_out, comp_out,
                                         comp_var_out, p, g);
         need_a_device(who);
-        const size_t elems = (size_t)width * height * 3, bytes = elems * sizeof(double);
-        const size_t felems = g.num_groups > 0 ? (size_t)width * height * g.num_channels : 0;
-        const char *what = "hipMalloc(nlm joint io)";
-        auto up = [&](gdpt::DeviceBuffer<double> &b, const double *src, size_t count) {
-            b.alloc(count, what);
-            if (count) ck(hipMemcpy(b, src, count * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-        };
-        gdpt::DeviceBuffer<double> d_img, d_var, d_feat, d_feat_var, d_out, d_var_out;
-        gdpt::DeviceBuffer<double> d_comp[GDPT_NLM_JOINT_MAX], d_comp_var[GDPT_NLM_JOINT_MAX], d_comp_out[GDPT_NLM_JOINT_MAX], d_comp_var_out[GDPT_NLM_JOINT_MAX];
-        up(d_img, img, elems); up(d_var, var, elems); up(d_feat, feat, felems); up(d_feat_var, feat_var, felems);
-        d_out.alloc(elems, what);
-        if (var_out) d_var_out.alloc(elems, what);
+        gdpt::FilmMirrors m(width, height, img, var, feat, feat_var, g.num_groups > 0 ? (size_t)width * height * g.num_channels : 0, out, var_out);
+        gdpt::Mirror m_comp[GDPT_NLM_JOINT_MAX], m_comp_var[GDPT_NLM_JOINT_MAX], m_comp_out[GDPT_NLM_JOINT_MAX], m_comp_var_out[GDPT_NLM_JOINT_MAX];
         const double *pc[GDPT_NLM_JOINT_MAX] = {}, *pcv[GDPT_NLM_JOINT_MAX] = {};
         double *pco[GDPT_NLM_JOINT_MAX] = {}, *pcvo[GDPT_NLM_JOINT_MAX] = {};
         for (int j = 0; j < n; j++) {
-            up(d_comp[j], comp[j], elems); up(d_comp_var[j], comp_var[j], elems);
-            d_comp_out[j].alloc(elems, what);
-            if (comp_var_out && comp_var_out[j]) d_comp_var_out[j].alloc(elems, what);
-            pc[j] = d_comp[j]; pcv[j] = d_comp_var[j]; pco[j] = d_comp_out[j];
-            pcvo[j] = comp_var_out && comp_var_out[j] ? d_comp_var_out[j].data() : nullptr;
+            m_comp[j].up(comp[j], m.elems); m_comp_var[j].up(comp_var[j], m.elems);
+            m_comp_out[j].make(comp_out[j], m.elems);
+            if (comp_var_out) m_comp_var_out[j].make(comp_var_out[j], m.elems);
+            pc[j] = m_comp[j].d; pcv[j] = m_comp_var[j].d; pco[j] = m_comp_out[j].d; pcvo[j] = m_comp_var_out[j].d;
         }
-        gdpt::denoise_nlm_joint_launch(width, height, d_img, d_var, d_feat, d_feat_var, n, pc, pcv, p, g, d_out, d_var_out, pco, pcvo, nullptr, stats);
-        ck(hipMemcpy(out, d_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
-        if (var_out) ck(hipMemcpy(var_out, d_var_out, bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+        gdpt::denoise_nlm_joint_launch(width, height, m.img.d, m.var.d, m.feat.d, m.fvar.d, n, pc, pcv, p, g, m.out.d, m.var_out.d, pco, pcvo, nullptr, stats);
+        m.down(out, var_out);
         for (int j = 0; j < n; j++) {
-            ck(hipMemcpy(comp_out[j], d_comp_out[j], bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
-            if (pcvo[j]) ck(hipMemcpy(comp_var_out[j], d_comp_var_out[j], bytes, hipMemcpyDeviceToHost), "hipMemcpy(D2H)");
+            m_comp_out[j].down(comp_out[j], m.elems);
+            if (comp_var_out) m_comp_var_out[j].down(comp_var_out[j], m.elems);
         }
     });
 }

@@ -28,6 +28,7 @@
 #include "image_kernels.h"
 #include "denoise_nlm.h"
 #include "nlm_pyramid.h"
+#include "nlm_host.h"
 
 #include <cmath>
 #include <initializer_list>
@@ -433,6 +434,8 @@ void denoise_nlm_multiscale_launch(int w, int h, const double *d_img, const doub
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
+using gdpt::Mirror;
 
 // what every entry point here refuses in a level's inputs; `who` names the caller. Returns the kind's blocks in force.
 gdpt::NlmKindBlocks check_level(const std::string &who, int width, int height, const double *img, const double *var, const double *feat,
@@ -485,24 +488,6 @@ GdptNlmParams check_multiscale(const std::string &who, const double *img, const 
     check_alias(who, "var_out", var_out, {img, var, feat, feat_var, out});
     return p;
 }
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
-}
-
-// a host array on the device (empty for a null pointer), and back
-struct Mirror {
-    gdpt::DeviceBuffer<double> d;
-    void up(const double *host, size_t n) {
-        if (!host) return;
-        d.alloc(n, "hipMalloc(nlm pyramid io)");
-        ck(hipMemcpy(d, host, n * sizeof(double), hipMemcpyHostToDevice), "hipMemcpy(H2D)");
-    }
-    void make(const double *host, size_t n) { if (host) d.alloc(n, "hipMalloc(nlm pyramid io)"); }
-    void down(double *host, size_t n) const { if (host) ck(hipMemcpy(host, d, n * sizeof(double), hipMemcpyDeviceToHost), "hipMemcpy(D2H)"); }
-};
 
 } // namespace
 
@@ -586,13 +571,10 @@ int gdpt_denoise_nlm_multiscale(int width, int height, const double *img, const 
         const gdpt::NlmKindBlocks kb = check_level(who, width, height, img, var, feat, feat_var, num_channels, kind, guide, demod);
         const GdptNlmParams p = check_multiscale(who, img, var, feat, feat_var, levels, params, out, var_out);
         need_a_device(who);
-        const size_t n = (size_t)width * height, ch = (size_t)kb.num_channels;
-        Mirror m_img, m_var, m_feat, m_fvar, o_out, o_var;
-        m_img.up(img, 3 * n); m_var.up(var, 3 * n); m_feat.up(feat, ch * n); m_fvar.up(feat_var, ch * n);
-        o_out.make(out, 3 * n); o_var.make(var_out, 3 * n);
-        gdpt::denoise_nlm_multiscale_launch(width, height, m_img.d, m_var.d, m_feat.d, m_fvar.d, kb, levels, p, o_out.d, o_var.d, nullptr, stats);
+        gdpt::FilmMirrors m(width, height, img, var, feat, feat_var, (size_t)width * height * kb.num_channels, out, var_out);
+        gdpt::denoise_nlm_multiscale_launch(width, height, m.img.d, m.var.d, m.feat.d, m.fvar.d, kb, levels, p, m.out.d, m.var_out.d, nullptr, stats);
         ck(hipStreamSynchronize(nullptr), "hipStreamSynchronize(nlm multiscale)");
-        o_out.down(out, 3 * n); o_var.down(var_out, 3 * n);
+        m.down(out, var_out);
     });
 }
 

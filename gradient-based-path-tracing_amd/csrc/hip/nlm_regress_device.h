@@ -1,8 +1,6 @@
-// nlm_regress_device.h — the device code the first-order regression (nlm_regress.hip) and its collaborative form (nlm_collab.hip) share:
-// the kernels' argument block, the regressors and a pair's design vector, the pair weight, the normal equations of a pixel (Fit), their
-// LDL^T in the header's order (include/gdpt.h: gdpt_denoise_nlm_regress*), the direct form's patch distance and the tiled form's stage
-// with its loop over the window offsets. Moved here from nlm_regress.hip as it stood: the regression kernels' machine code is what it
-// was before the move.
+// nlm_regress_device.h — the device code the first-order regression (nlm_regress.hip) and its collaborative form (nlm_collab.hip) share
+// beside nlm_device.h: the kernels' argument block, the regressors and a pair's design vector, the normal equations of a pixel (Fit) and
+// their LDL^T in the header's order (include/gdpt.h: gdpt_denoise_nlm_regress*).
 #pragma once
 #include "../../../include/gdpt.h"
 #include "image_kernels.h"
@@ -20,26 +18,12 @@ struct Regress {
     int m, ch[kMaxM];
     double scale[kMaxM], ridge;
 };
-struct Args {
-    static constexpr bool kGuided = true, kDemod = false;
-    TileGrid g;                  // 16 x 16 tiles
-    int r, f;
-    double k2, alpha, eps;
-    const double *img, *var;
-    double *out, *var_out;       // var_out nullable
-    double *partials;            // as denoise_nlm.hip's: six sums, gridDim.x doubles each
+// a regression kernel is a guided, not demodulated kernel to the helpers of nlm_device.h; gd.used: the channels some group or some
+// regressor names
+struct Args : GuidedArgs {
     int second;                  // whether the second sweep runs (var_out or the sums are asked for)
-    Guide gd;                    // `used`: the channels some group or some regressor names
     Regress rg;
 };
-
-// w_o(p) of a valid pair with C >= 1; Df: the pair's feature distance, >= 0
-__device__ __forceinline__ double pair_weight(double S, int C, double Df) {
-    double D = S / (double)C;
-    D = D > 0.0 ? D : 0.0;
-    D = fmax(D, Df);
-    return exp(-D);
-}
 
 // The thread's own regressor values, and the design vector of a pair. Unused regressors (j >= m) have z = 0.
 struct OwnRegressors {
@@ -121,70 +105,6 @@ struct Ldlt {
         for (int i = kD - 1; i >= 0; i--)
 #pragma unroll
             for (int k = i + 1; k < kD; k++) x[i] -= L[tri(k, i)] * x[k];
-    }
-};
-
-// direct form: S_o, C_o of the valid pair (x, y), (x + ox, y + oy), tap by tap from global memory
-__device__ __forceinline__ void patch_distance(const Args &a, int x, int y, int ox, int oy, double &S, int &C) {
-    const int f = a.f;
-    S = 0.0; C = 0;
-    for (int ny = -f; ny <= f; ny++)
-        for (int nx = -f; nx <= f; nx++) {
-            const int ax = x + nx, ay = y + ny, bx = ax + ox, by = ay + oy;
-            if (ax < 0 || ay < 0 || ax >= a.g.w || ay >= a.g.h || bx < 0 || by < 0 || bx >= a.g.w || by >= a.g.h) continue;
-            double ua[3], va[3], ub[3], vb[3];
-            const bool oka = load_pixel(a, ax, ay, ua, va), okb = load_pixel(a, bx, by, ub, vb);
-            if (!oka || !okb) continue;
-            S += pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
-            C++;
-        }
-}
-
-// The tiled form's stage and its loop over the window offsets, which both sweeps run: tap(iq, S, C, oy, ox) is called for the
-// thread's own pixel and every valid partner p + o, with the partner's index iq in the stage.
-struct Stage {
-    int r, f, sw, sn, ew, ep, taps, tid, pc;
-    double *su, *sv, *pe, *ph;
-    int *sflag, *ce, *ch;
-    int ia[2], ie[2], jrow[2];
-
-    template <class Tap>
-    __device__ __forceinline__ void sweep(const Args &a, bool okp, Tap tap) const {
-        for (int oy = -r; oy <= r; oy++)
-            for (int ox = -r; ox <= r; ox++) {
-                const int shift = oy * sw + ox;
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (ia[k] < 0) continue;
-                    const int i0 = ia[k], i1 = i0 + shift;
-                    const int both = sflag[i0] & sflag[i1];
-                    double e = 0.0;
-                    if (both) {
-                        double ua[3], va[3], ub[3], vb[3];
-#pragma unroll
-                        for (int c = 0; c < 3; c++) { ua[c] = su[c * sn + i0]; va[c] = sv[c * sn + i0]; ub[c] = su[c * sn + i1]; vb[c] = sv[c * sn + i1]; }
-                        e = pair_distance(ua, va, ub, vb, a.k2, a.alpha, a.eps);
-                    }
-                    pe[ie[k]] = e; ce[ie[k]] = both;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int k = 0; k < 2; k++) {
-                    if (jrow[k] < 0) continue;
-                    double S = 0.0;
-                    int C = 0;
-                    for (int n = 0; n < taps; n++) { S += pe[jrow[k] + n]; C += ce[jrow[k] + n]; }
-                    ph[tid + k * kBlock] = S; ch[tid + k * kBlock] = C;
-                }
-                __syncthreads();
-                const int iq = pc + shift;
-                if (okp && sflag[iq] != 0) {
-                    double S = 0.0;
-                    int C = 0;
-                    for (int n = 0; n < taps; n++) { S += ph[tid + n * kTile]; C += ch[tid + n * kTile]; }
-                    tap(iq, S, C, oy, ox);
-                }
-            }
     }
 };
 

@@ -197,6 +197,7 @@ ReconSpreadResult recon_spread_device(int w, int h, int n, const double *const *
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
 
 // what both entry points refuse; `who` names the caller
 void check_arguments(const std::string &who, int width, int height, int n, const double *const *images, const double *weights, const double *total,
@@ -217,12 +218,6 @@ void check_arguments(const std::string &who, int width, int height, int n, const
         for (int i = 0; i < n; i++) alias = alias || out == images[i];
         if (alias) throw std::runtime_error(who + ": an output must not alias an input or the other output");
     }
-}
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    ck(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
 }
 
 } // namespace

@@ -260,6 +260,7 @@ void variance_smooth_launch(int w, int h, const double *d_img, const double *d_v
 namespace {
 
 using gdpt::ck;
+using gdpt::need_a_device;
 
 // what both entry points refuse; `who` names the caller. Returns the parameters in force.
 GdptVarSmoothParams check_arguments(const std::string &who, int width, int height, const double *img, const double *var, const double *feat,
@@ -282,12 +283,6 @@ GdptVarSmoothParams check_arguments(const std::string &who, int width, int heigh
         gdpt::nlm_check_demod(who, *demod, num_channels);
     } else if (feat || feat_var) throw std::runtime_error(who + ": demod is null (feature planes need a demod block)");
     return p;
-}
-
-void need_a_device(const std::string &who) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess) { (void)hipGetLastError(); ndev = 0; }      // (without a device the count itself is an error)
-    if (ndev <= 0) throw std::runtime_error(who + ": no HIP device visible (this library has no CPU fallback)");
 }
 
 } // namespace

@@ -1,8 +1,10 @@
 """Manual (not collected by pytest): sha1 hashes of what the image-space kernels write, and the sums, energies and iteration counts
 they report, from two builds of the library, each in a fresh child process; the last line says whether all of them are equal.
 Poisson solve (the three solvers), gdpt_assemble_solve_device, L1 reconstruction (clean, NaN where no row reads, NaN inside),
-variance-weighted reconstruction with NaN / negative variances and an isolated pixel, spread at radius 0 and 2, NLM in both forms, and
-a progressive session's fold, merge and variance read-out; on a 37 x 21 film (ragged for both tile sizes, several blocks) and a
+variance-weighted reconstruction with NaN / negative variances and an isolated pixel, spread at radius 0 and 2, the non-local-means
+family in both forms of nlm_direct (plain; guided with 2 groups; demodulated with and without a guide; joint with 2 companions, guided
+and not; the regression and its collaborative form with 3 regressors, the coefficient film included; a-trous with 3 levels; every
+output film hashed, every reported sum bit for bit), and a progressive session's fold, merge and variance read-out; on a 37 x 21 film (ragged for both tile sizes, several blocks) and a
 1025 x 345 one (the second trip of every loop over groups or tiles, and of the partial reduction). Seeded inputs, small iteration caps.
     python tests/diag_image_hash.py <other.so>"""
 import hashlib
@@ -85,13 +87,51 @@ def child(lib_path):
         for radius in (0, 2):
             var, emap, st = G.recon_spread(members, [4.0, 8.0, 20.0], total=c, radius=radius)
             out[f"{tag} spread r{radius}"] = [sha(var), sha(emap), num(st.sum_var), num(st.sum_sq), st.pixels_left_out]
-        # --- NLM, both forms
+        # --- the NLM family, both forms: one pixel with a negative variance, one with a negative feature variance
         var = 0.0025 * (0.5 + rng.random((h, w, 3))); var[4, 6, 1] = -1.0
-        for form in (0, 1):
-            with G.debug_knobs(nlm_direct=form):
-                f, vf, st = G.denoise_nlm(c, var, window_radius=4, patch_radius=2)
-            out[f"{tag} nlm {'direct' if form else 'tiled'}"] = [sha(f), sha(vf), num(st.sum_var_in), num(st.sum_sq_in), num(st.sum_var_out), num(st.sum_sq_out),
-                                                                st.pixels_left_out]
+        yy, xx = np.mgrid[0:h, 0:w]
+        feat = np.stack([0.4 + 0.3 * np.sin(0.05 * (k + 1) * xx + 0.09 * yy + k) for k in range(8)]) + 0.02 * rng.standard_normal((8, h, w))
+        feat[7] = np.clip(feat[7] + 0.4, 0.0, 1.0)            # the coverage plane
+        fvar = 4e-4 * (0.5 + rng.random((8, h, w))); fvar[1, 9, 11] = -1.0
+        comps = [c[::-1].copy(), 0.5 * c + 0.1]; comp_vars = [var[::-1].copy(), 0.25 * var]
+        guide = G.nlm_guide(groups=[(0, 3, 1e-3), (3, 3, 1e-3)])
+        regress = G.nlm_regress(channels=[0, 3, 6], scales=[1.0, 0.5, 2.0])
+
+        def sums(st):
+            return [num(st.sum_var_in), num(st.sum_sq_in), num(st.sum_var_out), num(st.sum_sq_out), st.pixels_left_out]
+
+        def joint(**kw):
+            f, vf, co, cvo, st = G.denoise_nlm_joint(c, var, comps, comp_vars, **kw)
+            return [f, vf] + co + cvo, sums(st.guide) + [num(st.sum_var_in[j]) for j in range(2)] + [num(st.sum_var_out[j]) for j in range(2)]
+
+        def collab(**kw):
+            f, planes, st = G.denoise_nlm_collab(c, var, feat, fvar, guide=guide, regress=regress, coef=True, **kw)
+            return [f, planes], sums(st)
+
+        def films(call):          # a call that returns its output films and then its GdptNlmStats
+            def run(**kw):
+                *arrays, st = call(**kw)
+                return arrays, sums(st)
+            return run
+
+        rf = dict(window_radius=4, patch_radius=2)
+        cases = (("nlm", films(lambda **kw: G.denoise_nlm(c, var, **kw)), rf),
+                 ("nlm guided", films(lambda **kw: G.denoise_nlm_guided(c, var, feat, fvar, guide=guide, **kw)), rf),
+                 ("nlm demod", films(lambda **kw: G.denoise_nlm_demod(c, var, feat, fvar, **kw)), rf),
+                 ("nlm demod guided", films(lambda **kw: G.denoise_nlm_demod(c, var, feat, fvar, guide=guide, **kw)), rf),
+                 ("nlm joint", joint, rf),
+                 ("nlm joint guided", lambda **kw: joint(feat=feat, feat_var=fvar, guide=guide, **kw), rf),
+                 ("nlm regress", films(lambda **kw: G.denoise_nlm_regress(c, var, feat, fvar, guide=guide, regress=regress, **kw)), rf),
+                 ("nlm regress f0", films(lambda **kw: G.denoise_nlm_regress(c, var, feat, fvar, guide=guide, regress=regress, **kw)),
+                  dict(window_radius=3, patch_radius=0)),
+                 ("nlm collab", collab, rf),
+                 ("atrous", films(lambda **kw: G.denoise_atrous(c, var, **kw)), dict(levels=3)),
+                 ("atrous guided demod", films(lambda **kw: G.denoise_atrous(c, var, feat, fvar, guide=guide, demod=G.nlm_demod(), **kw)), dict(levels=3)))
+        for name, call, kw in cases:
+            for form in (0, 1):
+                with G.debug_knobs(nlm_direct=form):
+                    arrays, figures = call(**kw)
+                out[f"{tag} {name} {'direct' if form else 'tiled'}"] = [sha(a) for a in arrays] + figures
         # --- a progressive session: three folds, then two slice sessions merged into an accumulator, and the variance read-out of each
         with tempfile.TemporaryDirectory() as tmp:
             scene = G.Scene(G.parse_scene(scene_variant(tmp, "cbox/cbox_gdpt.xml", width=w, height=h)))

@@ -3,7 +3,7 @@ records. One process; HIP events (the library's own filter_ms: the filter kernel
 and the direct form (knob nlm_direct) alternate, five runs each after one warm-up run each, on a synthetic noisy film:
 512x512 at (r, f) = (10, 3) and (5, 1), 1280x720 at (10, 3). Every timed call runs under an alarm of its own: a call that
 overruns it ends the process, and nothing more is started.
-    python tests/time_nlm.py [--quick]"""
+    python tests/time_nlm.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -11,6 +11,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick = "--quick" in sys.argv
 RUNS = 2 if quick else 5

@@ -6,7 +6,7 @@ sweep, the regression without it, the collaborative form tiled (both passes, the
 nlm_collab_pass, on a coefficient film of the caller's) and direct (knob nlm_direct), on the synthetic noisy film and feature planes
 of tests/time_nlm_regress.py. Every timed call runs under an alarm of its own: a call that overruns it ends the process, and nothing
 more is started.
-    python tests/time_nlm_collab.py [--quick]"""
+    python tests/time_nlm_collab.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -14,6 +14,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick = "--quick" in sys.argv
 RUNS = 2 if quick else 5

@@ -4,7 +4,7 @@ runs each after one warm-up run each: demodulated and not, tiled and direct (kno
 planes) and not, on the synthetic noisy film of tests/time_nlm_guided.py with an albedo of 0.2 .. 0.9 in planes 0-2 and coverage 1 in
 plane 7. Every timed call runs under an alarm of its own: a call that overruns it ends the process, and nothing more is started.
 A checksum of every undemodulated form's output is printed, to hold it against another build's.
-    python tests/time_nlm_demod.py [--quick] [--plain-only]      --plain-only: the undemodulated forms alone (runs on a build before
+    python tests/time_nlm_demod.py [--quick] [--lib PATH] [--plain-only]      --plain-only: the undemodulated forms alone (runs on a build before
                                                                  this filter, to time the two builds alternately on one device)"""
 import hashlib, os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -13,6 +13,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick, plain_only = "--quick" in sys.argv, "--plain-only" in sys.argv
 RUNS = 2 if quick else 5

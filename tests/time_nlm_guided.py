@@ -4,7 +4,7 @@ profiles/nlm_guided_times.txt records. One process; HIP events (the library's ow
 each: guided tiled, guided direct, unguided tiled, unguided direct (knob nlm_direct), on the synthetic noisy film of
 tests/time_nlm.py with smooth noisy feature planes. Then the feature render of cbox 512x512x16 and sponza 1280x720x16, one run each
 after a warm-up. Every timed call runs under an alarm of its own: a call that overruns it ends the process, and nothing more is started.
-    python tests/time_nlm_guided.py [--quick]"""
+    python tests/time_nlm_guided.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,6 +12,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick = "--quick" in sys.argv
 RUNS = 2 if quick else 5

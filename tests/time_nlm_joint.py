@@ -4,7 +4,7 @@ default guide (albedo and normal groups over 8 planes), tiled form, these calls 
 gdpt_denoise_nlm_guided_device, gdpt_denoise_nlm_joint_device with n = 1, 2 and 4 companions, and the same pair unguided (n = 2), on
 the synthetic noisy film of tests/time_nlm_guided.py; the companions are noisy films of their own. Every timed call runs under an alarm
 of its own: a call that overruns it ends the process, and nothing more is started.
-    python tests/time_nlm_joint.py [--quick]"""
+    python tests/time_nlm_joint.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -12,6 +12,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick = "--quick" in sys.argv
 RUNS = 2 if quick else 5

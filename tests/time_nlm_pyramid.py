@@ -5,7 +5,7 @@ for the plain kind and for the demodulated kind with a coverage plane, and the w
 process for scale. total_ms of the whole call spans the waits for every level's stats (the call is timed as a session makes it). The
 film is the synthetic noisy film of tests/time_var_smooth.py. Every timed call runs under an alarm of its own: a call that overruns it
 ends the process, and nothing more is started.
-    python tests/time_nlm_pyramid.py [--quick]"""
+    python tests/time_nlm_pyramid.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -13,6 +13,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 RUNS = 2 if "--quick" in sys.argv else 5
 STEP_LIMIT_S = 60

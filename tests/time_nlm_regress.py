@@ -5,7 +5,7 @@ seven regressors albedo, normal and depth, four forms alternate, five runs each 
 direct (knob nlm_direct), guided tiled, and regress tiled with neither var_out nor the sums asked for (no second sweep), on the
 synthetic noisy film and feature planes of tests/time_nlm_guided.py. Every timed call runs under an alarm of its own: a call that
 overruns it ends the process, and nothing more is started.
-    python tests/time_nlm_regress.py [--quick]"""
+    python tests/time_nlm_regress.py [--quick] [--lib PATH]"""
 import os, signal, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -13,6 +13,8 @@ import torch
 dev = torch.device("cuda", 0)
 torch.zeros(1, device=dev)
 import gdpt_amd as G
+if "--lib" in sys.argv:          # another build of the library, so that one script times two builds
+    G.LIB_PATH = os.path.abspath(sys.argv[sys.argv.index("--lib") + 1])
 
 quick = "--quick" in sys.argv
 RUNS = 2 if quick else 5
