@@ -260,7 +260,7 @@ class GdptPreparedInfo(C.Structure):
 
 
 # include/gdpt_debug.h: gdpt_debug_kat_* (the per-vertex device functions on arrays of cases)
-KAT_FAMILIES = ("bsdf", "texture", "filter", "primary", "shading", "light")
+KAT_FAMILIES = ("bsdf", "texture", "filter", "primary", "shading", "light", "envmap")
 
 
 class GdptKatVariant(C.Structure):
@@ -324,6 +324,15 @@ class GdptKatLightResult(C.Structure):
     _fields_ = [("position", C.c_double * 3), ("normal", C.c_double * 3), ("pdf", C.c_double)]
 
 
+class GdptKatEnvmapQuery(C.Structure):
+    _fields_ = [("rnd", C.c_double * 2), ("dir", C.c_double * 3)]
+
+
+class GdptKatEnvmapResult(C.Structure):
+    _fields_ = [("sample_uv", C.c_double * 2), ("sample_dir", C.c_double * 3), ("sample_pdf", C.c_double), ("sample_emission", C.c_double * 3),
+                ("dir_uv", C.c_double * 2), ("dir_pdf", C.c_double), ("dir_emission", C.c_double * 3)]
+
+
 class GdptKatTraceVariant(C.Structure):
     _fields_ = [("name", C.c_char_p)] + [(k, C.c_int32) for k in ("ww", "wide", "flat", "spheres", "spec", "leaf_k", "lds_scene", "wavefront",
                                                                   "lds_stack_levels")]
@@ -340,4 +349,5 @@ class GdptKatTraceResult(C.Structure):
 
 KAT_STRUCTS = {"bsdf": (GdptKatBsdfQuery, GdptKatBsdfResult), "texture": (GdptKatTextureQuery, GdptKatTextureResult),
                "filter": (GdptKatFilterQuery, GdptKatFilterResult), "primary": (GdptKatPrimaryQuery, GdptKatPrimaryResult),
-               "shading": (GdptKatShadingQuery, GdptKatShadingResult), "light": (GdptKatLightQuery, GdptKatLightResult)}
+               "shading": (GdptKatShadingQuery, GdptKatShadingResult), "light": (GdptKatLightQuery, GdptKatLightResult),
+               "envmap": (GdptKatEnvmapQuery, GdptKatEnvmapResult)}

@@ -20,6 +20,7 @@ namespace {
 using gdpt::ck;
 constexpr int kKatBlock = 256;
 constexpr int kKatMaxCases = 1 << 22;
+constexpr int kKatEnvmapMaxCases = 1 << 20;
 
 __device__ __forceinline__ gd::D3 ld3(const double *p) { return gd::mk(p[0], p[1], p[2]); }
 __device__ __forceinline__ void st3(double *p, gd::D3 v) { p[0] = v.x; p[1] = v.y; p[2] = v.z; }
@@ -161,6 +162,29 @@ __global__ void __launch_bounds__(kKatBlock) kat_light_kernel(DevSceneView sv, i
     }
 }
 
+// ---- envmap: the environment-map code of render_path.h on the scene's own map (next-event estimation forms the pdf and the emission of
+// a sampled direction from its negative; the miss branches call envmap_emission(-ray.dir) and envmap_pdf(-dir_bsdf)) ----------------------
+__global__ void __launch_bounds__(kKatBlock) kat_envmap_kernel(DevSceneView sv, int n, const GdptKatEnvmapQuery *in, GdptKatEnvmapResult *out) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < n) {
+        const GdptKatEnvmapQuery q = in[i];
+        gd::D2 rnd; rnd.x = q.rnd[0]; rnd.y = q.rnd[1];
+        const gd::D3 dir = ld3(q.dir);
+        GdptKatEnvmapResult r;
+        const gd::D2 suv = gd::table2d_sample(sv, rnd);
+        r.sample_uv[0] = suv.x; r.sample_uv[1] = suv.y;
+        const gd::D3 sdir = gd::envmap_sample_dir(sv, rnd);
+        st3(r.sample_dir, sdir);
+        r.sample_pdf = gd::envmap_pdf(sv, -sdir);
+        st3(r.sample_emission, gd::envmap_emission(sv, -sdir));
+        const gd::D2 duv = gd::envmap_uv(gd::xform_vector16(sv.env_to_local, dir));
+        r.dir_uv[0] = duv.x; r.dir_uv[1] = duv.y;
+        r.dir_pdf = gd::envmap_pdf(sv, -dir);
+        st3(r.dir_emission, gd::envmap_emission(sv, -dir));
+        out[i] = r;
+    }
+}
+
 // ---- the tables of variants: one row each; the rows give the variants their names and, for bsdf, the triple to Python ----------
 dim3 kat_grid(int n) { return dim3((unsigned)((n + kKatBlock - 1) / kKatBlock)); }
 
@@ -198,7 +222,7 @@ int family_variants(const std::string &family, std::vector<GdptKatVariant> &rows
     rows.clear();
     if (family == "bsdf") { for (const BsdfVariant &b : kBsdfVariants) rows.push_back(b.row); return 0; }
     if (family == "primary") { rows.assign(kPrimaryVariants, kPrimaryVariants + 2); return 0; }
-    if (family == "texture" || family == "filter" || family == "shading" || family == "light") { rows.assign(kOneVariant, kOneVariant + 1); return 0; }
+    if (family == "texture" || family == "filter" || family == "shading" || family == "light" || family == "envmap") { rows.assign(kOneVariant, kOneVariant + 1); return 0; }
     if (family == "trace") {       // (the table itself: debug_kat_trace.hip)
         std::vector<GdptKatTraceVariant> t((size_t)std::max(0, gdpt_debug_kat_trace_variants(nullptr, 0)));
         if (gdpt_debug_kat_trace_variants(t.data(), (int)t.size()) != (int)t.size()) return 1;
@@ -255,7 +279,7 @@ int gdpt_debug_kat_variants(const char *family, GdptKatVariant *out, int capacit
     const int rc = gdpt::guarded([&]() {
         if (!family) throw std::runtime_error("gdpt_debug_kat_variants: null family");
         std::vector<GdptKatVariant> rows;
-        if (family_variants(family, rows)) throw std::runtime_error(std::string("gdpt_debug_kat_variants: unknown family '") + family + "' (bsdf, texture, filter, primary, shading, light, trace)");
+        if (family_variants(family, rows)) throw std::runtime_error(std::string("gdpt_debug_kat_variants: unknown family '") + family + "' (bsdf, texture, filter, primary, shading, light, envmap, trace)");
         if (out) {
             if (capacity < (int)rows.size()) throw std::runtime_error("gdpt_debug_kat_variants: capacity too small");
             for (size_t i = 0; i < rows.size(); i++) out[i] = rows[i];
@@ -345,6 +369,31 @@ int gdpt_debug_kat_light(const GdptScene *scene, int variant, int n, const GdptK
         }
         run_cases(scene, n, in, out, [](const DevSceneView &sv, int m, const GdptKatLightQuery *q, GdptKatLightResult *r, hipStream_t s) {
             hipLaunchKernelGGL(kat_light_kernel, kat_grid(m), dim3(kKatBlock), 0, s, sv, m, q, r);
+        });
+    });
+}
+
+int gdpt_debug_kat_envmap(const GdptScene *scene, int variant, int n, const GdptKatEnvmapQuery *in, GdptKatEnvmapResult *out) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_debug_kat_envmap";
+        check_common(who, scene, "envmap", variant, n, in, out);
+        if (n > kKatEnvmapMaxCases) throw std::runtime_error(who + ": n must be in [0, " + std::to_string(kKatEnvmapMaxCases) + "]");
+        const DevSceneView &v = scene->view;
+        if (!v.has_envmap || v.env_w < 1 || v.env_h < 1 || v.env_image_id < 0 || v.env_image_id >= v.num_images)
+            throw std::runtime_error(who + ": the scene has no environment map");
+        for (int i = 0; i < n; i++) {
+            const GdptKatEnvmapQuery &q = in[i];
+            for (double x : {q.rnd[0], q.rnd[1], q.dir[0], q.dir[1], q.dir[2]})
+                if (!std::isfinite(x)) throw std::runtime_error(who + ": case " + std::to_string(i) + ": a number that is not finite");
+            for (double x : q.rnd)
+                if (x < 0 || x > 1) throw std::runtime_error(who + ": case " + std::to_string(i) + ": a random number outside [0, 1]");
+            if (q.dir[0] == 0 && q.dir[1] == 0 && q.dir[2] == 0) throw std::runtime_error(who + ": case " + std::to_string(i) + ": dir is zero");
+            for (int k = 0; k < 3; k++)        // the local direction (xform_vector16): a NaN there would index the tables
+                if (!std::isfinite(v.env_to_local[4 * k] * q.dir[0] + v.env_to_local[4 * k + 1] * q.dir[1] + v.env_to_local[4 * k + 2] * q.dir[2]))
+                    throw std::runtime_error(who + ": case " + std::to_string(i) + ": a number that is not finite in the map's frame");
+        }
+        run_cases(scene, n, in, out, [](const DevSceneView &sv, int m, const GdptKatEnvmapQuery *q, GdptKatEnvmapResult *r, hipStream_t s) {
+            hipLaunchKernelGGL(kat_envmap_kernel, kat_grid(m), dim3(kKatBlock), 0, s, sv, m, q, r);
         });
     });
 }

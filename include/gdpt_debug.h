@@ -160,7 +160,7 @@ int gdpt_debug_prepare_scene(const struct GdptSceneDesc *desc, GdptPreparedInfo 
  *
  * gdpt_debug_kat_variants(family, out, capacity): the family's table of variants, one row each, in the order `variant` indexes; returns
  * their number (out == NULL: the number alone), -1 for an unknown family or a capacity too small. Families: "bsdf", "texture",
- * "filter", "primary", "shading", "light", "trace" (its rows carry the name alone: gdpt_debug_kat_trace_variants). The bsdf rows:
+ * "filter", "primary", "shading", "light", "envmap", "trace" (its rows carry the name alone: gdpt_debug_kat_trace_variants). The bsdf rows:
  *   - one per <ROUGH, TWOSIDED, MASK> triple of bsdf_sample / bsdf_eval / bsdf_pdf / bsdf_eval_pdf that a product kernel instantiates,
  *     the triple taken from the product's own constants (kAllMaterials, kSetGlass, the sets of render_phases_general_sets.h); `mask` bit
  *     t = material type t is in the kernel's set, `rough` / `twosided` = the RoughPlastic / RoughDielectric and the DisneyGlass /
@@ -173,7 +173,12 @@ int gdpt_debug_prepare_scene(const struct GdptSceneDesc *desc, GdptPreparedInfo 
  * bsdf results: [0] = at the direction bsdf_sample returned (zeros when sample_valid == 0), [1] = at dir_out2; f/pdf from the
  * separate bsdf_eval and bsdf_pdf, fused_f/fused_pdf from bsdf_eval_pdf. texture: tex3 / tex1 of texture `slot` of a material.
  * shading: shading_info_tri of global triangle `index` (need_uv as given) or shading_info_sphere of sphere `index`. light:
- * sample_point_on_light and pdf_point_on_light of that point, for area emitter `light_id`. */
+ * sample_point_on_light and pdf_point_on_light of that point, for area emitter `light_id` (the environment map's placeholder is refused).
+ * envmap: the environment-map code of render_path.h on the scene's own map, per case a pair of random numbers and a world direction
+ * `dir` towards the light. sample_uv = table2d_sample(rnd); sample_dir = envmap_sample_dir(rnd); sample_pdf = envmap_pdf(-sample_dir) and
+ * sample_emission = envmap_emission(-sample_dir), as next-event estimation forms them; dir_uv = envmap_uv of the local direction of `dir`;
+ * dir_pdf = envmap_pdf(-dir) and dir_emission = envmap_emission(-dir), as the miss branches call them. Refused on the host, before any
+ * launch: a scene without an environment map; a number that is not finite; a random number outside [0, 1]; a zero `dir`; n above 2^20. */
 typedef struct GdptKatVariant { const char *name; uint32_t mask; int32_t rough, twosided, inline_lambert, plain; } GdptKatVariant;
 typedef struct GdptKatVertex { double gn[3], fx[3], fy[3], fn[3], uv[2], uv_screen_size; } GdptKatVertex;   /* what the lobes read of gd::Vertex */
 typedef struct GdptKatBsdfQuery { int32_t material_id, pad; GdptKatVertex vertex; double dir_in[3], dir_out2[3], ruv[2], rw; } GdptKatBsdfQuery;
@@ -193,6 +198,11 @@ typedef struct GdptKatShadingQuery { int32_t is_sphere, index, need_uv, pad; dou
 typedef struct GdptKatShadingResult { double uv[2], fx[3], fy[3], fn[3], inv_uv_size; } GdptKatShadingResult;
 typedef struct GdptKatLightQuery { int32_t light_id, pad; double ref[3], uv[2], w; } GdptKatLightQuery;
 typedef struct GdptKatLightResult { double position[3], normal[3], pdf; } GdptKatLightResult;
+typedef struct GdptKatEnvmapQuery { double rnd[2], dir[3]; } GdptKatEnvmapQuery;
+typedef struct GdptKatEnvmapResult {
+    double sample_uv[2], sample_dir[3], sample_pdf, sample_emission[3];
+    double dir_uv[2], dir_pdf, dir_emission[3];
+} GdptKatEnvmapResult;
 int gdpt_debug_kat_variants(const char *family, GdptKatVariant *out, int capacity);
 int gdpt_debug_kat_bsdf(const struct GdptScene *scene, int variant, int n, const GdptKatBsdfQuery *in, GdptKatBsdfResult *out);
 int gdpt_debug_kat_texture(const struct GdptScene *scene, int variant, int n, const GdptKatTextureQuery *in, GdptKatTextureResult *out);
@@ -200,6 +210,7 @@ int gdpt_debug_kat_filter(const struct GdptScene *scene, int variant, int n, con
 int gdpt_debug_kat_primary(const struct GdptScene *scene, int variant, int n, const GdptKatPrimaryQuery *in, GdptKatPrimaryResult *out);
 int gdpt_debug_kat_shading(const struct GdptScene *scene, int variant, int n, const GdptKatShadingQuery *in, GdptKatShadingResult *out);
 int gdpt_debug_kat_light(const struct GdptScene *scene, int variant, int n, const GdptKatLightQuery *in, GdptKatLightResult *out);
+int gdpt_debug_kat_envmap(const struct GdptScene *scene, int variant, int n, const GdptKatEnvmapQuery *in, GdptKatEnvmapResult *out);
 /* ---- The BVH walks on arrays of rays (csrc/hip/debug_kat_trace.hip) -----------------------------------------------------------------
  * Family "trace": closest hit (device_trace.h: smallest fp32 t in [tnear, tfar), lowest primitive id on ties) or, with any_hit, whether
  * any primitive accepts the ray, by one of the walks the render kernels make. One thread per ray in 256-thread blocks, the lanes past n

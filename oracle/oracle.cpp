@@ -1763,6 +1763,36 @@ void oracle_table2d(const double *f, int width, int height, const double *rnd, i
     }
 }
 
+// ---- the environment map's own functions on arrays of cases (entry points only: the statics above as they are) ----
+int oracle_envmap_size(const OracleScene *s, int *width, int *height) {
+    if (!s->desc.has_envmap) return 0;
+    *width = s->env_table.width; *height = s->env_table.height;
+    return 1;
+}
+void oracle_envmap_tables(const OracleScene *s, double *cdf_rows, double *pdf_rows, double *cdf_marginals, double *pdf_marginals) {
+    const OracleScene::Table2D &t = s->env_table;
+    std::copy(t.cdf_rows.begin(), t.cdf_rows.end(), cdf_rows); std::copy(t.pdf_rows.begin(), t.pdf_rows.end(), pdf_rows);
+    std::copy(t.cdf_marginals.begin(), t.cdf_marginals.end(), cdf_marginals); std::copy(t.pdf_marginals.begin(), t.pdf_marginals.end(), pdf_marginals);
+}
+void oracle_envmap_table_sample(const OracleScene *s, int n, const double *rnd, double *uv) {
+    for (int i = 0; i < n; i++) { V2 r = table2d_sample(s->env_table, V2{rnd[2 * i], rnd[2 * i + 1]}); uv[2 * i] = r.x; uv[2 * i + 1] = r.y; }
+}
+void oracle_envmap_sample_dir(const OracleScene *s, int n, const double *rnd, double *dir) {
+    for (int i = 0; i < n; i++) { V3 d = envmap_sample_dir(*s, V2{rnd[2 * i], rnd[2 * i + 1]}); dir[3 * i] = d.x; dir[3 * i + 1] = d.y; dir[3 * i + 2] = d.z; }
+}
+void oracle_envmap_pdf(const OracleScene *s, int n, const double *normal, double *pdf) {
+    for (int i = 0; i < n; i++) pdf[i] = envmap_pdf(*s, V3{normal[3 * i], normal[3 * i + 1], normal[3 * i + 2]});
+}
+void oracle_envmap_emission(const OracleScene *s, int n, const double *view_dir, double *rgb) {
+    for (int i = 0; i < n; i++) { V3 e = envmap_emission(*s, V3{view_dir[3 * i], view_dir[3 * i + 1], view_dir[3 * i + 2]}); rgb[3 * i] = e.x; rgb[3 * i + 1] = e.y; rgb[3 * i + 2] = e.z; }
+}
+void oracle_envmap_dir_uv(const OracleScene *s, int n, const double *world_dir, double *uv) {
+    for (int i = 0; i < n; i++) {
+        V2 r = envmap_uv(xform_vector(s->desc.envmap.to_local, V3{world_dir[3 * i], world_dir[3 * i + 1], world_dir[3 * i + 2]}));
+        uv[2 * i] = r.x; uv[2 * i + 1] = r.y;
+    }
+}
+
 int oracle_path_render(const OracleScene *s, int spp, int rng_scheme, int row_begin, int row_end, int threads,
                        double *img, OracleStats *stats) {
     const OracleScene &sc = *s;

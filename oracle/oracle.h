@@ -99,6 +99,18 @@ void oracle_path_sample(const OracleScene *s, int x, int y, uint64_t *state, uin
  * Returns non-zero for scenes without any emitter. Environment maps: src/lights/envmap.inl. */
 /* TableDist2D (src/table_dist.cpp:40-150) built over f (row-major, height rows): sample(rnd) -> uv, pdf(uv). */
 void oracle_table2d(const double *f, int width, int height, const double *rnd, int n_rnd, double *uv_out, double *pdf_out, double *total);
+/* The environment map of a scene that has one (src/lights/envmap.inl), on arrays of n cases; entry points to the functions
+ * path_tracing calls, as they are. size: returns 0 for a scene without an environment map. tables: the scene's TableDist2D,
+ * h (w + 1), h w, h + 1 and h entries. table_sample: uv of sample(TableDist2D, rnd). sample_dir: the world direction of
+ * sample_point_on_light (its normal is -dir). pdf: pdf_point_on_light of a point whose normal is `normal`. emission: view_dir
+ * points away from the light. dir_uv: the (u, v) both of them look up for a world direction towards the light. */
+int oracle_envmap_size(const OracleScene *s, int *width, int *height);
+void oracle_envmap_tables(const OracleScene *s, double *cdf_rows, double *pdf_rows, double *cdf_marginals, double *pdf_marginals);
+void oracle_envmap_table_sample(const OracleScene *s, int n, const double *rnd, double *uv);
+void oracle_envmap_sample_dir(const OracleScene *s, int n, const double *rnd, double *dir);
+void oracle_envmap_pdf(const OracleScene *s, int n, const double *normal, double *pdf);
+void oracle_envmap_emission(const OracleScene *s, int n, const double *view_dir, double *rgb);
+void oracle_envmap_dir_uv(const OracleScene *s, int n, const double *world_dir, double *uv);
 /* GDPT_SHIFT_RECONNECT (sample-stream RNG only): restatement of csrc/hip/render_reconnect.hip; parity unpinned against the
  * reference (it has no such output), pinned by the mode's defining properties in tests/test_reconnect_shift.py. */
 int oracle_reconnect_render(const OracleScene *s, int spp, int row_begin, int row_end, int threads,

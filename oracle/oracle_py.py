@@ -92,6 +92,12 @@ def lib():
         L.oracle_path_render.restype = C.c_int
         L.oracle_path_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.POINTER(OracleStats)]
         L.oracle_table2d.argtypes = [dp, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp]
+        L.oracle_envmap_size.restype = C.c_int
+        L.oracle_envmap_size.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        L.oracle_envmap_tables.argtypes = [C.c_void_p, dp, dp, dp, dp]
+        for name in ("table_sample", "sample_dir", "pdf", "emission", "dir_uv"):
+            getattr(L, "oracle_envmap_" + name).argtypes = [C.c_void_p, C.c_int, dp, dp]
+            getattr(L, "oracle_envmap_" + name).restype = None
         L.oracle_assemble.argtypes = [C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
         L.oracle_poisson_dct.argtypes = [C.c_int, C.c_int, dp, dp, dp, C.c_double, dp]
         _LIB = L
@@ -237,7 +243,45 @@ def _path_methods():
             raise RuntimeError(f"oracle_reconnect_render failed ({rc})")
         return bufs, st
 
-    for f in (light_table, sample_point_on_shape, pdf_point_on_shape, occluded, path_sample, path_render, reconnect_render):
+    def envmap_size(self):
+        """(width, height) of the environment map's table, None for a scene without one."""
+        w, h = C.c_int(), C.c_int()
+        return (w.value, h.value) if lib().oracle_envmap_size(self.handle, C.byref(w), C.byref(h)) else None
+
+    def envmap_tables(self):
+        """The scene's TableDist2D: dict of cdf_rows (h, w + 1), pdf_rows (h, w), cdf_marginals (h + 1), pdf_marginals (h)."""
+        w, h = self.envmap_size()
+        t = {"cdf_rows": np.zeros((h, w + 1)), "pdf_rows": np.zeros((h, w)), "cdf_marginals": np.zeros(h + 1), "pdf_marginals": np.zeros(h)}
+        lib().oracle_envmap_tables(self.handle, *[_dp(t[k]) for k in ("cdf_rows", "pdf_rows", "cdf_marginals", "pdf_marginals")])
+        return t
+
+    def _envmap_cases(self, name, arg, width_in, width_out):
+        if self.envmap_size() is None:
+            raise RuntimeError("the scene has no environment map")
+        arg = np.ascontiguousarray(arg, dtype=np.float64).reshape(-1, width_in)
+        out = np.zeros((len(arg), width_out))
+        getattr(lib(), "oracle_envmap_" + name)(self.handle, len(arg), _dp(arg), _dp(out))
+        return out if width_out > 1 else out[:, 0]
+
+    def envmap_table_sample(self, rnd):
+        """uv of sample(TableDist2D, rnd) on the scene's table, for an n x 2 array."""
+        return self._envmap_cases("table_sample", rnd, 2, 2)
+
+    def envmap_sample_dir(self, rnd):
+        return self._envmap_cases("sample_dir", rnd, 2, 3)
+
+    def envmap_pdf(self, normal):
+        return self._envmap_cases("pdf", normal, 3, 1)
+
+    def envmap_emission(self, view_dir):
+        return self._envmap_cases("emission", view_dir, 3, 3)
+
+    def envmap_dir_uv(self, world_dir):
+        """The (u, v) that envmap_pdf and envmap_emission look up for world directions towards the light."""
+        return self._envmap_cases("dir_uv", world_dir, 3, 2)
+
+    for f in (light_table, sample_point_on_shape, pdf_point_on_shape, occluded, path_sample, path_render, reconnect_render,
+              envmap_size, envmap_tables, _envmap_cases, envmap_table_sample, envmap_sample_dir, envmap_pdf, envmap_emission, envmap_dir_uv):
         setattr(OracleScene, f.__name__, f)
 
 

@@ -50,7 +50,7 @@ def test_kat_struct_layouts_match_the_header(G, tmp_path):
     for family in G.KAT_FAMILIES:
         for s in G.KAT_STRUCTS[family]:
             structs[s.__name__] = s
-    assert len(structs) == 14
+    assert len(structs) == 16 and "envmap" in G.KAT_FAMILIES
     lines = []
     for name, s in structs.items():
         lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
@@ -71,6 +71,8 @@ def test_kat_struct_layouts_match_the_header(G, tmp_path):
                     base = base._type_
                 assert base in (C.c_double, C.c_int32, G.GdptKatVertex), (name, field)
     assert C.sizeof(G.GdptKatBsdfQuery) == 200 and C.sizeof(G.GdptKatBsdfResult) == 176 and C.sizeof(G.GdptKatVertex) == 120
+    assert C.sizeof(G.GdptKatEnvmapQuery) == 40 and C.sizeof(G.GdptKatEnvmapResult) == 120
+    assert hasattr(G.lib(), "gdpt_debug_kat_envmap") and [r["name"] for r in G.debug_knobs.kat_variants("envmap")] == ["product"]
     rows = G.debug_knobs.kat_variants("bsdf")
     names = [r["name"] for r in rows]
     assert len(set(names)) == len(names) and names[0] == "full" and rows[0]["mask"] == 0x1FF and rows[0]["rough"] and rows[0]["twosided"]
