@@ -2,6 +2,7 @@
 """Generates tests/golden/ref_kat.json from the reference's own code (development container only).
 
     make -C oracle ref && python oracle/gen_golden.py
+    make -C oracle ref_samples && python oracle/gen_golden.py samples      (tests/golden/ref_samples_*.npz, ref_fourier.npz)
 
 Runs oracle/_ref/ref_kat (built from /root/reference sources by oracle/Makefile) and stores its JSON.
 The spectra it integrates are read here from the scene XML and rounded through fp32 exactly as
@@ -139,8 +140,106 @@ def gen_images():
     print("wrote", dst, os.path.getsize(dst), "bytes")
 
 
+def write_npz(path, arrays):
+    """np.savez_compressed with fixed member dates, so that equal arrays give equal bytes."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.ascontiguousarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def gen_samples(only=None):
+    """tests/golden/ref_samples_<case>.npz and ref_fourier.npz from oracle/_ref/ref_samples: the reference's own
+    grad_path_tracing, path_tracing and fourierSolve (see oracle/ref_samples.cpp) on the cases of oracle/ref_cases.py."""
+    exe = os.path.join(HERE, "_ref", "ref_samples")
+    if not os.path.exists(exe):
+        sys.exit("oracle/_ref/ref_samples is missing: run `make -C oracle ref_samples` in the container that has /root/reference")
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    sys.path.insert(0, HERE)
+    import ref_cases as RC
+    from helpers import scene_variant
+    from test_poisson_oracle import lcg_fields
+    import shutil
+    golden = os.path.join(ROOT, "tests", "golden")
+    # a fixed folder: the reference reads past the end of some mip levels (below), and what lies there depends on the
+    # lengths of the path names it has allocated; with equal paths two runs give equal bytes
+    tmp = os.path.join(HERE, "_ref", "tmp")
+    shutil.rmtree(tmp, ignore_errors=True)
+    os.makedirs(tmp)
+    quiet = dict(stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+
+    def run_twice(args, out, load):
+        """Runs the generator twice: with two fill patterns for fresh and freed heap memory (glibc's MALLOC_PERTURB_) and two
+        values in the memory behind every allocation (GDPT_REF_PAD, oracle/ref_samples.cpp). Where the two results differ,
+        the reference's answer is no function of its source: make_mipmap (src/mipmap.h:33-43) halves a one-texel-high level
+        of a wider image to max(0, 1) = 1 rows and reads row 1 of it, past the end of the level's buffer. Returns both."""
+        res = []
+        for fill, pad in (("85", "0"), ("170", "1e-6")):
+            subprocess.check_call([exe] + args + [out], env=dict(os.environ, MALLOC_PERTURB_=fill, GDPT_REF_PAD=pad), **quiet)
+            res.append(load(out))
+        return res[0], res[1]
+    for case in RC.CASES:
+        if only and case.name not in only:
+            continue
+        grad = case.integrator == "gradpath"
+        arrays = {}
+        # (a) scattered samples on the scene's own film
+        xml = RC.variant_xml(scene_variant, tmp, case)
+        txt = os.path.join(tmp, case.name + ".txt")
+        rows, rows2 = run_twice(["samples", xml, str(case.count), str(case.stream_offset)], txt, lambda p: [line.split() for line in open(p)])
+        assert len(rows) == case.count
+        arrays["undefined"] = np.array([a != b for a, b in zip(rows, rows2)])
+        arrays["xy_stream"] = np.array([[int(v) for v in r[:3]] for r in rows], dtype=np.uint64)
+        arrays["state"] = np.array([int(r[-1]) for r in rows], dtype=np.uint64)
+        arrays["margin"] = np.array([float(r[-2]) for r in rows])
+        arrays["margin_kind"] = np.array([int(r[-3]) for r in rows], dtype=np.int64)     # rtc_standin.cpp's KIND_* of the minimum
+        arrays["record"] = np.array([[float(v) for v in r[3:-3]] for r in rows])
+        assert arrays["record"].shape[1] == (23 if grad else 3)
+        # (b) the small film in the reference's own tile order
+        xml = RC.variant_xml(scene_variant, tmp, case, film=RC.FILM)
+        raw = os.path.join(tmp, case.name + ".bin")
+        data, data2 = run_twice(["film", xml, str(case.film_spp)], raw, lambda p: np.fromfile(p, dtype=np.float64))
+        w, h = RC.FILM
+        nbuf = 5 if grad else 1
+        assert data.size == nbuf * w * h * 3 + w * h
+        arrays["film"] = data[: nbuf * w * h * 3].reshape(nbuf, h, w, 3)
+        arrays["film_margin"] = data[nbuf * w * h * 3:].reshape(h, w)
+        film2 = data2[: nbuf * w * h * 3].reshape(nbuf, h, w, 3)
+        arrays["film_undefined"] = ~((arrays["film"] == film2) | (np.isnan(arrays["film"]) & np.isnan(film2))).all(axis=(0, 3))
+        dst = os.path.join(golden, f"ref_samples_{case.name}.npz")
+        write_npz(dst, arrays)
+        low = ((arrays["margin"] < RC.MARGIN_THRESHOLD) | arrays["undefined"]).mean()
+        low_px = ((arrays["film_margin"] < RC.MARGIN_THRESHOLD) | arrays["film_undefined"]).mean()
+        print(f"wrote {dst} {os.path.getsize(dst)} bytes; margin < {RC.MARGIN_THRESHOLD:g} or undefined: {low:.4f} of samples "
+              f"({int(arrays['undefined'].sum())} undefined), {low_px:.4f} of film pixels ({int(arrays['film_undefined'].sum())} undefined)")
+        assert low <= RC.MARGIN_CAP and low_px <= RC.MARGIN_CAP, "change this case's stream_offset (oracle/ref_cases.py), not the cap"
+        assert os.path.getsize(dst) < 694 * 1024
+    if only and "fourier" not in only:
+        shutil.rmtree(tmp, ignore_errors=True)
+        return
+    arrays = {}
+    for (w, h, alpha) in RC.FOURIER_CASES:
+        c, gx, gy = lcg_fields(w, h)
+        src, raw = os.path.join(tmp, "fourier_in.bin"), os.path.join(tmp, "fourier_out.bin")
+        np.concatenate([c.ravel(), gx.ravel(), gy.ravel()]).tofile(src)
+        subprocess.check_call([exe, "fourier", str(w), str(h), repr(float(alpha)), src, raw], **quiet)
+        arrays[RC.fourier_key(w, h, alpha)] = np.fromfile(raw, dtype=np.float64).reshape(h, w, 3)
+    dst = os.path.join(golden, "ref_fourier.npz")
+    write_npz(dst, arrays)
+    print("wrote", dst, os.path.getsize(dst), "bytes")
+    shutil.rmtree(tmp, ignore_errors=True)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "images":
         gen_images()
+    elif len(sys.argv) > 1 and sys.argv[1] == "samples":
+        gen_samples(set(sys.argv[2:]))
     else:
         main()

@@ -16,6 +16,7 @@
 //     src/path_tracing.h:1007-1010, and cross-checked against the integer statistics the survey recorded
 //     from a shim-linked reference run.
 #include "oracle.h"
+#include "brute_hit.h"
 
 #include <algorithm>
 #include <atomic>
@@ -110,10 +111,7 @@ struct Vertex { // PathVertex, src/intersection.h:15-37
     Real t = 0;
 };
 
-struct Tri {            // fp32 traversal copy (src/shapes/triangle_mesh.inl:11-14) + ids
-    float v0[3], e1[3], e2[3];
-    int shape_id, prim_id;
-};
+using brute::Tri;      // fp32 traversal copy (src/shapes/triangle_mesh.inl:11-14) + ids, brute_hit.h
 struct Mip { int channels = 0; std::vector<int> w, h; std::vector<std::vector<double>> lv; };
 
 struct BNode { float mn[3], mx[3]; int left, right, first, count; };
@@ -143,29 +141,8 @@ struct OracleScene {
 
 namespace {
 
-// ---- fp32 ray/triangle (normative definition shared with the HIP kernel, bit for bit) -----------
-// Moller-Trumbore, two-sided, every product and sum rounded separately (no FMA), left-to-right sums.
-inline bool tri_hit(const float o[3], const float d[3], float tnear, float tfar, const Tri &tr, float *t_out, float *u_out, float *v_out) {
-    const float *e1 = tr.e1, *e2 = tr.e2;
-    float px = d[1] * e2[2] - d[2] * e2[1];
-    float py = d[2] * e2[0] - d[0] * e2[2];
-    float pz = d[0] * e2[1] - d[1] * e2[0];
-    float det = e1[0] * px + e1[1] * py + e1[2] * pz;
-    if (!(det != 0.0f)) return false;
-    float inv = 1.0f / det;
-    float sx = o[0] - tr.v0[0], sy = o[1] - tr.v0[1], sz = o[2] - tr.v0[2];
-    float u = (sx * px + sy * py + sz * pz) * inv;
-    if (!(u >= 0.0f && u <= 1.0f)) return false;
-    float qx = sy * e1[2] - sz * e1[1];
-    float qy = sz * e1[0] - sx * e1[2];
-    float qz = sx * e1[1] - sy * e1[0];
-    float v = (d[0] * qx + d[1] * qy + d[2] * qz) * inv;
-    if (!(v >= 0.0f && u + v <= 1.0f)) return false;
-    float t = (e2[0] * qx + e2[1] * qy + e2[2] * qz) * inv;
-    if (!(t >= tnear && t < tfar)) return false;
-    *t_out = t; *u_out = u; *v_out = v;
-    return true;
-}
+// ---- fp32 ray/triangle: the normative definition lives in brute_hit.h, shared with rtc_standin.cpp ----
+using brute::tri_hit;
 
 // Sphere primitive: fp64 quadratic on the fp32 ray, src/shapes/sphere.inl:15-106.
 inline bool solve_quadratic(Real a, Real b, Real c, Real *t0, Real *t1) {
@@ -209,20 +186,16 @@ inline void test_prim(const OracleScene &sc, int gid, const float o[3], const fl
         float t, u, v;
         // candidates beyond the current best are irrelevant; equal t is kept for the id tie-break
         if (!tri_hit(o, d, tnear, tfar, sc.tris[gid], &t, &u, &v)) return;
-        if (best.valid && !(t < best.t || (t == best.t && gid < best.gid))) return;
-        const Tri &tr = sc.tris[gid];
+        if (!brute::replaces(t, gid, best.valid, best.t, best.gid)) return;
         best.valid = true; best.t = t; best.u = u; best.v = v; best.gid = gid;
-        // Ng = e1 x e2 in fp32 (Embree reports an unnormalised fp32 Ng), one rounding per op
-        best.ng[0] = tr.e1[1] * tr.e2[2] - tr.e1[2] * tr.e2[1];
-        best.ng[1] = tr.e1[2] * tr.e2[0] - tr.e1[0] * tr.e2[2];
-        best.ng[2] = tr.e1[0] * tr.e2[1] - tr.e1[1] * tr.e2[0];
+        brute::tri_ng(sc.tris[gid], best.ng);
     } else {
         const GdptShape &sp = sc.desc.shapes[sc.sphere_shapes[gid - ntri]];
         SphereHit h;
         // the callback sees the ray's current tfar (src/shapes/sphere.inl:55-57); using the best hit so far
         // or the original tfar selects the same minimum
         if (!sphere_hit(o, d, tnear, tfar, sp, &h)) return;
-        if (best.valid && !(h.t < best.t || (h.t == best.t && gid < best.gid))) return;
+        if (!brute::replaces(h.t, gid, best.valid, best.t, best.gid)) return;
         best.valid = true; best.t = h.t; best.u = h.u; best.v = h.v; best.gid = gid;
         best.ng[0] = h.ng[0]; best.ng[1] = h.ng[1]; best.ng[2] = h.ng[2];
     }
@@ -307,8 +280,9 @@ Mip make_mip(const GdptImage &im) { // src/mipmap.h:27-48
         int nw = std::max(pw / 2, 1), nh = std::max(ph / 2, 1);
         const std::vector<double> &prev = m.lv.back();
         std::vector<double> next((size_t)nw * nh * im.channels);
-        // note: like the reference, reads (2x+1, 2y+1) without clamping; sizes that are not powers of two
-        // with an odd dimension of 1 would read out of range there — guard by clamping (never hit by the scenes)
+        // the reference reads (2x+1, 2y+1) without clamping: a level one texel high (or wide) whose other dimension still halves is
+        // read one row past its end there (src/mipmap.h:33-43), heap-dependent texels — clamped here (sponza's 155x23
+        // texture reaches it from level 5 on)
         auto P = [&](int x, int y, int c) { x = std::min(x, pw - 1); y = std::min(y, ph - 1); return prev[((size_t)y * pw + x) * im.channels + c]; };
         for (int y = 0; y < nh; y++) for (int x = 0; x < nw; x++) for (int c = 0; c < im.channels; c++)
             next[((size_t)y * nw + x) * im.channels + c] =
@@ -1469,11 +1443,9 @@ OracleScene *oracle_scene_create(const GdptSceneDesc *desc, int use_bvh) {
         const GdptShape &sh = desc->shapes[s];
         if (sh.type == GDPT_SHAPE_TRIMESH) {
             for (int t = 0; t < sh.num_triangles; t++) {
-                Tri tr; tr.shape_id = s; tr.prim_id = t;
                 float v[3][3];
                 for (int i = 0; i < 3; i++) for (int k = 0; k < 3; k++) v[i][k] = (float)sh.positions[3 * sh.indices[3 * t + i] + k];
-                for (int k = 0; k < 3; k++) { tr.v0[k] = v[0][k]; tr.e1[k] = v[1][k] - v[0][k]; tr.e2[k] = v[2][k] - v[0][k]; }
-                sc->tris.push_back(tr);
+                sc->tris.push_back(brute::make_tri(v[0], v[1], v[2], s, t));
             }
             // Embree's scene bounds cover the vertex buffer (fp32)
             for (int i = 0; i < sh.num_vertices; i++) for (int k = 0; k < 3; k++) {

@@ -17,9 +17,9 @@ if ORACLE_DIR not in sys.path:
 SCENES = os.path.join(ROOT, "scenes")
 
 
-def scene_variant(tmp_dir, scene_rel, width=None, height=None, integrator=None, max_depth=None, spp=None):
+def scene_variant(tmp_dir, scene_rel, width=None, height=None, integrator=None, max_depth=None, spp=None, rr_depth=None, tag="variant"):
     """Copies the scene's folder tree (XML + meshes; sibling folders it references) to tmp_dir and edits
-    film size / integrator type / maxDepth / sampleCount. Returns the path of the edited XML."""
+    film size / integrator type / maxDepth / rrDepth / sampleCount. Returns the path of the edited XML, <scene>_<tag>.xml."""
     src_dir = os.path.dirname(os.path.join(SCENES, scene_rel))
     dst_root = os.path.join(str(tmp_dir), "scenes")
     if not os.path.exists(dst_root):
@@ -34,9 +34,15 @@ def scene_variant(tmp_dir, scene_rel, width=None, height=None, integrator=None, 
         text = re.sub(r'(<integrator type=")\w+(")', r"\g<1>%s\2" % integrator, text)
     if max_depth is not None:
         text = re.sub(r'(<integer name="maxDepth" value=")-?\d+(")', r"\g<1>%d\2" % max_depth, text)
+    if rr_depth is not None:
+        if 'name="rrDepth"' in text:
+            text = re.sub(r'(<integer name="rrDepth" value=")-?\d+(")', r"\g<1>%d\2" % rr_depth, text)
+        else:       # next to the first (the live) integrator's maxDepth
+            text, n = re.subn(r'(<integer name="maxDepth" value="-?\d+"\s*/>)', r'\1<integer name="rrDepth" value="%d"/>' % rr_depth, text, count=1)
+            assert n == 1, "no maxDepth to put rrDepth next to"
     if spp is not None:
         text = re.sub(r'(<integer name="sampleCount" value=")\d+(")', r"\g<1>%d\2" % spp, text)
-    out = dst.replace(".xml", "_variant.xml")
+    out = dst.replace(".xml", "_%s.xml" % tag)
     with open(out, "w") as f:
         f.write(text)
     return out
