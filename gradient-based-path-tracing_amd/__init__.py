@@ -124,6 +124,17 @@ def lib():
         L.gdpt_denoise_atrous_device.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, atp, ngp, ndp, vp, vp, vp, nls]
         L.gdpt_denoise_atrous.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, atp, ngp, ndp, vp, vp, nls]
         L.gdpt_progressive_denoise_atrous.argtypes = [vp, atp, ngp, ndp, C.c_int, C.c_int, vp, vp, vp, vp, nls]
+        camp, tpp, tsp = C.POINTER(defs.GdptCamera), C.POINTER(defs.GdptTemporalParams), C.POINTER(defs.GdptTemporalStats)
+        L.gdpt_scene_set_camera.argtypes = [vp, camp]
+        L.gdpt_temporal_default_params.argtypes = [tpp]
+        L.gdpt_temporal_default_params.restype = None
+        L.gdpt_temporal_create.argtypes = [C.c_int, C.c_int, C.c_int, vp, C.POINTER(vp)]
+        L.gdpt_temporal_free.argtypes = [vp]
+        L.gdpt_temporal_free.restype = None
+        L.gdpt_temporal_reset.argtypes = [vp]
+        L.gdpt_temporal_world_to_sample.argtypes = [camp, dp]
+        L.gdpt_temporal_push_device.argtypes = [vp, camp, vp, vp, vp, tpp, vp, vp, vp, tsp]
+        L.gdpt_temporal_push.argtypes = [vp, camp, vp, vp, vp, tpp, vp, vp, vp, tsp]
         vsp, vss = C.POINTER(defs.GdptVarSmoothParams), C.POINTER(defs.GdptVarSmoothStats)
         L.gdpt_var_smooth_default_params.argtypes = [vsp]
         L.gdpt_var_smooth_default_params.restype = None
@@ -378,6 +389,12 @@ class Scene:
                                                  C.c_void_p(int(mean_ptr)) if mean_ptr else None, C.c_void_p(int(var_ptr)) if var_ptr else None,
                                                  C.c_void_p(int(stream) if stream else 0), C.byref(st) if st is not None else None))
         return st
+
+    def set_camera(self, camera):
+        """A new camera on the uploaded scene (gdpt_scene_set_camera): a GdptCamera with the uploaded film and pixel filter, whose
+        position stays inside the extent the scene was uploaded with. Renders enqueued before the call keep the old camera; every
+        later render returns the bits of a fresh upload with this camera. The description (`self.desc`) is not changed."""
+        _check(lib().gdpt_scene_set_camera(self.handle, C.byref(camera) if camera is not None else None))
 
     def tile_row_costs(self, spp=1):
         """Rays of a pilot render of every 16-pixel tile row (gdpt_tile_row_costs): what sharding.bands_weighted balances by."""
@@ -1377,6 +1394,129 @@ def denoise_atrous_device(width, height, img_ptr, var_ptr, feat_ptr, feat_var_pt
                                             C.byref(demod) if demod is not None else None, opt(out_ptr), opt(var_out_ptr), opt(stream),
                                             C.byref(st) if stats else None))
     return st
+
+
+def temporal_params(tau_z=None, tau_n=None, s_min=None, max_history=None):
+    """GdptTemporalParams (include/gdpt.h): the library's defaults (gdpt_temporal_default_params: tau_z 0.05, tau_n 0.9, s_min 1e-3,
+    max_history 32) with the keywords given in their places, taken literally."""
+    p = defs.GdptTemporalParams()
+    lib().gdpt_temporal_default_params(C.byref(p))
+    if tau_z is not None:
+        p.tau_z = float(tau_z)
+    if tau_n is not None:
+        p.tau_n = float(tau_n)
+    if s_min is not None:
+        p.s_min = float(s_min)
+    if max_history is not None:
+        p.max_history = int(max_history)
+    return p
+
+
+def temporal_world_to_sample(camera):
+    """M(camera) of the temporal definition (gdpt_temporal_world_to_sample): the 4x4 float64 inverse(sample_to_cam)
+    inverse(cam_to_world) as the library computes it."""
+    M = np.empty((4, 4), dtype=np.float64)
+    _check(lib().gdpt_temporal_world_to_sample(C.byref(camera) if camera is not None else None, _dp(M)))
+    return M
+
+
+def orbit_camera(camera, centre, degrees):
+    """A copy of the GdptCamera `camera` whose cam_to_world is turned by `degrees` about the world's vertical (y) axis through the point
+    `centre`: T(centre) R_y(degrees) T(-centre) cam_to_world, the camera of frame f of `lajolla --frames N --orbit DEG` at f DEG."""
+    a = np.radians(float(degrees))
+    cs, sn = np.cos(a), np.sin(a)
+    c = [float(x) for x in centre]
+    R = np.array([[cs, 0, sn, c[0] - cs * c[0] - sn * c[2]], [0, 1, 0, 0], [-sn, 0, cs, c[2] + sn * c[0] - cs * c[2]], [0, 0, 0, 1]])
+    out = defs.GdptCamera.from_buffer_copy(camera)
+    m = R @ np.array(list(camera.cam_to_world), dtype=np.float64).reshape(4, 4)
+    for i in range(16):
+        out.cam_to_world[i] = float(m.flat[i])
+    return out
+
+
+class Temporal:
+    """Temporal reprojection of an accumulated mean and its variance across a camera move (include/gdpt.h, gdpt_temporal_*): a handle
+    bound to (width, height, device, stream) that owns the history. `stream`: a hipStream_t address carrying the handle's work."""
+
+    def __init__(self, width, height, device=0, stream=None):
+        self.width, self.height = int(width), int(height)
+        h = C.c_void_p()
+        _check(lib().gdpt_temporal_create(self.width, self.height, int(device), C.c_void_p(int(stream) if stream else 0), C.byref(h)))
+        self.handle = h
+
+    def push(self, camera, img, var, feat, length=True, params=None, **kw):
+        """One frame into the history (gdpt_temporal_push). `img`, `var`: HxWx3 float64, the frame's mean and variance of the mean;
+        `feat`: the (8, H, W) float64 planes of a feature render of the frame; `params`: a GdptTemporalParams taken as it is (else the
+        keywords of temporal_params). Returns (out, var_out, HxW history length N' or None, GdptTemporalStats)."""
+        shape = (self.height, self.width, 3)
+        a = np.ascontiguousarray(img, dtype=np.float64)
+        v = np.ascontiguousarray(var, dtype=np.float64)
+        f = np.ascontiguousarray(feat, dtype=np.float64)
+        if a.shape != shape or v.shape != shape or f.shape != (defs.FEATURE_CHANNELS, self.height, self.width):
+            raise GdptError("Temporal.push: img and var must be HxWx3 and feat (8, H, W) arrays of the handle's film")
+        out, var_out = np.empty(shape, dtype=np.float64), np.empty(shape, dtype=np.float64)
+        n = np.empty(shape[:2], dtype=np.float64) if length else None
+        p, st = params if params is not None else temporal_params(**kw), defs.GdptTemporalStats()
+        _check(lib().gdpt_temporal_push(self.handle, C.byref(camera), C.c_void_p(a.ctypes.data), C.c_void_p(v.ctypes.data),
+                                        C.c_void_p(f.ctypes.data), C.byref(p), C.c_void_p(out.ctypes.data), C.c_void_p(var_out.ctypes.data),
+                                        C.c_void_p(n.ctypes.data) if n is not None else None, C.byref(st)))
+        return out, var_out, n, st
+
+    def push_device(self, camera, img_ptr, var_ptr, feat_ptr, out_ptr, var_out_ptr, len_ptr=None, stats=True, params=None, **kw):
+        """push() on device addresses (gdpt_temporal_push_device), enqueued on the handle's stream; enqueue-only with `stats` False.
+        Returns the GdptTemporalStats or None."""
+        p = params if params is not None else temporal_params(**kw)
+        st = defs.GdptTemporalStats() if stats else None
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        _check(lib().gdpt_temporal_push_device(self.handle, C.byref(camera) if camera is not None else None, opt(img_ptr), opt(var_ptr),
+                                               opt(feat_ptr), C.byref(p), opt(out_ptr), opt(var_out_ptr), opt(len_ptr),
+                                               C.byref(st) if stats else None))
+        return st
+
+    def frame(self, scene, camera, frame_index, frames, spp, pass_spp, path=True, atrous=None, feature_spp=None, params=None, **kw):
+        """One frame of a moving camera, from pieces that exist: scene.set_camera(camera); a slice session over the sample window
+        [frame_index spp, (frame_index + 1) spp) of frames spp streams, so that frames never repeat samples, in passes of `pass_spp`
+        (at least two, so that a variance exists); its mean and variance (the primal's, for GradPath: `path` False); the features on
+        the same window at `feature_spp` (None: spp) samples; push(). `atrous`: None, or a dict of atrous_params keywords: then
+        denoise_atrous on (out, var_out) under the frame's features with the default guide. The history keeps the unfiltered
+        accumulation. Returns a dict: out, var_out, length, stats, mean, var, feat, feat_var, and with `atrous` denoised,
+        denoised_var, atrous_stats."""
+        spp, pass_spp = int(spp), int(pass_spp)
+        if pass_spp < 1 or spp < 2 * pass_spp:
+            raise GdptError("Temporal.frame: spp must hold at least two passes of pass_spp")
+        scene.set_camera(camera)
+        first, block = int(frame_index) * spp, int(frames) * spp
+        session = Progressive(scene, block, path=path, slice=(first, spp))
+        try:
+            done = 0
+            while done < spp:
+                n = min(pass_spp, spp - done)
+                session.add_pass(n)
+                done += n
+            means, vars_, _ = session.read()
+        finally:
+            session.close()
+        feat, feat_var = scene.features(int(feature_spp) if feature_spp else spp, window=(block, first))
+        out, var_out, length, st = self.push(camera, means["img"], vars_["img"], feat, params=params, **kw)
+        r = dict(out=out, var_out=var_out, length=length, stats=st, mean=means["img"], var=vars_["img"], feat=feat, feat_var=feat_var)
+        if atrous is not None:
+            r["denoised"], r["denoised_var"], r["atrous_stats"] = denoise_atrous(out, var_out, feat, feat_var, guide=nlm_guide(), **atrous)
+        return r
+
+    def reset(self):
+        """The next push is a first push (gdpt_temporal_reset)."""
+        _check(lib().gdpt_temporal_reset(self.handle))
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().gdpt_temporal_free(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def var_smooth_params(radius=None):

@@ -178,6 +178,15 @@ class GdptAtrousParams(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class GdptTemporalParams(C.Structure):
+    _fields_ = [("tau_z", C.c_double), ("tau_n", C.c_double), ("s_min", C.c_double), ("max_history", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class GdptTemporalStats(C.Structure):
+    _fields_ = [("pixels_left_out", C.c_uint64), ("pixels_background", C.c_uint64), ("pixels_reset", C.c_uint64),
+                ("sum_history", C.c_double), ("push_ms", C.c_double)]
+
+
 VAR_SMOOTH_MAX_RADIUS = 4
 DENOISE_PLAIN, DENOISE_GUIDED, DENOISE_DEMOD = 0, 1, 2
 

@@ -554,6 +554,28 @@ void gdpt_scene_free(GdptScene *scene) {
     delete scene;
 }
 
+int gdpt_scene_set_camera(GdptScene *scene, const GdptCamera *camera) {
+    return gdpt::guarded([&]() {
+        const std::string who = "gdpt_scene_set_camera";
+        if (!scene) throw std::runtime_error(who + ": scene is null");
+        if (!camera) throw std::runtime_error(who + ": camera is null");
+        const DevCamera &old = scene->view.cam;
+        if (camera->width != old.width) throw std::runtime_error(who + ": width must stay as uploaded");
+        if (camera->height != old.height) throw std::runtime_error(who + ": height must stay as uploaded");
+        if (camera->filter_type != old.filter_type) throw std::runtime_error(who + ": filter_type must stay as uploaded");
+        if (!(camera->filter_param == old.filter_param)) throw std::runtime_error(who + ": filter_param must stay as uploaded");
+        for (int i = 0; i < 16; i++) {
+            if (!std::isfinite(camera->sample_to_cam[i])) throw std::runtime_error(who + ": sample_to_cam has a non-finite entry");
+            if (!std::isfinite(camera->cam_to_world[i])) throw std::runtime_error(who + ": cam_to_world has a non-finite entry");
+        }
+        // the tree is not rebuilt: its boxes keep the padding of the upload, which covers origins up to this extent (host/scene_prepare.cpp)
+        if (!(gdpt::camera_extent(*camera) <= scene->traits.pad_extent))
+            throw std::runtime_error(who + ": cam_to_world puts the camera outside the extent the scene was uploaded with");
+        // (launches in flight hold their own copy of the view: it is a kernel argument)
+        gdpt::fill_camera(*camera, &scene->view.cam);
+    });
+}
+
 int gdpt_scene_info(const GdptScene *scene, int32_t *num_nodes, int32_t *num_tris, int32_t *num_spheres, int32_t *bvh_depth) {
     return gdpt::guarded([&]() {
         if (!scene) throw std::runtime_error("null scene handle");

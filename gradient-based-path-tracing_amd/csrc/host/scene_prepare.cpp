@@ -143,10 +143,9 @@ void build_tree(const GdptCamera &cam, const Flat &f, const PrepareOptions &opt,
         float ext = 0.f;
         for (int k = 0; k < 3; k++) if (ub[k] >= lb[k]) ext = std::max(ext, std::max(std::fabs(ub[k]), std::fabs(lb[k])));
         for (auto &sp : spheres) for (int k = 0; k < 3; k++) ext = std::max(ext, (float)(std::fabs(sp.center[k]) + sp.radius));
-        {   // ray origins: surface points (inside the bounds) and the camera position, xform_point(cam_to_world, 0)
-            const double *m = cam.cam_to_world;
-            for (int k = 0; k < 3; k++) ext = std::max(ext, (float)std::fabs(m[4 * k + 3] / m[15]) * 1.0000002f);
-        }
+        // ray origins: surface points (inside the bounds) and the camera position, xform_point(cam_to_world, 0)
+        ext = std::max(ext, camera_extent(cam));
+        tr.pad_extent = ext;
         const float pad = ext * 1e-6f + 1e-30f;
         for (auto &n : bvh.nodes)
             for (int k = 0; k < 3; k++) {
@@ -263,16 +262,7 @@ double fill_view_and_traits(const GdptSceneDesc *desc, const Flat &f, PreparedSc
     const float *lb = f.lb, *ub = f.ub;
     SceneTraits &tr = ps->traits;
     DevSceneView &v = ps->view;
-    std::memcpy(v.cam.sample_to_cam, cam.sample_to_cam, sizeof(v.cam.sample_to_cam));
-    std::memcpy(v.cam.cam_to_world, cam.cam_to_world, sizeof(v.cam.cam_to_world));
-    {   // xform_point(cam_to_world, (0,0,0)), src/camera.cpp:42
-        const double *m = cam.cam_to_world;
-        double inv_w = 1.0 / m[15];
-        v.cam.org[0] = m[3] * inv_w; v.cam.org[1] = m[7] * inv_w; v.cam.org[2] = m[11] * inv_w;
-    }
-    v.cam.width = cam.width; v.cam.height = cam.height; v.cam.filter_type = cam.filter_type; v.cam.filter_param = cam.filter_param;
-    v.cam.pow2_film = ((cam.width & (cam.width - 1)) == 0 && (cam.height & (cam.height - 1)) == 0) ? 1 : 0;
-    v.cam.inv_width = 1.0 / (double)cam.width; v.cam.inv_height = 1.0 / (double)cam.height;
+    fill_camera(cam, &v.cam);
     v.num_nodes = (int)ps->nodes.size(); v.num_nodes4 = (int)ps->nodes4.size(); v.num_nodes8 = (int)ps->nodes8.size(); v.num_prims = (int)ps->prims.size();
     v.num_tris = (int)ps->tris.size(); v.num_spheres = (int)ps->spheres.size();
     v.num_materials = desc->num_materials; v.num_lights = desc->num_lights; v.num_images = desc->num_images;
@@ -366,6 +356,27 @@ void build_envmap(const GdptSceneDesc *desc, double radius, std::vector<double> 
 }
 
 } // namespace
+
+void fill_camera(const GdptCamera &cam, DevCamera *out) {
+    DevCamera &c = *out;
+    std::memcpy(c.sample_to_cam, cam.sample_to_cam, sizeof(c.sample_to_cam));
+    std::memcpy(c.cam_to_world, cam.cam_to_world, sizeof(c.cam_to_world));
+    {   // xform_point(cam_to_world, (0,0,0)), src/camera.cpp:42
+        const double *m = cam.cam_to_world;
+        double inv_w = 1.0 / m[15];
+        c.org[0] = m[3] * inv_w; c.org[1] = m[7] * inv_w; c.org[2] = m[11] * inv_w;
+    }
+    c.width = cam.width; c.height = cam.height; c.filter_type = cam.filter_type; c.filter_param = cam.filter_param;
+    c.pow2_film = ((cam.width & (cam.width - 1)) == 0 && (cam.height & (cam.height - 1)) == 0) ? 1 : 0;
+    c.inv_width = 1.0 / (double)cam.width; c.inv_height = 1.0 / (double)cam.height;
+}
+
+float camera_extent(const GdptCamera &cam) {
+    const double *m = cam.cam_to_world;
+    float ext = 0.f;
+    for (int k = 0; k < 3; k++) ext = std::max(ext, (float)std::fabs(m[4 * k + 3] / m[15]) * 1.0000002f);
+    return ext;
+}
 
 PreparedScene prepare_scene(const GdptSceneDesc &desc, const PrepareOptions &opt) {
     PreparedScene ps;

@@ -22,6 +22,7 @@ struct SceneTraits {
     unsigned material_mask = 0;    // bit t = a material of type t is present
     int plan_take_pct = 0;         // work-item plan: share of the unassigned samples a chunk takes (0 = default 55; 40 where a refractive lobe is present)
     float bounds[6] = {0, 0, 0, 0, 0, 0};   // fp32 scene bounds (min xyz, max xyz), as get_intersection_epsilon sees them
+    float pad_extent = 0;          // the extent the box padding was derived from (build_tree): what gdpt_scene_set_camera compares against
 };
 
 struct PreparedScene {
@@ -40,6 +41,12 @@ struct PreparedScene {
 // default rule (meshes of >= 4096 triangles only). with_bvh8 / with_q4: also the quantised 8-wide / 4-wide forms of the tree; the
 // caller decides (GDPT_HBM_BVH8 and GDPT_HBM_Q4 reach only the A/B translation units, never a host object).
 struct PrepareOptions { double presplit = -1.0, sbvh = -1.0; bool with_bvh8 = false, with_q4 = true; };
+
+// Everything a view derives from the camera (org, pow2_film, inv_width, ...): the one copy, for prepare_scene and for
+// gdpt_scene_set_camera (hip/capi_device.hip).
+void fill_camera(const GdptCamera &cam, DevCamera *out);
+// The camera position's term of the extent from which build_tree derives the box padding.
+float camera_extent(const GdptCamera &cam);
 
 // Throws std::runtime_error for a description no scene can be made of.
 PreparedScene prepare_scene(const GdptSceneDesc &desc, const PrepareOptions &opt);

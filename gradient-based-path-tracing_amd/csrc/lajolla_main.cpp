@@ -95,6 +95,18 @@
 //   --features PREFIX   writes the first-hit feature buffers of the film (gdpt_features_render): PREFIX_albedo.exr, PREFIX_normal.exr
 //                 and PREFIX_depth.pfm, means over --feature-spp N samples (default min(16, spp)) of the render's own camera rays.
 //                 Single device (not with --gpus / --devices / --sample-devices)
+//   --frames N    renders N frames of a moving camera on one uploaded scene (gdpt_scene_set_camera) and writes NAME_0000.exr,
+//                 NAME_0001.exr, ... from -o NAME.exr. Frame f turns cam_to_world by f times --orbit DEG degrees (default 0) about the
+//                 world's vertical (y) axis through the centre of the scene's bounds, and draws the sample window [f spp, (f + 1) spp)
+//                 of every pixel's N spp streams in passes of --pass-spp (needed, at least two passes a frame): frames never repeat
+//                 samples. Without --temporal a frame's file is its own image (the mean of an Integrator::Path scene, the
+//                 reconstruction of a GradPath one). --temporal carries the accumulated primal mean, its variance and the history
+//                 length from frame to frame through the first-hit depth (gdpt_temporal_push; --feature-spp as above, default the
+//                 frame's spp; --temporal-max-history M, default 32) and writes the accumulated mean; with it --denoised FILE
+//                 --atrous-levels L [--atrous-k K] also writes FILE_0000 ..., the a-trous filter on the accumulated mean and variance
+//                 under the frame's features (default guide). A camera that leaves the extent the scene was uploaded with is refused.
+//                 --orbit, --temporal and --temporal-max-history need --frames; none of them is combined with --gpus / --devices,
+//                 --sample-devices or --select, nor with the other filter, reconstruction and feature options
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
 #include "../../include/gdpt.h"
 
@@ -106,6 +118,116 @@
 #include <iostream>
 #include <string>
 #include <vector>
+
+namespace {
+
+// NAME.ext -> NAME_0007.ext
+std::string frame_name(const std::string &file, int f) {
+    char tag[16];
+    std::snprintf(tag, sizeof(tag), "_%04d", f);
+    const size_t dot = file.find_last_of('.'), slash = file.find_last_of('/');
+    if (dot == std::string::npos || (slash != std::string::npos && dot < slash)) return file + tag;
+    return file.substr(0, dot) + tag + file.substr(dot);
+}
+
+// the centre of the bounds of the description's shapes
+void scene_centre(const GdptSceneDesc *desc, double c[3]) {
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (int s = 0; s < desc->num_shapes; s++) {
+        const GdptShape &sh = desc->shapes[s];
+        if (sh.type == GDPT_SHAPE_SPHERE)
+            for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], sh.center[k] - sh.radius); hi[k] = std::max(hi[k], sh.center[k] + sh.radius); }
+        else if (sh.positions)
+            for (int i = 0; i < sh.num_vertices; i++)
+                for (int k = 0; k < 3; k++) { lo[k] = std::min(lo[k], sh.positions[3 * i + k]); hi[k] = std::max(hi[k], sh.positions[3 * i + k]); }
+    }
+    for (int k = 0; k < 3; k++) c[k] = lo[k] <= hi[k] ? 0.5 * (lo[k] + hi[k]) : 0.0;
+}
+
+// `cam` with cam_to_world turned by `deg` degrees about the vertical axis through c: T(c) R_y(deg) T(-c) cam_to_world
+GdptCamera orbit_camera(const GdptCamera &cam, const double c[3], double deg) {
+    const double a = deg * 3.14159265358979323846 / 180.0, cs = std::cos(a), sn = std::sin(a);
+    // rows of T(c) R_y T(-c)
+    const double R[4][4] = {{cs, 0, sn, c[0] - cs * c[0] - sn * c[2]}, {0, 1, 0, 0}, {-sn, 0, cs, c[2] + sn * c[0] - cs * c[2]}, {0, 0, 0, 1}};
+    GdptCamera out = cam;
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) {
+            double v = 0;
+            for (int k = 0; k < 4; k++) v += R[i][k] * cam.cam_to_world[4 * k + j];
+            out.cam_to_world[4 * i + j] = v;
+        }
+    return out;
+}
+
+struct FrameOptions {
+    int frames = 0, spp = 0, pass_spp = 0, feature_spp = 0, max_history = 0, device = 0;
+    double orbit = 0.0, alpha = 0.04;
+    bool temporal = false, atrous = false;
+    GdptAtrousParams atrous_params{};
+    std::string output, denoised;
+};
+
+// --frames: returns 0, or the status main ends with (the message is printed)
+int render_frames(GdptScene *scene, const GdptSceneDesc *desc, const FrameOptions &o) {
+    const int w = desc->camera.width, h = desc->camera.height;
+    const bool path = desc->integrator == GDPT_INTEGRATOR_PATH;
+    const int spp = o.spp > 0 ? o.spp : desc->samples_per_pixel;
+    if (spp < 2 * o.pass_spp) { std::cerr << "--frames: a frame's spp must hold at least two passes of --pass-spp" << std::endl; return 2; }
+    const size_t plane = (size_t)w * h;
+    std::vector<double> mean(plane * 3), var(plane * 3), out(plane * 3), var_out(plane * 3), filtered(plane * 3);
+    std::vector<double> fmean(plane * GDPT_FEATURE_CHANNELS), fvar(plane * GDPT_FEATURE_CHANNELS);
+    double centre[3];
+    scene_centre(desc, centre);
+    GdptTemporal *temporal = nullptr;
+    GdptTemporalParams tp{};
+    gdpt_temporal_default_params(&tp);
+    if (o.max_history > 0) tp.max_history = o.max_history;
+    GdptNlmGuide guide{};
+    gdpt_nlm_default_guide(&guide);
+    auto fail = [&]() { std::cerr << "terminate: " << gdpt_last_error() << std::endl; gdpt_temporal_free(temporal); return 134; };
+    if (o.temporal && gdpt_temporal_create(w, h, o.device, nullptr, &temporal) != 0) return fail();
+    GdptProgressiveConfig cfg{};
+    cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = GDPT_SHIFT_REFERENCE; cfg.budget_spp = o.frames * spp;
+    for (int f = 0; f < o.frames; f++) {
+        const GdptCamera cam = orbit_camera(desc->camera, centre, f * o.orbit);
+        if (gdpt_scene_set_camera(scene, &cam) != 0) return fail();
+        GdptProgressive *session = nullptr;
+        int rc = gdpt_progressive_create_slice(scene, &cfg, f * spp, spp, nullptr, &session);
+        for (int done = 0; rc == 0 && done < spp; done += o.pass_spp) rc = gdpt_progressive_add_pass(session, std::min(o.pass_spp, spp - done), nullptr);
+        double *means[5] = {mean.data(), nullptr, nullptr, nullptr, nullptr}, *vars[5] = {var.data(), nullptr, nullptr, nullptr, nullptr};
+        if (rc == 0) rc = gdpt_progressive_read(session, 0, means, vars, nullptr);
+        const double *image = mean.data();
+        if (rc == 0 && !o.temporal && !path) { rc = gdpt_progressive_reconstruct(session, o.alpha, nullptr, 0, out.data(), nullptr); image = out.data(); }
+        const std::string err = rc != 0 ? gdpt_last_error() : "";
+        gdpt_progressive_free(session);
+        if (rc != 0) { std::cerr << "terminate: " << err << std::endl; gdpt_temporal_free(temporal); return 134; }
+        GdptTemporalStats ts{};
+        if (o.temporal) {
+            GdptRenderParams fp{};
+            fp.spp = o.feature_spp > 0 ? o.feature_spp : spp; fp.rng_scheme = GDPT_RNG_SAMPLE;
+            const GdptSampleWindow win{o.frames * spp, f * spp};
+            if (gdpt_features_render(scene, &fp, &win, fmean.data(), fvar.data(), nullptr) != 0) return fail();
+            if (gdpt_temporal_push(temporal, &cam, mean.data(), var.data(), fmean.data(), &tp, out.data(), var_out.data(), nullptr, &ts) != 0) return fail();
+            image = out.data();
+            if (o.atrous) {
+                if (gdpt_denoise_atrous(w, h, out.data(), var_out.data(), fmean.data(), fvar.data(), GDPT_FEATURE_CHANNELS, &o.atrous_params, &guide, nullptr,
+                                        filtered.data(), nullptr, nullptr) != 0) return fail();
+                if (gdpt_imwrite(frame_name(o.denoised, f).c_str(), w, h, filtered.data()) != 0) return fail();
+            }
+        }
+        const std::string name = frame_name(o.output, f);
+        if (gdpt_imwrite(name.c_str(), w, h, image) != 0) return fail();
+        std::cout << "[gdpt] frame " << f << ": orbit " << f * o.orbit << " degrees, " << spp << " spp";
+        if (o.temporal)
+            std::cout << ", mean history " << ts.sum_history / (double)plane << " frames, " << ts.pixels_reset << " pixels reset, " << ts.pixels_background
+                      << " background, " << ts.pixels_left_out << " left out, push " << ts.push_ms << " ms";
+        std::cout << ", written to " << name << std::endl;
+    }
+    gdpt_temporal_free(temporal);
+    return 0;
+}
+
+} // namespace
 
 int main(int argc, char *argv[]) {
     if (argc <= 1) {
@@ -135,6 +257,9 @@ int main(int argc, char *argv[]) {
     double atrous_k = 0.0;
     bool atrous_k_set = false;
     int feature_spp = 0;
+    int frames = 0, temporal_max_history = 0;      // 0: not given
+    double orbit = 0.0;
+    bool orbit_set = false, temporal_on = false;
     std::string select_list = "", select_map_file = "", select_mse_file = "";
     int select_radius = 4;
     bool select_radius_set = false;
@@ -231,6 +356,13 @@ int main(int argc, char *argv[]) {
             nlm_var_smooth = std::stoi(next());
             if (nlm_var_smooth < 0 || nlm_var_smooth > GDPT_VAR_SMOOTH_MAX_RADIUS) { std::cerr << "--nlm-var-smooth takes a radius from 0 to 4" << std::endl; return 2; }
         }
+        else if (a == "--frames") { frames = std::stoi(next()); if (frames < 1) { std::cerr << "--frames takes a number of frames >= 1" << std::endl; return 2; } }
+        else if (a == "--orbit") { orbit = std::stod(next()); orbit_set = true; if (!std::isfinite(orbit)) { std::cerr << "--orbit takes a finite angle in degrees" << std::endl; return 2; } }
+        else if (a == "--temporal") temporal_on = true;
+        else if (a == "--temporal-max-history") {
+            temporal_max_history = std::stoi(next());
+            if (temporal_max_history < 1) { std::cerr << "--temporal-max-history takes a number of frames >= 1" << std::endl; return 2; }
+        }
         else if (a == "--select") select_list = next();
         else if (a == "--select-radius") {
             select_radius = std::stoi(next()); select_radius_set = true;
@@ -282,6 +414,30 @@ int main(int argc, char *argv[]) {
         if (recon.norm == GDPT_RECON_L1 && !weighted) {
             std::cerr << "--nlm-joint is not combined with --reconstruct l1: the unweighted IRLS solve has no variant that takes the filtered variances "
                          "(use l2, wl2 or wl1)" << std::endl;
+            return 2;
+        }
+    }
+    if (frames == 0 && (orbit_set || temporal_on || temporal_max_history > 0)) {
+        std::cerr << "--orbit, --temporal and --temporal-max-history need --frames" << std::endl;
+        return 2;
+    }
+    if (frames > 0) {
+        if (multi.num_devices > 0 || !sample_devices.empty() || !select_list.empty()) {
+            std::cerr << "--frames, --orbit and --temporal are single-device options (not with --gpus / --devices, --sample-devices or --select)" << std::endl;
+            return 2;
+        }
+        if (pass_spp <= 0) { std::cerr << "--frames needs --pass-spp: a frame is a session of at least two passes, so that a variance exists" << std::endl; return 2; }
+        if (temporal_max_history > 0 && !temporal_on) { std::cerr << "--temporal-max-history needs --temporal" << std::endl; return 2; }
+        if (!denoised_file.empty() && !(temporal_on && atrous_levels > 0)) {
+            std::cerr << "--frames writes --denoised only with --temporal and --atrous-levels: the a-trous filter on the accumulated mean" << std::endl;
+            return 2;
+        }
+        if (nlm_option || !nlm_guide_names.empty() || nlm_guide_option || nlm_demodulate || nlm_var_smooth >= 0 || nlm_joint || nlm_levels > 0 ||
+            !nlm_regress_names.empty() || nlm_regress_option || nlm_collaborative || !features_prefix.empty() || !variance_file.empty() ||
+            !confidence_file.empty() || weighted || recon.norm != GDPT_RECON_L2 || target_error != 0.0 || target_recon_error != 0.0 ||
+            !error_map_file.empty() || rng == GDPT_RNG_TILE || shift != GDPT_SHIFT_REFERENCE) {
+            std::cerr << "--frames is combined with -o, --spp, --pass-spp, --film, --device, --alpha, --feature-spp, --denoised, --atrous-levels and --atrous-k only"
+                      << std::endl;
             return 2;
         }
     }
@@ -443,7 +599,7 @@ int main(int argc, char *argv[]) {
         std::cerr << "--features is a single-device option (not with --gpus / --devices / --sample-devices)" << std::endl;
         return 2;
     }
-    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed && !atrous_on && !select_on) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
+    if (feature_spp > 0 && features_prefix.empty() && !guided && !nlm_demodulate && !regressed && !atrous_on && !select_on && !temporal_on) { std::cerr << "--feature-spp needs --features or --nlm-guide" << std::endl; return 2; }
     if (!features_prefix.empty() && rng == GDPT_RNG_TILE) { std::cerr << "--features needs --rng sample (the feature render draws per-sample streams)" << std::endl; return 2; }
     if (weighted && pass_spp <= 0) { std::cerr << "--reconstruct wl2 | wl1 needs --pass-spp: a one-shot render has no variances" << std::endl; return 2; }
     if (!weighted && (conf_floor != 0.0 || !confidence_file.empty())) { std::cerr << "--conf-floor and --confidence need --reconstruct wl2 | wl1" << std::endl; return 2; }
@@ -494,6 +650,17 @@ int main(int argc, char *argv[]) {
         auto t1 = clock::now();
         std::cout << "Done. Took " << std::chrono::duration<double>(t1 - t0).count() << " seconds." << std::endl;
         std::cout << "Rendering..." << std::endl;
+        if (frames > 0) {
+            FrameOptions fo;
+            fo.frames = frames; fo.spp = spp; fo.pass_spp = pass_spp; fo.feature_spp = feature_spp; fo.max_history = temporal_max_history;
+            fo.orbit = orbit; fo.alpha = alpha; fo.device = device; fo.temporal = temporal_on; fo.atrous = atrous_on; fo.atrous_params = atrous;
+            fo.output = outputfile.empty() ? desc->output_filename : outputfile; fo.denoised = denoised_file;
+            const int status = render_frames(scene, desc, fo);
+            gdpt_scene_free(scene);
+            gdpt_free_scene_desc(desc);
+            if (status != 0) return status;
+            continue;
+        }
         const int w = desc->camera.width, h = desc->camera.height;
         std::vector<double> image((size_t)w * h * 3);
         GdptRenderParams p{};

@@ -1280,6 +1280,86 @@ int gdpt_progressive_denoise_reconstruct(GdptProgressive *session, const GdptNlm
                                          double *const filtered[3] /* nullable */, double *const filtered_var[3] /* nullable */,
                                          GdptNlmJointStats *stats /* nullable */, GdptWeightedReconStats *recon_stats /* nullable */);
 
+/* ---- a new camera on an uploaded scene (not part of the reference) ----
+ * Replaces the camera of the handle: renders and feature renders enqueued before the call keep the old camera (the camera travels
+ * with each launch as a kernel argument), those enqueued after it use the new one. Everything an upload derives from the camera is
+ * derived again by the upload's own code. Refused, naming the field, before any device call and with the handle unchanged: a NULL
+ * scene or camera; a width, height, filter_type or filter_param other than the uploaded camera's (the film and everything sized by it
+ * stay as uploaded); a non-finite entry of sample_to_cam or cam_to_world; a camera position that would enlarge the extent from which
+ * the upload derived the padding of the tree's boxes (max |coordinate| over the scene's bounds, its spheres and the uploaded camera's
+ * position): the tree is not rebuilt, and the padding must stay sufficient for rays that start at the camera. For every accepted
+ * camera every render and feature entry of the handle returns, bit for bit, what a fresh gdpt_scene_upload of the same description
+ * with desc.camera replaced returns. The call takes no lock: it must not run beside another call on the same handle from another
+ * thread (a render call reads the camera while it enqueues). A live GdptProgressive session of the handle holds no camera of its own:
+ * its passes after the call render with the new camera and fold into the statistics of the old one, so a session is closed, or a new
+ * one created, across the call (Temporal.frame and lajolla --frames make one session a frame). */
+int gdpt_scene_set_camera(GdptScene *scene, const GdptCamera *camera);
+
+/* ---- temporal reprojection: accumulate frames across a camera move (not part of the reference) ----
+ * A progressive session is temporal accumulation under a fixed camera: a running mean with a variance of the mean. This carries the
+ * accumulated mean U, its variance of the mean V and the history length N through a camera move: each push reprojects them through
+ * the new frame's first-hit depth, rejects history where depth or normal disagree, and blends the new frame in (the temporal half of
+ * Schied et al., "Spatiotemporal variance-guided filtering", HPG 2017). The outputs are a mean and a variance of the mean, what every
+ * filter above takes. The history holds the unfiltered accumulation; nothing but the camera may move; an environment-map background
+ * is not reprojected by direction (background pixels restart every frame); GradPath gradients are not reprojected.
+ * A handle is bound to (width, height, device, stream) and owns two sets of history planes that alternate, so no launch writes a plane
+ * it reads: U and V (W*H*3 doubles, interleaved like the films), N (W*H doubles), the previous frame's unit normal (3 planes), depth
+ * and coverage planes, and the previous camera. One kernel per push, enqueued on the handle's stream.
+ * Inputs of a push: the frame's camera; img = u, var = v (W*H*3 doubles, interleaved); feat: the GDPT_FEATURE_CHANNELS planes of a
+ * feature render of that frame (planar), of which planes 3-5 (normal), 6 (depth) and 7 (coverage) are read.
+ * M(camera) = inverse(sample_to_cam) inverse(cam_to_world), 4x4 row-major, computed on the host in fp64 (gdpt_temporal_world_to_sample
+ * returns it); org(camera) is the camera position of an upload, cam_to_world (0, 0, 0). For pixel p = (x, y) of the current frame:
+ *   LEFT OUT    any of u_c(p), v_c(p) non-finite, or a v_c(p) < 0: out, var_out keep the input's bits, N' = 0, counted in
+ *               pixels_left_out; the pixel is never a valid tap later.
+ *   BACKGROUND  otherwise, coverage(p) not > 0: out = u, var_out = v, N' = 1, counted in pixels_background; never a valid tap.
+ *   SURFACE     otherwise. d = depth(p) / coverage(p) (the depth plane is a mean over hits and misses); n^ = the normal planes
+ *               divided by their length, (0, 0, 0) for a length not > 0, which means RESET.
+ *     X = org + d dir, (org, dir) the camera ray through the pixel centre: pt = sample_to_cam ((x + 1/2) / W, (y + 1/2) / H, 0)
+ *     as a point, dir = normalize(cam_to_world normalize(pt)) as a vector.
+ *     (sx, sy, ., w) = M(prev) (X, 1). RESET unless w > 0.
+ *     q = (sx / w W - 1/2, sy / w H - 1/2). RESET unless -1 <= q_x <= W and -1 <= q_y <= H (no tap lies in the film otherwise).
+ *     i0 = floor(q_x), j0 = floor(q_y), f_x = q_x - i0, f_y = q_y - j0. The taps t = (i0 + a, j0 + b), a, b in {0, 1}, have the
+ *     bilinear weights b_t = (a ? f_x : 1 - f_x) (b ? f_y : 1 - f_y). A tap is VALID if it lies in the film, N_prev(t) >= 1,
+ *     coverage_prev(t) > 0, |d_prev(t) - e| <= tau_z e with e = |X - org(prev)|, n^_prev(t) is not (0, 0, 0) (a pixel without a
+ *     normal is never a tap, at any tau_n), and n^ . n^_prev(t) >= tau_n.
+ *     S = sum of b_t over the valid taps, in the order (a, b) = (0,0), (1,0), (0,1), (1,1), as every sum below.
+ *     RESET       S < s_min, or the first push after create or reset: out = u, var_out = v, N' = 1, counted in pixels_reset.
+ *     otherwise   U = (sum b_t U_prev(t)) / S,  V = (sum (b_t b_t) V_prev(t)) / (S S),  N = (sum b_t N_prev(t)) / S;
+ *                 N' = min(N + 1, max_history),  alpha = 1 / N',  out = U + alpha (u - U),
+ *                 var_out = ((1 - alpha) (1 - alpha)) V + (alpha alpha) v;  where N' = 1 (alpha = 1) out = u and var_out = v, the
+ *                 input's bits, and the pixel is not counted as reset.
+ *   The new history is (out, var_out, N', n^, d, coverage) of the pixel (n^ = d = 0 where none was formed).
+ * V takes the four taps as independent, the convention of every var_out here: neighbouring history pixels that were themselves
+ * interpolated from common taps are correlated, so var_out underestimates. Defaults: tau_z 0.05, tau_n 0.9, s_min 1e-3, max_history
+ * 32; apart from max_history the customary SVGF-style values, not tuned on any scene of this project.
+ * Identities, exact: max_history = 1 returns the input bits always; so do the first push and the push after a reset, with N' = 1 on
+ * every surface and background pixel.
+ * GdptTemporalStats: the three pixel counts, sum_history = the sum of N' over the film (fixed order: the same bits every time), push_ms
+ * around the kernel. */
+typedef struct GdptTemporalParams { double tau_z, tau_n, s_min; int32_t max_history; int32_t reserved[3]; } GdptTemporalParams;
+typedef struct GdptTemporalStats  { uint64_t pixels_left_out, pixels_background, pixels_reset; double sum_history, push_ms; } GdptTemporalStats;
+typedef struct GdptTemporal GdptTemporal;   /* opaque */
+void gdpt_temporal_default_params(GdptTemporalParams *p);   /* 0.05, 0.9, 1e-3, 32; every field of a passed struct is taken literally */
+/* stream: a hipStream_t, NULL the null stream. Refused: NULL out, width or height < 1 or a film too large, a negative device index.
+ * Makes no device call: the planes are allocated by the first push, which fails on a device that does not exist. */
+int gdpt_temporal_create(int width, int height, int device, void *stream, GdptTemporal **out);
+void gdpt_temporal_free(GdptTemporal *t);   /* waits for the handle's stream first */
+int gdpt_temporal_reset(GdptTemporal *t);   /* the next push is a first push; host only, enqueues nothing */
+/* M(camera) of the definition. Refused: NULL arguments, a non-finite entry, a singular matrix. Host only. */
+int gdpt_temporal_world_to_sample(const GdptCamera *camera, double M[16]);
+/* Device pointers on the handle's device; enqueued on the handle's stream. Refused before any device call, naming the field: a NULL
+ * handle, camera, d_img, d_var, d_feat, d_out or d_var_out; an output aliasing an input or another output; a camera whose width or
+ * height differs from the handle's, or that gdpt_temporal_world_to_sample refuses; tau_z < 0 or non-finite, tau_n outside [-1, 1],
+ * s_min outside (0, 1], max_history < 1; non-zero reserved. d_len (nullable): W*H doubles, receives N'. With stats it waits for the
+ * stream; with stats == NULL it only enqueues. No CPU fallback. */
+int gdpt_temporal_push_device(GdptTemporal *t, const GdptCamera *camera, const double *d_img, const double *d_var, const double *d_feat,
+                              const GdptTemporalParams *params /* NULL: defaults */, double *d_out, double *d_var_out,
+                              double *d_len /* nullable */, GdptTemporalStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_temporal_push(GdptTemporal *t, const GdptCamera *camera, const double *img, const double *var, const double *feat,
+                       const GdptTemporalParams *params /* NULL: defaults */, double *out, double *var_out, double *len /* nullable */,
+                       GdptTemporalStats *stats /* nullable */);
+
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
 int gdpt_imwrite(const char *filename, int width, int height, const double *rgb);
