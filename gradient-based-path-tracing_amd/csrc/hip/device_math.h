@@ -72,9 +72,18 @@ GD double pcg_real(Pcg &r) { // next_pcg32_real<double>: 32 random mantissa bits
     uint64_t u = ((uint64_t)pcg_next(r) << 20) | 0x3ff0000000000000ULL;
     return __longlong_as_double((long long)u) - 1.0;
 }
+// A 64-bit literal in scalar registers. A literal that a vector multiply-add cannot encode is otherwise put into a vector register
+// pair, and where the use sits in a loop that pair is filled ahead of the loop and held across all of it.
+template <uint64_t C> GD uint64_t scalar_literal() {
+    uint32_t lo, hi;
+    asm("s_mov_b32 %0, %2\n\ts_mov_b32 %1, %3" : "=s"(lo), "=s"(hi) : "n"((uint32_t)C), "n"((uint32_t)(C >> 32)));
+    return ((uint64_t)hi << 32) | lo;
+}
+// pcg_jump2 (../pcg_jump.h) with its two constants held that way
+GD uint64_t pcg_jump2_device(uint64_t inc) { return inc * scalar_literal<kPcgJump2A>() + scalar_literal<kPcgJump2B>(); }
 // pcg_init(stream) followed by two draws whose results the caller has from elsewhere (../pcg_jump.h)
 GD Pcg pcg_init_behind_two(uint64_t stream) {
-    Pcg s; s.inc = pcg_stream_inc(stream); s.state = pcg_jump2(s.inc);
+    Pcg s; s.inc = pcg_stream_inc(stream); s.state = pcg_jump2_device(s.inc);
     return s;
 }
 

@@ -102,6 +102,7 @@ GD bool loop_allows(int max_depth, int num_vertices) { return max_depth == -1 ||
 // Two homes for a lane's 15 running sums: registers (serial kernels) or the block's LDS, one private slot per lane
 // and component, updated with return-less ds_add_f64 (frees 30 VGPRs; one writer per slot, so still deterministic).
 struct AccReg {
+    static constexpr bool kInLds = false;
     Accum a;
     GD void init() { a.r = a.dx0 = a.dy0 = a.dx1 = a.dy1 = splat(0); }
     GD void add(int which, D3 v) {     // which: 0 r, 1 dx0, 2 dy0, 3 dx1, 4 dy1
@@ -111,6 +112,7 @@ struct AccReg {
     GD Accum result() { return a; }
 };
 struct AccLds {
+    static constexpr bool kInLds = true;      // (the kernels that keep their sums in LDS keep LanePriv there too)
     double *slot;   // &s_acc[0][tid]; component c lives at slot[c * stride]
     int stride;
     GD void init() { for (int c = 0; c < 15; c++) slot[c * stride] = 0.0; }
@@ -160,6 +162,31 @@ GD void acc_no_offsets(ACC &a, D3 radiance, D3 contrib, double prob, double spp,
         a.add(1, t); a.add(2, t);
         a.add(3, -t); a.add(4, -t);
     }
+}
+
+// The lane machines' form of the three functions above (lane_consume): ONE block per step for whatever a lane adds in it. The arms of the
+// step only say what: an offset leaves its contribution cX and its weight w, the end of a sample without offsets a mark (ACT_END_NO_OFFSETS). A lane-step is either an offset step
+// or the end of a sample without offsets, never both, so one division, one non-finite test and one set of adds serve both:
+//   offset k        component {1, 3, 2, 4}[k] += (contrib - cX) * (w / (prob * spp))  (k = 0, 2)  or  (cX - contrib) * (same)  (k = 1, 3);
+//                   with k = 3 the sample ends: component 0 += radiance / spp
+//   no offsets      component 0 += radiance / spp; with t = contrib * (1.0 / (prob * spp)): components 1, 2 += t, components 3, 4 += -t
+// Same operand expressions as acc_offset / acc_base / acc_no_offsets, therefore the same bits:
+//   * radiance / spp is operator/ spelled out, radiance * (1.0 / spp), with the quotient formed once per launch (`inv_spp`);
+//   * for a sample without offsets acc_step takes cX = +0 and w = 1.0. contrib - (+0) is contrib bit for bit, for every contrib (x - (+0) = x in round to
+//     nearest, -0 and the infinities included; a NaN comes out quiet with its payload, as it does from the product that follows), so
+//     (contrib - cX) * (w / (prob * spp)) is contrib * (1.0 / (prob * spp)). The two differences stay two expressions behind a select;
+//     -(t) is formed from t as before;
+//   * a product and the add that consumes it stay in separate statements: nothing new is there to be contracted (-ffp-contract=on).
+// Non-finite samples count once, as above: an offset step counts its own operands unless the sample is flagged (Lane::kc); the step that
+// ends the sample also looks at prob and radiance. One test covers both ends: with cX = 0 and w = 1 it is acc_no_offsets' own.
+enum { SUM_NONE = 0, SUM_OFFSET = 1, SUM_NO_OFFSETS = 2 };
+struct SumOps { int k; D3 cX; double w; };              // (acc_step itself: behind LanePriv, which holds the radiance)
+
+// A wave-uniform double, told to the compiler as such (two scalar registers instead of a vector pair per lane).
+GD double wave_uniform(double v) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)u), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(u >> 32));
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -498,9 +525,13 @@ GD void trav_run(const DevSceneView &sv, const TraceCtx &tx, D3 org, D3 dir, flo
     // (org - o)/d with the node's origin: -2 and 1.6 at d = -1e-38 give 3.6e38). The box would be rejected although the ray lies
     // inside its slab. From |1/d| = kSlabInvMax on, inv and oi are therefore NaN, which drops the slab out of fmin/fmax: that only
     // ever admits a box, and the primitive test decides. Below it every product of a coordinate (< 1.8e19) and 1/d is finite.
+    // (the quiet NaN from a scalar register, device_math.h, in the walks of the plain LDS-resident lane machines, whose product kernel
+    // must stay within 192 VGPRs: as a literal it sits in a vector register across the whole loop. Every other walk keeps the literal and
+    // compiles as before.)
+    const float kSlabNan = (TC::LEAF_K > 0 && !TC::SPHERES) ? __uint_as_float((uint32_t)scalar_literal<0x7fc00000ull>()) : __builtin_nanf("");
 #pragma unroll
     for (int k = 0; k < 3; k++)
-        if (!(fabsf(inv[k]) < kSlabInvMax && fabsf(oi[k]) < __builtin_huge_valf())) { inv[k] = __builtin_nanf(""); oi[k] = __builtin_nanf(""); }
+        if (!(fabsf(inv[k]) < kSlabInvMax && fabsf(oi[k]) < __builtin_huge_valf())) { inv[k] = kSlabNan; oi[k] = kSlabNan; }
     constexpr bool kOvf = TC::WIDE && TC::FLAT && GDPT_HBM_BVH8;
     int cur = tv.cur, sp = tv.sp;
     Hit best = tv.best;
@@ -636,7 +667,8 @@ GD double mat_pdf(const DevSceneView &sv, const TraceCtx &tx, const Vertex &v, D
 //              vertex it leaves, so no vertex has to stay in registers across the traversal
 //   S_OFFSET   camera ray of offset k of a base path that stopped where offsets are observable (lazy, see header)
 enum { S_START = 0, S_PRIMARY = 1, S_BOUNCE = 2, S_OFFSET = 3, S_DONE = 4 };
-enum { ACT_NONE = 0, ACT_BOUNCE = 1, ACT_OFFSETS = 2, ACT_NEXT_SAMPLE = 3, ACT_PRIMARY_RAY = 4, ACT_OFFSET_RAY = 5 };
+enum { ACT_NONE = 0, ACT_BOUNCE = 1, ACT_OFFSETS = 2, ACT_NEXT_SAMPLE = 3, ACT_PRIMARY_RAY = 4, ACT_OFFSET_RAY = 5,
+       ACT_END_NO_OFFSETS = 6 };    // inside lane_consume only: ACT_NEXT_SAMPLE behind the "no offsets" sums of the sample that ends
 // why the base path stopped, which decides what the offsets still do
 enum { C_NO_LOOP = 0,        // the bounce loop never ran (max_depth < 2): jacobian 1
        C_AFTER_BOUNCE1 = 1,  // left the loop in bounce 1 after the updates: offsets were re-sampled in bounce 1
@@ -651,6 +683,16 @@ struct LanePriv {
     double *slot; int stride;
     GD D3 radiance() const { return mk(slot[0], slot[stride], slot[2 * stride]); }
     GD void set_radiance(D3 v) { slot[0] = v.x; slot[stride] = v.y; slot[2 * stride] = v.z; }
+    // radiance += v. LDS: the slots are in the block's LDS (the lane machines that keep their sums there, AccLds, keep these there too):
+    // three return-less ds_add_f64, one writer per slot as in AccLds, and the sum v is added to is not read into registers. Otherwise
+    // (the wavefront kernels keep the slots in global memory): read, add, write.
+    template <bool LDS> GD void add_radiance(D3 v) {
+        if (LDS) {
+            __hip_atomic_fetch_add(slot, v.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(slot + stride, v.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(slot + 2 * stride, v.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        } else set_radiance(radiance() + v);
+    }
     GD double p2_1() const { return slot[3 * stride]; }
     GD void set_p2_1(double v) { slot[3 * stride] = v; }
     GD FilterCache fc() const { FilterCache f; f.dx = slot[4 * stride]; f.dy = slot[5 * stride]; f.ox = slot[6 * stride]; f.oy = slot[7 * stride]; return f; }
@@ -684,17 +726,52 @@ struct Lane {
     GD int cmode() const { return (kc & ~kKcFlags) >> 2; }
 };
 
+// The sums of one lane-step (SumOps, above: what is added, and why the bits are those of acc_offset / acc_base / acc_no_offsets).
+// `flagged`: an earlier offset of this sample was non-finite. Returns whether this step's operands were.
+template <class ACC>
+GD bool acc_step(ACC &a, int mode, const SumOps &o, const LanePriv &lp, D3 contrib, double prob, double spp, double inv_spp, bool flagged, LaneCounters &lc) {
+    const bool off = mode == SUM_OFFSET;
+    const bool ends = !off || o.k == 3;                                    // the sample ends in this step: its radiance is added
+    D3 rad = splat(0);
+    if (ends) rad = lp.radiance();
+    // (only an offset step fills o; a sample that ends without offsets has contribX = 0, wX = 1: the struct defaults, src/intersection.h:65-77)
+    const D3 cX = mk(off ? o.cX.x : 0.0, off ? o.cX.y : 0.0, off ? o.cX.z : 0.0);
+    const double w = off ? o.w : 1.0;
+    const int k = off ? o.k : 0;
+    const bool fin_grad = isfinite(cX.x + cX.y + cX.z) && isfinite(w) && isfinite(contrib.x + contrib.y + contrib.z);
+    const bool fin_base = isfinite(prob) && isfinite(rad.x + rad.y + rad.z);
+    const bool bad = !fin_grad || (ends && !fin_base);
+    if (bad && !flagged) lc.nonfinite++;
+    if (prob > 0.0) {
+        if (ends) { const D3 b = rad * inv_spp; a.add(0, b); }
+        const double q = w / (prob * spp);
+        const D3 d = contrib - cX, e = cX - contrib;
+        const bool odd = off && (o.k & 1);                               // x1, y1: the offset minus the base
+        const D3 g = mk(odd ? e.x : d.x, odd ? e.y : d.y, odd ? e.z : d.z) * q;
+        a.add(1 + ((k & 1) << 1) + (k >> 1), g);                       // k = 0, 1, 2, 3 -> dx0 (1), dx1 (3), dy0 (2), dy1 (4)
+        if (!off) { const D3 n = -g; a.add(2, g); a.add(3, n); a.add(4, n); }
+    }
+    return bad;
+}
+
 // SERIAL_RNG: one PCG stream runs through consecutive samples (TILE scheme); otherwise each sample owns stream
 // `base + s` (SAMPLE scheme) and its sub-pixel / bounce-1 numbers are re-derived from it when an offset needs them.
 // PLAIN: device_trace.h (kPlainNoSpheres | kPlainConstTex): sphere / texture code is not compiled in.
 template <bool LAMBERT, bool SERIAL_RNG, class ACC, class STAMPS = Stamps<false>, int PLAIN = 0>
-GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, double spp, unsigned long long base,
+GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, double spp, double inv_spp, unsigned long long base,
                     Lane &L, Trav &tv, LanePriv &lp, ACC &acc, LaneCounters &lc, TraceCounters &tc, STAMPS *stp = nullptr) {
     STAMPS none{}; STAMPS &stamps = stp ? *stp : none;
     const DevCamera &cam = sv.cam;
     const int w = cam.width, h = cam.height;
     const int st0 = L.st;
     int act = ACT_NONE;
+    // What the arms share (one set of draws, one emission, one sums block) is built into the Lambertian machines. The kernels with the
+    // full material switch hold 84 spilled VGPRs as it is and each shared item costs them more (2 spilled VGPRs, 16 bytes of scratch): they
+    // keep every arm's own copy. Same expressions either way, so the two forms give the same bits.
+    constexpr bool SHARE = LAMBERT;
+    // SAMPLE scheme: the increment of the sample's stream follows from (base, s), for the base path's draws and for an offset's alike;
+    // formed where a draw is made, it need not be held in the lane (Lane::rng_inc is the TILE scheme's)
+    auto stream_inc = [&]() __attribute__((always_inline)) { return (SERIAL_RNG || !SHARE) ? L.rng_inc : (unsigned long long)pcg_stream_inc(base + (unsigned long long)L.s); };
     Vertex nv;
     Ray ray;
     ray.org = L.org; ray.dir = L.dir; ray.tfar = __builtin_huge_val();
@@ -707,6 +784,15 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
         hit = tv.best.gid >= 0;
         if (hit) make_vertex<PLAIN>(sv, tx.tris, tx.need_uv, ray, tv.best, 0.0, (st0 == S_BOUNCE) ? 0.0 : 0.25 / (double)max(w, h), nv);   // src/ray.h:33-35, :564
     }
+    // emission at the hit, once for the step's three consumers (a sample's primary hit, a bounce hit, an offset's primary hit): a lane
+    // is in one state, so at most one of them reads it
+    const bool emitter_here = SHARE && hit && nv.light_id >= 0;
+    auto is_emitter = [&]() __attribute__((always_inline)) { return SHARE ? emitter_here : (hit && nv.light_id >= 0); };      // (!SHARE: tested in the arm, as before)
+    D3 Le;                                        // (read only where the hit is an emitter)
+    if (emitter_here) Le = emission(tx.lights, nv, -ray.dir);
+    // (An offset lane reads it behind the BSDF block. It has no bounce ray pending, so L.f is free to carry its c0 there, :496-508:
+    // registers that are held across the block for the bouncing lanes anyway.)
+    if (SHARE && st0 == S_OFFSET) L.f = emitter_here ? Le : splat(1.0);
     stamps.mark(SEG_VERTEX);
     // ---------------- consume the hit ----------------
     if (st0 == S_START) {
@@ -718,7 +804,7 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             L.contrib = splat(1.0); L.throughput = splat(1.0);
             L.prob = 1.0;
             D3 rad0 = splat(0);
-            if (nv.light_id >= 0) { D3 Le = emission(tx.lights, nv, -ray.dir); rad0 = Le; L.contrib = Le; }   // :490-493
+            if (is_emitter()) { if (!SHARE) Le = emission(tx.lights, nv, -ray.dir); rad0 = Le; L.contrib = Le; }   // :490-493
             lp.set_radiance(rad0); lp.set_p2_1(1.0);
             L.num_vertices = 3;
             if (!loop_allows(max_depth, 3)) { L.kc = (L.kc & kKcSetupNext) | (C_NO_LOOP << 2); act = ACT_OFFSETS; } else act = ACT_BOUNCE;
@@ -731,18 +817,18 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
         double p2 = L.pdf * G;                                                      // :766
         L.contrib = L.contrib * f * G; L.prob *= p2;                                // :769-770
         if (first) lp.set_p2_1(p2);
-        if (hit && nv.light_id >= 0) {                                              // :971-980
-            D3 Le = emission(tx.lights, nv, -ray.dir);
+        if (is_emitter()) {                                                         // :971-980
+            if (!SHARE) Le = emission(tx.lights, nv, -ray.dir);
             D3 C2 = (G * f) * Le;
             L.contrib = L.contrib * Le;
-            lp.set_radiance(lp.radiance() + L.throughput * (C2 / p2));
+            { const D3 t = L.throughput * (C2 / p2); lp.template add_radiance<SHARE && ACC::kInLds>(t); }
         }
         bool stop = !hit;                                                           // :982-985
         if (!stop) {
             double rr_prob = 1;
             if (L.num_vertices - 1 >= sv.rr_depth) {                                // :992-999
                 rr_prob = fmin(maxc(1.0 * L.throughput), 0.95);                    // eta_scale == 1: one-sided lobes never refract
-                Pcg rr_rng; rr_rng.state = L.rng_state; rr_rng.inc = L.rng_inc;
+                Pcg rr_rng; rr_rng.state = L.rng_state; rr_rng.inc = stream_inc();
                 double u = pcg_real(rr_rng); L.rng_state = rr_rng.state;
                 if (u > rr_prob) stop = true;
             }
@@ -755,6 +841,7 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
         }
         if (!stop) act = ACT_BOUNCE;
         else if (first) { L.kc = (L.kc & kKcSetupNext) | (C_AFTER_BOUNCE1 << 2); act = ACT_OFFSETS; }
+        else if (SHARE) act = ACT_END_NO_OFFSETS;
         else { acc_no_offsets(acc, lp.radiance(), L.contrib, L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
         // (one-sided lobes: offsets alive after bounce 1 are retired by bounce 2's re-sampling, see file header)
     }
@@ -770,18 +857,24 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
     BsdfSample bs; D3 f; double pdf;
     if (!LAMBERT) { bs.dir_out = splat(0); bs.eta = 0; bs.roughness = 0; f = splat(0); pdf = 0; }
     if (act == ACT_BOUNCE || off_resample) {
+        // One set of draws for both groups. A bouncing lane draws from its own stream and keeps the state. An offset lane's numbers are
+        // the sample's bounce-1 numbers: the three draws behind the stream's seeding and the two sub-pixel draws, so it starts from that
+        // state (pcg_jump.h) and throws its copy away. (TILE scheme: one stream runs through the samples; the lane kept the numbers.)
         D2 ruv; double rw;
-        if (act == ACT_BOUNCE) {
-            lc.bounces++;
-            Pcg r; r.state = L.rng_state; r.inc = L.rng_inc;
-            ruv.x = pcg_real(r); ruv.y = pcg_real(r); rw = pcg_real(r);                              // :536-537
-            L.rng_state = r.state;
-            if (SERIAL_RNG && L.num_vertices == 3) { L.ruv1 = ruv; L.rw1 = rw; }
-        } else if (SERIAL_RNG) { ruv = L.ruv1; rw = L.rw1; }
-        else {
+        const bool bouncing = act == ACT_BOUNCE;
+        if (bouncing) lc.bounces++;
+        if (SERIAL_RNG && !bouncing) { ruv = L.ruv1; rw = L.rw1; }
+        else if (!SHARE && !bouncing) {
             Pcg r2 = pcg_init(base + (unsigned long long)L.s);
             (void)pcg_next(r2); (void)pcg_next(r2);
             ruv.x = pcg_real(r2); ruv.y = pcg_real(r2); rw = pcg_real(r2);
+        } else {
+            Pcg r;
+            r.inc = stream_inc();
+            r.state = (SERIAL_RNG || bouncing) ? L.rng_state : pcg_jump2_device(r.inc);                     // (pcg_init_behind_two, with the shared inc)
+            ruv.x = pcg_real(r); ruv.y = pcg_real(r); rw = pcg_real(r);                              // :536-537
+            if (bouncing) L.rng_state = r.state;
+            if (SERIAL_RNG && L.num_vertices == 3) { L.ruv1 = ruv; L.rw1 = rw; }                    // (SERIAL_RNG: only bouncing lanes get here)
         }
         const D3 dir_view = -ray.dir;
         // (PLAIN >> kPlainSetShift: the scene's material set, if the kernel was built for a small one — render_phases_general_sets.hip)
@@ -790,12 +883,12 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
         if (sampled) mat_eval_pdf<LAMBERT, false, false, kSet, PLAIN>(sv, tx, nv, dir_view, bs.dir_out, f, pdf);
     }
     stamps.mark(SEG_BSDF);
+    SumOps sums;                                                    // (filled by an offset step, read by acc_step for one)
     if (st0 == S_OFFSET) {
-        const int k = L.k();
         D3 cX = splat(0);
         double wgt = 1.0;
         if (off_valid) {
-            D3 c0 = (nv.light_id >= 0) ? emission(tx.lights, nv, -ray.dir) : splat(1.0);   // :496-508
+            const D3 c0 = SHARE ? L.f : (is_emitter() ? emission(tx.lights, nv, -ray.dir) : splat(1.0));   // :496-508 (SHARE: parked above)
             double jac = 1.0;
             bool alive = true;
             if (off_resample) {
@@ -803,11 +896,15 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             }
             if (alive) { cX = c0 * jac; wgt = L.prob / (L.prob + 1.0 * jac); }      // :1019-1045
         }
-        bool flagged = (L.kc & kKcNonfinite) != 0;
-        acc_offset(acc, k, L.contrib, cX, wgt, L.prob, spp, lc, flagged);
-        if (flagged) L.kc |= kKcNonfinite;
-        if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc, flagged); L.kc &= ~kKcNonfinite; act = ACT_NEXT_SAMPLE; }
-        else { L.kc = (L.kc & ~3) | (k + 1); act = ACT_OFFSET_RAY; }
+        if (SHARE) { sums.cX = cX; sums.w = wgt; }                                  // (k, the flag and what follows the offset: with the sums)
+        else {
+            const int k = L.k();
+            bool flagged = (L.kc & kKcNonfinite) != 0;
+            acc_offset(acc, k, L.contrib, cX, wgt, L.prob, spp, lc, flagged);
+            if (flagged) L.kc |= kKcNonfinite;
+            if (k == 3) { acc_base(acc, lp.radiance(), L.prob, spp, lc, flagged); L.kc &= ~kKcNonfinite; act = ACT_NEXT_SAMPLE; }
+            else { L.kc = (L.kc & ~3) | (k + 1); act = ACT_OFFSET_RAY; }
+        }
     } else if (act == ACT_BOUNCE) {                                                  // bounce iteration L.num_vertices starts at `nv`
         if (!sampled) act = ACT_NEXT_SAMPLE;                                        // :545-548: GraidentPTRadiance{}
         else {
@@ -815,14 +912,24 @@ GD int lane_consume(const DevSceneView &sv, const TraceCtx &tx, int max_depth, d
             if (pdf <= 0) {                                                         // :760-763: break before any update; the ray's
                 if (L.num_vertices == 3) { L.kc = (L.kc & kKcSetupNext) | (C_BROKE_BOUNCE1 << 2); act = ACT_OFFSETS; }           // hit is unobservable
                 else if (L.num_vertices == 4 && L.mat0() == L.mat1()) { L.kc = (L.kc & kKcSetupNext) | (C_BROKE_BOUNCE2 << 2); act = ACT_OFFSETS; }   // :607-612 passed
+                else if (SHARE) act = ACT_END_NO_OFFSETS;
                 else { acc_no_offsets(acc, lp.radiance(), L.contrib, L.prob, spp, lc); act = ACT_NEXT_SAMPLE; }
             } else arm = true;
         }
     }
-    stamps.mark(SEG_FINISH);
     // the bounce ray, written to the lane in one place at the function's top level: set inside the branches above, the pending ray, f
     // and pdf were copied aside and back at every join the lanes that do not bounce pass (act stays ACT_BOUNCE only here)
     if (arm) { L.org = nv.position; L.dir = bs.dir_out; L.f = f; L.pdf = pdf; L.st = S_BOUNCE; }
+    // ---------------- the step's sums: one block behind the arms ----------------
+    // (what a lane adds follows from its state: an offset step always adds its component; the arms mark a sample that ends without offsets)
+    if (SHARE && (st0 == S_OFFSET || act == ACT_END_NO_OFFSETS)) {
+        const bool off = st0 == S_OFFSET;
+        sums.k = L.k();
+        const bool bad = acc_step(acc, off ? SUM_OFFSET : SUM_NO_OFFSETS, sums, lp, L.contrib, L.prob, spp, inv_spp, off && (L.kc & kKcNonfinite) != 0, lc);
+        if (!off || sums.k == 3) { if (off) L.kc &= ~kKcNonfinite; act = ACT_NEXT_SAMPLE; }
+        else { L.kc = ((L.kc & ~3) | (sums.k + 1)) | (bad ? kKcNonfinite : 0); act = ACT_OFFSET_RAY; }
+    }
+    stamps.mark(SEG_FINISH);
     if (act == ACT_OFFSETS) { L.kc &= ~3; act = ACT_OFFSET_RAY; }
     if (act == ACT_NEXT_SAMPLE) {
         L.s++;
@@ -916,9 +1023,9 @@ GD void lane_camera_batched(CAM &cam, int act, bool fresh, int x, int y, unsigne
 
 // Both halves back to back (serial kernels, wavefront step kernel).
 template <bool LAMBERT, bool SERIAL_RNG, class ACC, class STAMPS = Stamps<false>, int PLAIN = 0>
-GD void lane_step(const DevSceneView &sv, const TraceCtx &tx, int max_depth, double spp, int x, int y, unsigned long long base,
+GD void lane_step(const DevSceneView &sv, const TraceCtx &tx, int max_depth, double spp, double inv_spp, int x, int y, unsigned long long base,
                   Lane &L, Trav &tv, LanePriv &lp, ACC &acc, LaneCounters &lc, TraceCounters &tc, STAMPS *stp = nullptr) {
-    const int act = lane_consume<LAMBERT, SERIAL_RNG, ACC, STAMPS, PLAIN>(sv, tx, max_depth, spp, base, L, tv, lp, acc, lc, tc, stp);
+    const int act = lane_consume<LAMBERT, SERIAL_RNG, ACC, STAMPS, PLAIN>(sv, tx, max_depth, spp, inv_spp, base, L, tv, lp, acc, lc, tc, stp);
     lane_camera<SERIAL_RNG, STAMPS>(sv, sv.cam, act, x, y, base, L, tv, lp, stp);
     lane_arm(sv, act, tv);
 }
@@ -1185,7 +1292,8 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
     TraceCtx tx = setup_trace<LDS_SCENE, WIDE>(sv, s_scene, s_stack, tid, kBlock, a.count != 0);
     if (!LDS_SCENE) __syncthreads();                                                // (for LDS scenes setup_trace ends with the barrier)
     const int W = sv.cam.width;
-    const double spp = (double)a.spp;
+    // launch constants of the step's sums (acc_step), in scalar registers; the kernels with the full material switch keep their own sums
+    const double spp = LAMBERT ? wave_uniform((double)a.spp) : (double)a.spp, inv_spp = LAMBERT ? wave_uniform(1.0 / spp) : 0.0;
     AccLds acc; acc.slot = s_acc + tid; acc.stride = kBlock;
     acc.init();
     LanePriv lp; lp.slot = s_priv + tid; lp.stride = kBlock;
@@ -1282,7 +1390,7 @@ __global__ __launch_bounds__(kBlock, 2) void gdpt_render_phases(DevSceneView sv,
         act = ACT_NONE;
         if (lane_ready(L, tv)) {
             if (tx.count) { tc.lane_steps++; if (wave_leader()) tc.wave_steps++; }
-            act = lane_consume<LAMBERT, false, AccLds, Stamps<STAMPED>, PLAIN>(sv, tx, a.max_depth, spp, base, L, tv, lp, acc, lc, tc, &stamps);
+            act = lane_consume<LAMBERT, false, AccLds, Stamps<STAMPED>, PLAIN>(sv, tx, a.max_depth, spp, inv_spp, base, L, tv, lp, acc, lc, tc, &stamps);
         }
         if (QUEUE_MID) hand_out(act, fresh);
         // ---- (S, second half) camera rays: next sample, next offset, first sample of a new item
@@ -1334,7 +1442,7 @@ __global__ __launch_bounds__(64) void gdpt_render_tile_stream_phases(DevSceneVie
     LaneCounters lc = {0, 0, 0};
     TraceCounters tc = {0, 0, 0, 0, 0, 0};
     const int W = sv.cam.width, H = sv.cam.height;
-    const double spp = (double)a.spp;
+    const double spp = (double)a.spp, inv_spp = 1.0 / spp;
     if (tile < ntx * nty) {
         const int txi = tile % ntx, tyi = tile / ntx;
         Lane L;
@@ -1352,7 +1460,7 @@ __global__ __launch_bounds__(64) void gdpt_render_tile_stream_phases(DevSceneVie
                 while (L.st != S_DONE) {
                     if (lane_tracing(L.st) && tv.cur != kTravDone)
                         trav_run<TraceHbm>(sv, tx, L.org, L.dir, (L.st == S_BOUNCE) ? (float)sv.isect_eps : 0.0f, __builtin_huge_valf(), tv, 0, 0, tc);
-                    lane_step<LAMBERT, true>(sv, tx, a.max_depth, spp, x, y, 0ull, L, tv, lp, acc, lc, tc);
+                    lane_step<LAMBERT, true>(sv, tx, a.max_depth, spp, inv_spp, x, y, 0ull, L, tv, lp, acc, lc, tc);
                 }
                 Accum sum = acc.result();
                 reduce_and_store(a, sum, 1, true, x, y, W);

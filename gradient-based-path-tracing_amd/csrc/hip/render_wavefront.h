@@ -78,6 +78,7 @@ struct WfBuf {
 constexpr int kWfMaxGen = 8192;
 
 struct AccMem {                     // the slot's 15 sums in HBM: one owner, plain read-modify-write
+    static constexpr bool kInLds = false;
     double *slot; long long stride;
     GD void init() { for (int c = 0; c < 15; c++) slot[c * stride] = 0.0; }
     GD void add(int which, D3 v) {
@@ -213,9 +214,11 @@ __global__ __launch_bounds__(kBlock) void gdpt_wf_step(DevSceneView sv, KernelAr
             if (tv.best.gid >= sv.num_tris) { const float4 h1 = w.hits[2 * slot + 1]; tv.best.ngx = h1.x; tv.best.ngy = h1.y; tv.best.ngz = h1.z; }
         }
         const unsigned long long base = ((unsigned long long)y * W + x) * (unsigned long long)a.stream_spp;
-        L.rng_inc = ((base + (unsigned long long)L.s) << 1u) | 1u;       // pcg_init's increment of the sample in flight
+        // pcg_init's increment of the sample in flight: read by the step with the full material switch; the Lambertian step forms it where
+        // it draws (lane_consume: stream_inc) and this folds away
+        L.rng_inc = ((base + (unsigned long long)L.s) << 1u) | 1u;
 
-        lane_step<LAMBERT, false>(sv, tx, a.max_depth, spp, x, y, base, L, tv, lp, acc, lc, tc);
+        lane_step<LAMBERT, false>(sv, tx, a.max_depth, spp, 1.0 / spp, x, y, base, L, tv, lp, acc, lc, tc);
 
         // ---- store, and emit the slot's next ray
         st_(WF_I0, pack2((unsigned)L.st, (unsigned)L.s));
