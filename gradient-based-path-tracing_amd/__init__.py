@@ -135,6 +135,11 @@ def lib():
         L.gdpt_temporal_world_to_sample.argtypes = [camp, dp]
         L.gdpt_temporal_push_device.argtypes = [vp, camp, vp, vp, vp, tpp, vp, vp, vp, tsp]
         L.gdpt_temporal_push.argtypes = [vp, camp, vp, vp, vp, tpp, vp, vp, vp, tsp]
+        tgp, tgs = C.POINTER(defs.GdptTemporalGradParams), C.POINTER(defs.GdptTemporalGradStats)
+        L.gdpt_temporal_default_grad_params.argtypes = [tgp]
+        L.gdpt_temporal_default_grad_params.restype = None
+        L.gdpt_temporal_push_gradients_device.argtypes = [vp, camp] + [vp] * 7 + [tpp, tgp] + [vp] * 8 + [tgs]
+        L.gdpt_temporal_push_gradients.argtypes = [vp, camp] + [vp] * 7 + [tpp, tgp] + [vp] * 8 + [tgs]
         vsp, vss = C.POINTER(defs.GdptVarSmoothParams), C.POINTER(defs.GdptVarSmoothStats)
         L.gdpt_var_smooth_default_params.argtypes = [vsp]
         L.gdpt_var_smooth_default_params.restype = None
@@ -1412,6 +1417,18 @@ def temporal_params(tau_z=None, tau_n=None, s_min=None, max_history=None):
     return p
 
 
+def temporal_grad_params(j_max=None, cos_min=None):
+    """GdptTemporalGradParams (include/gdpt.h): the library's defaults (gdpt_temporal_default_grad_params: j_max 4, cos_min 0.02) with
+    the keywords given in their places, taken literally."""
+    p = defs.GdptTemporalGradParams()
+    lib().gdpt_temporal_default_grad_params(C.byref(p))
+    if j_max is not None:
+        p.j_max = float(j_max)
+    if cos_min is not None:
+        p.cos_min = float(cos_min)
+    return p
+
+
 def temporal_world_to_sample(camera):
     """M(camera) of the temporal definition (gdpt_temporal_world_to_sample): the 4x4 float64 inverse(sample_to_cam)
     inverse(cam_to_world) as the library computes it."""
@@ -1473,17 +1490,121 @@ class Temporal:
                                                C.byref(st) if stats else None))
         return st
 
-    def frame(self, scene, camera, frame_index, frames, spp, pass_spp, path=True, atrous=None, feature_spp=None, params=None, **kw):
+    GRAD_OUTPUTS = ("gx_out", "gx_var_out", "gy_out", "gy_var_out")
+
+    @staticmethod
+    def _split_grad_keywords(kw):
+        """(keywords of temporal_params, keywords of temporal_grad_params)"""
+        g = {k: kw[k] for k in ("j_max", "cos_min") if k in kw}
+        return {k: v for k, v in kw.items() if k not in g}, g
+
+    def push_gradients(self, camera, img, var, feat, gx, gx_var, gy, gy_var, length=True, params=None, grad_params=None, **kw):
+        """One frame with its assembled gradients into the history (gdpt_temporal_push_gradients). `img`, `var`, `feat` as push();
+        `gx`, `gy`: HxWx3 float64, the assembled cx, cy; `gx_var`, `gy_var`: their variances of the mean; `grad_params`: a
+        GdptTemporalGradParams taken as it is (else the keywords j_max, cos_min of temporal_grad_params). Returns a dict: out, var_out,
+        length (N' or None), gx_out, gx_var_out, gy_out, gy_var_out, glength (N_g' or None), stats (GdptTemporalGradStats)."""
+        shape = (self.height, self.width, 3)
+        ins = [np.ascontiguousarray(x, dtype=np.float64) for x in (img, var, gx, gx_var, gy, gy_var)]
+        f = np.ascontiguousarray(feat, dtype=np.float64)
+        if any(x.shape != shape for x in ins) or f.shape != (defs.FEATURE_CHANNELS, self.height, self.width):
+            raise GdptError("Temporal.push_gradients: img, var and the gradients must be HxWx3 and feat (8, H, W) arrays of the handle's film")
+        kw, gkw = self._split_grad_keywords(kw)
+        p = params if params is not None else temporal_params(**kw)
+        gp = grad_params if grad_params is not None else temporal_grad_params(**gkw)
+        r = {k: np.empty(shape, dtype=np.float64) for k in ("out", "var_out") + self.GRAD_OUTPUTS}
+        r["length"] = np.empty(shape[:2], dtype=np.float64) if length else None
+        r["glength"] = np.empty(shape[:2], dtype=np.float64) if length else None
+        st = defs.GdptTemporalGradStats()
+        ptr = lambda x: C.c_void_p(x.ctypes.data) if x is not None else None      # noqa: E731
+        _check(lib().gdpt_temporal_push_gradients(self.handle, C.byref(camera), ptr(ins[0]), ptr(ins[1]), ptr(f), *[ptr(x) for x in ins[2:]],
+                                                  C.byref(p), C.byref(gp), ptr(r["out"]), ptr(r["var_out"]), ptr(r["length"]),
+                                                  *[ptr(r[k]) for k in self.GRAD_OUTPUTS], ptr(r["glength"]), C.byref(st)))
+        r["stats"] = st
+        return r
+
+    def push_gradients_device(self, camera, img_ptr, var_ptr, feat_ptr, grad_ptrs, out_ptr, var_out_ptr, grad_out_ptrs, len_ptr=None,
+                              glen_ptr=None, stats=True, params=None, grad_params=None, **kw):
+        """push_gradients() on device addresses (gdpt_temporal_push_gradients_device), enqueued on the handle's stream. `grad_ptrs`: the
+        four addresses of gx, gx_var, gy, gy_var; `grad_out_ptrs`: those of gx_out, gx_var_out, gy_out, gy_var_out. Enqueue-only with
+        `stats` False. Returns the GdptTemporalGradStats or None."""
+        kw, gkw = self._split_grad_keywords(kw)
+        p = params if params is not None else temporal_params(**kw)
+        gp = grad_params if grad_params is not None else temporal_grad_params(**gkw)
+        st = defs.GdptTemporalGradStats() if stats else None
+        opt = lambda x: C.c_void_p(int(x)) if x else None      # noqa: E731
+        gi, go = list(grad_ptrs), list(grad_out_ptrs)
+        if len(gi) != 4 or len(go) != 4:
+            raise GdptError("Temporal.push_gradients_device: grad_ptrs and grad_out_ptrs hold four addresses each")
+        _check(lib().gdpt_temporal_push_gradients_device(self.handle, C.byref(camera) if camera is not None else None, opt(img_ptr), opt(var_ptr),
+                                                         opt(feat_ptr), *[opt(x) for x in gi], C.byref(p), C.byref(gp), opt(out_ptr),
+                                                         opt(var_out_ptr), opt(len_ptr), *[opt(x) for x in go], opt(glen_ptr),
+                                                         C.byref(st) if stats else None))
+        return st
+
+    @staticmethod
+    def assemble(means):
+        """(c, cx, cy) of a GradPath session's five means, one addition a value: the bits of gdpt_assemble_device."""
+        cx, cy = means["cx0"].copy(), means["cy0"].copy()
+        cx[:, 1:] = means["cx0"][:, 1:] + means["cx1"][:, :-1]
+        cy[1:, :] = means["cy0"][1:, :] + means["cy1"][:-1, :]
+        return means["img"], cx, cy
+
+    def _frame_gradients(self, scene, camera, frame_index, frames, spp, pass_spp, atrous, feature_spp, params, reconstruct_, alpha, kw):
+        """frame() with gradients=True"""
+        if reconstruct_ not in (None, "l2", "wl2", "wl1"):
+            raise GdptError("Temporal.frame: reconstruct is None, 'l2', 'wl2' or 'wl1'")
+        if scene.desc.desc.integrator == defs.INTEGRATOR_PATH:
+            raise GdptError("Temporal.frame: gradients=True needs a GradPath scene; this one is Integrator::Path, which renders no gradients")
+        scene.set_camera(camera)
+        first, block = int(frame_index) * spp, int(frames) * spp
+        session = Progressive(scene, block, path=False, slice=(first, spp))
+        try:
+            done = 0
+            while done < spp:
+                n = min(pass_spp, spp - done)
+                session.add_pass(n)
+                done += n
+            means, vars_, asm = session.read()
+        finally:
+            session.close()
+        feat, feat_var = scene.features(int(feature_spp) if feature_spp else spp, window=(block, first))
+        c, cx, cy = self.assemble(means)
+        r = self.push_gradients(camera, c, asm["c"], feat, cx, asm["cx"], cy, asm["cy"], params=params, **kw)
+        r.update(mean=means["img"], var=vars_["img"], feat=feat, feat_var=feat_var, c=c, cx=cx, cy=cy, assembled_vars=asm)
+        if atrous is not None:
+            r["denoised"], r["denoised_var"], r["atrous_stats"] = denoise_atrous(r["out"], r["var_out"], feat, feat_var, guide=nlm_guide(), **atrous)
+        if reconstruct_ == "l2":
+            r["reconstructed"], r["recon_stats"] = reconstruct(self.width, self.height, r["out"], r["gx_out"], r["gy_out"], dataCost=alpha,
+                                                               norm=defs.RECON_L2)
+        elif reconstruct_ is not None:
+            r["reconstructed"], r["recon_stats"] = reconstruct_weighted(self.width, self.height, r["out"], r["gx_out"], r["gy_out"], r["var_out"],
+                                                                        r["gx_var_out"], r["gy_var_out"], dataCost=alpha,
+                                                                        norm=defs.RECON_L2 if reconstruct_ == "wl2" else defs.RECON_L1)
+        return r
+
+    def frame(self, scene, camera, frame_index, frames, spp, pass_spp, path=True, atrous=None, feature_spp=None, params=None, gradients=False,
+              reconstruct=None, alpha=0.04, **kw):
         """One frame of a moving camera, from pieces that exist: scene.set_camera(camera); a slice session over the sample window
         [frame_index spp, (frame_index + 1) spp) of frames spp streams, so that frames never repeat samples, in passes of `pass_spp`
         (at least two, so that a variance exists); its mean and variance (the primal's, for GradPath: `path` False); the features on
         the same window at `feature_spp` (None: spp) samples; push(). `atrous`: None, or a dict of atrous_params keywords: then
         denoise_atrous on (out, var_out) under the frame's features with the default guide. The history keeps the unfiltered
         accumulation. Returns a dict: out, var_out, length, stats, mean, var, feat, feat_var, and with `atrous` denoised,
-        denoised_var, atrous_stats."""
+        denoised_var, atrous_stats.
+        With `gradients` (needs `path` False and a GradPath scene): the session's five means are assembled into c, cx, cy (assemble()),
+        and push_gradients() takes them with the session's assembled variances (the keywords j_max, cos_min go to it). The dict gains
+        gx_out, gx_var_out, gy_out, gy_var_out, glength, c, cx, cy, assembled_vars, stats becomes a GdptTemporalGradStats, and with
+        `reconstruct` 'l2' | 'wl2' | 'wl1' it gains reconstructed (and recon_stats): reconstruct(norm=RECON_L2), or reconstruct_weighted
+        on the accumulated variances, of the accumulated triple at dataCost `alpha`. Without `gradients` nothing changes."""
         spp, pass_spp = int(spp), int(pass_spp)
         if pass_spp < 1 or spp < 2 * pass_spp:
             raise GdptError("Temporal.frame: spp must hold at least two passes of pass_spp")
+        if gradients:
+            if path:
+                raise GdptError("Temporal.frame: gradients=True needs path=False (a Path session renders no gradients)")
+            return self._frame_gradients(scene, camera, frame_index, frames, spp, pass_spp, atrous, feature_spp, params, reconstruct, alpha, kw)
+        if reconstruct is not None:
+            raise GdptError("Temporal.frame: reconstruct needs gradients=True")
         scene.set_camera(camera)
         first, block = int(frame_index) * spp, int(frames) * spp
         session = Progressive(scene, block, path=path, slice=(first, spp))

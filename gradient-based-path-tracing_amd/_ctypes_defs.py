@@ -187,6 +187,14 @@ class GdptTemporalStats(C.Structure):
                 ("sum_history", C.c_double), ("push_ms", C.c_double)]
 
 
+class GdptTemporalGradParams(C.Structure):
+    _fields_ = [("j_max", C.c_double), ("cos_min", C.c_double), ("reserved", C.c_int32 * 4)]
+
+
+class GdptTemporalGradStats(C.Structure):
+    _fields_ = [("base", GdptTemporalStats), ("pixels_gradient_reset", C.c_uint64), ("sum_gradient_history", C.c_double)]
+
+
 VAR_SMOOTH_MAX_RADIUS = 4
 DENOISE_PLAIN, DENOISE_GUIDED, DENOISE_DEMOD = 0, 1, 2
 

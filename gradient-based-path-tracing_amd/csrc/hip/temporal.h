@@ -19,4 +19,19 @@ void temporal_world_to_sample(const std::string &who, const GdptCamera &cam, dou
 void temporal_push_launch(GdptTemporal *t, const GdptCamera &cam, const double *d_img, const double *d_var, const double *d_feat,
                           const GdptTemporalParams &p, double *d_out, double *d_var_out, double *d_len, GdptTemporalStats *stats);
 
+// The gradient block's refusals (j_max, cos_min, reserved), as temporal_check_params. Host only.
+void temporal_check_grad_params(const std::string &who, const GdptTemporalGradParams &p);
+
+// The frame's assembled gradients with their variances, and where the accumulated ones go (gdpt_temporal_push_gradients_device).
+struct TemporalGradIO {
+    const double *gx, *gx_var, *gy, *gy_var;
+    double *gx_out, *gx_var_out, *gy_out, *gy_var_out, *glen;      // glen nullable
+};
+
+// temporal_push_launch with the gradients carried along: the gradient kernel in place of the plain one, the same grid, the same
+// stream; the gradient history is allocated by the first call.
+void temporal_push_gradients_launch(GdptTemporal *t, const GdptCamera &cam, const double *d_img, const double *d_var, const double *d_feat,
+                                    const TemporalGradIO &io, const GdptTemporalParams &p, const GdptTemporalGradParams &gp, double *d_out,
+                                    double *d_var_out, double *d_len, GdptTemporalGradStats *stats);
+
 } // namespace gdpt

@@ -105,6 +105,10 @@
 //                 frame's spp; --temporal-max-history M, default 32) and writes the accumulated mean; with it --denoised FILE
 //                 --atrous-levels L [--atrous-k K] also writes FILE_0000 ..., the a-trous filter on the accumulated mean and variance
 //                 under the frame's features (default guide). A camera that leaves the extent the scene was uploaded with is refused.
+//                 --temporal-gradients (with --temporal, GradPath scenes) carries the assembled gradients cx, cy and their variances along,
+//                 transformed by the Jacobian of the reprojection (gdpt_temporal_push_gradients), and writes to NAME_0000.exr ... the
+//                 reconstruction of the accumulated c, cx, cy: --reconstruct l2 (default) | wl2 | wl1, the weighted ones on the
+//                 accumulated variances; --denoised stays the a-trous filter on the accumulated primal.
 //                 --orbit, --temporal and --temporal-max-history need --frames; none of them is combined with --gpus / --devices,
 //                 --sample-devices or --select, nor with the other filter, reconstruction and feature options
 // `-t` is accepted for compatibility; rendering runs on the GPU, so it has no effect.
@@ -162,7 +166,9 @@ GdptCamera orbit_camera(const GdptCamera &cam, const double c[3], double deg) {
 struct FrameOptions {
     int frames = 0, spp = 0, pass_spp = 0, feature_spp = 0, max_history = 0, device = 0;
     double orbit = 0.0, alpha = 0.04;
-    bool temporal = false, atrous = false;
+    bool temporal = false, atrous = false, gradients = false;
+    int recon_norm = GDPT_RECON_L2;      // with gradients: the reconstruction of the accumulated triple ...
+    bool recon_weighted = false;         // ... on its accumulated variances (wl2 | wl1)
     GdptAtrousParams atrous_params{};
     std::string output, denoised;
 };
@@ -176,6 +182,14 @@ int render_frames(GdptScene *scene, const GdptSceneDesc *desc, const FrameOption
     const size_t plane = (size_t)w * h;
     std::vector<double> mean(plane * 3), var(plane * 3), out(plane * 3), var_out(plane * 3), filtered(plane * 3);
     std::vector<double> fmean(plane * GDPT_FEATURE_CHANNELS), fvar(plane * GDPT_FEATURE_CHANNELS);
+    // --temporal-gradients: the session's other four means, the assembled cx, cy, the three assembled variances, the accumulated
+    // gradients with their variances, and the reconstruction of the accumulated triple
+    std::vector<std::vector<double>> raw(4), asm_var(3), grad(2), grad_out(4);
+    std::vector<double> recon_out;
+    if (o.gradients) {
+        for (auto *set : {&raw, &asm_var, &grad, &grad_out}) for (auto &b : *set) b.resize(plane * 3);
+        recon_out.resize(plane * 3);
+    }
     double centre[3];
     scene_centre(desc, centre);
     GdptTemporal *temporal = nullptr;
@@ -195,20 +209,48 @@ int render_frames(GdptScene *scene, const GdptSceneDesc *desc, const FrameOption
         int rc = gdpt_progressive_create_slice(scene, &cfg, f * spp, spp, nullptr, &session);
         for (int done = 0; rc == 0 && done < spp; done += o.pass_spp) rc = gdpt_progressive_add_pass(session, std::min(o.pass_spp, spp - done), nullptr);
         double *means[5] = {mean.data(), nullptr, nullptr, nullptr, nullptr}, *vars[5] = {var.data(), nullptr, nullptr, nullptr, nullptr};
-        if (rc == 0) rc = gdpt_progressive_read(session, 0, means, vars, nullptr);
+        double *asm_vars[3] = {nullptr, nullptr, nullptr};
+        if (o.gradients) {
+            for (int k = 0; k < 4; k++) means[1 + k] = raw[k].data();
+            for (int k = 0; k < 3; k++) asm_vars[k] = asm_var[k].data();
+        }
+        if (rc == 0) rc = gdpt_progressive_read(session, 0, means, vars, o.gradients ? asm_vars : nullptr);
         const double *image = mean.data();
         if (rc == 0 && !o.temporal && !path) { rc = gdpt_progressive_reconstruct(session, o.alpha, nullptr, 0, out.data(), nullptr); image = out.data(); }
         const std::string err = rc != 0 ? gdpt_last_error() : "";
         gdpt_progressive_free(session);
         if (rc != 0) { std::cerr << "terminate: " << err << std::endl; gdpt_temporal_free(temporal); return 134; }
         GdptTemporalStats ts{};
+        GdptTemporalGradStats gs{};
         if (o.temporal) {
             GdptRenderParams fp{};
             fp.spp = o.feature_spp > 0 ? o.feature_spp : spp; fp.rng_scheme = GDPT_RNG_SAMPLE;
             const GdptSampleWindow win{o.frames * spp, f * spp};
             if (gdpt_features_render(scene, &fp, &win, fmean.data(), fvar.data(), nullptr) != 0) return fail();
-            if (gdpt_temporal_push(temporal, &cam, mean.data(), var.data(), fmean.data(), &tp, out.data(), var_out.data(), nullptr, &ts) != 0) return fail();
-            image = out.data();
+            if (o.gradients) {
+                // cx = cx0 + cx1(x - 1, y), cy = cy0 + cy1(x, y - 1): one addition a value, the bits of gdpt_assemble_device
+                const size_t row = (size_t)w * 3;
+                for (size_t i = 0; i < plane * 3; i++) {
+                    grad[0][i] = (i % row < 3) ? raw[0][i] : raw[0][i] + raw[2][i - 3];
+                    grad[1][i] = (i < row) ? raw[1][i] : raw[1][i] + raw[3][i - row];
+                }
+                if (gdpt_temporal_push_gradients(temporal, &cam, mean.data(), asm_var[0].data(), fmean.data(), grad[0].data(), asm_var[1].data(),
+                                                 grad[1].data(), asm_var[2].data(), &tp, nullptr, out.data(), var_out.data(), nullptr,
+                                                 grad_out[0].data(), grad_out[1].data(), grad_out[2].data(), grad_out[3].data(), nullptr, &gs) != 0)
+                    return fail();
+                ts = gs.base;
+                if (o.recon_weighted) {
+                    GdptWeightedReconParams wp{};
+                    wp.recon.norm = o.recon_norm;
+                    if (gdpt_reconstruct_weighted(w, h, out.data(), grad_out[0].data(), grad_out[2].data(), var_out.data(), grad_out[1].data(),
+                                                  grad_out[3].data(), o.alpha, &wp, recon_out.data(), nullptr, nullptr) != 0) return fail();
+                } else {
+                    GdptReconParams rp{};
+                    rp.norm = GDPT_RECON_L2;
+                    if (gdpt_reconstruct(w, h, out.data(), grad_out[0].data(), grad_out[2].data(), o.alpha, &rp, recon_out.data(), nullptr) != 0) return fail();
+                }
+            } else if (gdpt_temporal_push(temporal, &cam, mean.data(), var.data(), fmean.data(), &tp, out.data(), var_out.data(), nullptr, &ts) != 0) return fail();
+            image = o.gradients ? recon_out.data() : out.data();
             if (o.atrous) {
                 if (gdpt_denoise_atrous(w, h, out.data(), var_out.data(), fmean.data(), fvar.data(), GDPT_FEATURE_CHANNELS, &o.atrous_params, &guide, nullptr,
                                         filtered.data(), nullptr, nullptr) != 0) return fail();
@@ -221,6 +263,9 @@ int render_frames(GdptScene *scene, const GdptSceneDesc *desc, const FrameOption
         if (o.temporal)
             std::cout << ", mean history " << ts.sum_history / (double)plane << " frames, " << ts.pixels_reset << " pixels reset, " << ts.pixels_background
                       << " background, " << ts.pixels_left_out << " left out, push " << ts.push_ms << " ms";
+        if (o.gradients)
+            std::cout << ", mean gradient history " << gs.sum_gradient_history / (double)plane << " frames, " << gs.pixels_gradient_reset
+                      << " gradients reset";
         std::cout << ", written to " << name << std::endl;
     }
     gdpt_temporal_free(temporal);
@@ -259,7 +304,7 @@ int main(int argc, char *argv[]) {
     int feature_spp = 0;
     int frames = 0, temporal_max_history = 0;      // 0: not given
     double orbit = 0.0;
-    bool orbit_set = false, temporal_on = false;
+    bool orbit_set = false, temporal_on = false, temporal_gradients = false, reconstruct_set = false;
     std::string select_list = "", select_map_file = "", select_mse_file = "";
     int select_radius = 4;
     bool select_radius_set = false;
@@ -359,6 +404,7 @@ int main(int argc, char *argv[]) {
         else if (a == "--frames") { frames = std::stoi(next()); if (frames < 1) { std::cerr << "--frames takes a number of frames >= 1" << std::endl; return 2; } }
         else if (a == "--orbit") { orbit = std::stod(next()); orbit_set = true; if (!std::isfinite(orbit)) { std::cerr << "--orbit takes a finite angle in degrees" << std::endl; return 2; } }
         else if (a == "--temporal") temporal_on = true;
+        else if (a == "--temporal-gradients") temporal_gradients = true;
         else if (a == "--temporal-max-history") {
             temporal_max_history = std::stoi(next());
             if (temporal_max_history < 1) { std::cerr << "--temporal-max-history takes a number of frames >= 1" << std::endl; return 2; }
@@ -381,6 +427,7 @@ int main(int argc, char *argv[]) {
         }
         else if (a == "--reconstruct") {
             std::string v = next();
+            reconstruct_set = true;
             if (v == "l1") recon.norm = GDPT_RECON_L1;
             else if (v == "l2") recon.norm = GDPT_RECON_L2;
             else if (v == "wl1") { recon.norm = GDPT_RECON_L1; weighted = true; }
@@ -421,6 +468,15 @@ int main(int argc, char *argv[]) {
         std::cerr << "--orbit, --temporal and --temporal-max-history need --frames" << std::endl;
         return 2;
     }
+    if (temporal_gradients && !temporal_on) { std::cerr << "--temporal-gradients needs --temporal (and --frames)" << std::endl; return 2; }
+    if (frames > 0 && reconstruct_set && !temporal_gradients) {
+        std::cerr << "--frames takes --reconstruct only with --temporal-gradients: the reconstruction of the accumulated c, cx, cy" << std::endl;
+        return 2;
+    }
+    if (temporal_gradients && recon.norm == GDPT_RECON_L1 && !weighted) {
+        std::cerr << "--temporal-gradients takes --reconstruct l2 | wl2 | wl1 (not l1)" << std::endl;
+        return 2;
+    }
     if (frames > 0) {
         if (multi.num_devices > 0 || !sample_devices.empty() || !select_list.empty()) {
             std::cerr << "--frames, --orbit and --temporal are single-device options (not with --gpus / --devices, --sample-devices or --select)" << std::endl;
@@ -434,7 +490,7 @@ int main(int argc, char *argv[]) {
         }
         if (nlm_option || !nlm_guide_names.empty() || nlm_guide_option || nlm_demodulate || nlm_var_smooth >= 0 || nlm_joint || nlm_levels > 0 ||
             !nlm_regress_names.empty() || nlm_regress_option || nlm_collaborative || !features_prefix.empty() || !variance_file.empty() ||
-            !confidence_file.empty() || weighted || recon.norm != GDPT_RECON_L2 || target_error != 0.0 || target_recon_error != 0.0 ||
+            !confidence_file.empty() || ((weighted || recon.norm != GDPT_RECON_L2) && !temporal_gradients) || target_error != 0.0 || target_recon_error != 0.0 ||
             !error_map_file.empty() || rng == GDPT_RNG_TILE || shift != GDPT_SHIFT_REFERENCE) {
             std::cerr << "--frames is combined with -o, --spp, --pass-spp, --film, --device, --alpha, --feature-spp, --denoised, --atrous-levels and --atrous-k only"
                       << std::endl;
@@ -639,6 +695,10 @@ int main(int argc, char *argv[]) {
             std::cerr << "--nlm-joint needs a GradPath scene: an Integrator::Path scene has no gradients to filter beside the image" << std::endl;
             return 2;
         }
+        if (temporal_gradients && path) {
+            std::cerr << "--temporal-gradients needs a GradPath scene: an Integrator::Path scene renders no gradients" << std::endl;
+            return 2;
+        }
         GdptProgressiveConfig cfg{};      // of the session or group that --pass-spp asks for
         cfg.mode = path ? GDPT_PROGRESSIVE_PATH : GDPT_PROGRESSIVE_GRADPATH; cfg.shift_mode = shift; cfg.budget_spp = spp;
         if ((grouped   ? gdpt_progressive_group_create(desc, sample_devices.data(), (int)sample_devices.size(), &cfg, &group)
@@ -654,6 +714,7 @@ int main(int argc, char *argv[]) {
             FrameOptions fo;
             fo.frames = frames; fo.spp = spp; fo.pass_spp = pass_spp; fo.feature_spp = feature_spp; fo.max_history = temporal_max_history;
             fo.orbit = orbit; fo.alpha = alpha; fo.device = device; fo.temporal = temporal_on; fo.atrous = atrous_on; fo.atrous_params = atrous;
+            fo.gradients = temporal_gradients; fo.recon_norm = recon.norm; fo.recon_weighted = weighted;
             fo.output = outputfile.empty() ? desc->output_filename : outputfile; fo.denoised = denoised_file;
             const int status = render_frames(scene, desc, fo);
             gdpt_scene_free(scene);

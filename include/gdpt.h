@@ -1301,7 +1301,8 @@ int gdpt_scene_set_camera(GdptScene *scene, const GdptCamera *camera);
  * the new frame's first-hit depth, rejects history where depth or normal disagree, and blends the new frame in (the temporal half of
  * Schied et al., "Spatiotemporal variance-guided filtering", HPG 2017). The outputs are a mean and a variance of the mean, what every
  * filter above takes. The history holds the unfiltered accumulation; nothing but the camera may move; an environment-map background
- * is not reprojected by direction (background pixels restart every frame); GradPath gradients are not reprojected.
+ * is not reprojected by direction (background pixels restart every frame); GradPath gradients go through
+ * gdpt_temporal_push_gradients (below), not through this push.
  * A handle is bound to (width, height, device, stream) and owns two sets of history planes that alternate, so no launch writes a plane
  * it reads: U and V (W*H*3 doubles, interleaved like the films), N (W*H doubles), the previous frame's unit normal (3 planes), depth
  * and coverage planes, and the previous camera. One kernel per push, enqueued on the handle's stream.
@@ -1359,6 +1360,65 @@ int gdpt_temporal_push_device(GdptTemporal *t, const GdptCamera *camera, const d
 int gdpt_temporal_push(GdptTemporal *t, const GdptCamera *camera, const double *img, const double *var, const double *feat,
                        const GdptTemporalParams *params /* NULL: defaults */, double *out, double *var_out, double *len /* nullable */,
                        GdptTemporalStats *stats /* nullable */);
+
+/* ---- temporal reprojection of GradPath gradients (not part of the reference) ----
+ * A push that carries, beside the primal, the assembled gradients and their variances of the mean through the camera move, so that
+ * the accumulated triple (c, cx, cy) with its three variances is what gdpt_reconstruct_device, gdpt_reconstruct_weighted_device and
+ * gdpt_denoise_nlm_joint_device take. The difference convention is the project's (gdpt_assemble_device): cx(x, y) estimates
+ * I(x, y) - I(x - 1, y) and cy(x, y) estimates I(x, y) - I(x, y - 1). A gradient is not a colour: under a dolly or a rotation a unit
+ * pixel step of the new frame is not a unit pixel step of the old one, so the gathered history gradient is transformed by the
+ * Jacobian J of the reprojection q(x, y), taken by backward differences along the local tangent plane.
+ * Inputs beside those of gdpt_temporal_push: gx, gy (the assembled cx, cy) and gx_var, gy_var (their variances of the mean), W*H*3
+ * doubles each, interleaved. Outputs: gx_out, gx_var_out, gy_out, gy_var_out (the same shape) and glen (nullable, W*H doubles, N_g').
+ * The handle gains per history set the accumulated gradients and their variances (12 doubles a pixel, interleaved: G_x, G_y, VG_x,
+ * VG_y by channel) and a length plane N_g, allocated by the first gradient push. A plain gdpt_temporal_push makes the gradient
+ * history STALE (a host flag); so does gdpt_temporal_reset, beside what it does to the primal. Plain pushes keep their kernel.
+ * The primal follows the definition above with the same taps t, weights b_t, validity and S, with one addition: a pixel is LEFT OUT
+ * also if any of gx_c, gy_c, gx_var_c, gy_var_c at it is non-finite, or a gradient variance is < 0. With every gradient input valid
+ * everywhere, out, var_out, len and the GdptTemporalStats fields (except push_ms) are bit for bit gdpt_temporal_push's on the same
+ * sequence of frames. Per pixel, with g_k, v_k the inputs (k in {x, y}, channel by channel):
+ *   LEFT OUT: the gradient outputs keep the input's bits, N_g' = 0. BACKGROUND, and a SURFACE pixel whose primal RESETS: the input's
+ *   bits, N_g' = 1. A SURFACE pixel whose primal BLENDS, with X, n^, d, dir, q, the taps and S of the primal:
+ *     G_k = (sum b_t G_prev,k(t)) / S,  VG_k = (sum (b_t b_t) VG_prev,k(t)) / (S S),  N_g = (sum b_t N_g,prev(t)) / S, in the tap order
+ *     of the definition above.
+ *     The neighbour rays (org, dir_k) are camera rays like dir: dir_x through the sample ((x - 1/2) / W, (y + 1/2) / H), the centre
+ *     of the pixel the x-difference reaches back to, dir_y through ((x + 1/2) / W, (y - 1/2) / H); they are defined by the camera
+ *     alone, also at x = 0 and y = 0. They are cut with the plane through X with normal n^:
+ *     c0 = n^ . dir,  c_k = n^ . dir_k,  t_k = d (c0 / c_k),  X_k = org + t_k dir_k,
+ *     (sx_k, sy_k, ., w_k) = M(prev) (X_k, 1),  q_k = (sx_k / w_k W - 1/2, sy_k / w_k H - 1/2),
+ *     (Jxx, Jyx) = q - q_x,  (Jxy, Jyy) = q - q_y.
+ *     GRADIENT RESET, counted in pixels_gradient_reset: the outputs are the input's bits and N_g' = 1, if the gradient history is
+ *     stale, or |c_k| < cos_min for a k, or not c0 / c_k > 0, or not w_k > 0, or an entry of J is non-finite or |entry| > j_max.
+ *     Otherwise H_x = Jxx G_x + Jyx G_y,  H_y = Jxy G_x + Jyy G_y,
+ *               VH_x = (Jxx Jxx) VG_x + (Jyx Jyx) VG_y,  VH_y = (Jxy Jxy) VG_x + (Jyy Jyy) VG_y (the pair taken as independent, the
+ *               convention of every var_out here),
+ *               N_g' = min(N_g + 1, max_history),  alpha = 1 / N_g',  out_k = H_k + alpha (g_k - H_k),
+ *               var_out_k = ((1 - alpha) (1 - alpha)) VH_k + (alpha alpha) v_k;  where N_g' = 1 the input's bits.
+ *   The new gradient history is the four outputs and N_g' of the pixel.
+ * Defaults: j_max = 4, cos_min = 0.02. Both are choices, tuned on nothing: j_max bounds how far a history gradient may be stretched
+ * before it is dropped, cos_min keeps the division by c_k away from a grazing plane.
+ * GdptTemporalGradStats: base as above; pixels_gradient_reset; sum_gradient_history = the sum of N_g' over the film, in fixed order. */
+typedef struct GdptTemporalGradParams { double j_max, cos_min; int32_t reserved[4]; } GdptTemporalGradParams;
+typedef struct GdptTemporalGradStats  { GdptTemporalStats base; uint64_t pixels_gradient_reset; double sum_gradient_history; } GdptTemporalGradStats;
+void gdpt_temporal_default_grad_params(GdptTemporalGradParams *p);   /* 4, 0.02 */
+/* Device pointers on the handle's device; enqueued on the handle's stream. Refused before any device call, naming the field: what
+ * gdpt_temporal_push_device refuses; a NULL d_gx, d_gy, d_gx_var, d_gy_var, d_gx_out, d_gx_var_out, d_gy_out or d_gy_var_out; an
+ * output (d_glen included) aliasing an input or another output; j_max not finite or < 1, cos_min outside (0, 1], a non-zero reserved
+ * field of grad_params. With stats it waits for the stream; with stats == NULL it only enqueues. No CPU fallback. */
+int gdpt_temporal_push_gradients_device(GdptTemporal *t, const GdptCamera *camera, const double *d_img, const double *d_var,
+                                        const double *d_feat, const double *d_gx, const double *d_gx_var, const double *d_gy,
+                                        const double *d_gy_var, const GdptTemporalParams *params /* NULL: defaults */,
+                                        const GdptTemporalGradParams *grad_params /* NULL: defaults */, double *d_out, double *d_var_out,
+                                        double *d_len /* nullable */, double *d_gx_out, double *d_gx_var_out, double *d_gy_out,
+                                        double *d_gy_var_out, double *d_glen /* nullable */,
+                                        GdptTemporalGradStats *stats /* nullable: enqueue-only */);
+/* Host pointers. Blocking. */
+int gdpt_temporal_push_gradients(GdptTemporal *t, const GdptCamera *camera, const double *img, const double *var, const double *feat,
+                                 const double *gx, const double *gx_var, const double *gy, const double *gy_var,
+                                 const GdptTemporalParams *params /* NULL: defaults */,
+                                 const GdptTemporalGradParams *grad_params /* NULL: defaults */, double *out, double *var_out,
+                                 double *len /* nullable */, double *gx_out, double *gx_var_out, double *gy_out, double *gy_var_out,
+                                 double *glen /* nullable */, GdptTemporalGradStats *stats /* nullable */);
 
 /* ---- output ---- */
 /* By suffix: ".pfm" (fp32, header "PF\nW H\n-1\n", rows as stored) or ".exr" (fp16 RGB scanline). */
